@@ -20,6 +20,12 @@ secondary object `stand_in`.
 
 Tracks shard over ranks by global track id (weak scaling: 100k tracks per GPU).
 
+A plain run sets up (DEM, start cells, the potential solve), warms up, times K steps and prints the line.
+`--full` adds what the headline does not need, after the timed region: K1's own duration
+(`raster_mcells_per_s`), the dependent-chain probe, the `stand_in` and `full_chip` legs and the CPU
+baseline with its in-run parity check.  `--dump-outputs DIR` writes what the last timed step computed
+as .npy files (see dump_outputs).
+
 Launch: `python bench.py` (1 GPU) or
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
  --master-port P bench.py --gpus N --steps K --warmup W`.
@@ -98,7 +104,15 @@ def parse():
     ap.add_argument('--ring-table', action='store_true', help='f32 ring table (round 1 stepper) instead of the threshold table')
     ap.add_argument('--dem-noise', type=float, default=1.5,
                     help='sigma of the per-cell DEM noise in metres (SURVEY 8(d) prescribes 1.5 at every resolution)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region, also measure K1 alone, the dependent chain, the stand-in and full_chip '
+                         'legs and the CPU baseline (their options above apply only with --full)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write the outputs of the last timed step to DIR/<name>.npy (float32 / float64)')
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
 
 def host_cpu():
@@ -483,6 +497,36 @@ def attach_traffic(roof, variant_ok):
         pass
 
 
+DUMP_SAMPLE = 1 << 20       # elements kept of an output larger than this: 4 outputs stay under 28 MB
+DUMP_SEED = 20240611
+
+
+def dump_outputs(dirname, k1_out, lengths, hist):
+    """What the last timed step handed its caller, as DIR/<name>.npy: K1's orograph (f32) and usable updraft (f64)
+    rasters, the presence histogram (counts as f64, exact) and the length of every track of this rank (f64).
+    An output of more than DUMP_SAMPLE elements is sampled at DUMP_SAMPLE indices drawn from a fixed seed, the
+    same cells for all three rasters, so that two builds compare element for element."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+
+    def sample(t):
+        t = t.reshape(-1)
+        if t.numel() <= DUMP_SAMPLE:
+            return t
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(t.numel(), DUMP_SAMPLE, replace=False))
+        return t[torch.from_numpy(idx).to(t.device)]
+
+    counts = hist.to(torch.int64)
+    if hist.dtype == torch.int32:       # the kernels' uint32 counts
+        counts &= 0xFFFFFFFF
+    arrays = {'orograph': sample(k1_out[0]).to(torch.float32),
+              'usable_updraft': sample(k1_out[1]).to(torch.float64),
+              'presence_histogram': sample(counts).to(torch.float64),
+              'track_lengths': sample(lengths).to(torch.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + '.npy'), a.cpu().numpy())
+
+
 def main():
     args = parse()
     import torch
@@ -533,7 +577,8 @@ def main():
     dem = torch.from_numpy(dem_h).to(dev)
     starts = torch.from_numpy(starts_h[lo:hi]).to(dev)
     solved = args.potential == 'solve'
-    ramp = torch.from_numpy(ramp_potential(gridsize)).to(dev)
+    # the ramp: the potential of `--potential ramp`, and of the stand-in leg and the chain probe of `--full`
+    ramp = torch.from_numpy(ramp_potential(gridsize)).to(dev) if (args.full or not solved) else None
     ramp_label = ('LABELLED STAND-IN: linear ramp 1000(1-r/(R-1)) (exact solution for '
                   'uniform conductance); the reference spsolve is infeasible at 3e7 cells')
     solver = None
@@ -590,8 +635,9 @@ def main():
     # multi-rank run is int64; a single rank's uint32 counts are summed as such)
     hsum = int(hist.sum().item()) if hist.dtype == torch.int64 else int((hist.view(torch.int32).to(torch.int64) & 0xFFFFFFFF).sum().item())
     assert hsum == total_steps_all // K + n_total, 'histogram checksum failed'
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, main_leg.k1_out, last.lengths, hist)
     roof, kernel_s = stepper_roofline(args, acc, K, solved)
-    raster_s = main_leg.k1_kernel_seconds()
     out = {
         'metric': 'simulated tracks/sec (whole node)',
         'value': n_total * K / elapsed,
@@ -633,10 +679,6 @@ def main():
                  'near_ties_settled_at_32_bits': acc['roam_fine_settled'] // K,
                  'what': 'pair-table launches: pairs of moves run by their waves; how many sent a lane through the '
                          'single-move sequence (near-ties, flag entries); near-ties the 32-bit fine table settled'},
-        'raster_mcells_per_s': ncells / raster_s / 1e6 if raster_s > 0 else None,
-        'raster_gbps': ncells * RASTER_BYTES_PER_CELL / raster_s / 1e9 if raster_s > 0 else None,
-        'raster_timing': 'K1 kernel duration: 20 back-to-back launches between two HIP events (phase_ms_per_step.raster_k1 is the '
-                         'one launch inside a pass, host launch latency included)',
         'phase_ms_per_step': {
             'raster_k1': acc['raster_ms'] / K, 'table_k2a': acc['table_ms'] / K,
             'stepper_kernels_k2b': acc['step_kernel_ms'] / K,
@@ -651,6 +693,16 @@ def main():
                        or args.no_binning or args.no_schedule) and args.tracks == 100_000 and res == 10.0
                        and args.steps_per_launch in (0, 512) and args.dem_noise == 1.5)
     attach_traffic(roof, default_variant)
+    if not args.full:
+        print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    raster_s = main_leg.k1_kernel_seconds()
+    out['raster_mcells_per_s'] = ncells / raster_s / 1e6 if raster_s > 0 else None
+    out['raster_gbps'] = ncells * RASTER_BYTES_PER_CELL / raster_s / 1e9 if raster_s > 0 else None
+    out['raster_timing'] = ('K1 kernel duration: 20 back-to-back launches between two HIP events (phase_ms_per_step.raster_k1 '
+                            'is the one launch inside a pass, host launch latency included)')
     if world == 1 and not args.direct and not args.no_chain_probe:
         roof['dependent_chain'] = chain_probe(args, movmodel, layers, dem, ramp, starts_h, gridsize, res, seed)
     if world == 1 and solved and args.stand_in_steps > 0:

@@ -1,6 +1,6 @@
 #!/bin/bash
 # One GPU call, parametrised (replaces the one-shot r03_call*.sh wrappers):
-#   TAG=r04_x TESTS=all|none|"<pytest -k expression>"|"<test files>" SOAK=<seconds> BENCH="<bench.py args>"|none \
+#   TAG=r04_x TESTS=all|none|"<pytest -k expression>"|"<test files>" SOAK=<seconds> BENCH="<bench.py args; --full for the raster and cpu figures>"|none \
 #   EXTRA="<command run last>" bash tools/dev/gpu_call.sh
 # Every step writes under gpurun_out/$TAG/; a failing step ends the call (no GPU step after a failure).
 cd "${GRAFT_REPO_ROOT:-$PWD}" || exit 1

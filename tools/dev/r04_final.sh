@@ -8,8 +8,8 @@ tail -9 "$OUT/tests_full.log"; [ $rc -eq 0 ] || exit 1
 timeout -k 10 400 python tests/dev/soak_tracks.py ${1:-200} > "$OUT/soak_tracks.log" 2>&1; rc=$?; tail -1 "$OUT/soak_tracks.log"; [ $rc -eq 0 ] || exit 1
 python tests/dev/soak_potential.py ${2:-100} 777 > "$OUT/soak_pot_777.txt" 2>&1; rc=$?; tail -1 "$OUT/soak_pot_777.txt"; [ $rc -eq 0 ] || exit 1
 python tests/dev/soak_potential.py ${2:-100} 4242 > "$OUT/soak_pot_4242.txt" 2>&1; rc=$?; tail -1 "$OUT/soak_pot_4242.txt"; [ $rc -eq 0 ] || exit 1
-timeout -k 10 400 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || { tail -5 "$OUT/bench_default.err"; exit 1; }
-timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver_flags.json" 2> "$OUT/bench_driver.err" || { tail -5 "$OUT/bench_driver.err"; exit 1; }
+timeout -k 10 400 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || { tail -5 "$OUT/bench_default.err"; exit 1; }
+timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_driver_flags.json" 2> "$OUT/bench_driver.err" || { tail -5 "$OUT/bench_driver.err"; exit 1; }
 python - "$OUT/bench_driver_flags.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
