@@ -17,29 +17,31 @@ def _newest(paths):
     return max(os.path.getmtime(p) for p in paths)
 
 
+def hipcc():
+    return os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+
+
 def build(force=False, verbose=False):
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     srcs = [os.path.join(HERE, s) for s in SOURCES if os.path.exists(os.path.join(HERE, s))]
-    deps = srcs + [os.path.join(HERE, 'amg.h'), os.path.join(HERE, 'common.h'),
-                   os.path.join(os.path.dirname(PKG), 'include', 'ssrs_hip.h')]
-    if not force and os.path.exists(LIB) and os.path.getmtime(LIB) >= _newest(deps):
+    headers = [os.path.join(HERE, h) for h in ('amg.h', 'common.h', 'track_plan.h', 'track_policy.h')] + \
+              [os.path.join(os.path.dirname(PKG), 'include', 'ssrs_hip.h')]
+    if not force and os.path.exists(LIB) and os.path.getmtime(LIB) >= _newest(srcs + headers):
         return LIB
     objs = []
     procs = []
     for s in srcs:
         o = os.path.splitext(s)[0] + '.o'
         objs.append(o)
-        if not force and os.path.exists(o) and os.path.getmtime(o) >= _newest(
-                [s, deps[-1], deps[-2], deps[-3]]):     # every header: amg.h, common.h, ssrs_hip.h
+        if not force and os.path.exists(o) and os.path.getmtime(o) >= _newest([s] + headers):     # every header
             continue
-        cmd = [hipcc] + FLAGS + ['-c', s, '-o', o]
+        cmd = [hipcc()] + FLAGS + ['-c', s, '-o', o]
         if verbose:
             print(' '.join(cmd))
         procs.append((s, subprocess.Popen(cmd)))
     for s, p in procs:
         if p.wait() != 0:
             raise RuntimeError(f'hipcc failed on {s}')
-    cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', LIB] + objs + ['-ldl']
+    cmd = [hipcc(), '--offload-arch=gfx950', '-shared', '-fPIC', '-o', LIB] + objs + ['-ldl']
     if verbose:
         print(' '.join(cmd))
     subprocess.check_call(cmd)
@@ -49,32 +51,30 @@ def build(force=False, verbose=False):
 def build_probe(defines, tag):
     """Timing-probe variant of the library (tools/attic/probe_chain.py): tracks.hip recompiled with
     -D<defines>, linked with the product's other objects into libssrs_probe_<tag>.so."""
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     build()
     out = os.path.join(PKG, f'libssrs_probe_{tag}.so')
     obj = os.path.join(HERE, f'tracks_probe_{tag}.o')
-    subprocess.check_call([hipcc] + FLAGS + [f'-D{d}' for d in defines] +
+    subprocess.check_call([hipcc()] + FLAGS + [f'-D{d}' for d in defines] +
                           ['-c', os.path.join(HERE, 'tracks.hip'), '-o', obj])
     objs = [os.path.join(HERE, os.path.splitext(s)[0] + '.o') for s in SOURCES if s != 'tracks.hip'] + [obj]
-    subprocess.check_call([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', out] + objs)
+    subprocess.check_call([hipcc(), '--offload-arch=gfx950', '-shared', '-fPIC', '-o', out] + objs)
     return out
 
 
 def build_variant(defines, tag, sources=('amg.hip', 'potential.hip'), travel=False):
     """A/B variant of the product library: `sources` recompiled with -D<defines>, linked with the product's other
     objects into libssrs_probe_<tag>.so (SSRS_HIP_LIB selects it)."""
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     build()
     out = os.path.join(PKG, f'libssrs_{"ab" if travel else "probe"}_{tag}.so')      # (probe libraries do not travel to the GPU box)
     objs = []
     for s in SOURCES:
         if s in sources:
             o = os.path.join(HERE, os.path.splitext(s)[0] + f'_probe_{tag}.o')
-            subprocess.check_call([hipcc] + FLAGS + [f'-D{d}' for d in defines] + ['-c', os.path.join(HERE, s), '-o', o])
+            subprocess.check_call([hipcc()] + FLAGS + [f'-D{d}' for d in defines] + ['-c', os.path.join(HERE, s), '-o', o])
         else:
             o = os.path.join(HERE, os.path.splitext(s)[0] + '.o')
         objs.append(o)
-    subprocess.check_call([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', out] + objs + ['-ldl'])
+    subprocess.check_call([hipcc(), '--offload-arch=gfx950', '-shared', '-fPIC', '-o', out] + objs + ['-ldl'])
     return out
 
 

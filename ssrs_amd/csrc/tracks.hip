@@ -46,6 +46,8 @@
 #include <vector>
 
 #include "common.h"
+#include "track_plan.h"
+#include "track_policy.h"
 
 namespace ssrs {
 
@@ -658,12 +660,8 @@ struct alignas(16) TrackState {
                      // (memory == 0); bits 9-31: release step (coherent schedule)
 };
 
-// Live tracks are kept in kXcd separate lists, one per XCD: blocks are dealt to
-// the XCDs round-robin (block b runs on XCD b % 8), so block b serves list b % 8
-// and a track stays on the XCD it was dealt to.  With the coherent schedule the
-// lists are contiguous bands of the across-track coordinate: the table rows a
-// band walks over are fetched into ONE XCD's L2 instead of all eight.
-constexpr int kXcd = 8;
+// live tracks of list x: one list per XCD (kXcd, track_plan.h)
+static_assert(kPlanBlock == kBlock, "track_plan.h counts in stepper blocks");
 struct alignas(16) TrackCtl {
     uint32_t count[4][kXcd];     // live tracks of list x entering launch i at count[i & 3][x]
     uint32_t error;              // != 0: some start cell was outside the raster
@@ -678,23 +676,13 @@ struct alignas(16) TrackCtl {
     unsigned long long dbg_tsum, dbg_tmax, dbg_waves, dbg_slowmax;   // SSRS_TRACKS_DEBUG_ROAM: wave lifetimes of one launch
     uint32_t roam_stop;                                              // k_step_roam: launch + 1 of the launch whose first wave is through its steps
     uint32_t deal_live;                                              // k_wander_windows: live tracks it found (the host picks the deal's block width from it)
-    unsigned long long dbg_waits;                                    // same: polls of stepping waves that waited for a staged row
-    unsigned long long dbg_span, dbg_span_max;                       // same: virtual-row span of the blocks of a front (sum << 20 | blocks; max)
 };
 
 static_assert(sizeof(TrackCtl) <= 128 * sizeof(uint32_t), "final read-back slot of pinned_counts()");
 
-// block histogram windows of wandering batches (k_step_thr<6>, k_wander_windows)
-// 144 rows: 144 KB of LDS, one block per CU (rounds 2-3); 72 rows: 72 KB, two blocks per CU (-DSSRS_WIN_ROWS=72, A/B)
-#ifndef SSRS_WIN_ROWS
-#define SSRS_WIN_ROWS 144
-#endif
-constexpr int kWinRows = SSRS_WIN_ROWS, kWinCols = 256;
-static_assert(kWinRows == 144 || kWinRows == 72, "a window is 4 or 2 rows of coarse bins");
-constexpr int kWanderWindows = 16;
+// block histogram windows of wandering batches (k_step_thr<6>, k_wander_windows): kWinRows x kWinCols, kWanderWindows
+// of them (track_plan.h)
 constexpr uint32_t kWanderMix = 256;                 // low bits of a sort key: a per-sort hash of the track (k_wander_keys)
-constexpr uint32_t kDealBlocks = kWinRows == 144 ? 232 : 464;   // blocks the contiguous deal spreads the live tracks over (+ one per
-                                                   // window in use and the padding: under the 256 CUs x blocks per CU)
 constexpr int kBinRows = 36, kBinCols = kWinCols / 4;
 constexpr int kWinBinRows = kWinRows / kBinRows;
 constexpr int kWanderBins = 16384;           // 64 KB of LDS
@@ -810,9 +798,7 @@ struct StepArgs {
     const WanderWindows *wander; // k_step_thr<6>: the windows of the last wander sort (n = 0: none yet)
     const RoamEntry *roam;       // k_step_roam: the pair table (8 entries per cell of the raster), or NULL
     const void *fine;            // k_step_roam: 32-bit boundaries per (cell, last move) for near-ties, or NULL
-    int ordered;                 // k_step_tracks: block-ordered list reservation (see there)
     int roam_stop;               // k_step_roam: a launch ends when its FIRST wave is through its steps (A/B: SSRS_TRACKS_NO_ROAM_STOP)
-    int lr_wait;                 // k_step_thr<.., LR>: waves ahead of the ring wait for their row (SSRS_TRACKS_LDS_ROWS=2)
     int cheap_exact;             // k_step_thr: near-ties through exact_three first (A/B: SSRS_TRACKS_NO_CHEAP_EXACT)
     unsigned long long *dbg_buf; // diagnostic builds (SSRS_DEBUG_WAVE_DUMP): one record per wave
     int debug_roam;              // k_step_roam: wave lifetimes into the control block (SSRS_TRACKS_DEBUG_ROAM)
@@ -872,13 +858,6 @@ __global__ __launch_bounds__(kBlock) void k_tracks_init(
 template <int MODE>
 __global__ __launch_bounds__(kBlock) void k_step_tracks(const StepArgs a)
 {
-    // a.ordered: one list reservation per block with its waves in order (the first-move launch of a front whose
-    // later launches stage table rows in LDS: a block's tracks must stay neighbours)
-    __shared__ uint32_t s_cnt[kBlock / 64 + 1];
-    if (a.ordered) {
-        if (threadIdx.x <= kBlock / 64) s_cnt[threadIdx.x] = 0u;
-        __syncthreads();
-    }
     TrackCtl *ctl = a.ctl;
     const int in_slot = a.launch & 3, out_slot = (a.launch + 1) & 3;
     const uint32_t xcd = blockIdx.x % kXcd;
@@ -1067,22 +1046,8 @@ __global__ __launch_bounds__(kBlock) void k_step_tracks(const StepArgs a)
     const int lane = lane_id;
     const int nsurv = __popcll(live);
     uint32_t base = 0;
-    if (a.ordered) {
-        const int wv = threadIdx.x >> 6;
-        if (lane == 0) s_cnt[wv] = static_cast<uint32_t>(nsurv);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t tot = 0;
-            for (int q = 0; q < kBlock / 64; ++q) tot += s_cnt[q];
-            s_cnt[kBlock / 64] = tot ? atomicAdd(&ctl->count[out_slot][xcd], tot) : 0u;
-        }
-        __syncthreads();
-        base = s_cnt[kBlock / 64];
-        for (int q = 0; q < wv; ++q) base += s_cnt[q];
-    } else {
-        if (lane == 0 && nsurv) base = atomicAdd(&ctl->count[out_slot][xcd], static_cast<uint32_t>(nsurv));
-        base = __shfl(base, 0);
-    }
+    if (lane == 0 && nsurv) base = atomicAdd(&ctl->count[out_slot][xcd], static_cast<uint32_t>(nsurv));
+    base = __shfl(base, 0);
     if (active) {
         const int rank = __popcll(live & ((1ull << lane) - 1ull));
         a.list_out[xcd * a.cap + base + rank] = t;
@@ -1137,7 +1102,6 @@ __global__ void k_ctl_init(TrackCtl *ctl, const PriorArg pr, double *__restrict_
         }
         ctl->error = bad; ctl->par_min = 0xFFFFFFFFu; ctl->steps = 0; ctl->strays = 0; ctl->bin_done = 0; ctl->pad = 0; ctl->roam_slow = 0; ctl->roam_pairs = 0;
         ctl->dbg_tsum = ctl->dbg_tmax = ctl->dbg_waves = ctl->dbg_slowmax = 0;
-        ctl->dbg_span = ctl->dbg_span_max = ctl->dbg_waits = 0;
         ctl->roam_stop = ctl->deal_live = 0;
     }
     if (d < 9) ctl->prior[d] = pr.v[d];
@@ -1669,7 +1633,6 @@ struct PfArgs {              // by value: taking the kernel arguments' address w
     long long it_base;
     uint32_t cap;
     int coherent, steps, pf_dir, pf_rc, rows, cols, plane_shift;
-    int debug;
 };
 __device__ __forceinline__ void thr_prefetch_wave(const PfArgs a, uint32_t xcd, uint32_t nlive, const volatile int *s_it)
 {
@@ -1741,190 +1704,17 @@ __device__ __forceinline__ void thr_prefetch_wave(const PfArgs a, uint32_t xcd, 
     if (acc == 0x9E3779B9u && a.steps < 0) a.ctl->pad = 1;      // keeps the loads alive
 }
 
-// LR (round 3): the fifth wave of a front's block STAGES the table rows in LDS instead of pulling them through L2.
-// A north / south front advances a row per iteration, its block's 256 tracks span a few hundred columns, and
-// only the three planes around the heading are read: 16 rows x 3 planes x 384 columns of entries are 72 KB (two
-// blocks per CU).  The staging wave fills a ring of row slots ahead of the slowest stepping wave (each wave
-// publishes its iteration), a slot carries the row it holds as a tag, and a stepping lane reads
-// tag, entry, tag (three LDS reads, ~100 clocks, against 300-600 for the gather through L2): equal tags on both
-// sides of the entry mean the slot was not being rewritten (a wave's LDS operations execute in order, and the
-// staging wave invalidates the tag before it rewrites a slot and sets it after).  Anything else -- another plane,
-// a column outside the window, a row not staged yet or already gone -- is the global gather of before.
-constexpr int kLrRows = 16, kLrCols = 256;          // 48 KB: one dwordx4 wave-load + one ds_write_b128 per row and plane
-// LDS accesses of the ring by address space: a `volatile` generic pointer compiles to flat_load ... sc0 sc1 with a
-// wait after each (measured: the staged variant 2.5x SLOWER than the gather it replaces); these are ds_read / ds_write
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-__device__ __forceinline__ uint32_t lds_addr(const void *p)
-{
-    return static_cast<uint32_t>(reinterpret_cast<uintptr_t>((const lds_u32 *)p));
-}
-__device__ __forceinline__ uint32_t lds_ld(const void *p)
-{
-    return __hip_atomic_load((const lds_u32 *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void lds_st(void *p, uint32_t v)
-{
-    __hip_atomic_store((lds_u32 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-struct LrShared {
-    int c0, vr_lo, vr_hi, on;          // window origin (even), the block's virtual rows at iteration 0, any live track
-    int tag[kLrRows];                  // row held by each slot, -1: none / being rewritten
-    int itw[kBlock / 64];              // iteration each stepping wave has reached (0x3fffffff: left)
-};
-
-__device__ __forceinline__ void thr_stage_geometry(const PfArgs a, uint32_t xcd, uint32_t nlive, LrShared *g)
-{
-    const int lane = threadIdx.x & 63;
-    const uint32_t base = (blockIdx.x / kXcd) * kBlock;
-    int vr_lo = 0x7fffffff, vr_hi = -0x7fffffff, c_lo = 0x7fffffff, c_hi = -0x7fffffff;
-    for (int q = 0; q < kBlock / 64; ++q) {
-        const uint32_t il = base + q * 64 + lane;
-        if (il >= nlive) continue;
-        const uint32_t i = xcd * a.cap + il;
-        const int32_t t = a.list_in ? a.list_in[i] : static_cast<int32_t>(i);
-        const TrackState s = a.state[t];
-        if (s.k < 0) continue;
-        const int row = s.pos & 0xFFFF, col = (s.pos >> 16) & 0xFFFF;
-        const long long rel64 = (a.coherent ? static_cast<long long>(s.aux >> 9) : 0) + 1 - a.it_base;
-        const int rel = rel64 > a.steps ? a.steps : (rel64 < 0 ? 0 : static_cast<int>(rel64));
-        const int vr = row - a.pf_dir * rel;              // row at iteration `it` (once released): vr + pf_dir * it
-        vr_lo = vr < vr_lo ? vr : vr_lo;  vr_hi = vr > vr_hi ? vr : vr_hi;
-        c_lo = col < c_lo ? col : c_lo;   c_hi = col > c_hi ? col : c_hi;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        int o = __shfl_xor(vr_lo, off); vr_lo = o < vr_lo ? o : vr_lo;
-        o = __shfl_xor(vr_hi, off); vr_hi = o > vr_hi ? o : vr_hi;
-        o = __shfl_xor(c_lo, off); c_lo = o < c_lo ? o : c_lo;
-        o = __shfl_xor(c_hi, off); c_hi = o > c_hi ? o : c_hi;
-    }
-    if (lane < kLrRows) lds_st(&g->tag[lane], 0xFFFFFFFFu);
-    if (lane < kBlock / 64) lds_st(&g->itw[lane], (base + lane * 64 >= nlive) ? 0x3fffffffu : 0xFFFFFFFFu);     // (waves past the list leave at once)
-    if (lane == 0) {
-        const bool on = vr_lo <= vr_hi;
-        if (a.debug && on) {
-            atomicAdd(&a.ctl->dbg_span, (static_cast<unsigned long long>(vr_hi - vr_lo) << 20) | 1ull);
-            atomicMax(&a.ctl->dbg_span_max, static_cast<unsigned long long>(vr_hi - vr_lo));
-        }
-        if (vr_hi - vr_lo > kLrRows / 2) { if (a.pf_dir > 0) vr_hi = vr_lo + kLrRows / 2; else vr_lo = vr_hi - kLrRows / 2; }   // stragglers fall back
-        int c0 = (c_lo + c_hi + 1 - kLrCols) / 2;                           // window centred on the block's columns
-        const int cmax = a.cols - kLrCols;                                  // (>= 0: host)
-        c0 = c0 < 0 ? 0 : (c0 > cmax ? cmax : c0);
-        lds_st(&g->c0, static_cast<uint32_t>(c0));
-        lds_st(&g->vr_lo, static_cast<uint32_t>(vr_lo));
-        lds_st(&g->vr_hi, static_cast<uint32_t>(vr_hi));
-        lds_st(&g->on, on ? 1u : 0u);
-    }
-}
-
-__device__ __forceinline__ void thr_stage_wave(const PfArgs a, LrShared *g, uint32_t *ring)
-{
-    const int lane = threadIdx.x & 63;
-    if (!lds_ld(&g->on)) return;
-    __builtin_amdgcn_s_setprio(3);                       // ahead of the stepping waves that share its SIMD
-    const int dir = a.pf_dir, c0 = static_cast<int>(lds_ld(&g->c0)), vr_lo = static_cast<int>(lds_ld(&g->vr_lo)),
-              vr_hi = static_cast<int>(lds_ld(&g->vr_hi));
-    const int first = dir > 0 ? vr_lo : vr_hi;           // the row the front needs at iteration 0
-    const char *tab = reinterpret_cast<const char *>(a.table);
-    typedef __attribute__((address_space(1))) const void gmem_t;
-    typedef __attribute__((address_space(3))) void lmem_t;
-    // rows go from global memory straight into the ring (global_load_lds_dwordx4: 64 lanes x 16 bytes = one row of
-    // one plane per instruction, no registers in between), kBatch rows = 6 loads at a time and TWO batches in
-    // flight: a batch's tags are published when the NEXT batch has been issued and `s_waitcnt vmcnt(6)` says the
-    // older six have landed.  Every other LDS access of this loop is inline asm: the compiler orders what it
-    // sees of LDS against outstanding LDS-DMA with vmcnt(0), which would take the second batch out of flight.
-    constexpr int kBatch = 2;
-    static_assert(kLrCols == 256 && kLrRows % kBatch == 0, "64 lanes x 4 entries; a batch never wraps inside itself");
-    int next = first, pend = 0, pend_row = 0;
-    uint32_t n_blocked = 0, n_batches = 0;
-    const unsigned long long t_begin = __builtin_amdgcn_s_memtime();
-    const uint32_t itw_addr = lds_addr(&g->itw[0]), tag_addr = lds_addr(&g->tag[0]);
-    auto publish = [&](int row0) {
-        // lanes 0..kBatch-1: tag[slot of row0 + lane] = that row (rows outside the raster keep their -1)
-        const int row = row0 + dir * lane;
-        if (lane < kBatch && row >= 0 && row < a.rows)
-            asm volatile("ds_write_b32 %0, %1" : : "v"(tag_addr + 4u * static_cast<uint32_t>(row & (kLrRows - 1))), "v"(row) : "memory");
-    };
-    for (int spin = 0; spin < (1 << 20); ++spin) {       // (bounded: the stepping waves always leave)
-        int w0, w1, w2, w3;
-        static_assert(kBlock / 64 == 4, "four stepping waves");
-        asm volatile("ds_read_b32 %0, %4\n\tds_read_b32 %1, %4 offset:4\n\tds_read_b32 %2, %4 offset:8\n\t"
-                     "ds_read_b32 %3, %4 offset:12\n\ts_waitcnt lgkmcnt(0)"
-                     : "=&v"(w0), "=&v"(w1), "=&v"(w2), "=&v"(w3) : "v"(itw_addr) : "memory");
-        int itmin = w0 < w1 ? w0 : w1;
-        itmin = w2 < itmin ? w2 : itmin;
-        itmin = w3 < itmin ? w3 : itmin;
-        itmin = __builtin_amdgcn_readfirstlane(itmin);
-        if (itmin >= 0x3fffffff) break;                   // every stepping wave has left
-        itmin = itmin < 0 ? 0 : itmin;
-        // the slot of row `next` still holds row next -/+ kLrRows, which the slowest wave may need until it has
-        // passed it; and nothing beyond the rows this launch can reach
-        const int ahead = dir * (next - first);           // rows ahead of iteration 0's front
-        if (ahead + kBatch - 1 > itmin + kLrRows - 1 || ahead > a.steps + (vr_hi - vr_lo)) {
-            if (pend) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                publish(pend_row);
-                pend = 0;
-            } else {
-                ++n_blocked;
-                __builtin_amdgcn_s_sleep(1);
-            }
-            continue;
-        }
-        ++n_batches;
-        {   // the batch's slots are in flight from here on
-            const int row = next + dir * lane;
-            if (lane < kBatch)
-                asm volatile("ds_write_b32 %0, %1" : : "v"(tag_addr + 4u * static_cast<uint32_t>(row & (kLrRows - 1))), "v"(-1) : "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
-#pragma unroll
-        for (int q = 0; q < kBatch; ++q) {
-            const int row = next + dir * q, slot = row & (kLrRows - 1);
-            const int rr = row < 0 ? 0 : (row >= a.rows ? a.rows - 1 : row);      // (never published when clamped)
-            const uint32_t cellb = (static_cast<uint32_t>(rr) * static_cast<uint32_t>(a.cols) + static_cast<uint32_t>(c0)) * 4u;
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-                const uint32_t plane = static_cast<uint32_t>((a.pf_rc + 7 + p) & 7) << a.plane_shift;
-                // (4-byte aligned in global memory: row x cols + c0 is any integer)
-                __builtin_amdgcn_global_load_lds((gmem_t *)(tab + (plane + cellb + static_cast<uint32_t>(lane) * 16u)),
-                                                 (lmem_t *)&ring[(slot * 3 + p) * kLrCols], 16, 0, 0);
-            }
-        }
-        if (pend) {
-            asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            static_assert(kBatch * 3 == 6, "the count above");
-            publish(pend_row);
-        }
-        pend = 1;
-        pend_row = next;
-        next += dir * kBatch;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (nothing of this wave is in flight into LDS when it leaves)
-    if (a.debug && lane == 0) {
-        // diagnostics: batches staged, polls that found the ring full, rows staged, the wave's lifetime in clocks
-        atomicAdd(&a.ctl->roam_pairs, (static_cast<unsigned long long>(n_batches) << 32) | n_blocked);
-        atomicAdd(&a.ctl->roam_slow, ((static_cast<unsigned long long>(dir * (next - first)) & 0xFFFFFFFFull) << 32) |
-                                         ((__builtin_amdgcn_s_memtime() - t_begin) >> 8));
-    }
-}
-
 // REV: reversal rows decided in the fast path (ThrPrior::rev_*).  In the basins of a solved field a
 // track falls to the bottom of a pit (a move south, say), finds every way on uphill and the masked
 // prior empty, takes the unmasked prior's move north and falls back: every other step is a reversal,
 // and as a flag entry each one sent its whole wave through the slow path (1030 issue clocks per
 // wave-step against 490 on the ramp).  Three more instructions on the chain: variants without the
 // prefetch wave only.
-template <int HM, bool PF = false, bool REV = false, bool LR = false>
+template <int HM, bool PF = false, bool REV = false>
 __global__ __launch_bounds__(PF ? kBlock + 64 : kBlock) void k_step_thr(const StepArgs a, const ThrPrior pr)
 {
     static_assert(!(HM == 6 && PF), "the block window is for batches without a front");
-    static_assert(!LR || (PF && !REV), "staged rows: fronts with a fifth wave");
     __shared__ uint32_t s_win[HM == 6 ? kWinRows * kWinCols : 1];
-    __shared__ __attribute__((aligned(16))) uint32_t s_ring[LR ? kLrRows * 3 * kLrCols : 1];
-    __shared__ LrShared s_lr;
-    __shared__ uint32_t s_cnt[kBlock / 64 + 1];            // LR: survivors per wave (block-ordered list reservation)
-    if (LR && threadIdx.x <= kBlock / 64) s_cnt[threadIdx.x] = 0u;
     __shared__ int s_box[4];
     if (HM == 6) {
         for (int q = threadIdx.x; q < kWinRows * kWinCols; q += kBlock) s_win[q] = 0u;
@@ -1962,13 +1752,11 @@ __global__ __launch_bounds__(PF ? kBlock + 64 : kBlock) void k_step_thr(const St
     if (!PF) __syncthreads();
     if (PF) {
         const PfArgs pa = {a.list_in, a.state, reinterpret_cast<const char *>(a.table) + a.guard, a.ctl, a.it_base, a.cap, a.coherent, a.steps,
-                           a.pf_dir, a.pf_rc, a.rows, a.cols, a.plane_shift, a.debug_roam};
+                           a.pf_dir, a.pf_rc, a.rows, a.cols, a.plane_shift};
         if (threadIdx.x == 0) s_it = -1;
-        if (LR && threadIdx.x >= kBlock) thr_stage_geometry(pa, xcd, nlive, &s_lr);
         __syncthreads();
         if (threadIdx.x >= kBlock) {
-            if (LR) thr_stage_wave(pa, &s_lr, s_ring);
-            else thr_prefetch_wave(pa, xcd, nlive, &s_it);
+            thr_prefetch_wave(pa, xcd, nlive, &s_it);
             return;
         }
     }
@@ -2085,23 +1873,12 @@ __global__ __launch_bounds__(PF ? kBlock + 64 : kBlock) void k_step_thr(const St
         hbase = a.hist_copies + static_cast<size_t>((i >> 6) % static_cast<uint32_t>(a.ncopies)) * static_cast<size_t>(ncell);
     int it = 0;
     const bool cheap_exact = a.cheap_exact != 0;
-    // LR: row and window column of the cell (the staged rows are addressed by them), the staging wave's window
-    const int lr_c0 = LR ? static_cast<int>(lds_ld(&s_lr.c0)) : 0;
-    const uint32_t lr_h0 = static_cast<uint32_t>(a.pf_rc + 7) & 7u;              // first of the three staged planes
-    int lrow = s.pos & 0xFFFF, lcol = ((s.pos >> 16) & 0xFFFF) - lr_c0;
-    const uint32_t lr_tag0 = lds_addr(s_lr.tag), lr_ring0 = lds_addr(s_ring);   // LDS byte addresses
-    uint32_t lr_miss = 0;                                                       // wave-steps that fell back to the gather
-    uint32_t lr_why[4] = {0u, 0u, 0u, 0u};
-    uint32_t lr_waits = 0;                                                      // polls of a wave that waited for its row
     auto report = [&](int v) __attribute__((always_inline)) {                   // progress of this wave, for the fifth one
-        if ((threadIdx.x & 63) == 0) {
-            if (LR) lds_st(&s_lr.itw[(threadIdx.x >> 6) & (kBlock / 64 - 1)], static_cast<uint32_t>(v));
-            else atomicMax(&s_it, v);
-        }
+        if ((threadIdx.x & 63) == 0) atomicMax(&s_it, v);
     };
 
     auto one_step = [&](const bool even, const bool burn, const bool publish) __attribute__((always_inline)) {
-        if (PF && publish && even && (LR || (it & 7) == 0)) report(it);
+        if (PF && publish && even && (it & 7) == 0) report(it);
         // st: all ones when this lane steps now
         const uint32_t stm = (static_cast<uint32_t>(it - rel) < span) ? 0xFFFFFFFFu : 0u;
         uint32_t w0, w1;
@@ -2135,58 +1912,10 @@ __global__ __launch_bounds__(PF ? kBlock + 64 : kBlock) void k_step_thr(const St
             dl = s1 ? la : dl;  pl = s1 ? pa : pl;
             dl = stm ? dl : 0u; pl = stm ? pl : pcur;
             cell_n = cell + dl;
-            // which one it was (off the chain; LR: on it)
+            // which one it was (off the chain)
             const uint32_t fld = (lpk >> (s1 ? 0u : (s2 ? 8u : 16u))) & 0xFFu;
             nc = fld & 7u; dr = (fld >> 3) & 3u; dc = (fld >> 5) & 3u;
-            if (!LR) {
-                e_n = *reinterpret_cast<const uint32_t *>(tab + (pl + (cell_n << 2)));
-            } else {
-                // the entry of the cell the move leads to, from the staged rows: tag, entry, tag (in this order)
-                const int row_n = lrow + static_cast<int>((dr - 1u) & stm), col_n = lcol + static_cast<int>((dc - 1u) & stm);
-                const uint32_t pidx = ((stm ? nc : rc) - lr_h0) & 7u;
-                const uint32_t slot = static_cast<uint32_t>(row_n) & (kLrRows - 1);
-                const bool ok = (pidx < 3u) & (static_cast<uint32_t>(col_n) < static_cast<uint32_t>(kLrCols));
-                const uint32_t idx = ok ? (slot * 3u + pidx) * kLrCols + static_cast<uint32_t>(col_n) : 0u;
-                uint32_t t1, el, t2;
-                {
-                    const uint32_t ta = lr_tag0 + (slot << 2), ea = lr_ring0 + (idx << 2);
-                    asm volatile("ds_read_b32 %0, %3\n\tds_read_b32 %1, %4\n\tds_read_b32 %2, %3\n\ts_waitcnt lgkmcnt(0)"
-                                 : "=&v"(t1), "=&v"(el), "=&v"(t2) : "v"(ta), "v"(ea) : "memory");
-                }
-                bool need = (stm != 0u) & !(ok & (static_cast<int>(t1) == row_n) & (static_cast<int>(t2) == row_n));
-                e_n = stm ? el : e;                                    // (a lane that does not step keeps its entry)
-                if (__builtin_expect(__any(need), 0)) {
-                    // A row that is not there YET (slot empty or still holding the row of a ring turn before): this
-                    // wave is ahead of the block's slowest one by most of the ring.  It waits for the staging wave
-                    // instead of overtaking it with gathers -- the block ends with its slowest wave either way, and
-                    // waves that run apart find nothing staged from then on (measured: the waves of a block
-                    // diffuse apart through their exact decisions until the leaders ride the ring's edge, 68 % of
-                    // the wave-steps fell back).  Bounded: the slowest wave never waits, so the staging wave
-                    // always gets here; a row this launch never stages is gathered after the last poll.
-                    const int dirw = a.pf_dir;
-                    bool wait = need & ok & ((static_cast<int>(t1) < 0) | (dirw * (static_cast<int>(t1) - row_n) < 0));
-                    for (int sp = 0; a.lr_wait && sp < 256 && __any(wait); ++sp) {
-                        __builtin_amdgcn_s_sleep(2);
-                        const uint32_t ta = lr_tag0 + (slot << 2), ea = lr_ring0 + (idx << 2);
-                        asm volatile("ds_read_b32 %0, %3\n\tds_read_b32 %1, %4\n\tds_read_b32 %2, %3\n\ts_waitcnt lgkmcnt(0)"
-                                     : "=&v"(t1), "=&v"(el), "=&v"(t2) : "v"(ta), "v"(ea) : "memory");
-                        const bool hit = (static_cast<int>(t1) == row_n) & (static_cast<int>(t2) == row_n);
-                        if (wait & hit) { e_n = el; need = false; }
-                        wait = wait & !hit & ((static_cast<int>(t1) < 0) | (dirw * (static_cast<int>(t1) - row_n) < 0));
-                        if (a.debug_roam) ++lr_waits;
-                    }
-                }
-                if (__builtin_expect(__any(need), 0)) {
-                    if (need) e_n = *reinterpret_cast<const uint32_t *>(tab + (pl + (cell_n << 2)));
-                    ++lr_miss;
-                    if (a.debug_roam) {       // which kind (lane-steps): window / plane, slot empty, slot holds an older row, a newer one
-                        lr_why[0] += (need && !ok) ? 1u : 0u;
-                        lr_why[1] += (need && ok && static_cast<int>(t1) < 0) ? 1u : 0u;
-                        lr_why[2] += (need && ok && static_cast<int>(t1) >= 0 && static_cast<int>(t1) < row_n) ? 1u : 0u;
-                        lr_why[3] += (need && pidx >= 3u) ? 1u : 0u;          // (of the first kind: the plane)
-                    }
-                }
-            }
+            e_n = *reinterpret_cast<const uint32_t *>(tab + (pl + (cell_n << 2)));
         } else {
             // a reversal row is an ordinary row of the move along the heading with the prior's thresholds
             const bool rev = e == kThrReversal;
@@ -2205,7 +1934,6 @@ __global__ __launch_bounds__(PF ? kBlock + 64 : kBlock) void k_step_thr(const St
         }
         special = special & (stm != 0u);
         uint32_t base = cell, base_col = colv;
-        int base_row = 0;
         const uint32_t cell_before = cell;
         uint32_t go = stm;
         if (__builtin_expect(__any(special), 0)) {
@@ -2255,7 +1983,6 @@ __global__ __launch_bounds__(PF ? kBlock + 64 : kBlock) void k_step_thr(const St
                     nc = static_cast<uint32_t>(kRingOfK >> (4 * idx)) & 0xFu;
                     base = __umul24(static_cast<uint32_t>(er), ucols) + static_cast<uint32_t>(ec);
                     base_col = static_cast<uint32_t>(ec);
-                    base_row = er;
                     if (HM == 6) { wr += er - static_cast<int>(r); wc += ec - static_cast<int>(c); }      // the nudge
                 }
             }
@@ -2290,13 +2017,6 @@ __global__ __launch_bounds__(PF ? kBlock + 64 : kBlock) void k_step_thr(const St
             // column of the new cell (the exact path may have moved the base: recompute there)
             const uint32_t moved_col = base == cell_before ? colv + dc - 1u : base_col + dc - 1u;
             colv = (moved_col & go) | (colv & ~go);
-        }
-        if (LR) {
-            // (base_col is only meaningful where the exact path set it: base != cell_before)
-            const int nr = (base == cell_before ? lrow : base_row) + static_cast<int>(dr) - 1;
-            const int ncl = (base == cell_before ? lcol : static_cast<int>(base_col) - lr_c0) + static_cast<int>(dc) - 1;
-            lrow = go ? nr : lrow;
-            lcol = go ? ncl : lcol;
         }
         e = e_n;
         if (!arith) {
@@ -2351,7 +2071,6 @@ __global__ __launch_bounds__(PF ? kBlock + 64 : kBlock) void k_step_thr(const St
         if (PF) report(it);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            if (LR && u == 2) report(it);                  // (the staging wave looks at the slowest wave: every four iterations)
             one_step(true, false, false);
             one_step(false, false, false);
         }
@@ -2372,16 +2091,6 @@ __global__ __launch_bounds__(PF ? kBlock + 64 : kBlock) void k_step_thr(const St
             vrow16 += a.visit_stride;
         }
     if (PF) report(0x3fffffff);                                        // nothing left to wait for
-    if (LR && a.debug_roam) {
-        if ((threadIdx.x & 63) == 0) {
-            atomicAdd(&ctl->dbg_tsum, static_cast<unsigned long long>(lr_miss));
-            atomicAdd(&ctl->dbg_waves, static_cast<unsigned long long>(it));
-            atomicAdd(&ctl->dbg_waits, static_cast<unsigned long long>(lr_waits));
-        }
-        // (lane-steps by kind, packed: 16 bits of millions would overflow: two 64-bit words, 32 bits each)
-        atomicAdd(&ctl->dbg_tmax, (static_cast<unsigned long long>(lr_why[0]) << 32) | lr_why[1]);
-        atomicAdd(&ctl->dbg_slowmax, (static_cast<unsigned long long>(lr_why[2]) << 32) | lr_why[3]);
-    }
     if (HM == 6) {
         __syncthreads();
         for (int q = threadIdx.x; q < kWinRows * kWinCols; q += kBlock) {
@@ -2436,23 +2145,6 @@ __global__ __launch_bounds__(PF ? kBlock + 64 : kBlock) void k_step_thr(const St
                 a.state[t] = o;
             }
         }
-    } else if (LR) {
-        // one reservation per block, its waves in order: the block's tracks stay neighbours in the next list
-        // (per-wave reservations land in arrival order and scatter a block over its XCD's band of columns --
-        // harmless for gathers through L2, fatal for a 256-column window in LDS: a third of the lane-steps fell
-        // outside it).  The waves past the list and the staging wave have left; a barrier counts the waves
-        // that are still there.
-        const int wv = threadIdx.x >> 6;
-        if (lane == 0) s_cnt[wv] = static_cast<uint32_t>(nsurv);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t tot = 0;
-            for (int q = 0; q < kBlock / 64; ++q) tot += s_cnt[q];
-            s_cnt[kBlock / 64] = tot ? atomicAdd(&ctl->count[out_slot][xcd], tot) : 0u;
-        }
-        __syncthreads();
-        basei = s_cnt[kBlock / 64];
-        for (int q = 0; q < wv; ++q) basei += s_cnt[q];
     } else {
         if (lane == 0 && nsurv) basei = atomicAdd(&ctl->count[out_slot][xcd], static_cast<uint32_t>(nsurv));
         basei = __shfl(basei, 0);
@@ -3723,9 +3415,6 @@ __global__ __launch_bounds__(1024) void k_deal_sorted(const uint32_t *__restrict
     __shared__ uint32_t lo[kWanderWindows + 3], off[kWanderWindows + 3];
     __shared__ uint32_t s_fill;
     const uint32_t slots = cap * kXcd;
-    // width 2 / 4 (k_step_roam<REV, 512 / 1024>): a window's run is whole groups of `width` blocks and every list holds whole groups
-    const uint32_t uw = static_cast<uint32_t>(width);
-    const uint32_t kRun = kXcd * kBlock * uw;
     if (threadIdx.x <= kWanderWindows + 2) {
         // first index whose key is >= threadIdx.x
         uint32_t a = 0, b = slots;
@@ -3736,53 +3425,9 @@ __global__ __launch_bounds__(1024) void k_deal_sorted(const uint32_t *__restrict
         lo[threadIdx.x] = a;
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        // contiguous deal: a block keeps `fill` of its kBlock slots (the rest are tombstones), chosen so that the
-        // live tracks make about one block per CU.  A block-window kernel holds 144 KB of LDS, one block per
-        // CU, and a divergent gather costs its CU ~4 clocks per lane: 44k survivors in 180 full blocks leave 76
-        // CUs idle while the others take 1030 clocks per step.
-        const uint32_t live = lo[kWanderWindows + 1];
-        uint32_t fill = kBlock;
-        if (contiguous) {
-            // the blocks must stay under the 256 CUs x blocks per CU (a block beyond the first round of a launch finds the
-            // stop flag up and waits for the others to finish the pass): kDealBlocks + one partial block per window IN USE
-            // (round 4: the allowance of the unused ones goes to the deal, 246 instead of 232 blocks with two basins =
-            // 63 000 instead of 59 392 live tracks in one round) + the padding to whole blocks of every list.
-            // Wide: 216 groups + one per window + the padding
-            uint32_t in_use = 0;
-            for (int k = 0; k <= kWanderWindows; ++k) in_use += lo[k + 1] > lo[k] ? 1u : 0u;
-            const uint32_t deal_blocks = uw > 1u ? uw * 216u : kDealBlocks + (kWanderWindows + 1u - in_use);
-            fill = (live + deal_blocks - 1) / deal_blocks;
-            fill = fill < 64u ? 64u : (fill > kBlock ? kBlock : fill);
-        }
-        uint32_t run = 0;
-        for (int pass = 0; pass < 2; ++pass) {
-            run = 0;
-            for (int k = 0; k <= kWanderWindows; ++k) {              // (key kWanderWindows + 1 = dead: not dealt)
-                off[k] = run;
-                uint32_t blocks = (lo[k + 1] - lo[k] + fill - 1) / fill;
-                blocks = (blocks + uw - 1u) / uw * uw;
-                // round-robin deal: a window's run is whole blocks of EVERY list
-                run += contiguous ? blocks * kBlock : (blocks * kBlock + kRun - 1) / kRun * kRun;
-            }
-            run = (run + kRun - 1) / kRun * kRun;
-            if (run <= slots || fill == kBlock) break;
-            fill = kBlock;                                           // no room for the thinned blocks
-        }
-        off[kWanderWindows + 1] = run;
-        s_fill = fill;
-        if (run > slots) {
-            // no room for the padding (nearly every slot is live): dense deal, blocks may mix windows
-            run = 0;
-            for (int k = 0; k <= kWanderWindows + 1; ++k) { off[k] = run; if (k <= kWanderWindows) run += lo[k + 1] - lo[k]; }
-            off[kWanderWindows + 1] = (run + kRun - 1) / kRun * kRun;   // (<= slots: cap is a multiple of 4 blocks, workspace_layout)
-            off[kWanderWindows + 2] = 1;                             // dense
-        } else {
-            off[kWanderWindows + 2] = 0;
-        }
-    }
+    if (threadIdx.x == 0) s_fill = deal_plan(lo, cap, contiguous != 0, static_cast<uint32_t>(width), off);     // (track_plan.h)
     __syncthreads();
-    const uint32_t total = off[kWanderWindows + 1];                  // a multiple of kRun
+    const uint32_t total = off[kWanderWindows + 1];                  // a multiple of kXcd blocks of `width`
     const bool dense = off[kWanderWindows + 2] != 0;
     const uint32_t fill = s_fill;
     for (uint32_t g = blockIdx.x * 1024u + threadIdx.x; g < total; g += gridDim.x * 1024u) {
@@ -3832,7 +3477,6 @@ struct Workspace {
 };
 
 constexpr int kVisitSteps = 1024;  // binning mode covers launches of up to this many steps
-constexpr int64_t kWanderMinTracks = 8192;   // smaller batches are never sorted into windows
 
 static size_t sort_temp_size(int64_t n)
 {
@@ -3851,9 +3495,8 @@ static size_t sort_temp_size(int64_t n)
 static size_t workspace_layout(int64_t n, char *base, Workspace *ws)
 {
     size_t off = 0;
-    // kXcd lists of cap slots each; cap is a whole number of the widest blocks (k_step_roam<REV, 1024>: the wide deal rounds
-    // every list up to whole groups of blocks, and its dense fall-back must still fit)
-    const size_t cap = align_up((static_cast<size_t>(n) + kXcd - 1) / kXcd, 4 * kBlock);
+    // kXcd lists of cap slots each (list_cap: whole groups of the widest blocks)
+    const size_t cap = list_cap(n);
     const size_t slots = cap * kXcd;
     if (ws) ws->cap = static_cast<uint32_t>(cap);
     if (ws) ws->ctl = reinterpret_cast<TrackCtl *>(base + off);
@@ -4140,17 +3783,88 @@ extern "C" int ssrs_uniform_selftest(uint64_t seed, const uint64_t *track, const
     return SSRS_OK;
 }
 
-static int tracks_simulate_impl(const SsrsTrackParams *p, const double *updraft,
-                                const float *potential, const double *table,
-                                const int32_t *start_rc, int64_t ntracks, uint64_t seed,
-                                uint64_t track_id_base, uint32_t *hist, int16_t *end_rc,
-                                int32_t *lengths, int16_t *traj, const int64_t *traj_offsets,
-                                void *workspace, size_t workspace_bytes,
-                                SsrsTrackStats *stats, void *stream, SsrsTrajRecorder *rec,
-                                unsigned long long *hist64 = nullptr)
+// ------------------------------------------------------------------ the host side of a call
+// tracks_simulate_impl is the skeleton of a run.  TrackRun holds the run's state and does its phases;
+// TrackPolicy (no HIP) judges the batches as they are read back and picks the path of the launches to come.
+
+// The inputs of one call (ssrs_tracks_simulate, _rec, _h64)
+struct TrackCall {
+    const SsrsTrackParams *p;
+    const double *updraft; const float *potential; const double *table;
+    const int32_t *start_rc; int64_t ntracks; uint64_t seed, track_id_base;
+    uint32_t *hist; int16_t *end_rc; int32_t *lengths; int16_t *traj; const int64_t *traj_offsets;
+    void *workspace; size_t workspace_bytes; void *stream;
+    SsrsTrajRecorder *rec;
+    unsigned long long *hist64;  // h64: the 32-bit raster `hist` is drained into it
+};
+
+// The stepper's switches from the environment, read at the start of every call (tests set them between calls).
+// Each forces a path that the tests and soaks compare against the oracle; the results are the same either way.
+struct TrackSwitches {
+    bool debug, debug_roam;      // SSRS_TRACKS_DEBUG (launches, block-window batches), _DEBUG_ROAM (wave lifetimes) on stderr
+    // on unless SSRS_TRACKS_NO_ROAM_STOP, _NO_CHEAP_EXACT, _NO_BLOCK_WINDOW, _NO_FINE_TABLE, _NO_ROAM_TABLE, _NO_REV,
+    // _DEAL_ROUND_ROBIN, _NO_REBALANCE, _FIXED_STEPS is set
+    bool roam_stop, cheap_exact, block_window, fine_table, roam_table, rev, deal_contiguous, rebalance, grow_steps;
+    // wide roaming blocks (k_step_roam<REV, 512>): chosen at a deal when more tracks are alive than one round of 256-lane blocks
+    // holds (SSRS_TRACKS_ROAM_WIDE=<live tracks from which on>, 0: never, 1: always), kept until the next deal
+    long long roam_wide_from;
+    int roam_width;              // SSRS_TRACKS_ROAM_WIDTH=1|2|4: that width at every deal (A/B); 0: chosen
+    int roam_shuffle;            // batches between two shuffles of a settled roaming batch (SSRS_TRACKS_ROAM_SHUFFLE, 0: never)
+};
+
+static TrackSwitches read_track_switches()
 {
+    auto set = [](const char *name) { return std::getenv(name) != nullptr; };
+    TrackSwitches sw;
+    sw.debug = set("SSRS_TRACKS_DEBUG");
+    sw.debug_roam = set("SSRS_TRACKS_DEBUG_ROAM");
+    sw.roam_stop = !set("SSRS_TRACKS_NO_ROAM_STOP");
+    sw.cheap_exact = !set("SSRS_TRACKS_NO_CHEAP_EXACT");
+    sw.block_window = !set("SSRS_TRACKS_NO_BLOCK_WINDOW");
+    sw.fine_table = !set("SSRS_TRACKS_NO_FINE_TABLE");
+    sw.roam_table = !set("SSRS_TRACKS_NO_ROAM_TABLE");
+    sw.rev = !set("SSRS_TRACKS_NO_REV");
+    sw.deal_contiguous = !set("SSRS_TRACKS_DEAL_ROUND_ROBIN");
+    sw.rebalance = !set("SSRS_TRACKS_NO_REBALANCE");
+    sw.grow_steps = !set("SSRS_TRACKS_FIXED_STEPS");
+    sw.roam_wide_from = static_cast<long long>(kDealBlocks + kWanderWindows - 2) * kBlock + 1;   // (62 977: one more than a narrow deal with three windows in use holds, 246 blocks)
+    if (const char *e = std::getenv("SSRS_TRACKS_ROAM_WIDE")) sw.roam_wide_from = std::atoll(e);
+    sw.roam_width = 0;
+    if (const char *e = std::getenv("SSRS_TRACKS_ROAM_WIDTH")) { const int w = std::atoi(e); if (w == 1 || w == 2 || w == 4) sw.roam_width = w; }
+    sw.roam_shuffle = 16;
+    if (const char *e = std::getenv("SSRS_TRACKS_ROAM_SHUFFLE")) sw.roam_shuffle = std::atoi(e);
+    return sw;
+}
+
+static_assert(offsetof(TrackCtl, steps) == kSlotSteps * sizeof(uint32_t) &&
+              offsetof(TrackCtl, strays) == kSlotSteps * sizeof(uint32_t) + sizeof(unsigned long long), "read-back slot");
+
+// The events of a call, released on every way out of it
+struct TrackEvents {
+    hipEvent_t first = nullptr, last = nullptr;
+    hipEvent_t batch[kRing] = {};            // profile mode: the batches' marks (owned by `marks`)
+    bool own_batch = false;
+    std::vector<hipEvent_t> marks;
+    std::vector<int> kind;
+    TrackEvents() = default;
+    TrackEvents(const TrackEvents &) = delete;
+    TrackEvents &operator=(const TrackEvents &) = delete;
+    ~TrackEvents()
+    {
+        for (hipEvent_t e : marks) (void)hipEventDestroy(e);
+        if (own_batch)
+            for (hipEvent_t e : batch)
+                if (e) (void)hipEventDestroy(e);
+        if (first) (void)hipEventDestroy(first);
+        if (last) (void)hipEventDestroy(last);
+    }
+};
+
+static int check_track_args(const TrackCall &c)
+{
+    const SsrsTrackParams *p = c.p;
     SSRS_REQUIRE(p != nullptr, "ssrs_tracks_simulate: params is NULL");
-    SSRS_REQUIRE(hist64 == nullptr || hist != nullptr, "ssrs_tracks_simulate_h64: the 32-bit raster the kernels count into is NULL");
+    SSRS_REQUIRE(c.hist64 == nullptr || c.hist != nullptr, "ssrs_tracks_simulate_h64: the 32-bit raster the kernels count into is NULL");
     SSRS_REQUIRE(p->rows >= 5 && p->cols >= 5, "ssrs_tracks_simulate: need rows, cols >= 5 (got %d x %d)",
                  p->rows, p->cols);
     SSRS_REQUIRE(p->rows <= 32767 && p->cols <= 32767,
@@ -4161,124 +3875,169 @@ static int tracks_simulate_impl(const SsrsTrackParams *p, const double *updraft,
     SSRS_REQUIRE(p->max_moves >= 0 && p->max_moves < (1ll << 31) - 1,
                  "ssrs_tracks_simulate: max_moves out of range");
     SSRS_REQUIRE(p->burnin >= 0, "ssrs_tracks_simulate: burnin must be >= 0");
-    SSRS_REQUIRE(ntracks >= 0 && ntracks < (1ll << 31) - 64, "ssrs_tracks_simulate: bad ntracks");
-    SSRS_REQUIRE(!(potential && !updraft && !table),
+    SSRS_REQUIRE(c.ntracks >= 0 && c.ntracks < (1ll << 31) - 64, "ssrs_tracks_simulate: bad ntracks");
+    SSRS_REQUIRE(!(c.potential && !c.updraft && !c.table),
                  "ssrs_tracks_simulate: potential_field needs updraft_field (reference raises)");
-    SSRS_REQUIRE(!(traj && !traj_offsets), "ssrs_tracks_simulate: traj needs traj_offsets");
-    SSRS_REQUIRE(!(table && (reinterpret_cast<uintptr_t>(table) & 63u)),
+    SSRS_REQUIRE(!(c.traj && !c.traj_offsets), "ssrs_tracks_simulate: traj needs traj_offsets");
+    SSRS_REQUIRE(!(c.table && (reinterpret_cast<uintptr_t>(c.table) & 63u)),
                  "ssrs_tracks_simulate: table must be 64-byte aligned");
-    if (stats) *stats = SsrsTrackStats{};
-    if (rec) {
-        rec->used = 0;
-        rec->chunks.clear();
-        rec->complete = 1;
-        rec->rows = p->rows;
-        rec->cols = p->cols;
-        rec->ntracks = ntracks;
+    return SSRS_OK;
+}
+
+struct TrackRun {
+    const TrackCall c;
+    const SsrsTrackParams *p;
+    const TrackSwitches sw;
+    hipStream_t st;
+    Workspace ws = {};
+    uint32_t *host_counts = nullptr;
+    int S = 0, mode = 0, mode0 = 0;
+    bool profile = false, coherent = false, lean = false, ring = false, thr = false;
+    PlanGeom geom = {};
+    ThrPrior thr_prior = {};
+    StepArgs a = {};
+    // the front paths and the room behind the regular workspace
+    uint32_t ntc = 0, ntiles = 0;
+    size_t ncell = 0;
+    bool roam_ok = false, rev = false, wander_sort_ok = false, v16_ok = false;
+    uint32_t *hist_t = nullptr;              // the transposed histogram of an east / west batch
+    uint32_t *copies_ptr = nullptr;          // private histogram copies of a scattered batch
+    int ncopies = 0;
+    bool copies_live = false;
+    bool roam_ready = false;
+    int roam_width = 1;                      // 1, 2, 4: blocks of 256, 512, 1024 lanes
+    TrackPolicy pol;
+    // the launches so far
+    int launch = 0, batches = 0, last_Sl = 0;
+    long long it_done = 0;                   // threshold stepper: iterations of the launches so far (after the first move)
+    int window_launches = 0, tile_launches = 0, block_window_launches = 0, roam_launches = 0, roam_wide_launches = 0;
+    int slot_row[kRing] = {};
+    bool slot_block_window[kRing] = {};      // the batch's launches counted in block windows
+    TrackEvents ev;
+    bool marks_adjacent = false;             // the last mark is the start of whatever is queued next
+
+    explicit TrackRun(const TrackCall &call)
+        : c(call), p(call.p), sw(read_track_switches()), st(as_stream(call.stream)) {}
+
+    // SSRS_TRACKS_PROFILE: ONE event per boundary (an event record costs the stream ~5 us): a stepper
+    // launch runs from the mark before it to its own mark (kind 1), its binning kernels from there to
+    // theirs (kind 2); an explicit start mark (kind 0) only where something else was queued in between
+    void mark(int kind)
+    {
+        hipEvent_t e;
+        if (hipEventCreate(&e) != hipSuccess) return;
+        (void)hipEventRecord(e, st);
+        ev.marks.push_back(e);
+        ev.kind.push_back(kind);
+        marks_adjacent = true;
     }
-    if (ntracks == 0) return SSRS_OK;
-    SSRS_REQUIRE(start_rc != nullptr, "ssrs_tracks_simulate: start_rc is NULL");
-    SSRS_REQUIRE(workspace && workspace_bytes >= ssrs_tracks_workspace_bytes(ntracks),
-                 "ssrs_tracks_simulate: workspace too small (need %zu bytes)",
-                 ssrs_tracks_workspace_bytes(ntracks));
-    SSRS_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0,
-                 "ssrs_tracks_simulate: workspace must be 256-byte aligned");
 
-    hipStream_t st = as_stream(stream);
-    Workspace ws;
-    workspace_layout(ntracks, static_cast<char *>(workspace), &ws);
-    uint32_t *host_counts = pinned_counts();
-    SSRS_REQUIRE(host_counts != nullptr, "ssrs_tracks_simulate: hipHostMalloc failed");
+    int check_thr_header();
+    int plan_and_init();
+    int choose_front_path();
+    int launch_steps(bool first_move, unsigned blocks, uint32_t *vcap, long long *vstride) const;
+    int record_launch(unsigned blocks, int Sl, bool bin_window, const uint32_t **rec_counts);
+    void launch_stepper(bool first_move, bool v16, unsigned blocks, int Sl, bool *block_window);
+    void bin_launch(unsigned blocks, int Sl, bool bin_window, bool bin_tiles, bool v16, const uint32_t *rec_counts,
+                    uint32_t *read_back, bool *read_back_done);
+    int wander_sort();
+    void build_roam_tables();
+    void rebalance();
+    int queue_batch();
+    int examine_batches();
+    int finish(int rc, SsrsTrackStats *stats);
+};
 
-    const int S = p->steps_per_launch > 0 ? p->steps_per_launch : 512;
-    const bool profile = (p->flags & SSRS_TRACKS_PROFILE) != 0;
-    const int mode = table ? MODE_TABLE : (updraft ? (potential ? MODE_FLUIDFLOW : MODE_UPDRAFT)
-                                                   : MODE_PRIOR);
+int TrackRun::check_thr_header()
+{
+    // A threshold table names its raster and prior in its leading guard band.  The header is read back
+    // and checked HERE, before any stepper kernel gathers from the table: a table built for a smaller
+    // raster would send those gathers out of bounds (k_ctl_init's device-side check of the same
+    // header is only acted on when the run is over).  88 bytes and one stream wait per call.
+    SSRS_REQUIRE(c.table != nullptr, "ssrs_tracks_simulate: SSRS_TRACKS_THR_TABLE needs `table`");
+    ThrHeader *hh = reinterpret_cast<ThrHeader *>(host_counts + kHeaderSlot);
+    SSRS_HIP_CHECK(hipMemcpyAsync(hh, c.table, sizeof(ThrHeader), hipMemcpyDeviceToHost, st));
+    SSRS_HIP_CHECK(hipStreamSynchronize(st));
+    bool bad = hh->magic != kThrMagic || hh->rows != p->rows || hh->cols != p->cols;
+    for (int k = 0; k < 9; ++k) bad |= hh->prior[k] != p->prior[k];
+    if (bad)
+        return set_error(SSRS_ERR_INVALID, "ssrs_tracks_simulate: `table` is not a threshold table built by "
+                         "ssrs_transition_thr_build for this %d x %d raster and params->prior (nothing was launched)",
+                         p->rows, p->cols);
+    return SSRS_OK;
+}
 
-    if (p->flags & SSRS_TRACKS_THR_TABLE) {
-        // A threshold table names its raster and prior in its leading guard band.  The header is read back
-        // and checked HERE, before any stepper kernel gathers from the table: a table built for a smaller
-        // raster would send those gathers out of bounds (k_ctl_init's device-side check of the same
-        // header is only acted on when the run is over).  88 bytes and one stream wait per call.
-        SSRS_REQUIRE(table != nullptr, "ssrs_tracks_simulate: SSRS_TRACKS_THR_TABLE needs `table`");
-        ThrHeader *hh = reinterpret_cast<ThrHeader *>(host_counts + kHeaderSlot);
-        SSRS_HIP_CHECK(hipMemcpyAsync(hh, table, sizeof(ThrHeader), hipMemcpyDeviceToHost, st));
-        SSRS_HIP_CHECK(hipStreamSynchronize(st));
-        bool bad = hh->magic != kThrMagic || hh->rows != p->rows || hh->cols != p->cols;
-        for (int k = 0; k < 9; ++k) bad |= hh->prior[k] != p->prior[k];
-        if (bad)
-            return set_error(SSRS_ERR_INVALID, "ssrs_tracks_simulate: `table` is not a threshold table built by "
-                             "ssrs_transition_thr_build for this %d x %d raster and params->prior (nothing was launched)",
-                             p->rows, p->cols);
-    }
-
-    hipEvent_t ev_first = nullptr, ev_last = nullptr;
-    SSRS_HIP_CHECK(hipEventCreate(&ev_first));
-    SSRS_HIP_CHECK(hipEventCreate(&ev_last));
-    SSRS_HIP_CHECK(hipEventRecord(ev_first, st));
+// The control block, the plan (coherent schedule: tracks sorted along the heading), the tracks' state and the
+// stepper arguments
+int TrackRun::plan_and_init()
+{
+    const int64_t ntracks = c.ntracks;
+    SSRS_HIP_CHECK(hipEventCreate(&ev.first));
+    SSRS_HIP_CHECK(hipEventCreate(&ev.last));
+    SSRS_HIP_CHECK(hipEventRecord(ev.first, st));
     {
         PriorArg pa;
         for (int k = 0; k < 9; ++k) pa.v[k] = p->prior[k];
         // (a threshold table names its raster and prior in its leading guard band: checked on the device)
-        const ThrHeader *header = (p->flags & SSRS_TRACKS_THR_TABLE) ? reinterpret_cast<const ThrHeader *>(table) : nullptr;
+        const ThrHeader *header = (p->flags & SSRS_TRACKS_THR_TABLE) ? reinterpret_cast<const ThrHeader *>(c.table) : nullptr;
         hipLaunchKernelGGL(k_ctl_init, dim3(1), dim3(64), 0, st, ws.ctl, pa, ws.thr, ws.wander, header, p->rows, p->cols);
         SSRS_HIP_CHECK(hipGetLastError());
     }
-    const bool coherent = (p->flags & SSRS_TRACKS_NO_SCHEDULE) == 0;
-    PlanGeom geom = {};
-    {
-        const unsigned blocks = static_cast<unsigned>((ntracks + kBlock - 1) / kBlock);
-        if (coherent) {
-            // movement direction from the prior: its lobe peaks along the heading
-            // (movmodel.py:247-257), so the weighted neighbour offsets give it back
-            double vr = 0.0, vc = 0.0;
-            for (int k = 0; k < 9; ++k) { vr += p->prior[k] * dr_of(k); vc += p->prior[k] * dc_of(k); }
-            const double nrm = std::sqrt(vr * vr + vc * vc);
-            geom.cos_t = nrm > 0.0 ? vr / nrm : 1.0;
-            geom.sin_t = nrm > 0.0 ? vc / nrm : 0.0;
-            geom.offset = p->rows + p->cols;
-            int par_bits = 1;
-            while ((1ll << par_bits) <= 2ll * geom.offset) ++par_bits;       // <= 18 (rows, cols <= 32767)
-            size_t temp_bytes = ws.sort_temp_bytes;
-            if (2 * par_bits <= 32) {
-                uint32_t *k0 = reinterpret_cast<uint32_t *>(ws.keys[0]), *k1 = reinterpret_cast<uint32_t *>(ws.keys[1]);
-                hipLaunchKernelGGL(k_plan_keys<uint32_t>, dim3(blocks), dim3(kBlock), 0, st, start_rc,
-                                   static_cast<long long>(ntracks), geom, k0, ws.list[1], ws.ctl, par_bits);
-                SSRS_HIP_CHECK(hipGetLastError());
-                SSRS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(
-                    ws.sort_temp, temp_bytes, k0, k1, ws.list[1], ws.list[0], static_cast<int>(ntracks), 0, 2 * par_bits, st));
-            } else {
-                hipLaunchKernelGGL(k_plan_keys<unsigned long long>, dim3(blocks), dim3(kBlock), 0, st, start_rc,
-                                   static_cast<long long>(ntracks), geom, ws.keys[0], ws.list[1], ws.ctl, par_bits);
-                SSRS_HIP_CHECK(hipGetLastError());
-                SSRS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(
-                    ws.sort_temp, temp_bytes, ws.keys[0], ws.keys[1], ws.list[1], ws.list[0],
-                    static_cast<int>(ntracks), 0, 2 * par_bits, st));
-            }
+    coherent = (p->flags & SSRS_TRACKS_NO_SCHEDULE) == 0;
+    const unsigned blocks = static_cast<unsigned>((ntracks + kBlock - 1) / kBlock);
+    if (coherent) {
+        // movement direction from the prior: its lobe peaks along the heading
+        // (movmodel.py:247-257), so the weighted neighbour offsets give it back
+        double vr = 0.0, vc = 0.0;
+        for (int k = 0; k < 9; ++k) { vr += p->prior[k] * dr_of(k); vc += p->prior[k] * dc_of(k); }
+        const double nrm = std::sqrt(vr * vr + vc * vc);
+        geom.cos_t = nrm > 0.0 ? vr / nrm : 1.0;
+        geom.sin_t = nrm > 0.0 ? vc / nrm : 0.0;
+        geom.offset = p->rows + p->cols;
+        int par_bits = 1;
+        while ((1ll << par_bits) <= 2ll * geom.offset) ++par_bits;       // <= 18 (rows, cols <= 32767)
+        size_t temp_bytes = ws.sort_temp_bytes;
+        if (2 * par_bits <= 32) {
+            uint32_t *k0 = reinterpret_cast<uint32_t *>(ws.keys[0]), *k1 = reinterpret_cast<uint32_t *>(ws.keys[1]);
+            hipLaunchKernelGGL(k_plan_keys<uint32_t>, dim3(blocks), dim3(kBlock), 0, st, c.start_rc,
+                               static_cast<long long>(ntracks), geom, k0, ws.list[1], ws.ctl, par_bits);
+            SSRS_HIP_CHECK(hipGetLastError());
+            SSRS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(
+                ws.sort_temp, temp_bytes, k0, k1, ws.list[1], ws.list[0], static_cast<int>(ntracks), 0, 2 * par_bits, st));
+        } else {
+            hipLaunchKernelGGL(k_plan_keys<unsigned long long>, dim3(blocks), dim3(kBlock), 0, st, c.start_rc,
+                               static_cast<long long>(ntracks), geom, ws.keys[0], ws.list[1], ws.ctl, par_bits);
+            SSRS_HIP_CHECK(hipGetLastError());
+            SSRS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(
+                ws.sort_temp, temp_bytes, ws.keys[0], ws.keys[1], ws.list[1], ws.list[0],
+                static_cast<int>(ntracks), 0, 2 * par_bits, st));
         }
-        hipLaunchKernelGGL(k_tracks_init, dim3(blocks), dim3(kBlock), 0, st, start_rc,
-                           static_cast<long long>(ntracks), p->rows, p->cols, hist, traj,
-                           reinterpret_cast<const long long *>(traj_offsets), lengths, end_rc,
-                           ws.state, ws.ctl, geom, coherent ? 1 : 0, ws.cap);
-        SSRS_HIP_CHECK(hipGetLastError());
     }
+    hipLaunchKernelGGL(k_tracks_init, dim3(blocks), dim3(kBlock), 0, st, c.start_rc,
+                       static_cast<long long>(ntracks), p->rows, p->cols, c.hist, c.traj,
+                       reinterpret_cast<const long long *>(c.traj_offsets), c.lengths, c.end_rc,
+                       ws.state, ws.ctl, geom, coherent ? 1 : 0, ws.cap);
+    SSRS_HIP_CHECK(hipGetLastError());
 
-    StepArgs a = {};
+    S = p->steps_per_launch > 0 ? p->steps_per_launch : 512;
+    profile = (p->flags & SSRS_TRACKS_PROFILE) != 0;
+    mode = c.table ? MODE_TABLE : (c.updraft ? (c.potential ? MODE_FLUIDFLOW : MODE_UPDRAFT) : MODE_PRIOR);
+    mode0 = c.updraft ? (c.potential ? MODE_FLUIDFLOW : MODE_UPDRAFT) : MODE_PRIOR;   // thr: first move
     a.rows = p->rows; a.cols = p->cols; a.burnin = p->burnin; a.memory = p->memory_parameter;
     a.max_k = p->max_moves; a.nu = p->scaling_parameter;
     a.prior = ws.ctl->prior;
-    a.updraft = updraft; a.potential = potential; a.table = table;
-    a.seed = seed; a.track_base = track_id_base;
-    a.hist = hist; a.end_rc = end_rc; a.lengths = lengths; a.traj = traj;
-    a.traj_off = reinterpret_cast<const long long *>(traj_offsets);
+    a.updraft = c.updraft; a.potential = c.potential; a.table = c.table;
+    a.seed = c.seed; a.track_base = c.track_id_base;
+    a.hist = c.hist; a.end_rc = c.end_rc; a.lengths = c.lengths; a.traj = c.traj;
+    a.traj_off = reinterpret_cast<const long long *>(c.traj_offsets);
     a.state = ws.state; a.ctl = ws.ctl; a.steps = S;
     a.fast = ((p->flags & SSRS_TRACKS_EXACT_ONLY) == 0 && p->scaling_parameter == 1.0) ? 1 : 0;
     a.coherent = coherent ? 1 : 0;
     a.cap = ws.cap;
     a.thr = ws.thr;
     a.wander = ws.wander;
-    a.debug_roam = std::getenv("SSRS_TRACKS_DEBUG_ROAM") != nullptr ? 1 : 0;
-    a.roam_stop = std::getenv("SSRS_TRACKS_NO_ROAM_STOP") == nullptr ? 1 : 0;
+    a.debug_roam = sw.debug_roam ? 1 : 0;
+    a.roam_stop = sw.roam_stop ? 1 : 0;
     a.dbg_buf = nullptr;
 #ifdef SSRS_DEBUG_WAVE_DUMP
     {
@@ -4288,14 +4047,13 @@ static int tracks_simulate_impl(const SsrsTrackParams *p, const double *updraft,
         a.dbg_buf = dump_buf;
     }
 #endif
-    a.cheap_exact = std::getenv("SSRS_TRACKS_NO_CHEAP_EXACT") == nullptr ? 1 : 0;
+    a.cheap_exact = sw.cheap_exact ? 1 : 0;
     a.vcap = ws.cap;
-    const bool lean = p->memory_parameter == 1 && traj == nullptr;
-    const bool ring = (p->flags & SSRS_TRACKS_RING_TABLE) != 0;
-    const bool thr = (p->flags & SSRS_TRACKS_THR_TABLE) != 0;
-    ThrPrior thr_prior = {};
+    lean = p->memory_parameter == 1 && c.traj == nullptr;
+    ring = (p->flags & SSRS_TRACKS_RING_TABLE) != 0;
+    thr = (p->flags & SSRS_TRACKS_THR_TABLE) != 0;
     if (thr) {
-        SSRS_REQUIRE(!ring && table && updraft && lean && a.fast && (S & 1) == 0,
+        SSRS_REQUIRE(!ring && c.table && c.updraft && lean && a.fast && (S & 1) == 0,
                      "ssrs_tracks_simulate: SSRS_TRACKS_THR_TABLE needs table + updraft, memory_parameter 1, "
                      "scaling_parameter 1, no direct trajectory output, no EXACT_ONLY and an even steps_per_launch");
         SSRS_REQUIRE(static_cast<size_t>(p->rows) * static_cast<size_t>(p->cols) <= (1ull << 26),
@@ -4303,16 +4061,23 @@ static int tracks_simulate_impl(const SsrsTrackParams *p, const double *updraft,
         prior_tables(p->prior, &thr_prior);
         a.plane_shift = thr_plane_shift(p->rows, p->cols);
         a.guard = static_cast<uint32_t>(thr_guard_bytes(p->cols));
-        // prefetch wave: the heading's ring position (0 = north, 4 = south); A/B switch SSRS_TRACKS_NO_PREFETCH
-        a.pf_dir = (coherent && std::getenv("SSRS_TRACKS_NO_PREFETCH") == nullptr)
-                       ? (geom.cos_t > 0.98 ? 1 : (geom.cos_t < -0.98 ? -1 : 0)) : 0;
+        // prefetch wave: the heading's ring position (0 = north, 4 = south)
+        a.pf_dir = coherent ? (geom.cos_t > 0.98 ? 1 : (geom.cos_t < -0.98 ? -1 : 0)) : 0;
         a.pf_rc = a.pf_dir < 0 ? 4 : 0;
     }
-    const int mode0 = updraft ? (potential ? MODE_FLUIDFLOW : MODE_UPDRAFT) : MODE_PRIOR;   // thr: first move
     if (ring)
-        SSRS_REQUIRE(table && updraft && lean && a.fast && (S & 1) == 0,
+        SSRS_REQUIRE(c.table && c.updraft && lean && a.fast && (S & 1) == 0,
                      "ssrs_tracks_simulate: SSRS_TRACKS_RING_TABLE needs table + updraft, memory_parameter 1, "
                      "scaling_parameter 1, no trajectory output, no EXACT_ONLY and an even steps_per_launch");
+    return SSRS_OK;
+}
+
+// The first launches' path (binning, tiles, transposed, scattered, cached) and the room behind the regular
+// workspace: the pair and fine tables, the transposed histogram, the private copies
+int TrackRun::choose_front_path()
+{
+    const int64_t ntracks = c.ntracks;
+    uint32_t *const hist = c.hist;
     // binning needs the coherent front (a step's visits fall into a few rows).  The
     // binning kernel runs on the SAME stream, after its stepper launch: running it on a
     // side stream to overlap the next launch was measured and rejected (its 1024-thread /
@@ -4322,659 +4087,523 @@ static int tracks_simulate_impl(const SsrsTrackParams *p, const double *updraft,
     // histogram (needs one raster of extra workspace, see below)
     // oblique headings: visits bucketed by raster tile (k_tile_sort / k_bin_bucket)
     const double off_axis = std::fabs(geom.sin_t) < std::fabs(geom.cos_t) ? std::fabs(geom.sin_t) : std::fabs(geom.cos_t);
-    const uint32_t ntc = static_cast<uint32_t>((p->cols + kTileCols - 1) / kTileCols);
-    const uint32_t ntiles = ntc * static_cast<uint32_t>((p->rows + kTileRows - 1) / kTileRows);
+    ntc = static_cast<uint32_t>((p->cols + kTileCols - 1) / kTileCols);
+    ntiles = ntc * static_cast<uint32_t>((p->rows + kTileRows - 1) / kTileRows);
     // (bucket offsets are 32-bit: a launch must make fewer than 2^32 visits)
     const bool tiles_ok = hist != nullptr && coherent && S <= kVisitSteps && ntracks >= 8192 && ntiles <= kTilesMax &&
                           static_cast<unsigned long long>(ws.cap) * kXcd * static_cast<unsigned long long>(S) < (1ull << 32) &&
-                          (p->flags & SSRS_TRACKS_NO_BINNING) == 0 && std::getenv("SSRS_TRACKS_NO_TILES") == nullptr;
-    const bool force_tiles = tiles_ok && std::getenv("SSRS_TRACKS_FORCE_TILES") != nullptr;   // A/B switch
-    bool tiles_on = tiles_ok && (off_axis > 0.17 || force_tiles);   // more than ~10 degrees off a raster axis
+                          (p->flags & SSRS_TRACKS_NO_BINNING) == 0;
+    bool tiles_on = tiles_ok && off_axis > 0.17;   // more than ~10 degrees off a raster axis
     const bool want_transposed = coherent && !tiles_on && std::fabs(geom.sin_t) > std::fabs(geom.cos_t);
-    bool binning = hist != nullptr && coherent && S <= kVisitSteps &&
-                   (p->flags & SSRS_TRACKS_NO_BINNING) == 0 &&
-                   (want_transposed ? p->rows : p->cols) <= kBinCells;
+    const bool binning = hist != nullptr && coherent && S <= kVisitSteps &&
+                         (p->flags & SSRS_TRACKS_NO_BINNING) == 0 &&
+                         (want_transposed ? p->rows : p->cols) <= kBinCells;
     a.visits = nullptr;
     a.visit_stride = ws.visit_stride;
     bool binning_on = binning && ntracks >= 8192 && !tiles_on;   // small batches: plain atomics are cheaper
     // SSRS_TRACKS_SCATTERED forces the zero-mask variant from the first launch,
     // SSRS_TRACKS_NO_SCATTERED keeps it off (A/B switches; results are identical)
     const bool never_scattered = (p->flags & SSRS_TRACKS_NO_SCATTERED) != 0;
-    bool scattered = (p->flags & SSRS_TRACKS_SCATTERED) != 0;
+    const bool scattered = (p->flags & SSRS_TRACKS_SCATTERED) != 0;
     if (scattered) binning_on = tiles_on = false;
     // threshold stepper, front outgrown the row window (tracks wander): atomics behind the per-lane
     // block windows in LDS instead of tile buckets (A/B switch SSRS_TRACKS_NO_BLOCK_WINDOW)
     // (never while trajectories are recorded: those launches use the visit-buffer kernels, which
     // know no tombstones)
-    const bool cache_ok = thr && hist != nullptr && !(rec && rec->complete) && std::getenv("SSRS_TRACKS_NO_BLOCK_WINDOW") == nullptr;
-    bool cached = cache_ok && scattered;
-    bool want_wander_sort = cached;
-    int wander_sorts = 0, wander_cooldown = 0, stable_batches = 0, upper_from = 0;
+    const bool cache_ok = thr && hist != nullptr && !(c.rec && c.rec->complete) && sw.block_window;
     size_t ws_base = align_up(ssrs_tracks_workspace_bytes(ntracks), 256);
     // room behind the regular workspace: first the pair table of the roaming regime (threshold stepper only)
     {
         const size_t pb = thr ? pair_table_bytes(ntracks, p->rows, p->cols) : 0;
-        if (pb && workspace_bytes >= ws_base + pb) {
-            ws.roam = reinterpret_cast<RoamEntry *>(static_cast<char *>(workspace) + ws_base);
-            if (std::getenv("SSRS_TRACKS_NO_FINE_TABLE") == nullptr)          // A/B switch
-                a.fine = static_cast<char *>(workspace) + ws_base +
+        if (pb && c.workspace_bytes >= ws_base + pb) {
+            ws.roam = reinterpret_cast<RoamEntry *>(static_cast<char *>(c.workspace) + ws_base);
+            if (sw.fine_table)
+                a.fine = static_cast<char *>(c.workspace) + ws_base +
                          align_up(static_cast<size_t>(p->rows) * static_cast<size_t>(p->cols) * 8 * sizeof(RoamEntry), 256);
             ws_base += pb;
         }
         a.roam = ws.roam;
     }
     // pair table (k_step_roam): built when the batch starts to roam; A/B switches SSRS_TRACKS_NO_ROAM_TABLE, SSRS_TRACKS_DEAL_ROUND_ROBIN
-    const bool roam_ok = cache_ok && ws.roam != nullptr && std::getenv("SSRS_TRACKS_NO_ROAM_TABLE") == nullptr;
-    const bool roam_rev = thr_prior.rev_ok != 0 && std::getenv("SSRS_TRACKS_NO_REV") == nullptr;
-    const bool deal_contiguous = std::getenv("SSRS_TRACKS_DEAL_ROUND_ROBIN") == nullptr;
-    // LDS-staged table rows for fronts (k_step_thr<.., LR = true>): built and parity-tested, measured SLOWER than the
-    // gather behind the prefetch wave (profiles/r03_notes.md section 7), so it is off unless asked for
-    // (=2: waves that are ahead of the ring wait for their row instead of gathering it -- slower still)
-    const char *lds_rows_env = std::getenv("SSRS_TRACKS_LDS_ROWS");
-    const bool lds_rows = lds_rows_env != nullptr;
-    a.lr_wait = (lds_rows && std::atoi(lds_rows_env) == 2) ? 1 : 0;
-    bool roam_ready = false;
-    // wide roaming blocks (k_step_roam<REV, 512>): chosen at a deal when more tracks are alive than one round of 256-lane blocks
-    // holds (SSRS_TRACKS_ROAM_WIDE=<live tracks from which on>, 0: never, 1: always), kept until the next deal
-    int roam_width = 1;                      // 1, 2, 4: blocks of 256, 512, 1024 lanes
-    long long roam_wide_from = static_cast<long long>(kDealBlocks + kWanderWindows - 2) * kBlock + 1;   // (62 977: one more than a narrow deal with three windows in use holds, 246 blocks)
-    if (const char *e = std::getenv("SSRS_TRACKS_ROAM_WIDE")) roam_wide_from = std::atoll(e);
-    int roam_width_forced = 0;               // SSRS_TRACKS_ROAM_WIDTH=1|2|4: that width at every deal (A/B)
-    if (const char *e = std::getenv("SSRS_TRACKS_ROAM_WIDTH")) { const int w = std::atoi(e); if (w == 1 || w == 2 || w == 4) roam_width_forced = w; }
-    int roam_wide_launches = 0;
-    int roam_launches = 0, stable_roam = 0, since_shuffle = 0, roam_shuffles = 0;
-    bool sort_is_periodic = false;
-    int roam_shuffle = 16;                   // batches between two shuffles of a settled roaming batch (SSRS_TRACKS_ROAM_SHUFFLE, 0: never)
-    if (const char *e = std::getenv("SSRS_TRACKS_ROAM_SHUFFLE")) roam_shuffle = std::atoi(e);
-    int roam_steps = 128 * S;                // A/B: SSRS_TRACKS_ROAM_STEPS (4096: 0.0073, 16384: 0.0060, 65536: 0.0053 ns per step at C2)
-    if (const char *e = std::getenv("SSRS_TRACKS_ROAM_STEPS")) {
-        const int v = std::atoi(e);
-        if (v >= 2 && v <= (1 << 20)) roam_steps = v & ~1;
-    }
-    uint32_t prev_total = 0;
+    roam_ok = cache_ok && ws.roam != nullptr && sw.roam_table;
+    rev = thr_prior.rev_ok != 0 && sw.rev;
     // (the key arrays hold 2 n words >= the list slots; the coarse grid of k_wander_windows fits its LDS)
-    const bool wander_sort_ok = ntracks >= kWanderMinTracks &&
-                                static_cast<long long>((p->rows + kBinRows - 1) / kBinRows) * ((p->cols + kBinCols - 1) / kBinCols) <= kWanderBins;
+    wander_sort_ok = ntracks >= kWanderMinTracks &&
+                     static_cast<long long>((p->rows + kBinRows - 1) / kBinRows) * ((p->cols + kBinCols - 1) / kBinCols) <= kWanderBins;
     // private histogram copies live behind the regular workspace when the caller gave room
-    const size_t ncell = static_cast<size_t>(p->rows) * static_cast<size_t>(p->cols);
-    int ncopies = 0;
-    if (hist && workspace_bytes > ws_base) ncopies = static_cast<int>((workspace_bytes - ws_base) / (ncell * sizeof(uint32_t)));
-    uint32_t *extra = reinterpret_cast<uint32_t *>(static_cast<char *>(workspace) + ws_base);
+    ncell = static_cast<size_t>(p->rows) * static_cast<size_t>(p->cols);
+    if (hist && c.workspace_bytes > ws_base) ncopies = static_cast<int>((c.workspace_bytes - ws_base) / (ncell * sizeof(uint32_t)));
+    uint32_t *extra = reinterpret_cast<uint32_t *>(static_cast<char *>(c.workspace) + ws_base);
     // the first extra raster is the transposed histogram of an east / west batch
-    uint32_t *hist_t = nullptr;
     if (want_transposed && binning_on) {
         if (ncopies >= 1) { hist_t = extra; extra += ncell; --ncopies; }
-        else { binning = false; binning_on = false; }      // no room: per-step atomics
+        else binning_on = false;            // no room: per-step atomics
     }
     if (hist_t) SSRS_HIP_CHECK(hipMemsetAsync(hist_t, 0, sizeof(uint32_t) * ncell, st));
-    a.vis_r = hist_t ? 1u : static_cast<uint32_t>(p->cols);
-    a.vis_c = hist_t ? static_cast<uint32_t>(p->rows) : 1u;
     ncopies = ncopies > 64 ? 64 : ncopies;
-    uint32_t *copies_ptr = ncopies >= 2 ? extra : nullptr;
-    bool copies_live = false;
+    copies_ptr = ncopies >= 2 ? extra : nullptr;
     a.hist_copies = nullptr;
     a.ncopies = 1;
-    a.zmask = ring ? reinterpret_cast<const uint8_t *>(table) + ring_mask_offset(p->rows, p->cols) : nullptr;
-    unsigned long long seen_steps = 0, seen_strays = 0;
-    // Launch loop.  Launches are queued kBatch deep; the live count of a batch
-    // is copied back asynchronously and examined while the next batch runs, so
-    // the GPU never waits on the host.  Launches past the end see count 0.
-    constexpr int kBatch = 2, kRing = 8;
-    constexpr int kSlotWords = 40;           // 160 bytes of TrackCtl: counts .. strays
-    static_assert(offsetof(TrackCtl, strays) + sizeof(unsigned long long) <= kSlotWords * sizeof(uint32_t), "read-back slot");
-    int slot_row[kRing] = {};
-    bool slot_block_window[kRing] = {};      // the batch's launches counted in block windows
-    long long block_window_steps = 0;
-    const bool direct_read_back = std::getenv("SSRS_TRACKS_COPY_READ_BACK") == nullptr;      // A/B switch
-    // (profile mode: every batch gets its own event, which is also the start mark of the next launch)
-    hipEvent_t ev_batch[kRing] = {};
-    if (!profile)
-        for (int i = 0; i < kRing; ++i) SSRS_HIP_CHECK(hipEventCreate(&ev_batch[i]));
-    // SSRS_TRACKS_PROFILE: ONE event per boundary (an event record costs the stream ~5 us): a stepper
-    // launch runs from the mark before it to its own mark (kind 1), its binning kernels from there to
-    // theirs (kind 2); an explicit start mark (kind 0) only where something else was queued in between
-    std::vector<hipEvent_t> ev_marks;
-    std::vector<int> mark_kind;
-    bool marks_adjacent = false;             // the last mark is the start of whatever is queued next
-    auto mark = [&](int kind) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return;
-        (void)hipEventRecord(e, st);
-        ev_marks.push_back(e);
-        mark_kind.push_back(kind);
-        marks_adjacent = true;
-    };
-    int launch = 0;
-    long long it_done = 0;                   // threshold stepper: iterations of the launches so far (after the first move)
-    bool want_rebalance = false;
-    int rebalance_cooldown = 0;              // batches to look past after a re-deal (their counts are older than it)
-    const bool may_rebalance = std::getenv("SSRS_TRACKS_NO_REBALANCE") == nullptr;
-    const bool grow_steps = std::getenv("SSRS_TRACKS_FIXED_STEPS") == nullptr;      // A/B switch
-    const bool v16_ok = 5ll * p->cols <= kBinCells && std::getenv("SSRS_TRACKS_NO_VISITS16") == nullptr;
+    a.zmask = ring ? reinterpret_cast<const uint8_t *>(c.table) + ring_mask_offset(p->rows, p->cols) : nullptr;
+    v16_ok = 5ll * p->cols <= kBinCells;
     a.v16_offset = geom.offset;
-    // bound on the longest XCD list
-    uint32_t upper = static_cast<uint32_t>(ntracks < static_cast<int64_t>(ws.cap) ? ntracks : ws.cap);
-    int batches = 0, checked = 0, judge_from = 0, last_Sl = 0;
-    int window_launches = 0, tile_launches = 0, block_window_launches = 0;
-    bool finished = false;
-    int rc = SSRS_OK;
-    // Termination: every live track either finishes or takes S moves per
-    // launch and k < max_moves, so the live count reaches 0.
-    while (!finished && rc == SSRS_OK) {
-        if (want_wander_sort && cached && wander_sort_ok && launch > 0) {
-            // pseudo-launch: list[launch & 1] -> windows, keys, sort -> padded deal into list[(launch + 1) & 1]
-            const uint32_t slots = ws.cap * kXcd;
-            uint32_t *k0 = reinterpret_cast<uint32_t *>(ws.keys[0]), *k1 = reinterpret_cast<uint32_t *>(ws.keys[1]);
-            int32_t *sorted = reinterpret_cast<int32_t *>(ws.bucket);
-            hipLaunchKernelGGL(k_wander_windows, dim3(1), dim3(1024), 0, st, ws.list[launch & 1], ws.state, ws.ctl, launch & 3, ws.cap,
-                               p->rows, p->cols, ws.wander);
-            hipLaunchKernelGGL(k_wander_keys, dim3((slots + kBlock - 1) / kBlock), dim3(kBlock), 0, st, ws.list[launch & 1], ws.state,
-                               ws.ctl, launch & 3, ws.cap, ws.wander, k0, sort_is_periodic ? static_cast<uint32_t>(launch) : 0u);
-            size_t temp_bytes = ws.sort_temp_bytes;
-            if (hipcub::DeviceRadixSort::SortPairs(ws.sort_temp, temp_bytes, k0, k1, ws.list[launch & 1], sorted,
-                                                   static_cast<int>(slots), 0, 13, st) != hipSuccess) {
-                rc = set_error(SSRS_ERR_HIP, "wander sort failed");
-                break;
-            }
-            // block width of the deal: 512-lane blocks when more tracks are alive than one round of 256-lane blocks holds (216 x 512
-            // in one round; beyond that several rounds either way, 512 lanes never slower: profiles/r04_roam_fill.txt; 1024-lane
-            // blocks measured 3-4x slower than either -- four waves per SIMD and a launch that ends with its first wave --,
-            // SSRS_TRACKS_ROAM_WIDTH=4 keeps the A/B).  The lists' lengths count tombstones and padding, so the width goes by
-            // the live tracks k_wander_windows has just counted: one word read back synchronously, and only when the lists are
-            // long enough for the question to arise
-            roam_width = 1;
-            if (roam_ok && deal_contiguous) {
-                if (roam_wide_from == 1) {
-                    roam_width = 2;
-                } else if (roam_wide_from > 1 && static_cast<long long>(prev_total) >= roam_wide_from) {
-                    uint32_t *word = &host_counts[kFinalSlot];
-                    if (hipMemcpyAsync(word, &ws.ctl->deal_live, sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                        hipStreamSynchronize(st) != hipSuccess) {
-                        rc = set_error(SSRS_ERR_HIP, "live-count read-back at the deal failed");
-                        break;
-                    }
-                    if (static_cast<long long>(*word) >= roam_wide_from) roam_width = 2;
-                }
-                if (roam_width_forced) roam_width = roam_width_forced;
-            }
-            hipLaunchKernelGGL(k_deal_sorted, dim3(64), dim3(1024), 0, st, k1, sorted, ws.list[(launch + 1) & 1], ws.ctl,
-                               (launch + 1) & 3, (launch + 2) & 3, ws.cap, deal_contiguous ? 1 : 0, roam_width);
-            ++launch;
-            ++wander_sorts;
-            want_wander_sort = false;
-            want_rebalance = false;
-            wander_cooldown = 3;
-            stable_roam = sort_is_periodic ? 2 : 0;      // (a shuffle of a settled batch: the launches stay long)
-            if (sort_is_periodic) ++roam_shuffles;
-            sort_is_periodic = false;
-            marks_adjacent = false;
-            // the padded deal makes the lists LONGER (each window's run is rounded up to whole blocks of
-            // every list): raise the bound now, and let no batch queued before this point lower it
-            // (thinned blocks: at most kDealBlocks + one per window + the padding, 264 blocks = 33 per list)
-            const unsigned long long wf = static_cast<unsigned long long>(roam_width);    // (wide: runs are whole groups of blocks)
-            unsigned long long padded = static_cast<unsigned long long>(upper) + (kWanderWindows + 1ull) * kBlock * wf;
-            const unsigned long long kDealPerList = (wf * kDealBlocks + wf * (kWanderWindows + 1)) / kXcd + 3;      // 34 blocks per list (144 rows)
-            if (deal_contiguous && padded < kDealPerList * kBlock) padded = kDealPerList * kBlock;
-            upper = padded > ws.cap ? ws.cap : static_cast<uint32_t>(padded);
-            upper_from = batches;
-        }
-        if (cached) want_rebalance = false;          // (the lists carry tombstones; the wander sort deals evenly)
-        if (cached && roam_ok && !roam_ready) {
-            // the batch starts to roam: the pair table, for the whole raster (~2 ms at 5000 x 6000)
-            const char *tabc = reinterpret_cast<const char *>(table);
-            const unsigned grid = 256 * 16;
-            if (roam_rev) hipLaunchKernelGGL(k_roam_build<true>, dim3(grid), dim3(kBlock), 0, st, tabc, a.guard, a.plane_shift, p->rows, p->cols,
-                                             ws.roam, thr_prior);
-            else hipLaunchKernelGGL(k_roam_build<false>, dim3(grid), dim3(kBlock), 0, st, tabc, a.guard, a.plane_shift, p->rows, p->cols,
-                                    ws.roam, thr_prior);
-            if (a.fine) {
-                FinePrior fp;
-                fine_prior_tables(p->prior, &fp);
-                const int tx = (p->cols + kTabW - 1) / kTabW, ty = (p->rows + kTabH - 1) / kTabH, nt = tx * ty;
-                FineEntry *fine_out = reinterpret_cast<FineEntry *>(const_cast<void *>(a.fine));
-                if (potential) hipLaunchKernelGGL(k_fine_build<true>, dim3(static_cast<unsigned>(nt)), dim3(kBlock), 0, st, updraft, potential,
-                                                  fine_out, p->rows, p->cols, tx, nt, fp);
-                else hipLaunchKernelGGL(k_fine_build<false>, dim3(static_cast<unsigned>(nt)), dim3(kBlock), 0, st, updraft, potential,
-                                        fine_out, p->rows, p->cols, tx, nt, fp);
-            }
-            roam_ready = true;
-            marks_adjacent = false;
-        }
-        if (want_rebalance && launch > 0) {
-            // pseudo-launch: list[launch & 1] -> list[(launch + 1) & 1], counts likewise
-            hipLaunchKernelGGL(k_rebalance_lists, dim3(1), dim3(1024), 0, st, ws.list[launch & 1], ws.list[(launch + 1) & 1],
-                               ws.ctl, launch & 3, (launch + 1) & 3, (launch + 2) & 3, ws.cap);
-            marks_adjacent = false;
-            ++launch;
-            want_rebalance = false;
-            rebalance_cooldown = 3;
-        }
-        // one launch per batch while launches are long and few (the host then sees the batch die one
-        // launch earlier: one empty launch at the end of a short run instead of two); two otherwise
-        const int depth = (thr && last_Sl >= 512 && launch < 24) ? 1 : kBatch;
-        const int slot = batches % kRing;
-        bool read_back_done = false;             // the batch's last binning kernel wrote the slot itself
-        bool batch_block_window = false;
-        for (int j = 0; j < depth; ++j, ++launch) {
-            a.launch = launch;
-            a.list_in = (launch == 0 && !coherent) ? nullptr : ws.list[launch & 1];
-            a.list_out = ws.list[(launch + 1) & 1];
-            // threshold table: launch 0 is ONE iteration of the window-gather kernel for every
-            // track at once (the first move has eight admissible cells), the rest are S deep
-            const bool first_move = thr && launch == 0;
-            const unsigned blocks = kXcd * ((upper + kBlock - 1) / kBlock);
-            int Sl = first_move ? 1 : S;
-            uint32_t vcap_l = ws.cap;
-            long long vstride_l = ws.visit_stride;
-            if (thr && !first_move && cached && !(rec && rec->complete) && grow_steps) {
-                // no visit buffer to fit: only the read-back interval matters.  Once the roam table is in use the
-                // launches are long: a launch lasts as long as its slowest wave (a lane on the slow path --
-                // near-ties, a track that leaves its region on its way out of the basin -- holds its wave
-                // back), and over more steps the waves' slow episodes average out
-                Sl = (roam_ok && roam_ready && stable_roam >= 2) ? roam_steps : 8 * S;
-            } else if (thr && !first_move && (binning_on || tiles_on) && !(rec && rec->complete) && grow_steps) {
-                // Few live tracks left (the long tail of a batch; tracks that wander until max_moves):
-                // the visit buffer then holds MORE iterations of the shrunken lists, and a launch of
-                // up to 8 S steps amortises the per-launch kernels (binning, read-back) over them
-                const uint32_t vc = (blocks / kXcd) * kBlock;                   // slots per list this launch
-                const long long room = (ws.visit_stride * kVisitSteps) / (static_cast<long long>(kXcd) * vc);
-                long long grown = room < 8ll * S ? room : 8ll * S;
-                grown &= ~1ll;
-                if (grown >= S + S / 4) {
-                    Sl = static_cast<int>(grown);
-                    vcap_l = vc;
-                    vstride_l = static_cast<long long>(kXcd) * vc;
-                }
-            }
-            if (std::getenv("SSRS_TRACKS_DEBUG") && (launch < 40 || launch % 500 == 0))
-                fprintf(stderr, "[tracks] launch %d upper %u blocks %u Sl %d binning %d tiles %d scattered %d cached %d cap %u\n", launch, upper, blocks, Sl,
-                        binning_on ? 1 : 0, tiles_on ? 1 : 0, scattered ? 1 : 0, cached ? 1 : 0, ws.cap);
-            a.steps = Sl;
-            a.coherent = (coherent && !first_move) ? 1 : 0;
-            a.ordered = (first_move && a.pf_dir != 0 && lds_rows && p->cols >= kLrCols) ? 1 : 0;
-            a.it_base = thr && launch > 0 ? it_done : 0;
-            a.visits = nullptr;
-            if (!binning_on && scattered && copies_ptr && !copies_live && !cached) {
-                // first scattered launch: zero the private copies, count into them from now on
-                if (hipMemsetAsync(copies_ptr, 0, sizeof(uint32_t) * ncell * ncopies, st) != hipSuccess) {
-                    rc = set_error(SSRS_ERR_HIP, "histogram copies memset failed");
-                    break;
-                }
-                copies_live = true;
-                marks_adjacent = false;
-                a.hist_copies = copies_ptr;
-                a.ncopies = ncopies;
-            }
-            // the first-move launch is one iteration deep: its visits go straight to the histogram
-            // (one binning block for the whole batch took 170 us); generic kernel, plain keys
-            const bool bin_window = binning_on && !first_move, bin_tiles = tiles_on && !first_move;
-            const uint32_t keep_r = a.vis_r, keep_c = a.vis_c;
-            if (first_move) { a.vis_r = static_cast<uint32_t>(p->cols); a.vis_c = 1u; }
-            if (bin_window || bin_tiles) a.visits = ws.visits;
-            a.visit_stride = vstride_l;
-            a.vcap = vcap_l;
-            const uint32_t *rec_counts = nullptr;
-            if (rec && rec->complete) {
-                // this launch's own region of the pool: [counts][slot -> track list][visits]
-                const uint32_t vcap = (blocks / kXcd) * kBlock;
-                const bool identity = a.list_in == nullptr;
-                const size_t list_bytes = identity ? 0 : align_up(sizeof(int32_t) * kXcd * static_cast<size_t>(vcap), 256);
-                const size_t vis_bytes = align_up(sizeof(uint32_t) * kXcd * static_cast<size_t>(vcap) * static_cast<size_t>(Sl), 256);
-                const size_t need = 256 + list_bytes + vis_bytes;
-                if (rec->bytes - rec->used < need) {
-                    rec->complete = 0;           // pool exhausted: the rest of the run is not recorded
-                } else {
-                    char *base = rec->pool + rec->used;
-                    rec->used += need;
-                    TrajChunk ch = {};
-                    ch.counts = reinterpret_cast<const uint32_t *>(base);
-                    ch.list = identity ? nullptr : reinterpret_cast<const int32_t *>(base + 256);
-                    ch.visits = reinterpret_cast<const uint32_t *>(base + 256 + list_bytes);
-                    ch.vcap = vcap;
-                    ch.cap = ws.cap;
-                    ch.steps = Sl;
-                    ch.transposed = (hist_t && bin_window) ? 1 : 0;
-                    hipError_t e1 = hipMemcpyAsync(base, ws.ctl->count[launch & 3], kXcd * sizeof(uint32_t),
-                                                   hipMemcpyDeviceToDevice, st);
-                    hipError_t e2 = identity ? hipSuccess
-                                             : hipMemcpy2DAsync(base + 256, sizeof(int32_t) * vcap, a.list_in,
-                                                                sizeof(int32_t) * ws.cap, sizeof(int32_t) * vcap, kXcd,
-                                                                hipMemcpyDeviceToDevice, st);
-                    if (e1 != hipSuccess || e2 != hipSuccess) { rc = set_error(SSRS_ERR_HIP, "trajectory record copy failed"); break; }
-                    rec->chunks.push_back(ch);
-                    marks_adjacent = false;
-                    a.visits = const_cast<uint32_t *>(ch.visits);
-                    a.visit_stride = static_cast<long long>(kXcd) * vcap;
-                    a.vcap = vcap;
-                    rec_counts = ch.counts;
-                }
-            }
-            if (profile && !marks_adjacent) mark(0);
-            bool is_block_window = false;
-            // 16-bit visit keys: north-bound front through the row window, nothing recorded
-            // (the stepper forms the key base (first start row + iteration - 1) * cols in 32 bits)
-            const bool v16 = thr && bin_window && a.visits == ws.visits && a.pf_dir == 1 && !hist_t && v16_ok &&
-                             (it_done + Sl + 2ll * geom.offset) * p->cols < (1ll << 31);
-            switch (first_move ? mode0 : mode) {
-            case MODE_TABLE:
-                if (thr) {
-                    // front-shaped batches heading north / south get the prefetch wave; once the front has
-                    // outgrown the row window (tile buckets) it streams rows nobody reads: 7.40 -> 7.06 s
-                    // per 100k tracks on the solved 10 m field without it
-                    const bool pf = a.pf_dir != 0 && a.coherent && !scattered && !tiles_on;
-                    // (staged rows: opt-in switch SSRS_TRACKS_LDS_ROWS; the window is kLrCols wide)
-                    const bool lr = pf && p->cols >= kLrCols && lds_rows;
-                    if (v16) {
-                        if (lr) hipLaunchKernelGGL((k_step_thr<4, true, false, true>), dim3(blocks), dim3(kBlock + 64), 0, st, a, thr_prior);
-                        else hipLaunchKernelGGL((k_step_thr<4, true>), dim3(blocks), dim3(kBlock + 64), 0, st, a, thr_prior);
-                        break;
-                    }
-                    const bool rev = thr_prior.rev_ok != 0 && std::getenv("SSRS_TRACKS_NO_REV") == nullptr;
-                    if (cached && !a.visits) {
-                        ++block_window_launches;
-                        batch_block_window = is_block_window = true;
-                        if (roam_ok && roam_ready) {
-                            ++roam_launches;
-                            if (roam_width > 1) {
-                                const unsigned bt = static_cast<unsigned>(roam_width) * kBlock;
-                                const unsigned wblocks = kXcd * ((upper + bt - 1) / bt);
-                                ++roam_wide_launches;
-                                if (roam_width == 2) {
-                                    if (rev) hipLaunchKernelGGL((k_step_roam<true, 2 * kBlock>), dim3(wblocks), dim3(bt), 0, st, a, thr_prior);
-                                    else hipLaunchKernelGGL((k_step_roam<false, 2 * kBlock>), dim3(wblocks), dim3(bt), 0, st, a, thr_prior);
-                                } else {
-                                    if (rev) hipLaunchKernelGGL((k_step_roam<true, 4 * kBlock>), dim3(wblocks), dim3(bt), 0, st, a, thr_prior);
-                                    else hipLaunchKernelGGL((k_step_roam<false, 4 * kBlock>), dim3(wblocks), dim3(bt), 0, st, a, thr_prior);
-                                }
-                            } else if (rev) hipLaunchKernelGGL(k_step_roam<true>, dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
-                            else hipLaunchKernelGGL(k_step_roam<false>, dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
-#ifdef SSRS_DEBUG_WAVE_DUMP
-                            if (a.debug_roam && launch == SSRS_DEBUG_WAVE_DUMP && a.dbg_buf) {
-                                std::vector<unsigned long long> rec(8ull * blocks * (kBlock / 64));
-                                (void)hipStreamSynchronize(st);
-                                (void)hipMemcpy(rec.data(), a.dbg_buf, rec.size() * 8, hipMemcpyDeviceToHost);
-                                // block, wave, live lanes, clocks, pairs, slow pairs, strays, window origin, fast lanes
-                                for (uint32_t w = 0; w < blocks * (kBlock / 64); ++w) {
-                                    const unsigned long long *r = &rec[8ull * w];
-                                    fprintf(stderr, "W %u %u %llu %llu %llu %llu %llu %lld %lld %llu\n", w / (kBlock / 64), w % (kBlock / 64), r[1], r[0], r[2], r[3], r[4],
-                                            static_cast<long long>(r[5]), static_cast<long long>(r[6]), r[7]);
-                                }
-                            }
-#endif
-                            if (a.debug_roam) {
-                                // diagnostics only: one synchronous read of the control block per launch
-                                TrackCtl c;
-                                (void)hipMemcpyAsync(&host_counts[kFinalSlot], ws.ctl, sizeof(TrackCtl), hipMemcpyDeviceToHost, st);
-                                (void)hipStreamSynchronize(st);
-                                memcpy(&c, &host_counts[kFinalSlot], sizeof(TrackCtl));
-                                if (c.dbg_waves)
-                                    fprintf(stderr, "[roam] launch %d blocks %u Sl %d: %llu waves, mean %.0f clk, max %.0f clk (x%.2f); slowest-by-slow-pairs wave: %llu of %llu pairs slow\n",
-                                            launch, blocks, Sl, c.dbg_waves, static_cast<double>(c.dbg_tsum) / c.dbg_waves, static_cast<double>(c.dbg_tmax),
-                                            static_cast<double>(c.dbg_tmax) * c.dbg_waves / static_cast<double>(c.dbg_tsum), c.dbg_slowmax >> 32, c.dbg_slowmax & 0xFFFFFFFFull);
-                                (void)hipMemsetAsync(&ws.ctl->dbg_tsum, 0, 4 * sizeof(unsigned long long), st);
-                            }
-                            break;
-                        }
-                        if (rev) hipLaunchKernelGGL((k_step_thr<6, false, true>), dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
-                        else hipLaunchKernelGGL((k_step_thr<6>), dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
-                        break;
-                    }
-                    if (a.visits && hist_t && binning_on) hipLaunchKernelGGL((k_step_thr<2>), dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
-                    else if (a.visits && lr) hipLaunchKernelGGL((k_step_thr<1, true, false, true>), dim3(blocks), dim3(kBlock + 64), 0, st, a, thr_prior);
-                    else if (a.visits && pf) hipLaunchKernelGGL((k_step_thr<1, true>), dim3(blocks), dim3(kBlock + 64), 0, st, a, thr_prior);
-                    else if (a.visits && rev) hipLaunchKernelGGL((k_step_thr<1, false, true>), dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
-                    else if (a.visits) hipLaunchKernelGGL((k_step_thr<1>), dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
-                    else if (a.hist && pf) hipLaunchKernelGGL((k_step_thr<3, true>), dim3(blocks), dim3(kBlock + 64), 0, st, a, thr_prior);
-                    else if (a.hist && rev) hipLaunchKernelGGL((k_step_thr<3, false, true>), dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
-                    else if (a.hist) hipLaunchKernelGGL((k_step_thr<3>), dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
-                    else if (pf) hipLaunchKernelGGL((k_step_thr<0, true>), dim3(blocks), dim3(kBlock + 64), 0, st, a, thr_prior);
-                    else if (rev) hipLaunchKernelGGL((k_step_thr<0, false, true>), dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
-                    else hipLaunchKernelGGL((k_step_thr<0>), dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
-                    break;
-                }
-                // (the zero-mask variant only pays under in-stepper atomics: with tile buckets it
-                // was measured slower, 7.0 -> 8.3 s per 100k wandering tracks)
-                if (ring && scattered && !binning_on && !tiles_on) hipLaunchKernelGGL((k_step_lean<true, true>), dim3(blocks), dim3(kBlock), 0, st, a);
-                else if (ring && hist_t && binning_on) hipLaunchKernelGGL((k_step_lean<true, false, true>), dim3(blocks), dim3(kBlock), 0, st, a);
-                else if (ring) hipLaunchKernelGGL((k_step_lean<true, false>), dim3(blocks), dim3(kBlock), 0, st, a);
-                else if (lean && a.fast && (S & 1) == 0 && hist_t && binning_on) hipLaunchKernelGGL((k_step_lean<false, false, true>), dim3(blocks), dim3(kBlock), 0, st, a);
-                else if (lean && a.fast && (S & 1) == 0) hipLaunchKernelGGL((k_step_lean<false, false>), dim3(blocks), dim3(kBlock), 0, st, a);
-                else hipLaunchKernelGGL(k_step_tracks<MODE_TABLE>, dim3(blocks), dim3(kBlock), 0, st, a);
-                break;
-            case MODE_FLUIDFLOW: hipLaunchKernelGGL(k_step_tracks<MODE_FLUIDFLOW>, dim3(blocks), dim3(kBlock), 0, st, a); break;
-            case MODE_UPDRAFT: hipLaunchKernelGGL(k_step_tracks<MODE_UPDRAFT>, dim3(blocks), dim3(kBlock), 0, st, a); break;
-            default: hipLaunchKernelGGL(k_step_tracks<MODE_PRIOR>, dim3(blocks), dim3(kBlock), 0, st, a); break;
-            }
-            if (profile) mark(is_block_window ? 3 : 1);      // end of the stepper launch
-            if (bin_window) {
-                ++window_launches;
-                if (v16) {
-                    uint32_t *out = (j == depth - 1 && direct_read_back) ? &host_counts[kSlotWords * slot] : nullptr;
-                    hipLaunchKernelGGL(k_bin_visits16, dim3((Sl + 1) / 2), dim3(kBinThreads), 0, st, reinterpret_cast<const uint16_t *>(a.visits),
-                                       a.visit_stride, Sl, ws.ctl, launch & 3, hist, p->rows, p->cols, a.vcap, a.v16_offset, a.it_base,
-                                       out, kSlotWords);
-                    read_back_done = out != nullptr;
-                }
-                else if (hist_t)
-                    hipLaunchKernelGGL(k_bin_visits, dim3(Sl), dim3(kBinThreads), 0, st, a.visits, a.visit_stride,
-                                       ws.ctl, launch & 3, hist_t, p->cols, p->rows, a.vcap);
-                else
-                    hipLaunchKernelGGL(k_bin_visits, dim3(Sl), dim3(kBinThreads), 0, st, a.visits, a.visit_stride,
-                                       ws.ctl, launch & 3, hist, p->rows, p->cols, a.vcap);
-                if (profile && !read_back_done) mark(2);      // (else the batch's event below is this mark)
-            }
-            if (bin_tiles) {
-                ++tile_launches;
-                const double inv_cols = 1.0 / static_cast<double>(p->cols);
-                const uint32_t ucols = static_cast<uint32_t>(p->cols), ucell = static_cast<uint32_t>(ncell);
-                (void)hipMemsetAsync(ws.tile_count, 0, sizeof(uint32_t) * ntiles, st);
-                hipLaunchKernelGGL((k_tile_sort<false>), dim3(blocks, kStepSplit), dim3(kBlock), 0, st, a.visits, a.visit_stride, Sl,
-                                   ws.ctl, launch & 3, ucols, inv_cols, ucell, a.vcap, ntc, ntiles, ws.tile_count,
-                                   ws.tile_cursor, ws.bucket);
-                hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(kTileThreads), 0, st, ws.tile_count, ntiles, ws.tile_start,
-                                   ws.tile_cursor, ws.item_start);
-                hipLaunchKernelGGL((k_tile_sort<true>), dim3(blocks, kStepSplit), dim3(kBlock), 0, st, a.visits, a.visit_stride, Sl,
-                                   ws.ctl, launch & 3, ucols, inv_cols, ucell, a.vcap, ntc, ntiles, ws.tile_count,
-                                   ws.tile_cursor, ws.bucket);
-                // at most S visits per slot of the launch, and one partly filled item per tile
-                const unsigned long long max_visits = static_cast<unsigned long long>(blocks) * kBlock * Sl;
-                const unsigned items = static_cast<unsigned>(max_visits / kItemVisits) + ntiles;
-                hipLaunchKernelGGL(k_bin_bucket, dim3(items), dim3(kTileThreads), 0, st, ws.bucket, ws.tile_start,
-                                   ws.tile_count, ws.ctl, hist, static_cast<uint32_t>(p->rows), ucols, inv_cols, ntc,
-                                   ntiles, ws.item_start);
-                if (profile) mark(2);
-            }
-            if (rec_counts && hist && !bin_window && !bin_tiles) {    // recorded launch outside both binning paths
-                hipLaunchKernelGGL(k_count_visits, dim3(blocks), dim3(kBlock), 0, st, a.visits, a.vcap, Sl, rec_counts, hist,
-                                   static_cast<uint32_t>(ncell));
-                marks_adjacent = false;
-            }
-            a.vis_r = keep_r;
-            a.vis_c = keep_c;
-            if (thr && !first_move) it_done += Sl;
-            last_Sl = Sl;
-            if (hipGetLastError() != hipSuccess) { rc = set_error(SSRS_ERR_HIP, "stepper launch failed"); break; }
-        }
-        if (rc != SSRS_OK) break;
-        if (hist64 && cached && (batches & 1)) {          // (block windows flush whole launches' counts at once)
-            hipLaunchKernelGGL(k_drain64, dim3(4096), dim3(kBlock), 0, st, hist, hist64, ncell);
-            marks_adjacent = false;
-        }
-        // survivors of this batch = input count of the next launch
-        // ring slot = the head of the control block in one copy: [4][8] list counts, error, par_min,
-        // steps (2 words), strays (2 words); the row this batch's survivors went to is count[launch & 3]
-        bool queued = read_back_done || hipMemcpyAsync(&host_counts[kSlotWords * slot], ws.ctl, kSlotWords * sizeof(uint32_t),
-                                                       hipMemcpyDeviceToHost, st) == hipSuccess;
-        if (queued && profile) {
-            const size_t before = ev_marks.size();
-            mark(read_back_done ? 2 : 0);
-            queued = ev_marks.size() > before;
-            if (queued) ev_batch[slot] = ev_marks.back();
-        } else if (queued) {
-            queued = hipEventRecord(ev_batch[slot], st) == hipSuccess;
-            marks_adjacent = false;
-        }
-        if (!queued) {
-            rc = set_error(SSRS_ERR_HIP, "live-count read-back failed");
-            break;
-        }
-        slot_row[slot] = launch & 3;
-        slot_block_window[slot] = batch_block_window;
-        ++batches;
-        // examine every batch but the one just queued (it keeps the GPU busy)
-        while (checked < batches - 1) {
-            const int cs = checked % kRing;
-            if (hipEventSynchronize(ev_batch[cs]) != hipSuccess) { rc = set_error(SSRS_ERR_HIP, "event sync failed"); break; }
-            uint32_t c = 0;                         // longest list
-            const uint32_t *cnt = &host_counts[kSlotWords * cs + kXcd * slot_row[cs]];
-            for (int x = 0; x < kXcd; ++x) c = cnt[x] > c ? cnt[x] : c;
-            unsigned long long tot[2];
-            memcpy(tot, &host_counts[kSlotWords * cs + offsetof(TrackCtl, steps) / sizeof(uint32_t)], sizeof(tot));
-            ++checked;
-            if (slot_block_window[cs]) block_window_steps += static_cast<long long>(tot[0] - seen_steps);
-            if (c == 0) { finished = true; break; }
-            // the live count only shrinks, a stale bound is safe -- except across a wander sort
-            upper = (checked - 1 >= upper_from || c > upper) ? c : upper;
-            uint32_t total = 0;
-            for (int x = 0; x < kXcd; ++x) total += cnt[x];
-            if (tiles_on && cache_ok && !force_tiles && a.pf_dir != 0) {
-                // a front that outgrew the row window goes through tile buckets while part of the batch
-                // still travels; once nobody finishes any more (the survivors roam their basins until
-                // max_moves) the block windows take over
-                // (nobody finishing YET is not stable: some must have finished, or the batch is older
-                // than two raster crossings)
-                const bool started = static_cast<long long>(total) * 50 < static_cast<long long>(ntracks) * 49 ||
-                                     it_done > 2ll * (p->rows + p->cols);
-                if (started && prev_total != 0 && total >= prev_total - prev_total / 32 && ++stable_batches >= 2) {
-                    tiles_on = false;
-                    cached = true;
-                    want_wander_sort = true;
-                }
-                if (prev_total == 0 || total < prev_total - prev_total / 32) stable_batches = 0;
-            }
-            prev_total = total;
-            if (thr && may_rebalance) {
-                if (rebalance_cooldown > 0) --rebalance_cooldown;
-                else if (c >= 1024 && 5ull * c >= static_cast<unsigned long long>(total) + 64ull) want_rebalance = true;   // longest list >= 1.6 x the mean
-            }
-            // binning pays only while the batch moves as a front: once more than a
-            // quarter of a batch's visits miss the LDS window, later launches go back
-            // to in-stepper atomics
-            if (binning_on || tiles_on) {
-                // row window: strays = visits outside it (stop above a quarter); tiles:
-                // strays = cells flushed (stop below two visits per cell)
-                // (batches queued before a switch still report the old path's strays)
-                const unsigned long long dsteps = tot[0] - seen_steps, dstray = tot[1] - seen_strays;
-                if (checked - 1 >= judge_from && dsteps > 0 && dstray * (tiles_on ? 2 : 4) > dsteps && !force_tiles) {
-                    judge_from = batches;
-                    if (binning_on && cache_ok && !tiles_ok) {
-                        // the front has outgrown the row window and there are no tile buckets
-                        binning_on = false;
-                        cached = true;
-                        want_wander_sort = true;
-                        a.vis_r = static_cast<uint32_t>(p->cols);
-                        a.vis_c = 1u;
-                    } else if (binning_on && tiles_ok) {
-                        // the front has outgrown the row window; its visits may still cluster
-                        binning_on = false;
-                        tiles_on = true;
-                        a.vis_r = static_cast<uint32_t>(p->cols);      // plain visit keys from now on
-                        a.vis_c = 1u;
-                    } else {
-                        binning_on = tiles_on = false;
-                        a.vis_r = static_cast<uint32_t>(p->cols);
-                        a.vis_c = 1u;
-                        scattered = !never_scattered;      // no front any more: zero-mask variant
-                        cached = cache_ok && scattered;
-                        want_wander_sort = cached;
-                    }
-                }
-            }
-            if (cached && !(binning_on || tiles_on)) {
-                // block windows: strays = visits outside them.  Tracks still on their way into a basin
-                // (or out of their block's box) show up here: sort again, a few times at most
-                const unsigned long long dsteps = tot[0] - seen_steps, dstray = tot[1] - seen_strays;
-                if (std::getenv("SSRS_TRACKS_DEBUG") && checked < 60)
-                    fprintf(stderr, "[tracks] batch %d block windows: %llu steps, %llu strays (%.3f), live %u\n", checked, dsteps, dstray,
-                            dsteps ? static_cast<double>(dstray) / static_cast<double>(dsteps) : 0.0, total);
-                if (wander_cooldown > 0) --wander_cooldown;
-                else if (dsteps > 0 && dstray * 64 > dsteps && wander_sorts < 12) want_wander_sort = true;
-                else if (roam_shuffle > 0 && ++since_shuffle >= roam_shuffle && stable_roam >= 2 && roam_ready) {
-                    want_wander_sort = true;            // settled: every roam_shuffle batches the windows' tracks are dealt afresh
-                    sort_is_periodic = true;
-                    since_shuffle = 0;
-                } else ++stable_roam;                   // settled in its windows: the launches may grow
-            }
-            // batches that never binned (small, unsorted, very wide rasters) give no stray
-            // signal: tracks still alive after four raster crossings are wandering
-            if (!binning_on && !tiles_on && !scattered && !never_scattered &&
-                (thr ? it_done : static_cast<long long>(launch) * S) > 4ll * (p->rows + p->cols)) {
-                scattered = true;
-                if (cache_ok && !cached) { cached = true; want_wander_sort = true; }
-            }
-            seen_steps = tot[0];
-            seen_strays = tot[1];
+
+    pol.thr = thr; pol.tiles_ok = tiles_ok; pol.cache_ok = cache_ok; pol.never_scattered = never_scattered;
+    pol.front = a.pf_dir != 0; pol.may_rebalance = sw.rebalance; pol.debug = sw.debug; pol.roam_shuffle = sw.roam_shuffle;
+    pol.ntracks = ntracks; pol.crossing = p->rows + p->cols;
+    pol.binning_on = binning_on; pol.tiles_on = tiles_on; pol.scattered = scattered;
+    pol.cached = cache_ok && scattered;
+    pol.want_wander_sort = pol.cached;
+    pol.upper = static_cast<uint32_t>(ntracks < static_cast<int64_t>(ws.cap) ? ntracks : ws.cap);
+    // (profile mode: every batch gets its own event, which is also the start mark of the next launch)
+    ev.own_batch = !profile;
+    if (!profile)
+        for (int i = 0; i < kRing; ++i) SSRS_HIP_CHECK(hipEventCreate(&ev.batch[i]));
+    return SSRS_OK;
+}
+
+// Steps of a launch.  A launch that grows past S in binning mode covers fewer slots per list in the visit buffer
+// (*vcap, *vstride: the launch's own bound)
+int TrackRun::launch_steps(bool first_move, unsigned blocks, uint32_t *vcap, long long *vstride) const
+{
+    *vcap = ws.cap;
+    *vstride = ws.visit_stride;
+    if (first_move) return 1;
+    const bool recording = c.rec && c.rec->complete;
+    if (thr && pol.cached && !recording && sw.grow_steps) {
+        // no visit buffer to fit: only the read-back interval matters.  Once the roam table is in use the
+        // launches are long: a launch lasts as long as its slowest wave (a lane on the slow path --
+        // near-ties, a track that leaves its region on its way out of the basin -- holds its wave
+        // back), and over more steps the waves' slow episodes average out
+        // (128 S steps: 4096: 0.0073, 16384: 0.0060, 65536: 0.0053 ns per step at C2)
+        return (roam_ok && roam_ready && pol.stable_roam >= 2) ? 128 * S : 8 * S;
+    }
+    if (thr && (pol.binning_on || pol.tiles_on) && !recording && sw.grow_steps) {
+        // Few live tracks left (the long tail of a batch; tracks that wander until max_moves):
+        // the visit buffer then holds MORE iterations of the shrunken lists, and a launch of
+        // up to 8 S steps amortises the per-launch kernels (binning, read-back) over them
+        const uint32_t vc = (blocks / kXcd) * kBlock;                   // slots per list this launch
+        const long long room = (ws.visit_stride * kVisitSteps) / (static_cast<long long>(kXcd) * vc);
+        long long grown = room < 8ll * S ? room : 8ll * S;
+        grown &= ~1ll;
+        if (grown >= S + S / 4) {
+            *vcap = vc;
+            *vstride = static_cast<long long>(kXcd) * vc;
+            return static_cast<int>(grown);
         }
     }
-    if (copies_live && rc == SSRS_OK)
+    return S;
+}
+
+// Trajectory recorder: this launch's own region of the pool, [counts][slot -> track list][visits]; the launch
+// writes its visits there.  *rec_counts: the region's counts, or nullptr once the pool is exhausted
+int TrackRun::record_launch(unsigned blocks, int Sl, bool bin_window, const uint32_t **rec_counts)
+{
+    SsrsTrajRecorder *rec = c.rec;
+    const uint32_t vcap = (blocks / kXcd) * kBlock;
+    const bool identity = a.list_in == nullptr;
+    const size_t list_bytes = identity ? 0 : align_up(sizeof(int32_t) * kXcd * static_cast<size_t>(vcap), 256);
+    const size_t vis_bytes = align_up(sizeof(uint32_t) * kXcd * static_cast<size_t>(vcap) * static_cast<size_t>(Sl), 256);
+    const size_t need = 256 + list_bytes + vis_bytes;
+    if (rec->bytes - rec->used < need) {
+        rec->complete = 0;           // pool exhausted: the rest of the run is not recorded
+        return SSRS_OK;
+    }
+    char *base = rec->pool + rec->used;
+    rec->used += need;
+    TrajChunk ch = {};
+    ch.counts = reinterpret_cast<const uint32_t *>(base);
+    ch.list = identity ? nullptr : reinterpret_cast<const int32_t *>(base + 256);
+    ch.visits = reinterpret_cast<const uint32_t *>(base + 256 + list_bytes);
+    ch.vcap = vcap;
+    ch.cap = ws.cap;
+    ch.steps = Sl;
+    ch.transposed = (hist_t && bin_window) ? 1 : 0;
+    hipError_t e1 = hipMemcpyAsync(base, ws.ctl->count[launch & 3], kXcd * sizeof(uint32_t),
+                                   hipMemcpyDeviceToDevice, st);
+    hipError_t e2 = identity ? hipSuccess
+                             : hipMemcpy2DAsync(base + 256, sizeof(int32_t) * vcap, a.list_in,
+                                                sizeof(int32_t) * ws.cap, sizeof(int32_t) * vcap, kXcd,
+                                                hipMemcpyDeviceToDevice, st);
+    if (e1 != hipSuccess || e2 != hipSuccess) return set_error(SSRS_ERR_HIP, "trajectory record copy failed");
+    rec->chunks.push_back(ch);
+    marks_adjacent = false;
+    a.visits = const_cast<uint32_t *>(ch.visits);
+    a.visit_stride = static_cast<long long>(kXcd) * vcap;
+    a.vcap = vcap;
+    *rec_counts = ch.counts;
+    return SSRS_OK;
+}
+
+// The stepper kernel of a launch, by movement model, data path and the batch's path.  *block_window: the launch
+// counts in block windows (k_step_thr<6>, k_step_roam)
+void TrackRun::launch_stepper(bool first_move, bool v16, unsigned blocks, int Sl, bool *block_window)
+{
+    const bool binning_on = pol.binning_on, tiles_on = pol.tiles_on, scattered = pol.scattered;
+    switch (first_move ? mode0 : mode) {
+    case MODE_TABLE:
+        if (thr) {
+            // front-shaped batches heading north / south get the prefetch wave; once the front has
+            // outgrown the row window (tile buckets) it streams rows nobody reads: 7.40 -> 7.06 s
+            // per 100k tracks on the solved 10 m field without it
+            const bool pf = a.pf_dir != 0 && a.coherent && !scattered && !tiles_on;
+            if (v16) {
+                hipLaunchKernelGGL((k_step_thr<4, true>), dim3(blocks), dim3(kBlock + 64), 0, st, a, thr_prior);
+                return;
+            }
+            if (pol.cached && !a.visits) {
+                ++block_window_launches;
+                *block_window = true;
+                if (roam_ok && roam_ready) {
+                    ++roam_launches;
+                    if (roam_width > 1) {
+                        const unsigned bt = static_cast<unsigned>(roam_width) * kBlock;
+                        const unsigned wblocks = kXcd * ((pol.upper + bt - 1) / bt);
+                        ++roam_wide_launches;
+                        if (roam_width == 2) {
+                            if (rev) hipLaunchKernelGGL((k_step_roam<true, 2 * kBlock>), dim3(wblocks), dim3(bt), 0, st, a, thr_prior);
+                            else hipLaunchKernelGGL((k_step_roam<false, 2 * kBlock>), dim3(wblocks), dim3(bt), 0, st, a, thr_prior);
+                        } else {
+                            if (rev) hipLaunchKernelGGL((k_step_roam<true, 4 * kBlock>), dim3(wblocks), dim3(bt), 0, st, a, thr_prior);
+                            else hipLaunchKernelGGL((k_step_roam<false, 4 * kBlock>), dim3(wblocks), dim3(bt), 0, st, a, thr_prior);
+                        }
+                    } else if (rev) hipLaunchKernelGGL(k_step_roam<true>, dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
+                    else hipLaunchKernelGGL(k_step_roam<false>, dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
+#ifdef SSRS_DEBUG_WAVE_DUMP
+                    if (a.debug_roam && launch == SSRS_DEBUG_WAVE_DUMP && a.dbg_buf) {
+                        std::vector<unsigned long long> rec(8ull * blocks * (kBlock / 64));
+                        (void)hipStreamSynchronize(st);
+                        (void)hipMemcpy(rec.data(), a.dbg_buf, rec.size() * 8, hipMemcpyDeviceToHost);
+                        // block, wave, live lanes, clocks, pairs, slow pairs, strays, window origin, fast lanes
+                        for (uint32_t w = 0; w < blocks * (kBlock / 64); ++w) {
+                            const unsigned long long *r = &rec[8ull * w];
+                            fprintf(stderr, "W %u %u %llu %llu %llu %llu %llu %lld %lld %llu\n", w / (kBlock / 64), w % (kBlock / 64), r[1], r[0], r[2], r[3], r[4],
+                                    static_cast<long long>(r[5]), static_cast<long long>(r[6]), r[7]);
+                        }
+                    }
+#endif
+                    if (a.debug_roam) {
+                        // diagnostics only: one synchronous read of the control block per launch
+                        TrackCtl cb;
+                        (void)hipMemcpyAsync(&host_counts[kFinalSlot], ws.ctl, sizeof(TrackCtl), hipMemcpyDeviceToHost, st);
+                        (void)hipStreamSynchronize(st);
+                        memcpy(&cb, &host_counts[kFinalSlot], sizeof(TrackCtl));
+                        if (cb.dbg_waves)
+                            fprintf(stderr, "[roam] launch %d blocks %u Sl %d: %llu waves, mean %.0f clk, max %.0f clk (x%.2f); slowest-by-slow-pairs wave: %llu of %llu pairs slow\n",
+                                    launch, blocks, Sl, cb.dbg_waves, static_cast<double>(cb.dbg_tsum) / cb.dbg_waves, static_cast<double>(cb.dbg_tmax),
+                                    static_cast<double>(cb.dbg_tmax) * cb.dbg_waves / static_cast<double>(cb.dbg_tsum), cb.dbg_slowmax >> 32, cb.dbg_slowmax & 0xFFFFFFFFull);
+                        (void)hipMemsetAsync(&ws.ctl->dbg_tsum, 0, 4 * sizeof(unsigned long long), st);
+                    }
+                    return;
+                }
+                if (rev) hipLaunchKernelGGL((k_step_thr<6, false, true>), dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
+                else hipLaunchKernelGGL((k_step_thr<6>), dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
+                return;
+            }
+            if (a.visits && hist_t && binning_on) hipLaunchKernelGGL((k_step_thr<2>), dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
+            else if (a.visits && pf) hipLaunchKernelGGL((k_step_thr<1, true>), dim3(blocks), dim3(kBlock + 64), 0, st, a, thr_prior);
+            else if (a.visits && rev) hipLaunchKernelGGL((k_step_thr<1, false, true>), dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
+            else if (a.visits) hipLaunchKernelGGL((k_step_thr<1>), dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
+            else if (a.hist && pf) hipLaunchKernelGGL((k_step_thr<3, true>), dim3(blocks), dim3(kBlock + 64), 0, st, a, thr_prior);
+            else if (a.hist && rev) hipLaunchKernelGGL((k_step_thr<3, false, true>), dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
+            else if (a.hist) hipLaunchKernelGGL((k_step_thr<3>), dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
+            else if (pf) hipLaunchKernelGGL((k_step_thr<0, true>), dim3(blocks), dim3(kBlock + 64), 0, st, a, thr_prior);
+            else if (rev) hipLaunchKernelGGL((k_step_thr<0, false, true>), dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
+            else hipLaunchKernelGGL((k_step_thr<0>), dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
+            return;
+        }
+        // (the zero-mask variant only pays under in-stepper atomics: with tile buckets it
+        // was measured slower, 7.0 -> 8.3 s per 100k wandering tracks)
+        if (ring && scattered && !binning_on && !tiles_on) hipLaunchKernelGGL((k_step_lean<true, true>), dim3(blocks), dim3(kBlock), 0, st, a);
+        else if (ring && hist_t && binning_on) hipLaunchKernelGGL((k_step_lean<true, false, true>), dim3(blocks), dim3(kBlock), 0, st, a);
+        else if (ring) hipLaunchKernelGGL((k_step_lean<true, false>), dim3(blocks), dim3(kBlock), 0, st, a);
+        else if (lean && a.fast && (S & 1) == 0 && hist_t && binning_on) hipLaunchKernelGGL((k_step_lean<false, false, true>), dim3(blocks), dim3(kBlock), 0, st, a);
+        else if (lean && a.fast && (S & 1) == 0) hipLaunchKernelGGL((k_step_lean<false, false>), dim3(blocks), dim3(kBlock), 0, st, a);
+        else hipLaunchKernelGGL(k_step_tracks<MODE_TABLE>, dim3(blocks), dim3(kBlock), 0, st, a);
+        return;
+    case MODE_FLUIDFLOW: hipLaunchKernelGGL(k_step_tracks<MODE_FLUIDFLOW>, dim3(blocks), dim3(kBlock), 0, st, a); return;
+    case MODE_UPDRAFT: hipLaunchKernelGGL(k_step_tracks<MODE_UPDRAFT>, dim3(blocks), dim3(kBlock), 0, st, a); return;
+    default: hipLaunchKernelGGL(k_step_tracks<MODE_PRIOR>, dim3(blocks), dim3(kBlock), 0, st, a); return;
+    }
+}
+
+// The histogram of a launch's visits: the row window (16- or 32-bit keys), the tile buckets, or plain atomics for
+// a recorded launch outside both.  read_back: the batch's read-back slot when the 16-bit binning kernel may write
+// it itself (the batch's last launch), or nullptr
+void TrackRun::bin_launch(unsigned blocks, int Sl, bool bin_window, bool bin_tiles, bool v16, const uint32_t *rec_counts,
+                          uint32_t *read_back, bool *read_back_done)
+{
+    uint32_t *const hist = c.hist;
+    if (bin_window) {
+        ++window_launches;
+        if (v16) {
+            hipLaunchKernelGGL(k_bin_visits16, dim3((Sl + 1) / 2), dim3(kBinThreads), 0, st, reinterpret_cast<const uint16_t *>(a.visits),
+                               a.visit_stride, Sl, ws.ctl, launch & 3, hist, p->rows, p->cols, a.vcap, a.v16_offset, a.it_base,
+                               read_back, kSlotWords);
+            *read_back_done = read_back != nullptr;
+        }
+        else if (hist_t)
+            hipLaunchKernelGGL(k_bin_visits, dim3(Sl), dim3(kBinThreads), 0, st, a.visits, a.visit_stride,
+                               ws.ctl, launch & 3, hist_t, p->cols, p->rows, a.vcap);
+        else
+            hipLaunchKernelGGL(k_bin_visits, dim3(Sl), dim3(kBinThreads), 0, st, a.visits, a.visit_stride,
+                               ws.ctl, launch & 3, hist, p->rows, p->cols, a.vcap);
+        if (profile && !*read_back_done) mark(2);      // (else the batch's event below is this mark)
+    }
+    if (bin_tiles) {
+        ++tile_launches;
+        const double inv_cols = 1.0 / static_cast<double>(p->cols);
+        const uint32_t ucols = static_cast<uint32_t>(p->cols), ucell = static_cast<uint32_t>(ncell);
+        (void)hipMemsetAsync(ws.tile_count, 0, sizeof(uint32_t) * ntiles, st);
+        hipLaunchKernelGGL((k_tile_sort<false>), dim3(blocks, kStepSplit), dim3(kBlock), 0, st, a.visits, a.visit_stride, Sl,
+                           ws.ctl, launch & 3, ucols, inv_cols, ucell, a.vcap, ntc, ntiles, ws.tile_count,
+                           ws.tile_cursor, ws.bucket);
+        hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(kTileThreads), 0, st, ws.tile_count, ntiles, ws.tile_start,
+                           ws.tile_cursor, ws.item_start);
+        hipLaunchKernelGGL((k_tile_sort<true>), dim3(blocks, kStepSplit), dim3(kBlock), 0, st, a.visits, a.visit_stride, Sl,
+                           ws.ctl, launch & 3, ucols, inv_cols, ucell, a.vcap, ntc, ntiles, ws.tile_count,
+                           ws.tile_cursor, ws.bucket);
+        // at most S visits per slot of the launch, and one partly filled item per tile
+        const unsigned long long max_visits = static_cast<unsigned long long>(blocks) * kBlock * Sl;
+        const unsigned items = static_cast<unsigned>(max_visits / kItemVisits) + ntiles;
+        hipLaunchKernelGGL(k_bin_bucket, dim3(items), dim3(kTileThreads), 0, st, ws.bucket, ws.tile_start,
+                           ws.tile_count, ws.ctl, hist, static_cast<uint32_t>(p->rows), ucols, inv_cols, ntc,
+                           ntiles, ws.item_start);
+        if (profile) mark(2);
+    }
+    if (rec_counts && hist && !bin_window && !bin_tiles) {    // recorded launch outside both binning paths
+        hipLaunchKernelGGL(k_count_visits, dim3(blocks), dim3(kBlock), 0, st, a.visits, a.vcap, Sl, rec_counts, hist,
+                           static_cast<uint32_t>(ncell));
+        marks_adjacent = false;
+    }
+}
+
+// Pseudo-launch: list[launch & 1] -> windows, keys, sort -> padded deal into list[(launch + 1) & 1]
+int TrackRun::wander_sort()
+{
+    const uint32_t slots = ws.cap * kXcd;
+    uint32_t *k0 = reinterpret_cast<uint32_t *>(ws.keys[0]), *k1 = reinterpret_cast<uint32_t *>(ws.keys[1]);
+    int32_t *sorted = reinterpret_cast<int32_t *>(ws.bucket);
+    hipLaunchKernelGGL(k_wander_windows, dim3(1), dim3(1024), 0, st, ws.list[launch & 1], ws.state, ws.ctl, launch & 3, ws.cap,
+                       p->rows, p->cols, ws.wander);
+    hipLaunchKernelGGL(k_wander_keys, dim3((slots + kBlock - 1) / kBlock), dim3(kBlock), 0, st, ws.list[launch & 1], ws.state,
+                       ws.ctl, launch & 3, ws.cap, ws.wander, k0, pol.sort_is_periodic ? static_cast<uint32_t>(launch) : 0u);
+    size_t temp_bytes = ws.sort_temp_bytes;
+    if (hipcub::DeviceRadixSort::SortPairs(ws.sort_temp, temp_bytes, k0, k1, ws.list[launch & 1], sorted,
+                                           static_cast<int>(slots), 0, 13, st) != hipSuccess)
+        return set_error(SSRS_ERR_HIP, "wander sort failed");
+    // block width of the deal: 512-lane blocks when more tracks are alive than one round of 256-lane blocks holds (216 x 512
+    // in one round; beyond that several rounds either way, 512 lanes never slower: profiles/r04_roam_fill.txt; 1024-lane
+    // blocks measured 3-4x slower than either -- four waves per SIMD and a launch that ends with its first wave --,
+    // SSRS_TRACKS_ROAM_WIDTH=4 keeps the A/B).  The lists' lengths count tombstones and padding, so the width goes by
+    // the live tracks k_wander_windows has just counted: one word read back synchronously, and only when the lists are
+    // long enough for the question to arise
+    roam_width = 1;
+    if (roam_ok && sw.deal_contiguous) {
+        if (sw.roam_wide_from == 1) {
+            roam_width = 2;
+        } else if (sw.roam_wide_from > 1 && static_cast<long long>(pol.prev_total) >= sw.roam_wide_from) {
+            uint32_t *word = &host_counts[kFinalSlot];
+            if (hipMemcpyAsync(word, &ws.ctl->deal_live, sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipStreamSynchronize(st) != hipSuccess)
+                return set_error(SSRS_ERR_HIP, "live-count read-back at the deal failed");
+            if (static_cast<long long>(*word) >= sw.roam_wide_from) roam_width = 2;
+        }
+        if (sw.roam_width) roam_width = sw.roam_width;
+    }
+    hipLaunchKernelGGL(k_deal_sorted, dim3(64), dim3(1024), 0, st, k1, sorted, ws.list[(launch + 1) & 1], ws.ctl,
+                       (launch + 1) & 3, (launch + 2) & 3, ws.cap, sw.deal_contiguous ? 1 : 0, roam_width);
+    ++launch;
+    marks_adjacent = false;
+    pol.dealt(batches, ws.cap, sw.deal_contiguous, roam_width);
+    return SSRS_OK;
+}
+
+// The batch starts to roam: the pair table, for the whole raster (~2 ms at 5000 x 6000), and the fine table
+void TrackRun::build_roam_tables()
+{
+    const char *tabc = reinterpret_cast<const char *>(c.table);
+    const unsigned grid = 256 * 16;
+    if (rev) hipLaunchKernelGGL(k_roam_build<true>, dim3(grid), dim3(kBlock), 0, st, tabc, a.guard, a.plane_shift, p->rows, p->cols,
+                                ws.roam, thr_prior);
+    else hipLaunchKernelGGL(k_roam_build<false>, dim3(grid), dim3(kBlock), 0, st, tabc, a.guard, a.plane_shift, p->rows, p->cols,
+                            ws.roam, thr_prior);
+    if (a.fine) {
+        FinePrior fp;
+        fine_prior_tables(p->prior, &fp);
+        const int tx = (p->cols + kTabW - 1) / kTabW, ty = (p->rows + kTabH - 1) / kTabH, nt = tx * ty;
+        FineEntry *fine_out = reinterpret_cast<FineEntry *>(const_cast<void *>(a.fine));
+        if (c.potential) hipLaunchKernelGGL(k_fine_build<true>, dim3(static_cast<unsigned>(nt)), dim3(kBlock), 0, st, c.updraft, c.potential,
+                                            fine_out, p->rows, p->cols, tx, nt, fp);
+        else hipLaunchKernelGGL(k_fine_build<false>, dim3(static_cast<unsigned>(nt)), dim3(kBlock), 0, st, c.updraft, c.potential,
+                                fine_out, p->rows, p->cols, tx, nt, fp);
+    }
+    roam_ready = true;
+    marks_adjacent = false;
+}
+
+// Pseudo-launch: list[launch & 1] -> list[(launch + 1) & 1], counts likewise
+void TrackRun::rebalance()
+{
+    hipLaunchKernelGGL(k_rebalance_lists, dim3(1), dim3(1024), 0, st, ws.list[launch & 1], ws.list[(launch + 1) & 1],
+                       ws.ctl, launch & 3, (launch + 1) & 3, (launch + 2) & 3, ws.cap);
+    marks_adjacent = false;
+    ++launch;
+    pol.rebalanced();
+}
+
+// One batch: its launches, each with its binning, then the read-back of its live counts into a ring slot
+int TrackRun::queue_batch()
+{
+    // one launch per batch while launches are long and few (the host then sees the batch die one
+    // launch earlier: one empty launch at the end of a short run instead of two); two otherwise
+    const int depth = (thr && last_Sl >= 512 && launch < 24) ? 1 : kBatch;
+    const int slot = batches % kRing;
+    bool read_back_done = false;             // the batch's last binning kernel wrote the slot itself
+    bool batch_block_window = false;
+    for (int j = 0; j < depth; ++j, ++launch) {
+        a.launch = launch;
+        a.list_in = (launch == 0 && !coherent) ? nullptr : ws.list[launch & 1];
+        a.list_out = ws.list[(launch + 1) & 1];
+        // threshold table: launch 0 is ONE iteration of the window-gather kernel for every
+        // track at once (the first move has eight admissible cells), the rest are S deep
+        const bool first_move = thr && launch == 0;
+        const unsigned blocks = kXcd * ((pol.upper + kBlock - 1) / kBlock);
+        uint32_t vcap_l;
+        long long vstride_l;
+        const int Sl = launch_steps(first_move, blocks, &vcap_l, &vstride_l);
+        if (sw.debug && (launch < 40 || launch % 500 == 0))
+            fprintf(stderr, "[tracks] launch %d upper %u blocks %u Sl %d binning %d tiles %d scattered %d cached %d cap %u\n", launch, pol.upper, blocks, Sl,
+                    pol.binning_on ? 1 : 0, pol.tiles_on ? 1 : 0, pol.scattered ? 1 : 0, pol.cached ? 1 : 0, ws.cap);
+        a.steps = Sl;
+        a.coherent = (coherent && !first_move) ? 1 : 0;
+        a.it_base = thr && launch > 0 ? it_done : 0;
+        a.visits = nullptr;
+        if (!pol.binning_on && pol.scattered && copies_ptr && !copies_live && !pol.cached) {
+            // first scattered launch: zero the private copies, count into them from now on
+            if (hipMemsetAsync(copies_ptr, 0, sizeof(uint32_t) * ncell * ncopies, st) != hipSuccess)
+                return set_error(SSRS_ERR_HIP, "histogram copies memset failed");
+            copies_live = true;
+            marks_adjacent = false;
+            a.hist_copies = copies_ptr;
+            a.ncopies = ncopies;
+        }
+        // the first-move launch is one iteration deep: its visits go straight to the histogram
+        // (one binning block for the whole batch took 170 us); generic kernel, plain keys
+        const bool bin_window = pol.binning_on && !first_move, bin_tiles = pol.tiles_on && !first_move;
+        // visit key = row * vis_r + col * vis_c: transposed while an east / west front bins in the row window
+        const bool transposed = hist_t && bin_window;
+        a.vis_r = transposed ? 1u : static_cast<uint32_t>(p->cols);
+        a.vis_c = transposed ? static_cast<uint32_t>(p->rows) : 1u;
+        if (bin_window || bin_tiles) a.visits = ws.visits;
+        a.visit_stride = vstride_l;
+        a.vcap = vcap_l;
+        const uint32_t *rec_counts = nullptr;
+        if (c.rec && c.rec->complete) {
+            const int rc = record_launch(blocks, Sl, bin_window, &rec_counts);
+            if (rc != SSRS_OK) return rc;
+        }
+        if (profile && !marks_adjacent) mark(0);
+        // 16-bit visit keys: north-bound front through the row window, nothing recorded
+        // (the stepper forms the key base (first start row + iteration - 1) * cols in 32 bits)
+        const bool v16 = thr && bin_window && a.visits == ws.visits && a.pf_dir == 1 && !hist_t && v16_ok &&
+                         (it_done + Sl + 2ll * geom.offset) * p->cols < (1ll << 31);
+        bool is_block_window = false;
+        launch_stepper(first_move, v16, blocks, Sl, &is_block_window);
+        batch_block_window |= is_block_window;
+        if (profile) mark(is_block_window ? 3 : 1);      // end of the stepper launch
+        uint32_t *read_back = j == depth - 1 ? &host_counts[kSlotWords * slot] : nullptr;
+        bin_launch(blocks, Sl, bin_window, bin_tiles, v16, rec_counts, read_back, &read_back_done);
+        if (thr && !first_move) it_done += Sl;
+        last_Sl = Sl;
+        if (hipGetLastError() != hipSuccess) return set_error(SSRS_ERR_HIP, "stepper launch failed");
+    }
+    if (c.hist64 && pol.cached && (batches & 1)) {          // (block windows flush whole launches' counts at once)
+        hipLaunchKernelGGL(k_drain64, dim3(4096), dim3(kBlock), 0, st, c.hist, c.hist64, ncell);
+        marks_adjacent = false;
+    }
+    // survivors of this batch = input count of the next launch
+    // ring slot = the head of the control block in one copy: [4][8] list counts, error, par_min,
+    // steps (2 words), strays (2 words); the row this batch's survivors went to is count[launch & 3]
+    bool queued = read_back_done || hipMemcpyAsync(&host_counts[kSlotWords * slot], ws.ctl, kSlotWords * sizeof(uint32_t),
+                                                   hipMemcpyDeviceToHost, st) == hipSuccess;
+    if (queued && profile) {
+        const size_t before = ev.marks.size();
+        mark(read_back_done ? 2 : 0);
+        queued = ev.marks.size() > before;
+        if (queued) ev.batch[slot] = ev.marks.back();
+    } else if (queued) {
+        queued = hipEventRecord(ev.batch[slot], st) == hipSuccess;
+        marks_adjacent = false;
+    }
+    if (!queued) return set_error(SSRS_ERR_HIP, "live-count read-back failed");
+    slot_row[slot] = launch & 3;
+    slot_block_window[slot] = batch_block_window;
+    ++batches;
+    return SSRS_OK;
+}
+
+// Examine every batch but the one just queued (it keeps the GPU busy)
+int TrackRun::examine_batches()
+{
+    while (pol.checked < batches - 1 && !pol.finished) {
+        const int cs = pol.checked % kRing;
+        if (hipEventSynchronize(ev.batch[cs]) != hipSuccess) return set_error(SSRS_ERR_HIP, "event sync failed");
+        pol.examine(&host_counts[kSlotWords * cs], slot_row[cs], slot_block_window[cs], batches, it_done,
+                    static_cast<long long>(launch) * S, roam_ready);
+    }
+    return SSRS_OK;
+}
+
+// The histogram's last parts (private copies, the transposed raster, the 64-bit drain), the final read-back,
+// the error flags and the statistics
+int TrackRun::finish(int rc, SsrsTrackStats *stats)
+{
+    uint32_t *const hist = c.hist;
+    if (rc != SSRS_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    if (copies_live)
         hipLaunchKernelGGL(k_fold_copies, dim3(4096), dim3(kBlock), 0, st, copies_ptr, ncopies, ncell, hist);
-    if (hist_t && rc == SSRS_OK)
+    if (hist_t)
         hipLaunchKernelGGL(k_transpose_add, dim3(static_cast<unsigned>(((p->rows + 31) / 32) * ((p->cols + 31) / 32))),
                            dim3(kBlock), 0, st, hist_t, p->rows, p->cols, hist);
-    if (hist64 && rc == SSRS_OK) hipLaunchKernelGGL(k_drain64, dim3(4096), dim3(kBlock), 0, st, hist, hist64, ncell);
-    (void)hipEventRecord(ev_last, st);
+    if (c.hist64) hipLaunchKernelGGL(k_drain64, dim3(4096), dim3(kBlock), 0, st, hist, c.hist64, ncell);
+    (void)hipEventRecord(ev.last, st);
     // fetch step total + error flag
     TrackCtl host_ctl = {};
-    if (rc == SSRS_OK) {
-        if (hipMemcpyAsync(&host_counts[kFinalSlot], ws.ctl, sizeof(TrackCtl), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-            rc = set_error(SSRS_ERR_HIP, "final read-back failed");
-        else
-            memcpy(&host_ctl, &host_counts[kFinalSlot], sizeof(TrackCtl));
-    } else {
-        (void)hipStreamSynchronize(st);
-    }
-    if (a.debug_roam && rc == SSRS_OK && roam_launches == 0 && host_ctl.dbg_waves)
-        fprintf(stderr, "[front] staged rows: %llu wave-steps, %llu of them fell back to the gather (%.4f); lane-steps: outside window / plane %llu, "
-                        "slot empty %llu, slot holds another row %llu; outside by its plane (of the first) %llu\n", host_ctl.dbg_waves,
-                host_ctl.dbg_tsum, static_cast<double>(host_ctl.dbg_tsum) / static_cast<double>(host_ctl.dbg_waves),
-                host_ctl.dbg_tmax >> 32, host_ctl.dbg_tmax & 0xFFFFFFFFull, host_ctl.dbg_slowmax >> 32, host_ctl.dbg_slowmax & 0xFFFFFFFFull);
-    if (a.debug_roam && rc == SSRS_OK && roam_launches == 0 && host_ctl.roam_pairs)
-        fprintf(stderr, "[front] staging waves: %llu batches, %llu polls that found the ring full, %llu rows, %.3e clocks of lifetime in all\n",
-                host_ctl.roam_pairs >> 32, host_ctl.roam_pairs & 0xFFFFFFFFull, host_ctl.roam_slow >> 32,
-                static_cast<double>(host_ctl.roam_slow & 0xFFFFFFFFull) * 256.0);
-    if (a.debug_roam && rc == SSRS_OK && roam_launches == 0 && (host_ctl.dbg_span & 0xFFFFFull))
-        fprintf(stderr, "[front] rows between the first and the last track of a block's front (by the row each would be on at iteration 0): "
-                        "mean %.1f over %llu blocks, max %llu; the ring holds %d; %llu polls of stepping waves that waited for their row\n",
-                static_cast<double>(host_ctl.dbg_span >> 20) / static_cast<double>(host_ctl.dbg_span & 0xFFFFFull),
-                host_ctl.dbg_span & 0xFFFFFull, host_ctl.dbg_span_max, kLrRows, host_ctl.dbg_waits);
-    if (stats && rc == SSRS_OK) {
+    if (hipMemcpyAsync(&host_counts[kFinalSlot], ws.ctl, sizeof(TrackCtl), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return set_error(SSRS_ERR_HIP, "final read-back failed");
+    memcpy(&host_ctl, &host_counts[kFinalSlot], sizeof(TrackCtl));
+    if (stats) {
         stats->total_steps = static_cast<int64_t>(host_ctl.steps);
         stats->launches = launch;
         stats->window_launches = window_launches;
         stats->tile_launches = tile_launches;
         stats->block_window_launches = block_window_launches;
-        stats->wander_sorts = wander_sorts;
+        stats->wander_sorts = pol.wander_sorts;
         stats->roam_launches = roam_launches;
-        stats->roam_shuffles = roam_shuffles;
+        stats->roam_shuffles = pol.roam_shuffles;
         stats->roam_wide_launches = roam_wide_launches;
         stats->roam_wave_pairs = static_cast<int64_t>(host_ctl.roam_pairs);
         stats->roam_slow_wave_pairs = static_cast<int64_t>(host_ctl.roam_slow);
         stats->reserved0 = static_cast<int32_t>(host_ctl.pad);                   // near-ties settled by the fine table
         // (batches still unexamined when the loop ended: the last one or two of the run)
-        stats->block_window_steps = block_window_steps;
+        stats->block_window_steps = pol.block_window_steps;
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ev_first, ev_last) == hipSuccess) stats->wall_ms = ms;
+        if (hipEventElapsedTime(&ms, ev.first, ev.last) == hipSuccess) stats->wall_ms = ms;
         if (profile) {
             float sum = 0.f, hsum = 0.f;
             int timed = 0;
-            for (size_t i = 1; i < ev_marks.size(); ++i) {
-                if (mark_kind[i] == 0 || hipEventElapsedTime(&ms, ev_marks[i - 1], ev_marks[i]) != hipSuccess) continue;
-                if (mark_kind[i] == 1 || mark_kind[i] == 3) {
+            for (size_t i = 1; i < ev.marks.size(); ++i) {
+                if (ev.kind[i] == 0 || hipEventElapsedTime(&ms, ev.marks[i - 1], ev.marks[i]) != hipSuccess) continue;
+                if (ev.kind[i] == 1 || ev.kind[i] == 3) {
                     sum += ms;
                     if (timed == 0 && thr) stats->first_move_ms = ms;      // (launch 0 of a threshold-table call)
                     ++timed;
-                    if (mark_kind[i] == 3) { stats->block_window_ms += ms; ++stats->block_window_timed; }
+                    if (ev.kind[i] == 3) { stats->block_window_ms += ms; ++stats->block_window_timed; }
                 } else {
                     hsum += ms;
                 }
@@ -4984,12 +4613,6 @@ static int tracks_simulate_impl(const SsrsTrackParams *p, const double *updraft,
             stats->hist_ms = hsum;
         }
     }
-    for (hipEvent_t e : ev_marks) (void)hipEventDestroy(e);
-    if (!profile)
-        for (int i = 0; i < kRing; ++i) (void)hipEventDestroy(ev_batch[i]);
-    (void)hipEventDestroy(ev_first);
-    (void)hipEventDestroy(ev_last);
-    if (rc != SSRS_OK) return rc;
     if (host_ctl.error & 2u)
         return set_error(SSRS_ERR_INVALID, "ssrs_tracks_simulate: `table` is not a threshold table built by "
                          "ssrs_transition_thr_build for this %d x %d raster and params->prior (results discarded)",
@@ -5000,6 +4623,55 @@ static int tracks_simulate_impl(const SsrsTrackParams *p, const double *updraft,
     return SSRS_OK;
 }
 
+static int tracks_simulate_impl(const TrackCall &c, SsrsTrackStats *stats)
+{
+    int rc = check_track_args(c);
+    if (rc != SSRS_OK) return rc;
+    if (stats) *stats = SsrsTrackStats{};
+    if (SsrsTrajRecorder *rec = c.rec) {
+        rec->used = 0;
+        rec->chunks.clear();
+        rec->complete = 1;
+        rec->rows = c.p->rows;
+        rec->cols = c.p->cols;
+        rec->ntracks = c.ntracks;
+    }
+    if (c.ntracks == 0) return SSRS_OK;
+    SSRS_REQUIRE(c.start_rc != nullptr, "ssrs_tracks_simulate: start_rc is NULL");
+    SSRS_REQUIRE(c.workspace && c.workspace_bytes >= ssrs_tracks_workspace_bytes(c.ntracks),
+                 "ssrs_tracks_simulate: workspace too small (need %zu bytes)",
+                 ssrs_tracks_workspace_bytes(c.ntracks));
+    SSRS_REQUIRE((reinterpret_cast<uintptr_t>(c.workspace) & 255u) == 0,
+                 "ssrs_tracks_simulate: workspace must be 256-byte aligned");
+
+    TrackRun run(c);
+    workspace_layout(c.ntracks, static_cast<char *>(c.workspace), &run.ws);
+    run.host_counts = pinned_counts();
+    SSRS_REQUIRE(run.host_counts != nullptr, "ssrs_tracks_simulate: hipHostMalloc failed");
+    if (c.p->flags & SSRS_TRACKS_THR_TABLE) {
+        if ((rc = run.check_thr_header()) != SSRS_OK) return rc;
+    }
+    if ((rc = run.plan_and_init()) != SSRS_OK) return rc;
+    if ((rc = run.choose_front_path()) != SSRS_OK) return rc;
+    TrackPolicy &pol = run.pol;
+    // Launch loop.  Launches are queued kBatch deep; the live count of a batch
+    // is copied back asynchronously and examined while the next batch runs, so
+    // the GPU never waits on the host.  Launches past the end see count 0.
+    // Termination: every live track either finishes or takes S moves per
+    // launch and k < max_moves, so the live count reaches 0.
+    while (!pol.finished && rc == SSRS_OK) {
+        if (pol.want_wander_sort && pol.cached && run.wander_sort_ok && run.launch > 0) {
+            if ((rc = run.wander_sort()) != SSRS_OK) break;
+        }
+        if (pol.cached) pol.want_rebalance = false;          // (the lists carry tombstones; the wander sort deals evenly)
+        if (pol.cached && run.roam_ok && !run.roam_ready) run.build_roam_tables();
+        if (pol.want_rebalance && run.launch > 0) run.rebalance();
+        rc = run.queue_batch();
+        if (rc == SSRS_OK) rc = run.examine_batches();
+    }
+    return run.finish(rc, stats);
+}
+
 extern "C" int ssrs_tracks_simulate(const SsrsTrackParams *p, const double *updraft,
                                     const float *potential, const double *table,
                                     const int32_t *start_rc, int64_t ntracks, uint64_t seed,
@@ -5008,8 +4680,8 @@ extern "C" int ssrs_tracks_simulate(const SsrsTrackParams *p, const double *updr
                                     void *workspace, size_t workspace_bytes,
                                     SsrsTrackStats *stats, void *stream)
 {
-    return tracks_simulate_impl(p, updraft, potential, table, start_rc, ntracks, seed, track_id_base, hist, end_rc,
-                                lengths, traj, traj_offsets, workspace, workspace_bytes, stats, stream, nullptr);
+    return tracks_simulate_impl({p, updraft, potential, table, start_rc, ntracks, seed, track_id_base, hist, end_rc,
+                                 lengths, traj, traj_offsets, workspace, workspace_bytes, stream, nullptr, nullptr}, stats);
 }
 
 extern "C" int ssrs_tracks_simulate_h64(const SsrsTrackParams *p, const double *updraft,
@@ -5021,9 +4693,9 @@ extern "C" int ssrs_tracks_simulate_h64(const SsrsTrackParams *p, const double *
 {
     SSRS_REQUIRE(hist_scratch != nullptr && hist64 != nullptr, "ssrs_tracks_simulate_h64: NULL histogram");
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "64-bit counts");
-    return tracks_simulate_impl(p, updraft, potential, table, start_rc, ntracks, seed, track_id_base, hist_scratch, end_rc,
-                                lengths, nullptr, nullptr, workspace, workspace_bytes, stats, stream, nullptr,
-                                reinterpret_cast<unsigned long long *>(hist64));
+    return tracks_simulate_impl({p, updraft, potential, table, start_rc, ntracks, seed, track_id_base, hist_scratch, end_rc,
+                                 lengths, nullptr, nullptr, workspace, workspace_bytes, stream, nullptr,
+                                 reinterpret_cast<unsigned long long *>(hist64)}, stats);
 }
 
 extern "C" SsrsTrajRecorder *ssrs_traj_recorder_create(void *pool, size_t pool_bytes)
@@ -5058,8 +4730,8 @@ extern "C" int ssrs_tracks_simulate_rec(const SsrsTrackParams *p, const double *
                                         SsrsTrackStats *stats, void *stream)
 {
     SSRS_REQUIRE(recorder != nullptr, "ssrs_tracks_simulate_rec: recorder is NULL");
-    return tracks_simulate_impl(p, updraft, potential, table, start_rc, ntracks, seed, track_id_base, hist, end_rc,
-                                lengths, nullptr, nullptr, workspace, workspace_bytes, stats, stream, recorder);
+    return tracks_simulate_impl({p, updraft, potential, table, start_rc, ntracks, seed, track_id_base, hist, end_rc,
+                                 lengths, nullptr, nullptr, workspace, workspace_bytes, stream, recorder, nullptr}, stats);
 }
 
 extern "C" int ssrs_tracks_gather(const SsrsTrajRecorder *rec, const int32_t *start_rc, int64_t ntracks,

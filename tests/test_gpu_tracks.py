@@ -781,11 +781,9 @@ def test_thr_table_large_batch_equals_f64_table(gpu):
 
 @pytest.mark.parametrize('dirn', [0., 180.])
 def test_front_kernel_variants_give_the_oracles_integers(gpu, dirn):
-    """North / south fronts on a raster at least 256 columns wide, through the variants of the front kernel
-    behind their switches: SSRS_TRACKS_LDS_ROWS (table rows staged in LDS by a fifth wave with
-    global_load_lds, read through a tag / entry / tag sequence; opt-in: measured slower than the gather,
-    profiles/r03_notes.md section 7) and SSRS_TRACKS_NO_CHEAP_EXACT (near-ties straight to the full exact
-    sequence instead of the seven-division decision).  Same lengths, ends and histogram as the C oracle."""
+    """North / south fronts on a raster at least 256 columns wide, through the front kernel as shipped and
+    behind SSRS_TRACKS_NO_CHEAP_EXACT (near-ties straight to the full exact sequence instead of the
+    seven-division decision).  Same lengths, ends and histogram as the C oracle."""
     import os
     from ssrs_amd import movmodel
     from oracle import c_oracle
@@ -799,8 +797,7 @@ def test_front_kernel_variants_give_the_oracles_integers(gpu, dirn):
     t = rng.integers(2, 30, n)
     starts = np.stack([t if dirn == 0. else rows - 1 - t, rng.integers(0, cols, n)], 1)
     ref = c_oracle.simulate_tracks(dirn, starts, (rows, cols), 1, 1., upd, pot, seed=17, want_traj=False)
-    for switch, value in ((None, ''), ('SSRS_TRACKS_LDS_ROWS', '1'), ('SSRS_TRACKS_LDS_ROWS', '2'),
-                          ('SSRS_TRACKS_NO_CHEAP_EXACT', '1')):
+    for switch, value in ((None, ''), ('SSRS_TRACKS_NO_CHEAP_EXACT', '1')):
         if switch:
             os.environ[switch] = value
         try:
