@@ -329,7 +329,10 @@ int ssrs_tracks_simulate(const SsrsTrackParams *params, const double *updraft,
  * (movmodel.py:415) wraps at 32 767 visits and this library's uint32 one at 2^32 - 1, which the trap cells of a solved 10 m
  * field reach from ~250 000 tracks of one call on (1.7e4 visits per track).  The kernels count into `hist_scratch`
  * (uint32 (rows, cols), zeroed by the caller: whatever it holds is counted too) and the library empties it into `hist64`
- * (uint64 (rows, cols), ACCUMULATED) every other batch of launches and before it returns, on `stream`. */
+ * (uint64 (rows, cols), ACCUMULATED) every other batch of launches and before it returns, on `stream`, whatever the
+ * table, switches and stepper path.  The 32-bit rasters behind the regular workspace (the private copies of a scattered
+ * batch, the transposed raster of an east / west front) are added into `hist64` with 64-bit sums before one of their
+ * cells could pass 2^32 - 1 (bounded by the tracks times the steps of the launches since) and before it returns. */
 int ssrs_tracks_simulate_h64(const SsrsTrackParams *params, const double *updraft,
                              const float *potential, const double *table,
                              const int32_t *start_rc, int64_t ntracks, uint64_t seed,

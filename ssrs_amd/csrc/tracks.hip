@@ -2931,7 +2931,8 @@ __global__ __launch_bounds__(kBinThreads) void k_bin_visits16(const uint16_t *__
 // the copies are added to `hist` once at the end.  5.8 -> 14 (K = 16) / 17.5 (K = 64)
 // G steps/s on the C2 run.
 // hist64 += hist32, hist32 = 0 (ssrs_tracks_simulate_h64: a roaming batch's trap cells pass 2^32 visits from ~250 000 tracks
-// on: the 32-bit raster the kernels count into is emptied into the caller's 64-bit one every other batch and at the end)
+// on: the 32-bit raster the kernels count into is emptied into the caller's 64-bit one every other batch and at the end,
+// on every stepper path; the copies and the transposed raster go straight into the 64-bit one, TrackRun::fold_private)
 __global__ __launch_bounds__(kBlock) void k_drain64(uint32_t *__restrict__ lo, unsigned long long *__restrict__ acc, size_t n)
 {
     for (size_t i = blockIdx.x * static_cast<size_t>(kBlock) + threadIdx.x; i < n; i += static_cast<size_t>(gridDim.x) * kBlock) {
@@ -2940,13 +2941,21 @@ __global__ __launch_bounds__(kBlock) void k_drain64(uint32_t *__restrict__ lo, u
     }
 }
 
-__global__ __launch_bounds__(kBlock) void k_fold_copies(const uint32_t *__restrict__ copies, int ncopies,
-                                                       size_t ncell, uint32_t *__restrict__ hist)
+// hist += the sum of the copies, in hist's width T: uint32 (ssrs_tracks_simulate: the sum is taken modulo 2^32 like the
+// raster it lands in) or 64-bit (h64, where no cell may lose a multiple of 2^32).  ZERO: empty the copies too (a fold in
+// the middle of a run; the kernels go on counting into them)
+template <typename T, bool ZERO>
+__global__ __launch_bounds__(kBlock) void k_fold_copies(uint32_t *__restrict__ copies, int ncopies,
+                                                       size_t ncell, T *__restrict__ hist)
 {
     for (size_t i = blockIdx.x * static_cast<size_t>(kBlock) + threadIdx.x; i < ncell;
          i += static_cast<size_t>(gridDim.x) * kBlock) {
-        uint32_t s = 0;
-        for (int c = 0; c < ncopies; ++c) s += copies[static_cast<size_t>(c) * ncell + i];
+        T s = 0;
+        for (int c = 0; c < ncopies; ++c) {
+            const uint32_t v = copies[static_cast<size_t>(c) * ncell + i];
+            s += v;
+            if (ZERO && v) copies[static_cast<size_t>(c) * ncell + i] = 0u;
+        }
         if (s) hist[i] += s;
     }
 }
@@ -3180,9 +3189,10 @@ __global__ __launch_bounds__(kTileThreads) void k_bin_bucket(const uint32_t *__r
 
 // hist (rows x cols) += transpose of hist_t (cols x rows): the transposed histogram that
 // east / west batches bin into (there a step's visits fill a few COLUMNS, which are rows
-// of hist_t, so the LDS window of k_bin_visits and its contiguous flush work unchanged)
+// of hist_t, so the LDS window of k_bin_visits and its contiguous flush work unchanged).  T: uint32, or 64-bit for h64
+template <typename T>
 __global__ __launch_bounds__(kBlock) void k_transpose_add(const uint32_t *__restrict__ hist_t, int rows,
-                                                         int cols, uint32_t *__restrict__ hist)
+                                                         int cols, T *__restrict__ hist)
 {
     __shared__ uint32_t tile[32][33];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;           // 32 x 8
@@ -3904,6 +3914,9 @@ struct TrackRun {
     uint32_t *copies_ptr = nullptr;          // private histogram copies of a scattered batch
     int ncopies = 0;
     bool copies_live = false;
+    // h64: a bound on the visits counted into the copies and hist_t since they were last folded into hist64 (one launch
+    // of Sl steps adds at most Sl + 1 points per track)
+    unsigned long long private_visits = 0;
     bool roam_ready = false;
     int roam_width = 1;                      // 1, 2, 4: blocks of 256, 512, 1024 lanes
     TrackPolicy pol;
@@ -3943,6 +3956,7 @@ struct TrackRun {
     int wander_sort();
     void build_roam_tables();
     void rebalance();
+    void fold_private(bool zero);
     int queue_batch();
     int examine_batches();
     int finish(int rc, SsrsTrackStats *stats);
@@ -4488,6 +4502,12 @@ int TrackRun::queue_batch()
             a.hist_copies = copies_ptr;
             a.ncopies = ncopies;
         }
+        if (c.hist64 && (copies_live || hist_t)) {
+            // the copies and hist_t are 32-bit too: folded into hist64 before this launch could take a cell past 2^32 - 1
+            const unsigned long long bound = static_cast<unsigned long long>(c.ntracks) * static_cast<unsigned long long>(Sl + 1);
+            if (private_visits && private_visits + bound > 0xFFFFFFFFull) fold_private(true);
+            private_visits += bound;
+        }
         // the first-move launch is one iteration deep: its visits go straight to the histogram
         // (one binning block for the whole batch took 170 us); generic kernel, plain keys
         const bool bin_window = pol.binning_on && !first_move, bin_tiles = pol.tiles_on && !first_move;
@@ -4518,7 +4538,7 @@ int TrackRun::queue_batch()
         last_Sl = Sl;
         if (hipGetLastError() != hipSuccess) return set_error(SSRS_ERR_HIP, "stepper launch failed");
     }
-    if (c.hist64 && pol.cached && (batches & 1)) {          // (block windows flush whole launches' counts at once)
+    if (c.hist64 && (batches & 1)) {                         // every path: the kernels count into c.hist
         hipLaunchKernelGGL(k_drain64, dim3(4096), dim3(kBlock), 0, st, c.hist, c.hist64, ncell);
         marks_adjacent = false;
     }
@@ -4555,6 +4575,22 @@ int TrackRun::examine_batches()
     return SSRS_OK;
 }
 
+// h64: the private copies and the transposed raster into hist64, 64-bit sums; zero: empty them for the launches to come
+void TrackRun::fold_private(bool zero)
+{
+    if (copies_live) {
+        if (zero) hipLaunchKernelGGL((k_fold_copies<unsigned long long, true>), dim3(4096), dim3(kBlock), 0, st, copies_ptr, ncopies, ncell, c.hist64);
+        else hipLaunchKernelGGL((k_fold_copies<unsigned long long, false>), dim3(4096), dim3(kBlock), 0, st, copies_ptr, ncopies, ncell, c.hist64);
+    }
+    if (hist_t) {
+        hipLaunchKernelGGL(k_transpose_add<unsigned long long>, dim3(static_cast<unsigned>(((p->rows + 31) / 32) * ((p->cols + 31) / 32))),
+                           dim3(kBlock), 0, st, hist_t, p->rows, p->cols, c.hist64);
+        if (zero) (void)hipMemsetAsync(hist_t, 0, sizeof(uint32_t) * ncell, st);
+    }
+    private_visits = 0;
+    marks_adjacent = false;
+}
+
 // The histogram's last parts (private copies, the transposed raster, the 64-bit drain), the final read-back,
 // the error flags and the statistics
 int TrackRun::finish(int rc, SsrsTrackStats *stats)
@@ -4564,12 +4600,16 @@ int TrackRun::finish(int rc, SsrsTrackStats *stats)
         (void)hipStreamSynchronize(st);
         return rc;
     }
-    if (copies_live)
-        hipLaunchKernelGGL(k_fold_copies, dim3(4096), dim3(kBlock), 0, st, copies_ptr, ncopies, ncell, hist);
-    if (hist_t)
-        hipLaunchKernelGGL(k_transpose_add, dim3(static_cast<unsigned>(((p->rows + 31) / 32) * ((p->cols + 31) / 32))),
-                           dim3(kBlock), 0, st, hist_t, p->rows, p->cols, hist);
-    if (c.hist64) hipLaunchKernelGGL(k_drain64, dim3(4096), dim3(kBlock), 0, st, hist, c.hist64, ncell);
+    if (c.hist64) {
+        fold_private(false);
+        hipLaunchKernelGGL(k_drain64, dim3(4096), dim3(kBlock), 0, st, hist, c.hist64, ncell);
+    } else {
+        if (copies_live)
+            hipLaunchKernelGGL((k_fold_copies<uint32_t, false>), dim3(4096), dim3(kBlock), 0, st, copies_ptr, ncopies, ncell, hist);
+        if (hist_t)
+            hipLaunchKernelGGL(k_transpose_add<uint32_t>, dim3(static_cast<unsigned>(((p->rows + 31) / 32) * ((p->cols + 31) / 32))),
+                               dim3(kBlock), 0, st, hist_t, p->rows, p->cols, hist);
+    }
     (void)hipEventRecord(ev.last, st);
     // fetch step total + error flag
     TrackCtl host_ctl = {};

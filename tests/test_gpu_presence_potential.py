@@ -59,6 +59,90 @@ def test_presence_smoothing_large_radius_vs_oracle(gpu):
         assert ulp_diff_f32(got, ref).max() <= 1
 
 
+def disk_sums_exact(cnt, krad):
+    """The zero-padded 'same' sums over the disk x^2 + y^2 <= krad^2 in int64 (chords of row prefix sums) and the tap
+    count: the exact form of compute_smooth_presence_counts before its one multiply by 1/ntaps."""
+    import math
+    cnt = np.asarray(cnt, dtype=np.int64)
+    rows, cols = cnt.shape
+    pre = np.zeros((rows, cols + 1), dtype=np.int64)
+    np.cumsum(cnt, axis=1, out=pre[:, 1:])
+    c = np.arange(cols)
+    out = np.zeros((rows, cols), dtype=np.int64)
+    ntaps = 0
+    for dy in range(-krad, krad + 1):
+        h = math.isqrt(krad * krad - dy * dy)
+        ntaps += 2 * h + 1
+        r0, r1 = max(0, -dy), min(rows, rows - dy)               # output rows whose row r + dy exists
+        if r0 >= r1:
+            continue
+        src = pre[r0 + dy:r1 + dy]
+        out[r0:r1] += src[:, np.minimum(c + h + 1, cols)] - src[:, np.maximum(c - h, 0)]
+    return out, ntaps
+
+
+def smooth_exact(cnt, krad):
+    sums, ntaps = disk_sums_exact(cnt, krad)
+    assert int(sums.max()) < 2 ** 53                             # f64(sum) is exact
+    return (sums.astype(np.float64) * (1.0 / ntaps)).astype(np.float32)
+
+
+def smooth_scipy(cnt, krad):
+    """The reference's form (movmodel.py:431-439): convolve2d of the f64 counts with the normalised disk."""
+    from scipy.signal import convolve2d
+    y, x = np.mgrid[-krad:krad + 1, -krad:krad + 1]
+    kernel = (x * x + y * y <= krad * krad).astype(np.float64)
+    kernel /= np.sum(kernel)
+    return convolve2d(np.asarray(cnt, dtype=np.float64), kernel, mode='same').astype(np.float32)
+
+
+def _hot_counts(shape, lo, hi, seed):
+    """Small counts with a few hot cells in [lo, hi)."""
+    rng = np.random.default_rng(seed)
+    cnt = rng.integers(0, 50, shape).astype(np.int64)
+    nhot = max(1, cnt.size // 40)
+    idx = rng.choice(cnt.size, nhot, replace=False)
+    cnt.flat[idx] = rng.integers(lo, hi, nhot, dtype=np.int64)
+    return cnt
+
+
+# 1 x N, N x 1, cols not a multiple of 256, rows / cols below 2 krad + 1
+_SMOOTH_SHAPES = [(1, 300), (300, 1), (37, 300), (5, 700), (7, 9), (64, 257)]
+
+
+def _radii(shape):
+    return sorted({0, 1, 2, 10, max(shape) + 3})
+
+
+@pytest.mark.parametrize('shape', _SMOOTH_SHAPES)
+def test_presence_smoothing_u64_counts_past_2_32(gpu, shape):
+    """ssrs_presence_smooth_u64 (int64 counts: a 64-bit histogram) with hot cells in [2^32, 2^40): bit-equal to the
+    integer disk sums times 1/ntaps, and within 1 f32 ulp of the reference's f64 convolution."""
+    from ssrs_amd import presence
+    cnt = _hot_counts(shape, 2 ** 32, 2 ** 40, seed=shape[0] * 1000 + shape[1])
+    dev = torch.from_numpy(cnt).cuda()
+    for krad in _radii(shape):
+        got = presence.smooth_presence_counts(dev, krad).cpu().numpy()
+        exact = smooth_exact(cnt, krad)
+        assert np.array_equal(got.view(np.int32), exact.view(np.int32)), (shape, krad)
+        assert ulp_diff_f32(got, smooth_scipy(cnt, krad)).max() <= 1, (shape, krad)
+
+
+@pytest.mark.parametrize('shape', _SMOOTH_SHAPES)
+def test_presence_smoothing_u32_counts_from_2_31(gpu, shape):
+    """ssrs_presence_smooth on uint32 counts of 2^31 and more (int32 tensors hold them as negative numbers): read as
+    unsigned, bit-equal to the integer reference, within 1 ulp of the reference's form."""
+    from ssrs_amd import presence
+    cnt = _hot_counts(shape, 2 ** 31, 2 ** 32, seed=shape[0] * 1000 + shape[1] + 1)
+    dev = torch.from_numpy(cnt.astype(np.uint32).view(np.int32)).cuda()
+    assert int(dev.min().item()) < 0
+    for krad in _radii(shape):
+        got = presence.smooth_presence_counts(dev, krad).cpu().numpy()
+        exact = smooth_exact(cnt, krad)
+        assert np.array_equal(got.view(np.int32), exact.view(np.int32)), (shape, krad)
+        assert ulp_diff_f32(got, smooth_scipy(cnt, krad)).max() <= 1, (shape, krad)
+
+
 def test_boundary_nodes_vs_golden(golden):
     from ssrs_amd.potential import get_boundary_nodes
     g = golden('g5_potential.npz')

@@ -111,3 +111,9 @@ def test_single_rank_histogram_guard_and_64_bit_sub_batches(gpu, tmp_path):
     assert torch.equal(lib64._presence_counts[('s10d270', 0)], halves)
     out = safe.compute_presence_map(radius=100.)
     assert out.dtype == np.float32 and float(out.max()) == 1.0 and np.isfinite(out).all()
+    # the 64-bit smoothing of these counts (past 2^32): bit-equal to the integer disk sums times 1/ntaps
+    from ssrs_amd import presence
+    from test_gpu_presence_potential import smooth_exact
+    krad = presence.presence_kernel_radius(100., 10., (rows, cols))
+    smoothed = presence.smooth_presence_counts(hist, krad).cpu().numpy()
+    assert np.array_equal(smoothed.view(np.int32), smooth_exact(hist.cpu().numpy(), krad).view(np.int32))
