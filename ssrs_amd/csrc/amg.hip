@@ -31,7 +31,6 @@
 
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -400,17 +399,12 @@ __global__ __launch_bounds__(kBlock) void k_unpack_coarse(const unsigned long lo
 }
 
 // ---- cycle kernels --------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_jacobi_first(const cv_t *__restrict__ dinv,
-                                                        const cv_t *__restrict__ b, int n,
-                                                        cv_t *__restrict__ x, double w)
+__global__ __launch_bounds__(kBlock) void k_jacobi_first(const double *__restrict__ dinv,
+                                                        const double *__restrict__ b, int n,
+                                                        double *__restrict__ x, double w)
 {
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock)
-        x[i] = static_cast<cv_t>(w * dinv[i] * b[i]);
-}
-
-__global__ __launch_bounds__(kBlock) void k_to_cv(const double *__restrict__ a, int n, cv_t *__restrict__ out)
-{
-    for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) out[i] = static_cast<cv_t>(a[i]);
+        x[i] = w * dinv[i] * b[i];
 }
 
 // Four lanes per row for the large CSR levels: a thread-per-row walk reads val/col
@@ -420,7 +414,7 @@ __global__ __launch_bounds__(kBlock) void k_to_cv(const double *__restrict__ a, 
 constexpr int kRowLanes = 4;
 template <class V>
 __device__ __forceinline__ double row_dot4(const int *__restrict__ rowptr, const int *__restrict__ col,
-                                           const V *__restrict__ val, const cv_t *__restrict__ x,
+                                           const V *__restrict__ val, const double *__restrict__ x,
                                            int row, int sub)
 {
     double ax = 0.0;
@@ -438,7 +432,7 @@ __device__ __forceinline__ double row_dot4(const int *__restrict__ rowptr, const
 constexpr int kRowsPerGroup = 4;
 template <class V>
 __device__ __forceinline__ void rows_dot4(const int *__restrict__ rowptr, const int *__restrict__ col,
-                                          const V *__restrict__ val, const cv_t *__restrict__ x,
+                                          const V *__restrict__ val, const double *__restrict__ x,
                                           const long long (&row)[kRowsPerGroup], int n, int sub,
                                           double (&ax)[kRowsPerGroup])
 {
@@ -482,10 +476,10 @@ template <class V>
 __global__ __launch_bounds__(kBlock) void k_jacobi4(const int *__restrict__ rowptr,
                                                    const int *__restrict__ col,
                                                    const V *__restrict__ val,
-                                                   const cv_t *__restrict__ dinv,
-                                                   const cv_t *__restrict__ b,
-                                                   const cv_t *__restrict__ x, int n,
-                                                   cv_t *__restrict__ xn, double w)
+                                                   const double *__restrict__ dinv,
+                                                   const double *__restrict__ b,
+                                                   const double *__restrict__ x, int n,
+                                                   double *__restrict__ xn, double w)
 {
     const int sub = threadIdx.x % kRowLanes;
     const long long groups = static_cast<long long>(gridDim.x) * (kBlock / kRowLanes);
@@ -499,7 +493,7 @@ __global__ __launch_bounds__(kBlock) void k_jacobi4(const int *__restrict__ rowp
         rows_dot4(rowptr, col, val, x, row, n, sub, ax);
 #pragma unroll
         for (int u = 0; u < kRowsPerGroup; ++u)
-            if (sub == 0 && row[u] < n) xn[row[u]] = static_cast<cv_t>(x[row[u]] + w * dinv[row[u]] * (b[row[u]] - ax[u]));
+            if (sub == 0 && row[u] < n) xn[row[u]] = x[row[u]] + w * dinv[row[u]] * (b[row[u]] - ax[u]);
     }
 }
 
@@ -507,9 +501,9 @@ template <class V>
 __global__ __launch_bounds__(kBlock) void k_residual4(const int *__restrict__ rowptr,
                                                      const int *__restrict__ col,
                                                      const V *__restrict__ val,
-                                                     const cv_t *__restrict__ b,
-                                                     const cv_t *__restrict__ x, int n,
-                                                     cv_t *__restrict__ r)
+                                                     const double *__restrict__ b,
+                                                     const double *__restrict__ x, int n,
+                                                     double *__restrict__ r)
 {
     const int sub = threadIdx.x % kRowLanes;
     const long long groups = static_cast<long long>(gridDim.x) * (kBlock / kRowLanes);
@@ -522,7 +516,7 @@ __global__ __launch_bounds__(kBlock) void k_residual4(const int *__restrict__ ro
         rows_dot4(rowptr, col, val, x, row, n, sub, ax);
 #pragma unroll
         for (int u = 0; u < kRowsPerGroup; ++u)
-            if (sub == 0 && row[u] < n) r[row[u]] = static_cast<cv_t>(b[row[u]] - ax[u]);
+            if (sub == 0 && row[u] < n) r[row[u]] = b[row[u]] - ax[u];
     }
 }
 
@@ -561,9 +555,9 @@ __global__ __launch_bounds__(kBlock) void k_sell_fill(const int *__restrict__ ro
 // JAC: xn = x + w D^-1 (b - A x); else r = b - A x.  One wave = one slice; four entries per lane in flight
 template <bool JAC>
 __global__ __launch_bounds__(kBlock) void k_sweep_sell(const int *__restrict__ sell_ptr, const int *__restrict__ sell_col,
-                                                      const float *__restrict__ sell_val, const cv_t *__restrict__ dinv,
-                                                      const cv_t *__restrict__ b, const cv_t *__restrict__ x, int n, int nsl,
-                                                      cv_t *__restrict__ out, double w)
+                                                      const float *__restrict__ sell_val, const double *__restrict__ dinv,
+                                                      const double *__restrict__ b, const double *__restrict__ x, int n, int nsl,
+                                                      double *__restrict__ out, double w)
 {
     const int lane = threadIdx.x & 63;
     for (int s = blockIdx.x * (kBlock / 64) + static_cast<int>(threadIdx.x >> 6); s < nsl; s += gridDim.x * (kBlock / 64)) {
@@ -581,7 +575,7 @@ __global__ __launch_bounds__(kBlock) void k_sweep_sell(const int *__restrict__ s
         }
         for (; p < p1; p += 64) ax += static_cast<double>(sell_val[p]) * x[sell_col[p]];
         const int row = s * 64 + lane;
-        if (row < n) out[row] = static_cast<cv_t>(JAC ? x[row] + w * dinv[row] * (b[row] - ax) : b[row] - ax);
+        if (row < n) out[row] = JAC ? x[row] + w * dinv[row] * (b[row] - ax) : b[row] - ax;
     }
 }
 
@@ -589,15 +583,15 @@ template <class V>
 __global__ __launch_bounds__(kBlock) void k_jacobi(const int *__restrict__ rowptr,
                                                   const int *__restrict__ col,
                                                   const V *__restrict__ val,
-                                                  const cv_t *__restrict__ dinv,
-                                                  const cv_t *__restrict__ b,
-                                                  const cv_t *__restrict__ x, int n,
-                                                  cv_t *__restrict__ xn, double w)
+                                                  const double *__restrict__ dinv,
+                                                  const double *__restrict__ b,
+                                                  const double *__restrict__ x, int n,
+                                                  double *__restrict__ xn, double w)
 {
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
         double ax = 0.0;
         for (int p = rowptr[i]; p < rowptr[i + 1]; ++p) ax += static_cast<double>(val[p]) * x[col[p]];
-        xn[i] = static_cast<cv_t>(x[i] + w * dinv[i] * (b[i] - ax));
+        xn[i] = x[i] + w * dinv[i] * (b[i] - ax);
     }
 }
 
@@ -605,14 +599,14 @@ template <class V>
 __global__ __launch_bounds__(kBlock) void k_residual(const int *__restrict__ rowptr,
                                                     const int *__restrict__ col,
                                                     const V *__restrict__ val,
-                                                    const cv_t *__restrict__ b,
-                                                    const cv_t *__restrict__ x, int n,
-                                                    cv_t *__restrict__ r)
+                                                    const double *__restrict__ b,
+                                                    const double *__restrict__ x, int n,
+                                                    double *__restrict__ r)
 {
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
         double ax = 0.0;
         for (int p = rowptr[i]; p < rowptr[i + 1]; ++p) ax += static_cast<double>(val[p]) * x[col[p]];
-        r[i] = static_cast<cv_t>(b[i] - ax);
+        r[i] = b[i] - ax;
     }
 }
 
@@ -636,7 +630,7 @@ __global__ __launch_bounds__(kBlock) void k_val32(const int *__restrict__ rowptr
 // the five level-0 sweeps were two thirds of a V-cycle.  The CSR copy of level 0 is
 // still built: the aggregation and the Galerkin product read it.
 struct L0Stencil {
-    const cv_t *rinv;         // 1 / cond, 0 where cond == 0 (then every link is 1e-8); the sign
+    const double *rinv;       // 1 / cond, 0 where cond == 0 (then every link is 1e-8); the sign
                               // bit marks Dirichlet cells (saves nine byte loads per cell)
     const uint8_t *fixed;
     int rows, cols;
@@ -655,10 +649,9 @@ __global__ __launch_bounds__(kBlock) void k_l0_rinv(const double *__restrict__ c
 }
 
 // (A x)_i of the level-0 operator.  The weights are those of k_l0_fill up to rounding
-// (diagonal links are multiplied by 1/sqrt(2) instead of divided by sqrt(2), and the whole row is
-// evaluated in the cycle's precision): this operator only preconditions, what it must be is
-// symmetric (w_ij is a function of ri + rj) and diagonally dominant (diag = the sum of the same
-// w_ij), which it is by construction.
+// (diagonal links are multiplied by 1/sqrt(2) instead of divided by sqrt(2)): this operator
+// only preconditions, what it must be is symmetric (w_ij is a function of ri + rj) and
+// diagonally dominant (diag = the sum of the same w_ij), which it is by construction.
 constexpr double kInvFacDiag = 1.0 / 1.41421353816986083984375;
 
 // One wave = one row segment of 62 cells plus a halo lane on either side: every lane loads
@@ -666,51 +659,8 @@ constexpr double kInvFacDiag = 1.0 / 1.41421353816986083984375;
 // arrive by lane shuffles.  The kernels were bound by the number of load instructions (21
 // per cell with a thread-per-cell stencil: 0.66 ms per sweep at 5000 x 6000), not by bytes.
 constexpr int kL0Cols = 62;                                   // cells per wave
-__device__ __forceinline__ cv_t l0_apply_wave(const L0Stencil &a, const cv_t *__restrict__ x,
-                                              int r, int c, bool &centre, size_t &i, cv_t &xi)
-{
-    const int lane = threadIdx.x & 63;
-    const bool col_ok = c >= 0 && c < a.cols;
-    const cv_t inf = static_cast<cv_t>(__builtin_inf());
-    cv_t xv[3], sv[3];                                        // rows r-1, r, r+1 of this lane's column
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const int rr = r + d - 1;
-        const bool ok = col_ok && rr >= 0 && rr < a.rows;
-        const size_t j = static_cast<size_t>(ok ? rr : r) * a.cols + (col_ok ? c : 0);
-        xv[d] = ok ? x[j] : static_cast<cv_t>(0);
-        sv[d] = ok ? a.rinv[j] : inf;                         // +inf: outside the raster, no link
-    }
-    i = static_cast<size_t>(r) * a.cols + (col_ok ? c : 0);
-    centre = col_ok && lane >= 1 && lane <= kL0Cols;
-    xi = xv[1];
-    const cv_t si = sv[1], ri = fabs(si);
-    cv_t diag = 0, off = 0;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {                             // same order as before: rows south to north
-        if (k == 4) continue;
-        const int d = k / 3, dc = k % 3 - 1;
-        cv_t sj = sv[d], xj = xv[d];
-        if (dc < 0) { sj = __shfl_up(sj, 1); xj = __shfl_up(xj, 1); }
-        if (dc > 0) { sj = __shfl_down(sj, 1); xj = __shfl_down(xj, 1); }
-        const cv_t rj = fabs(sj);
-        cv_t w = (ri != 0 && rj != 0) ? static_cast<cv_t>(2) / (ri + rj) : static_cast<cv_t>(1e-08);
-        if (rj == inf) w = 0;
-        if (d != 1 && dc != 0) w = w * static_cast<cv_t>(kInvFacDiag);
-        diag += w;
-        if (!signbit(sj)) off += w * xj;
-    }
-    if (signbit(si)) return xv[1];                            // Dirichlet cell: identity row
-    return diag * xv[1] - off;
-}
 
-// ---- level 0 of the V(1,1) cycle in two passes (f64 cycle only).  Unfused it is: copy rhs -> b (2 array passes), x = w D^-1 b
-// (3), r = b - A x (4), [restrict], x += P x_c (2.5), x = x + w D^-1 (b - A x) (5), copy x -> out (2) = 18.5 passes of 240 MB
-// at 5000 x 6000; fused: pre (b, dinv, rinv -> x, r: 5) and post (x, agg, x_c, rinv, b, dinv -> out: 6.5) = 11.5.
-struct L0Slots { const double *rhs; double *out; };
-__global__ void k_set_slots(L0Slots *s, const double *rhs, double *out) { s->rhs = rhs; s->out = out; }
-
-// the stencil of l0_apply_wave on values the caller has in registers: xv / sv = this lane's column of rows r-1, r, r+1
+// the stencil on values the caller has in registers: xv / sv = this lane's column of rows r-1, r, r+1 (rows south to north)
 __device__ __forceinline__ double l0_core(const double (&xv)[3], const double (&sv)[3])
 {
     const double inf = __builtin_inf();
@@ -734,70 +684,38 @@ __device__ __forceinline__ double l0_core(const double (&xv)[3], const double (&
     return diag * xv[1] - off;
 }
 
-// pre: x = w D^-1 b and r = b - A x in one pass (the neighbours' x is recomputed from their b and dinv)
-__global__ __launch_bounds__(kBlock) void k_l0_pre_fused(const double *__restrict__ rinv, int rows, int cols,
-                                                        const double *__restrict__ dinv, const L0Slots *__restrict__ slots,
-                                                        double w, double *__restrict__ x, double *__restrict__ r)
+__device__ __forceinline__ double l0_apply_wave(const L0Stencil &a, const double *__restrict__ x,
+                                                int r, int c, bool &centre, size_t &i, double &xi)
 {
-    const double *__restrict__ b = slots->rhs;
-    const int c = (static_cast<int>(blockIdx.x) * (kBlock / 64) + static_cast<int>(threadIdx.x >> 6)) * kL0Cols +
-                  static_cast<int>(threadIdx.x & 63) - 1;
-    const int row = static_cast<int>(blockIdx.y), lane = threadIdx.x & 63;
-    const bool col_ok = c >= 0 && c < cols;
-    double xv[3], sv[3], bc = 0.0;
+    const int lane = threadIdx.x & 63;
+    const bool col_ok = c >= 0 && c < a.cols;
+    double xv[3], sv[3];                                      // rows r-1, r, r+1 of this lane's column
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
-        const int rr = row + d - 1;
-        const bool ok = col_ok && rr >= 0 && rr < rows;
-        const size_t j = static_cast<size_t>(ok ? rr : row) * cols + (col_ok ? c : 0);
-        const double bj = ok ? b[j] : 0.0;
-        xv[d] = ok ? w * dinv[j] * bj : 0.0;
-        sv[d] = ok ? rinv[j] : __builtin_inf();
-        if (d == 1) bc = bj;
+        const int rr = r + d - 1;
+        const bool ok = col_ok && rr >= 0 && rr < a.rows;
+        const size_t j = static_cast<size_t>(ok ? rr : r) * a.cols + (col_ok ? c : 0);
+        xv[d] = ok ? x[j] : 0.0;
+        sv[d] = ok ? a.rinv[j] : __builtin_inf();             // +inf: outside the raster, no link
     }
-    const double ax = l0_core(xv, sv);
-    if (col_ok && lane >= 1 && lane <= kL0Cols) {
-        const size_t i = static_cast<size_t>(row) * cols + c;
-        x[i] = xv[1];
-        r[i] = bc - ax;
-    }
+    i = static_cast<size_t>(r) * a.cols + (col_ok ? c : 0);
+    centre = col_ok && lane >= 1 && lane <= kL0Cols;
+    xi = xv[1];
+    return l0_core(xv, sv);
 }
 
-// post: x' = x + P x_c (recomputed for the neighbours) and out = x' + w D^-1 (b - A x') in one pass
-__global__ __launch_bounds__(kBlock) void k_l0_post_fused(const double *__restrict__ rinv, int rows, int cols,
-                                                         const double *__restrict__ dinv, const L0Slots *__restrict__ slots,
-                                                         const int *__restrict__ agg, const double *__restrict__ xc,
-                                                         const double *__restrict__ x, double w)
-{
-    const double *__restrict__ b = slots->rhs;
-    double *__restrict__ out = slots->out;
-    const int c = (static_cast<int>(blockIdx.x) * (kBlock / 64) + static_cast<int>(threadIdx.x >> 6)) * kL0Cols +
-                  static_cast<int>(threadIdx.x & 63) - 1;
-    const int row = static_cast<int>(blockIdx.y), lane = threadIdx.x & 63;
-    const bool col_ok = c >= 0 && c < cols;
-    double xv[3], sv[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const int rr = row + d - 1;
-        const bool ok = col_ok && rr >= 0 && rr < rows;
-        const size_t j = static_cast<size_t>(ok ? rr : row) * cols + (col_ok ? c : 0);
-        const int a = ok ? agg[j] : -1;
-        xv[d] = ok ? x[j] + (a >= 0 ? xc[a] : 0.0) : 0.0;
-        sv[d] = ok ? rinv[j] : __builtin_inf();
-    }
-    const double ax = l0_core(xv, sv);
-    if (col_ok && lane >= 1 && lane <= kL0Cols) {
-        const size_t i = static_cast<size_t>(row) * cols + c;
-        out[i] = xv[1] + w * dinv[i] * (b[i] - ax);
-    }
-}
+// ---- level 0 of the V(1,1) cycle in two passes.  Unfused it is: copy rhs -> b (2 array passes), x = w D^-1 b
+// (3), r = b - A x (4), [restrict], x += P x_c (2.5), x = x + w D^-1 (b - A x) (5), copy x -> out (2) = 18.5 passes of 240 MB
+// at 5000 x 6000; fused: pre (b, dinv, rinv -> x, r: 5) and post (x, agg, x_c, rinv, b, dinv -> out: 6.5) = 11.5.
+struct L0Slots { const double *rhs; double *out; };
+__global__ void k_set_slots(L0Slots *s, const double *rhs, double *out) { s->rhs = rhs; s->out = out; }
 
-// ---- the same two passes for TWO raster rows per wave (round 4, late): a wave that computes rows 2R and 2R + 1 loads rows
-// 2R - 1 .. 2R + 2 once -- 12 loads for two rows of the pre pass instead of 18, 20 instead of 28 in the post pass (the
-// kernels are bound by their load instructions) -- and, since level 1's aggregates are the parts of the aligned 2 x 2 blocks
+// Each wave computes TWO raster rows (round 4, late): a wave that computes rows 2R and 2R + 1 loads rows 2R - 1 .. 2R + 2
+// once -- 12 loads for two rows of the pre pass instead of 18, 20 instead of 28 in the post pass (the kernels are bound by
+// their load instructions) -- and, since level 1's aggregates are the parts of the aligned 2 x 2 blocks
 // (k_block_agg), the pre pass has every member of an aggregate in two neighbouring lanes: it writes the restricted residual
 // itself (members added in index order, as k_restrict does) instead of writing r for k_restrict to gather.  Same arithmetic
-// per cell in the same order as l0_core: bit-identical to the one-row kernels (SSRS_AMG_L0_ONE_ROW) and to the unfused path.
+// per cell in the same order as l0_core: bit-identical to the unfused path.
 __device__ __forceinline__ void l0_shift4(const double (&v)[4], double (&l)[4], double (&r)[4])
 {
 #pragma unroll
@@ -926,48 +844,48 @@ __global__ __launch_bounds__(kBlock) void k_l0_post2(const double *__restrict__ 
     }
 }
 
-__global__ __launch_bounds__(kBlock) void k_l0_jacobi(L0Stencil a, const cv_t *__restrict__ dinv,
-                                                     const cv_t *__restrict__ b,
-                                                     const cv_t *__restrict__ x,
-                                                     cv_t *__restrict__ xn, cv_t w)
+__global__ __launch_bounds__(kBlock) void k_l0_jacobi(L0Stencil a, const double *__restrict__ dinv,
+                                                     const double *__restrict__ b,
+                                                     const double *__restrict__ x,
+                                                     double *__restrict__ xn, double w)
 {
     const int c = (static_cast<int>(blockIdx.x) * (kBlock / 64) + static_cast<int>(threadIdx.x >> 6)) * kL0Cols +
                   static_cast<int>(threadIdx.x & 63) - 1;
     bool centre;
     size_t i;
-    cv_t xi;
-    const cv_t ax = l0_apply_wave(a, x, static_cast<int>(blockIdx.y), c, centre, i, xi);
+    double xi;
+    const double ax = l0_apply_wave(a, x, static_cast<int>(blockIdx.y), c, centre, i, xi);
     if (centre) xn[i] = xi + w * dinv[i] * (b[i] - ax);
 }
 
-__global__ __launch_bounds__(kBlock) void k_l0_residual(L0Stencil a, const cv_t *__restrict__ b,
-                                                       const cv_t *__restrict__ x,
-                                                       cv_t *__restrict__ r)
+__global__ __launch_bounds__(kBlock) void k_l0_residual(L0Stencil a, const double *__restrict__ b,
+                                                       const double *__restrict__ x,
+                                                       double *__restrict__ r)
 {
     const int c = (static_cast<int>(blockIdx.x) * (kBlock / 64) + static_cast<int>(threadIdx.x >> 6)) * kL0Cols +
                   static_cast<int>(threadIdx.x & 63) - 1;
     bool centre;
     size_t i;
-    cv_t xi;
-    const cv_t ax = l0_apply_wave(a, x, static_cast<int>(blockIdx.y), c, centre, i, xi);
+    double xi;
+    const double ax = l0_apply_wave(a, x, static_cast<int>(blockIdx.y), c, centre, i, xi);
     if (centre) r[i] = b[i] - ax;
 }
 
 __global__ __launch_bounds__(kBlock) void k_restrict(const int *__restrict__ memptr,
                                                     const int *__restrict__ memidx,
-                                                    const cv_t *__restrict__ r, int nc,
-                                                    cv_t *__restrict__ bc)
+                                                    const double *__restrict__ r, int nc,
+                                                    double *__restrict__ bc)
 {
     for (int I = blockIdx.x * kBlock + threadIdx.x; I < nc; I += gridDim.x * kBlock) {
         double s = 0.0;                                   // members in index order: reproducible
         for (int p = memptr[I]; p < memptr[I + 1]; ++p) s += r[memidx[p]];
-        bc[I] = static_cast<cv_t>(s);
+        bc[I] = s;
     }
 }
 
 __global__ __launch_bounds__(kBlock) void k_prolong_add(const int *__restrict__ agg,
-                                                       const cv_t *__restrict__ xc, int n,
-                                                       cv_t *__restrict__ x)
+                                                       const double *__restrict__ xc, int n,
+                                                       double *__restrict__ x)
 {
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
         const int a = agg[i];
@@ -1031,8 +949,8 @@ __global__ __launch_bounds__(kBlock) void k_gj_finish(const double *__restrict__
 // (coalesced), shuffle reduction.  (One thread per row walked 800 strided
 // loads serially and was ~40 % of a whole V-cycle at 500 x 600.)
 __global__ __launch_bounds__(kBlock) void k_dense_apply(const double *__restrict__ inv,
-                                                       const cv_t *__restrict__ b, int n,
-                                                       cv_t *__restrict__ x)
+                                                       const double *__restrict__ b, int n,
+                                                       double *__restrict__ x)
 {
     const int lane = threadIdx.x & 63;
     const int row = (blockIdx.x * kBlock + threadIdx.x) >> 6;
@@ -1042,40 +960,19 @@ __global__ __launch_bounds__(kBlock) void k_dense_apply(const double *__restrict
     for (int j = lane; j < n; j += 64) s += r[j] * b[j];
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-    if (lane == 0) x[row] = static_cast<cv_t>(s);
+    if (lane == 0) x[row] = s;
 }
 
-__global__ __launch_bounds__(kBlock) void k_axpy1(const cv_t *__restrict__ a, int n, cv_t *__restrict__ x)
+__global__ __launch_bounds__(kBlock) void k_axpy1(const double *__restrict__ a, int n, double *__restrict__ x)
 {
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) x[i] += a[i];
 }
 
-__global__ void k_copy(const cv_t *__restrict__ a, cv_t *__restrict__ b, size_t n)
+__global__ void k_copy(const double *__restrict__ a, double *__restrict__ b, size_t n)
 {
     for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < n;
          i += static_cast<size_t>(gridDim.x) * blockDim.x)
         b[i] = a[i];
-}
-
-// the cycle's way in and out: b = rhs / sqrt(norm2) in the cycle's precision, out = x * sqrt(norm2) (M is linear)
-__device__ __forceinline__ double cycle_scale(const double *norm2)
-{
-    const double v = norm2 ? *norm2 : 1.0;
-    return (v > 0.0 && v < 1e300) ? sqrt(v) : 1.0;
-}
-__global__ void k_cycle_in(const double *__restrict__ rhs, const double *__restrict__ norm2, cv_t *__restrict__ b, size_t n)
-{
-    const double inv = 1.0 / cycle_scale(norm2);
-    for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < n;
-         i += static_cast<size_t>(gridDim.x) * blockDim.x)
-        b[i] = static_cast<cv_t>(rhs[i] * inv);
-}
-__global__ void k_cycle_out(const cv_t *__restrict__ x, const double *__restrict__ norm2, double *__restrict__ out, size_t n)
-{
-    const double sc = cycle_scale(norm2);
-    for (size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; i < n;
-         i += static_cast<size_t>(gridDim.x) * blockDim.x)
-        out[i] = static_cast<double>(x[i]) * sc;
 }
 
 // ---- K-cycle (Notay): two flexible-CG steps on a coarse level, each
@@ -1088,13 +985,13 @@ struct KScalars {
 __global__ __launch_bounds__(kBlock) void k_spmv(const int *__restrict__ rowptr,
                                                 const int *__restrict__ col,
                                                 const double *__restrict__ val,
-                                                const cv_t *__restrict__ x, int n,
-                                                cv_t *__restrict__ y)
+                                                const double *__restrict__ x, int n,
+                                                double *__restrict__ y)
 {
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
         double ax = 0.0;
         for (int p = rowptr[i]; p < rowptr[i + 1]; ++p) ax += val[p] * x[col[p]];
-        y[i] = static_cast<cv_t>(ax);
+        y[i] = ax;
     }
 }
 
@@ -1112,17 +1009,17 @@ __device__ __forceinline__ double kblock_sum(double v, double *lds)
 }
 
 // up to three dot products a_k . b_k in one pass (NULL pairs are skipped)
-__global__ __launch_bounds__(kBlock) void k_dots(const cv_t *a0, const cv_t *b0,
-                                                const cv_t *a1, const cv_t *b1,
-                                                const cv_t *a2, const cv_t *b2, int n,
+__global__ __launch_bounds__(kBlock) void k_dots(const double *a0, const double *b0,
+                                                const double *a1, const double *b1,
+                                                const double *a2, const double *b2, int n,
                                                 KScalars *s)
 {
     __shared__ double lds[kBlock / 64];
     double d0 = 0.0, d1 = 0.0, d2 = 0.0;
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
-        d0 += static_cast<double>(a0[i]) * b0[i];
-        if (a1) d1 += static_cast<double>(a1[i]) * b1[i];
-        if (a2) d2 += static_cast<double>(a2[i]) * b2[i];
+        d0 += a0[i] * b0[i];
+        if (a1) d1 += a1[i] * b1[i];
+        if (a2) d2 += a2[i] * b2[i];
     }
     d0 = kblock_sum(d0, lds);
     d1 = kblock_sum(d1, lds);
@@ -1157,78 +1054,24 @@ __global__ __launch_bounds__(kBlock) void k_kfinish(KScalars *s, int stage, int 
     }
 }
 
-// ---- single-level K-cycle: flexible CG(1) on one coarse level, scalars on the device
-// stage 1: beta = -(z, q_prev) / (p_prev, q_prev);  stage 2: pq = (p, q), alpha = (p, r) / pq
-__global__ __launch_bounds__(kBlock) void k_k1finish(KScalars *s, int stage, int nblocks, int linear)
-{
-    __shared__ double lds[kBlock / 64];
-    double t[2];
-    for (int k = 0; k < 2; ++k) {
-        double d = 0.0;
-        for (int i = threadIdx.x; i < nblocks; i += kBlock) d += s->part[k][i];
-        t[k] = kblock_sum(d, lds);
-    }
-    if (threadIdx.x != 0) return;
-    if (stage == 1) s->beta = (s->rho1 != 0.0 && !linear) ? -t[0] / s->rho1 : 0.0;          // rho1 holds (p_prev, q_prev)
-    else { s->rho1 = t[0]; s->alpha1 = linear ? 1.0 : (t[0] != 0.0 ? t[1] / t[0] : 0.0); }
-}
-// p = z + beta p (first: p = z)
-__global__ __launch_bounds__(kBlock) void k_k1p(const cv_t *__restrict__ z, int n, const KScalars *s, int first,
-                                               cv_t *__restrict__ p)
-{
-    const double beta = first ? 0.0 : s->beta;
-    for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock)
-        p[i] = static_cast<cv_t>(z[i] + beta * (first ? 0.0 : static_cast<double>(p[i])));
-}
-// x += alpha p (first: x = alpha p);  r -= alpha q
-__global__ __launch_bounds__(kBlock) void k_k1xr(const cv_t *__restrict__ p, const cv_t *__restrict__ q, int n,
-                                                const KScalars *s, int first, cv_t *__restrict__ x, cv_t *__restrict__ r)
-{
-    const double alpha = s->alpha1;
-    for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
-        x[i] = static_cast<cv_t>((first ? 0.0 : static_cast<double>(x[i])) + alpha * p[i]);
-        r[i] = static_cast<cv_t>(r[i] - alpha * q[i]);
-    }
-}
-// q = A p with four lanes per row (the CSR sweeps' walk)
-template <class V>
-__global__ __launch_bounds__(kBlock) void k_spmv4(const int *__restrict__ rowptr, const int *__restrict__ col,
-                                                 const V *__restrict__ val, const cv_t *__restrict__ x, int n,
-                                                 cv_t *__restrict__ y)
-{
-    const int sub = threadIdx.x % kRowLanes;
-    const long long groups = static_cast<long long>(gridDim.x) * (kBlock / kRowLanes);
-    for (long long i = blockIdx.x * static_cast<long long>(kBlock / kRowLanes) + threadIdx.x / kRowLanes; i < n;
-         i += groups * kRowsPerGroup) {
-        long long row[kRowsPerGroup];
-        double ax[kRowsPerGroup];
-#pragma unroll
-        for (int u = 0; u < kRowsPerGroup; ++u) row[u] = i + u * groups;
-        rows_dot4(rowptr, col, val, x, row, n, sub, ax);
-#pragma unroll
-        for (int u = 0; u < kRowsPerGroup; ++u)
-            if (sub == 0 && row[u] < n) y[row[u]] = static_cast<cv_t>(ax[u]);
-    }
-}
-
 // r1 = b - f1 v1
-__global__ __launch_bounds__(kBlock) void k_kresid(const cv_t *__restrict__ b,
-                                                  const cv_t *__restrict__ v1, int n,
-                                                  const KScalars *s, cv_t *__restrict__ r1)
+__global__ __launch_bounds__(kBlock) void k_kresid(const double *__restrict__ b,
+                                                  const double *__restrict__ v1, int n,
+                                                  const KScalars *s, double *__restrict__ r1)
 {
     const double f1 = s->f1;
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock)
-        r1[i] = static_cast<cv_t>(b[i] - f1 * v1[i]);
+        r1[i] = b[i] - f1 * v1[i];
 }
 
 // x = f1 c1 + f2 c2
-__global__ __launch_bounds__(kBlock) void k_kcombine(const cv_t *__restrict__ c1,
-                                                    const cv_t *__restrict__ c2, int n,
-                                                    const KScalars *s, cv_t *__restrict__ x)
+__global__ __launch_bounds__(kBlock) void k_kcombine(const double *__restrict__ c1,
+                                                    const double *__restrict__ c2, int n,
+                                                    const KScalars *s, double *__restrict__ x)
 {
     const double f1 = s->f1, f2 = s->f2;
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock)
-        x[i] = static_cast<cv_t>(f1 * c1[i] + f2 * c2[i]);
+        x[i] = f1 * c1[i] + f2 * c2[i];
 }
 
 }  // namespace
@@ -1287,10 +1130,6 @@ int amg_setup(AmgHierarchy &h, const double *cond, const uint8_t *fixed, int row
         AMG_TAKE(rinv, double, n0);
         hipLaunchKernelGGL(k_l0_rinv, dim3(grid_for(n0)), dim3(kBlock), 0, st, cond, fixed, static_cast<size_t>(n0), rinv);
         h.l0_rinv = rinv;
-        cv_t *rinvc;
-        AMG_TAKE(rinvc, cv_t, n0);
-        hipLaunchKernelGGL(k_to_cv, dim3(grid_for(n0)), dim3(kBlock), 0, st, rinv, n0, rinvc);
-        h.l0_rinvc = rinvc;
         void *slots;
         AMG_TAKE(slots, char, 256);
         h.l0_slots = slots;
@@ -1323,22 +1162,20 @@ int amg_setup(AmgHierarchy &h, const double *cond, const uint8_t *fixed, int row
     for (int lev = 0;; ++lev) {
         const int n = L.n;
         AMG_TAKE(L.dinv, double, n);
-        AMG_TAKE(L.dinvc, cv_t, n);
-        AMG_TAKE(L.x, cv_t, n);
-        AMG_TAKE(L.xt, cv_t, n);
-        AMG_TAKE(L.b, cv_t, n);
-        AMG_TAKE(L.r, cv_t, n);
-        if ((lev >= 1 && lev <= h.kdepth) || (lev >= 1 && lev == h.klevel && h.kinner > 0)) {
-            AMG_TAKE(L.kb, cv_t, n);
-            AMG_TAKE(L.c1, cv_t, n);
-            AMG_TAKE(L.v1, cv_t, n);
-            AMG_TAKE(L.v2, cv_t, n);
+        AMG_TAKE(L.x, double, n);
+        AMG_TAKE(L.xt, double, n);
+        AMG_TAKE(L.b, double, n);
+        AMG_TAKE(L.r, double, n);
+        if (lev >= 1 && lev <= h.kdepth) {
+            AMG_TAKE(L.kb, double, n);
+            AMG_TAKE(L.c1, double, n);
+            AMG_TAKE(L.v1, double, n);
+            AMG_TAKE(L.v2, double, n);
             void *ks;
             AMG_TAKE(ks, char, sizeof(KScalars));
             L.kscal = ks;
         }
         hipLaunchKernelGGL(k_dinv, dim3(grid_for(n)), dim3(kBlock), 0, st, L.rowptr, L.col, L.val, n, L.dinv);
-        hipLaunchKernelGGL(k_to_cv, dim3(grid_for(n)), dim3(kBlock), 0, st, L.dinv, n, L.dinvc);
         L.agg = nullptr;
         L.memptr = nullptr;
         L.memidx = nullptr;
@@ -1354,7 +1191,7 @@ int amg_setup(AmgHierarchy &h, const double *cond, const uint8_t *fixed, int row
         AMG_TAKE(flag, int, n + 1);
         AMG_TAKE(cid, int, n + 1);
         int nc = 0;
-        const bool blocks0 = lev == 0 && h.symmetric && !std::getenv("SSRS_AMG_NO_BLOCKS");      // A/B: pairwise matching on level 0 too
+        const bool blocks0 = lev == 0 && h.symmetric && h.blocks0;
         for (int attempt = 0; attempt < 2; ++attempt) {
             if (blocks0) {
                 const long long nb = static_cast<long long>((rows + 1) / 2) * ((cols + 1) / 2);
@@ -1423,7 +1260,7 @@ int amg_setup(AmgHierarchy &h, const double *cond, const uint8_t *fixed, int row
         SSRS_HIP_CHECK(hipStreamSynchronize(st));
         if (last_key == ~0ull) --nuniq;            // the parked bucket
 
-        if (std::getenv("SSRS_PROGRESS"))
+        if (h.progress)
             fprintf(stderr, "[amg] level %d: %d rows, %d nnz -> %d rows, %d nnz%s\n", lev, n, L.nnz, nc, nuniq,
                     permissive ? " (permissive)" : "");
         AmgLevel C{};
@@ -1441,7 +1278,7 @@ int amg_setup(AmgHierarchy &h, const double *cond, const uint8_t *fixed, int row
     if (h.levels.empty()) return set_error(SSRS_ERR_INVALID, "amg: empty hierarchy");
 
     // ---- f32 copies of the coarse matrices for the cycle, in the (now free) sort scratch
-    if (!std::getenv("SSRS_AMG_F64")) {
+    {
         float *pool = reinterpret_cast<float *>(vals_b);
         const size_t room = 2 * static_cast<size_t>(h.levels[0].nnz);
         size_t used = 0;
@@ -1456,28 +1293,26 @@ int amg_setup(AmgHierarchy &h, const double *cond, const uint8_t *fixed, int row
         SSRS_HIP_CHECK(hipGetLastError());
     }
     // ---- sliced ELL copies of the large levels (the ones whose sweeps ran four lanes per row)
-    if (!std::getenv("SSRS_AMG_NO_SELL")) {
-        for (size_t lev = 1; lev < h.levels.size(); ++lev) {
-            AmgLevel &Lv = h.levels[lev];
-            if (Lv.n < kSellRows || !Lv.val32) continue;
-            const int nsl = (Lv.n + 63) / 64;
-            int *cnt;
-            AMG_TAKE(cnt, int, nsl + 1);
-            AMG_TAKE(Lv.sell_ptr, int, nsl + 1);
-            hipLaunchKernelGGL(k_sell_widths, dim3(grid_for(static_cast<size_t>(nsl) * 64)), dim3(kBlock), 0, st, Lv.rowptr, Lv.n, nsl, cnt);
-            size_t tb = cub_tb;
-            SSRS_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(cub_tmp, tb, cnt, Lv.sell_ptr, nsl + 1, st));
-            int total = 0;
-            SSRS_HIP_CHECK(hipMemcpyAsync(&total, Lv.sell_ptr + nsl, sizeof(int), hipMemcpyDeviceToHost, st));
-            SSRS_HIP_CHECK(hipStreamSynchronize(st));
-            if (total <= 0 || static_cast<size_t>(total) > 2 * static_cast<size_t>(Lv.nnz) + 64u * 64u) { Lv.sell_ptr = nullptr; continue; }   // (padding would double it: CSR)
-            AMG_TAKE(Lv.sell_col, int, total);
-            AMG_TAKE(Lv.sell_val, float, total);
-            hipLaunchKernelGGL(k_sell_fill, dim3(grid_for(static_cast<size_t>(nsl) * 64)), dim3(kBlock), 0, st, Lv.rowptr, Lv.col, Lv.val32, Lv.n, nsl,
-                               Lv.sell_ptr, Lv.sell_col, Lv.sell_val);
-        }
-        SSRS_HIP_CHECK(hipGetLastError());
+    for (size_t lev = 1; lev < h.levels.size(); ++lev) {
+        AmgLevel &Lv = h.levels[lev];
+        if (Lv.n < kSellRows || !Lv.val32) continue;
+        const int nsl = (Lv.n + 63) / 64;
+        int *cnt;
+        AMG_TAKE(cnt, int, nsl + 1);
+        AMG_TAKE(Lv.sell_ptr, int, nsl + 1);
+        hipLaunchKernelGGL(k_sell_widths, dim3(grid_for(static_cast<size_t>(nsl) * 64)), dim3(kBlock), 0, st, Lv.rowptr, Lv.n, nsl, cnt);
+        size_t tb = cub_tb;
+        SSRS_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(cub_tmp, tb, cnt, Lv.sell_ptr, nsl + 1, st));
+        int total = 0;
+        SSRS_HIP_CHECK(hipMemcpyAsync(&total, Lv.sell_ptr + nsl, sizeof(int), hipMemcpyDeviceToHost, st));
+        SSRS_HIP_CHECK(hipStreamSynchronize(st));
+        if (total <= 0 || static_cast<size_t>(total) > 2 * static_cast<size_t>(Lv.nnz) + 64u * 64u) { Lv.sell_ptr = nullptr; continue; }   // (padding would double it: CSR)
+        AMG_TAKE(Lv.sell_col, int, total);
+        AMG_TAKE(Lv.sell_val, float, total);
+        hipLaunchKernelGGL(k_sell_fill, dim3(grid_for(static_cast<size_t>(nsl) * 64)), dim3(kBlock), 0, st, Lv.rowptr, Lv.col, Lv.val32, Lv.n, nsl,
+                           Lv.sell_ptr, Lv.sell_col, Lv.sell_val);
     }
+    SSRS_HIP_CHECK(hipGetLastError());
 
     // ---- dense inverse of the coarsest level when it is small enough
     AmgLevel &B = h.levels.back();
@@ -1498,11 +1333,11 @@ int amg_setup(AmgHierarchy &h, const double *cond, const uint8_t *fixed, int row
     }
     SSRS_HIP_CHECK(hipStreamSynchronize(st));
     h.workspace_used = bump.off;
+    h.fuse0 = h.fuse && h.nu0 == 1 && h.levels.size() > 1 && h.levels[0].agg;
     return SSRS_OK;
 }
 
 static void solve_level(AmgHierarchy &h, size_t lev, hipStream_t st);
-
 
 // one wave per slice of 64 rows, at most 16 384 blocks (the kernels stride)
 static dim3 sell_grid(int n)
@@ -1518,39 +1353,40 @@ static dim3 l0_grid(const AmgHierarchy &h)
     return dim3(static_cast<unsigned>((h.l0_cols + per_block - 1) / per_block), static_cast<unsigned>(h.l0_rows));
 }
 
-static void launch_jacobi(AmgHierarchy &h, size_t lev, const cv_t *x, cv_t *xn, hipStream_t st, double w = kOmega)
+static void launch_jacobi(AmgHierarchy &h, size_t lev, const double *x, double *xn, hipStream_t st)
 {
+    const double w = kOmega;
     AmgLevel &L = h.levels[lev];
-    if (lev == 0 && h.l0_rinvc && !getenv("SSRS_AMG_L0_CSR")) {
-        const L0Stencil a{h.l0_rinvc, h.l0_fixed, h.l0_rows, h.l0_cols};
-        hipLaunchKernelGGL(k_l0_jacobi, l0_grid(h), dim3(kBlock), 0, st, a, L.dinvc, L.b, x, xn, static_cast<cv_t>(w));
+    if (lev == 0) {
+        const L0Stencil a{h.l0_rinv, h.l0_fixed, h.l0_rows, h.l0_cols};
+        hipLaunchKernelGGL(k_l0_jacobi, l0_grid(h), dim3(kBlock), 0, st, a, L.dinv, L.b, x, xn, w);
     } else {
         const dim3 g4(grid_for((static_cast<size_t>(L.n) + kRowsPerGroup - 1) / kRowsPerGroup * kRowLanes)), g1(grid_for(L.n));
         if (L.sell_ptr && L.sell_val)
-            hipLaunchKernelGGL(k_sweep_sell<true>, sell_grid(L.n), dim3(kBlock), 0, st, L.sell_ptr, L.sell_col, L.sell_val, L.dinvc, L.b, x, L.n,
+            hipLaunchKernelGGL(k_sweep_sell<true>, sell_grid(L.n), dim3(kBlock), 0, st, L.sell_ptr, L.sell_col, L.sell_val, L.dinv, L.b, x, L.n,
                                (L.n + 63) / 64, xn, w);
         else if (L.n >= kVectorRows && L.val32)
-            hipLaunchKernelGGL(k_jacobi4<float>, g4, dim3(kBlock), 0, st, L.rowptr, L.col, L.val32, L.dinvc, L.b, x, L.n, xn, w);
+            hipLaunchKernelGGL(k_jacobi4<float>, g4, dim3(kBlock), 0, st, L.rowptr, L.col, L.val32, L.dinv, L.b, x, L.n, xn, w);
         else if (L.n >= kVectorRows)
-            hipLaunchKernelGGL(k_jacobi4<double>, g4, dim3(kBlock), 0, st, L.rowptr, L.col, L.val, L.dinvc, L.b, x, L.n, xn, w);
+            hipLaunchKernelGGL(k_jacobi4<double>, g4, dim3(kBlock), 0, st, L.rowptr, L.col, L.val, L.dinv, L.b, x, L.n, xn, w);
         else if (L.val32)
-            hipLaunchKernelGGL(k_jacobi<float>, g1, dim3(kBlock), 0, st, L.rowptr, L.col, L.val32, L.dinvc, L.b, x, L.n, xn, w);
+            hipLaunchKernelGGL(k_jacobi<float>, g1, dim3(kBlock), 0, st, L.rowptr, L.col, L.val32, L.dinv, L.b, x, L.n, xn, w);
         else
-            hipLaunchKernelGGL(k_jacobi<double>, g1, dim3(kBlock), 0, st, L.rowptr, L.col, L.val, L.dinvc, L.b, x, L.n, xn, w);
+            hipLaunchKernelGGL(k_jacobi<double>, g1, dim3(kBlock), 0, st, L.rowptr, L.col, L.val, L.dinv, L.b, x, L.n, xn, w);
     }
 }
 
-static void launch_residual(AmgHierarchy &h, size_t lev, hipStream_t st, const cv_t *x = nullptr)
+static void launch_residual(AmgHierarchy &h, size_t lev, hipStream_t st, const double *x = nullptr)
 {
     AmgLevel &L = h.levels[lev];
     if (!x) x = L.x;
-    if (lev == 0 && h.l0_rinvc && !getenv("SSRS_AMG_L0_CSR")) {
-        const L0Stencil a{h.l0_rinvc, h.l0_fixed, h.l0_rows, h.l0_cols};
+    if (lev == 0) {
+        const L0Stencil a{h.l0_rinv, h.l0_fixed, h.l0_rows, h.l0_cols};
         hipLaunchKernelGGL(k_l0_residual, l0_grid(h), dim3(kBlock), 0, st, a, L.b, x, L.r);
     } else {
         const dim3 g4(grid_for((static_cast<size_t>(L.n) + kRowsPerGroup - 1) / kRowsPerGroup * kRowLanes)), g1(grid_for(L.n));
         if (L.sell_ptr && L.sell_val)
-            hipLaunchKernelGGL(k_sweep_sell<false>, sell_grid(L.n), dim3(kBlock), 0, st, L.sell_ptr, L.sell_col, L.sell_val, L.dinvc, L.b, x, L.n,
+            hipLaunchKernelGGL(k_sweep_sell<false>, sell_grid(L.n), dim3(kBlock), 0, st, L.sell_ptr, L.sell_col, L.sell_val, L.dinv, L.b, x, L.n,
                                (L.n + 63) / 64, L.r, 0.0);
         else if (L.n >= kVectorRows && L.val32)
             hipLaunchKernelGGL(k_residual4<float>, g4, dim3(kBlock), 0, st, L.rowptr, L.col, L.val32, L.b, x, L.n, L.r);
@@ -1579,63 +1415,46 @@ static void cycle(AmgHierarchy &h, size_t lev, hipStream_t st)
             hipLaunchKernelGGL(k_dense_apply, dim3(gd), dim3(kBlock), 0, st, h.dense_inv, L.r, n, L.xt);
             hipLaunchKernelGGL(k_axpy1, dim3(g), dim3(kBlock), 0, st, L.xt, n, L.x);
         } else {                                   // stalled coarsening: relax
-            hipLaunchKernelGGL(k_jacobi_first, dim3(g), dim3(kBlock), 0, st, L.dinvc, L.b, n, L.x, kOmega);
+            hipLaunchKernelGGL(k_jacobi_first, dim3(g), dim3(kBlock), 0, st, L.dinv, L.b, n, L.x, kOmega);
             for (int s = 0; s < 20; ++s) {
-                hipLaunchKernelGGL(k_jacobi, dim3(g), dim3(kBlock), 0, st, L.rowptr, L.col, L.val, L.dinvc, L.b, L.x, n, L.xt, kOmega);
-                hipLaunchKernelGGL(k_jacobi, dim3(g), dim3(kBlock), 0, st, L.rowptr, L.col, L.val, L.dinvc, L.b, L.xt, n, L.x, kOmega);
+                hipLaunchKernelGGL(k_jacobi, dim3(g), dim3(kBlock), 0, st, L.rowptr, L.col, L.val, L.dinv, L.b, L.x, n, L.xt, kOmega);
+                hipLaunchKernelGGL(k_jacobi, dim3(g), dim3(kBlock), 0, st, L.rowptr, L.col, L.val, L.dinv, L.b, L.xt, n, L.x, kOmega);
             }
         }
         return;
     }
     if (!h.robust && lev == 0 && h.fuse0) {
-        if constexpr (sizeof(cv_t) == sizeof(double)) {
-            const double *rinv = reinterpret_cast<const double *>(h.l0_rinvc);
-            const L0Slots *slots = static_cast<const L0Slots *>(h.l0_slots);
-            AmgLevel &C1 = h.levels[1];
-            if (!std::getenv("SSRS_AMG_L0_ONE_ROW")) {
-                dim3 g2 = l0_grid(h);
-                g2.y = (g2.y + 1) / 2;
-                const bool in_place = h.l0_blocks && (kL0Cols % 2) == 0;       // restriction inside the pre pass
-                hipLaunchKernelGGL(k_l0_pre2, g2, dim3(kBlock), 0, st, rinv, h.l0_rows, h.l0_cols, reinterpret_cast<const double *>(L.dinvc),
-                                   slots, h.om[0], reinterpret_cast<double *>(L.xt), reinterpret_cast<double *>(L.r),
-                                   in_place ? L.agg : static_cast<const int *>(nullptr), reinterpret_cast<double *>(C1.b));
-                if (!in_place) hipLaunchKernelGGL(k_restrict, dim3(grid_for(C1.n)), dim3(kBlock), 0, st, L.memptr, L.memidx, L.r, C1.n, C1.b);
-                solve_level(h, 1, st);
-                hipLaunchKernelGGL(k_l0_post2, g2, dim3(kBlock), 0, st, rinv, h.l0_rows, h.l0_cols, reinterpret_cast<const double *>(L.dinvc),
-                                   slots, L.agg, reinterpret_cast<const double *>(C1.x), reinterpret_cast<const double *>(L.xt), h.om[0]);
-                return;
-            }
-            hipLaunchKernelGGL(k_l0_pre_fused, l0_grid(h), dim3(kBlock), 0, st, rinv, h.l0_rows, h.l0_cols,
-                               reinterpret_cast<const double *>(L.dinvc), slots, h.om[0], reinterpret_cast<double *>(L.xt),
-                               reinterpret_cast<double *>(L.r));
-            hipLaunchKernelGGL(k_restrict, dim3(grid_for(C1.n)), dim3(kBlock), 0, st, L.memptr, L.memidx, L.r, C1.n, C1.b);
-            solve_level(h, 1, st);
-            hipLaunchKernelGGL(k_l0_post_fused, l0_grid(h), dim3(kBlock), 0, st, rinv, h.l0_rows, h.l0_cols,
-                               reinterpret_cast<const double *>(L.dinvc), slots, L.agg, reinterpret_cast<const double *>(C1.x),
-                               reinterpret_cast<const double *>(L.xt), h.om[0]);
-        }
+        const L0Slots *slots = static_cast<const L0Slots *>(h.l0_slots);
+        AmgLevel &C1 = h.levels[1];
+        dim3 g2 = l0_grid(h);
+        g2.y = (g2.y + 1) / 2;
+        const bool in_place = h.l0_blocks && (kL0Cols % 2) == 0;       // restriction inside the pre pass
+        hipLaunchKernelGGL(k_l0_pre2, g2, dim3(kBlock), 0, st, h.l0_rinv, h.l0_rows, h.l0_cols, L.dinv, slots, kOmega, L.xt, L.r,
+                           in_place ? L.agg : static_cast<const int *>(nullptr), C1.b);
+        if (!in_place) hipLaunchKernelGGL(k_restrict, dim3(grid_for(C1.n)), dim3(kBlock), 0, st, L.memptr, L.memidx, L.r, C1.n, C1.b);
+        solve_level(h, 1, st);
+        hipLaunchKernelGGL(k_l0_post2, g2, dim3(kBlock), 0, st, h.l0_rinv, h.l0_rows, h.l0_cols, L.dinv, slots, L.agg, C1.x, L.xt,
+                           kOmega);
         return;
     }
     if (!h.robust && (lev == 0 ? h.nu0 : h.nuc) == 1) {
         // V(1,1): x = w D^-1 b, coarse correction, one sweep with the same step (self-adjoint in the D inner product);
         // the iterate lives in L.xt until the last sweep writes L.x
-        hipLaunchKernelGGL(k_jacobi_first, dim3(g), dim3(kBlock), 0, st, L.dinvc, L.b, n, L.xt, h.om[0]);
+        hipLaunchKernelGGL(k_jacobi_first, dim3(g), dim3(kBlock), 0, st, L.dinv, L.b, n, L.xt, kOmega);
         launch_residual(h, lev, st, L.xt);
         AmgLevel &C1 = h.levels[lev + 1];
         hipLaunchKernelGGL(k_restrict, dim3(grid_for(C1.n)), dim3(kBlock), 0, st, L.memptr, L.memidx, L.r, C1.n, C1.b);
         solve_level(h, lev + 1, st);
         hipLaunchKernelGGL(k_prolong_add, dim3(g), dim3(kBlock), 0, st, L.agg, C1.x, n, L.xt);
-        launch_jacobi(h, lev, L.xt, L.x, st, h.om[0]);
+        launch_jacobi(h, lev, L.xt, L.x, st);
         return;
     }
     // pre-smoothing: 2*sweeps Jacobi sweeps from x = 0
-    // (step sizes of a pair of sweeps: h.om[0], h.om[1] before the coarse correction, the same in reverse after it --
-    // the smoother stays self-adjoint in the D inner product whatever the two are)
-    hipLaunchKernelGGL(k_jacobi_first, dim3(g), dim3(kBlock), 0, st, L.dinvc, L.b, n, L.xt, h.om[0]);
-    launch_jacobi(h, lev, L.xt, L.x, st, h.om[1]);
+    hipLaunchKernelGGL(k_jacobi_first, dim3(g), dim3(kBlock), 0, st, L.dinv, L.b, n, L.xt, kOmega);
+    launch_jacobi(h, lev, L.xt, L.x, st);
     for (int s = 1; s < h.sweeps; ++s) {
-        launch_jacobi(h, lev, L.x, L.xt, st, h.om[0]);
-        launch_jacobi(h, lev, L.xt, L.x, st, h.om[1]);
+        launch_jacobi(h, lev, L.x, L.xt, st);
+        launch_jacobi(h, lev, L.xt, L.x, st);
     }
     launch_residual(h, lev, st);
     AmgLevel &C = h.levels[lev + 1];
@@ -1644,8 +1463,8 @@ static void cycle(AmgHierarchy &h, size_t lev, hipStream_t st)
     hipLaunchKernelGGL(k_prolong_add, dim3(g), dim3(kBlock), 0, st, L.agg, C.x, n, L.x);
     // post-smoothing
     for (int s = 0; s < h.sweeps; ++s) {
-        launch_jacobi(h, lev, L.x, L.xt, st, h.om[1]);
-        launch_jacobi(h, lev, L.xt, L.x, st, h.om[0]);
+        launch_jacobi(h, lev, L.x, L.xt, st);
+        launch_jacobi(h, lev, L.xt, L.x, st);
     }
 }
 
@@ -1655,35 +1474,7 @@ static void cycle(AmgHierarchy &h, size_t lev, hipStream_t st)
 static void solve_level(AmgHierarchy &h, size_t lev, hipStream_t st)
 {
     AmgLevel &L = h.levels[lev];
-    if (lev + 1 != h.levels.size() && static_cast<int>(lev) == h.klevel && h.kinner > 0 && L.kscal && !h.robust) {
-        // single-level K-cycle: kinner steps of flexible CG(1) on this level's system, each preconditioned by the
-        // cycle from here down.  r = L.kb, x = L.c1, p = L.v1, q = L.v2, z = L.x
-        const int n = L.n, g = grid_for(n);
-        const int gb = g > 256 ? 256 : g;
-        const dim3 g4(grid_for((static_cast<size_t>(n) + kRowsPerGroup - 1) / kRowsPerGroup * kRowLanes));
-        KScalars *ks = static_cast<KScalars *>(L.kscal);
-        const int klin = std::getenv("SSRS_AMG_K_LINEAR") != nullptr ? 1 : 0;     // experiment: plain repeated cycles (alpha 1, beta 0)
-        hipLaunchKernelGGL(k_copy, dim3(g), dim3(256), 0, st, L.b, L.kb, static_cast<size_t>(n));
-        for (int k = 0; k < h.kinner; ++k) {
-            if (k > 0) hipLaunchKernelGGL(k_copy, dim3(g), dim3(256), 0, st, L.kb, L.b, static_cast<size_t>(n));
-            cycle(h, lev, st);                                                             // z = B r (in L.x)
-            if (k > 0) {
-                hipLaunchKernelGGL(k_dots, dim3(gb), dim3(kBlock), 0, st, L.x, L.v2, nullptr, nullptr, nullptr, nullptr, n, ks);
-                hipLaunchKernelGGL(k_k1finish, dim3(1), dim3(kBlock), 0, st, ks, 1, gb, klin);
-            }
-            hipLaunchKernelGGL(k_k1p, dim3(g), dim3(kBlock), 0, st, L.x, n, ks, k == 0 ? 1 : 0, L.v1);
-            // q = A p from the f64 entries: the f32 copies the sweeps read round the diagonal up and the off-diagonals toward
-            // zero, which multiplies the energy (p, A p) of a floating cluster's level -- a row sum of 1e-8 of the diagonal --
-            // by ~100; the step sizes would come out 100 times too small (measured: alpha 0.01, 1 555 outer iterations)
-            hipLaunchKernelGGL(k_spmv4<double>, g4, dim3(kBlock), 0, st, L.rowptr, L.col, L.val, L.v1, n, L.v2);
-            hipLaunchKernelGGL(k_dots, dim3(gb), dim3(kBlock), 0, st, L.v1, L.v2, L.v1, L.kb, nullptr, nullptr, n, ks);
-            hipLaunchKernelGGL(k_k1finish, dim3(1), dim3(kBlock), 0, st, ks, 2, gb, klin);
-            hipLaunchKernelGGL(k_k1xr, dim3(g), dim3(kBlock), 0, st, L.v1, L.v2, n, ks, k == 0 ? 1 : 0, L.c1, L.kb);
-        }
-        hipLaunchKernelGGL(k_copy, dim3(g), dim3(256), 0, st, L.c1, L.x, static_cast<size_t>(n));
-        return;
-    }
-    if (lev + 1 == h.levels.size() || static_cast<int>(lev) > h.kdepth || !L.kscal || (h.klevel > 0 && h.kinner > 0)) {
+    if (lev + 1 == h.levels.size() || static_cast<int>(lev) > h.kdepth || !L.kscal) {
         cycle(h, lev, st);
         return;
     }
@@ -1720,14 +1511,14 @@ static void ensure_graph(AmgHierarchy &h, hipStream_t st)
     hipGraph_t graph = nullptr;
     hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
     if (e != hipSuccess) {
-        if (std::getenv("SSRS_PROGRESS")) fprintf(stderr, "[amg] begin capture failed: %s\n", hipGetErrorString(e));
+        if (h.progress) fprintf(stderr, "[amg] begin capture failed: %s\n", hipGetErrorString(e));
         (void)hipGetLastError();
         return;
     }
     cycle(h, 0, st);
     e = hipStreamEndCapture(st, &graph);
     if (e != hipSuccess || graph == nullptr) {
-        if (std::getenv("SSRS_PROGRESS")) fprintf(stderr, "[amg] end capture failed: %s\n", hipGetErrorString(e));
+        if (h.progress) fprintf(stderr, "[amg] end capture failed: %s\n", hipGetErrorString(e));
         (void)hipGetLastError();
         return;
     }
@@ -1735,7 +1526,7 @@ static void ensure_graph(AmgHierarchy &h, hipStream_t st)
     e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     if (e == hipSuccess) h.graph_exec[which] = exec;
     else (void)hipGetLastError();
-    if (std::getenv("SSRS_PROGRESS"))
+    if (h.progress)
         fprintf(stderr, "[amg] V-cycle graph: %s\n", e == hipSuccess ? "captured" : hipGetErrorString(e));
     (void)hipGraphDestroy(graph);
 }
@@ -1748,12 +1539,10 @@ void amg_release(AmgHierarchy &h)
     }
 }
 
-void amg_apply(AmgHierarchy &h, const double *rhs, double *out, const double *norm2, hipStream_t st, bool robust)
+void amg_apply(AmgHierarchy &h, const double *rhs, double *out, hipStream_t st, bool robust)
 {
     AmgLevel &L = h.levels[0];
     h.robust = robust;
-    h.fuse0 = sizeof(cv_t) == sizeof(double) && h.l0_rinvc && h.l0_slots && h.nu0 == 1 && h.levels.size() > 1 && h.levels[0].agg &&
-              !std::getenv("SSRS_AMG_L0_CSR") && !std::getenv("SSRS_AMG_NO_FUSE");
     ensure_graph(h, st);
     if (!robust && h.fuse0) {
         // the fused level 0 reads `rhs` and writes `out` itself: no staging copies
@@ -1762,12 +1551,11 @@ void amg_apply(AmgHierarchy &h, const double *rhs, double *out, const double *no
         if (fexec == nullptr || hipGraphLaunch(static_cast<hipGraphExec_t>(fexec), st) != hipSuccess) cycle(h, 0, st);
         return;
     }
-    if (sizeof(cv_t) == sizeof(double)) norm2 = nullptr;      // the scaling only serves the f32 option's range
-    hipLaunchKernelGGL(k_cycle_in, dim3(grid_for(L.n)), dim3(256), 0, st, rhs, norm2, L.b, static_cast<size_t>(L.n));
+    hipLaunchKernelGGL(k_copy, dim3(grid_for(L.n)), dim3(256), 0, st, rhs, L.b, static_cast<size_t>(L.n));
     void *exec = h.graph_exec[robust ? 1 : 0];
     if (exec == nullptr || hipGraphLaunch(static_cast<hipGraphExec_t>(exec), st) != hipSuccess)
         cycle(h, 0, st);
-    hipLaunchKernelGGL(k_cycle_out, dim3(grid_for(L.n)), dim3(256), 0, st, h.levels[0].x, norm2, out, static_cast<size_t>(L.n));
+    hipLaunchKernelGGL(k_copy, dim3(grid_for(L.n)), dim3(256), 0, st, L.x, out, static_cast<size_t>(L.n));
 }
 
 }  // namespace ssrs

@@ -537,6 +537,47 @@ __global__ __launch_bounds__(kBlock) void k_to_f32(const double *__restrict__ x,
 
 static size_t vec_bytes(size_t n) { return (n * 8 + 255) / 256 * 256; }
 
+// The solver's switches from the environment, read at the start of every call (tests set them between calls)
+struct SolverSwitches {
+    bool progress;               // SSRS_PROGRESS: heartbeat, carried against recomputed residuals on stderr
+    bool progress_every;         // SSRS_PROGRESS=2: a line at every check
+    bool fallback;               // off if SSRS_SOLVE_NO_FALLBACK: BiCGStab's answer as it is, no defect correction
+    bool blocks0, fuse;          // off if SSRS_AMG_NO_BLOCKS, SSRS_AMG_NO_FUSE (amg.h)
+    int nu0, nuc;                // SSRS_AMG_NU=a,b (amg.h)
+};
+
+static SolverSwitches read_solver_switches()
+{
+    auto set = [](const char *name) { return std::getenv(name) != nullptr; };
+    SolverSwitches sw;
+    const char *progress = std::getenv("SSRS_PROGRESS");
+    sw.progress = progress != nullptr;
+    sw.progress_every = progress != nullptr && std::atoi(progress) >= 2;
+    sw.fallback = !set("SSRS_SOLVE_NO_FALLBACK");
+    sw.blocks0 = !set("SSRS_AMG_NO_BLOCKS");
+    sw.fuse = !set("SSRS_AMG_NO_FUSE");
+    sw.nu0 = sw.nuc = 1;
+    if (const char *e = std::getenv("SSRS_AMG_NU")) {
+        int a0 = 2, a1 = 2;
+        if (std::sscanf(e, "%d,%d", &a0, &a1) == 2) { sw.nu0 = a0 == 1 ? 1 : 2; sw.nuc = a1 == 1 ? 1 : 2; }
+    }
+    return sw;
+}
+
+// The events of a call, released on every way out of it
+struct SolveEvents {
+    hipEvent_t setup0 = nullptr, setup1 = nullptr;   // around the AMG set-up
+    hipEvent_t first = nullptr, last = nullptr;      // around the iteration
+    SolveEvents() = default;
+    SolveEvents(const SolveEvents &) = delete;
+    SolveEvents &operator=(const SolveEvents &) = delete;
+    ~SolveEvents()
+    {
+        for (hipEvent_t e : {setup0, setup1, first, last})
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
 }  // namespace ssrs
 
 using namespace ssrs;
@@ -557,6 +598,361 @@ typedef struct SsrsSolveStatsInternal {
     uint64_t workspace_used;
 } SsrsSolveStatsInternal;
 static_assert(sizeof(SsrsSolveStatsInternal) == sizeof(SsrsSolveStats), "stats layout");
+
+namespace {
+
+// One call of ssrs_potential_solve: the workspace's vectors, the hierarchy and the state the phases hand on
+struct SolveRun {
+    const double *cond, *fixed_values, *guess;
+    const uint8_t *fixed;
+    float *potential;
+    int rows, cols;
+    double rel_tol;
+    int max_iterations;
+    void *workspace;
+    size_t workspace_bytes;
+    hipStream_t st;
+    const SolverSwitches sw;
+    SolveEvents ev;
+    const size_t n;
+    Scalars *sc;
+    char *base;                            // the solver's vectors, then the hierarchy's workspace
+    double *x, *r, *rhat, *p, *v, *sv, *t;
+    double *xbest, *phat, *shat;
+    double *x_pcg;                         // PCG's iterate, kept for the fall-back of phase 2
+    // right-preconditioned BiCGStab: M = one AMG V-cycle of the symmetric operator
+    const bool use_amg;
+    AmgHierarchy amg;
+    float setup_ms = 0.f;
+    size_t ws_used;
+    StencilArgs a = {}, as = {};           // the exact operator; the symmetric one (natural weights)
+    int nb = 0;
+    double host[2] = {0.0, 0.0};
+    // PCG
+    int cg_iterations = 0;
+    bool restart_dirs = true;
+    bool pcg_ok = false;                   // PCG reached rel_tol on the symmetric operator
+    // BiCGStab
+    int it = 0, converged = 0, robust_from = -1;
+    double rel = 1.0, best = 1e300;
+
+    SolveRun(const double *conductivity, const uint8_t *fixed_mask, const double *fixed_vals, const double *initial_guess,
+             float *pot, int rows_, int cols_, double tol, int max_it, int flags, void *ws, size_t ws_bytes, hipStream_t stream)
+        : cond(conductivity), fixed_values(fixed_vals), guess(initial_guess), fixed(fixed_mask), potential(pot),
+          rows(rows_), cols(cols_), rel_tol(tol), max_iterations(max_it), workspace(ws), workspace_bytes(ws_bytes), st(stream),
+          sw(read_solver_switches()), n(static_cast<size_t>(rows_) * cols_), use_amg((flags & SSRS_SOLVE_NO_AMG) == 0)
+    {
+        base = static_cast<char *>(workspace);
+        sc = reinterpret_cast<Scalars *>(base);
+        base += (sizeof(Scalars) + 255) / 256 * 256;
+        double *vec[11];
+        for (int i = 0; i < 11; ++i) vec[i] = reinterpret_cast<double *>(base + i * vec_bytes(n));
+        x = vec[0]; r = vec[1]; rhat = vec[2]; p = vec[3]; v = vec[4]; sv = vec[5]; t = vec[6];
+        xbest = vec[7]; phat = vec[8]; shat = vec[9]; x_pcg = vec[10];
+        amg.sweeps = 1 + ((flags >> 4) & 7);
+        amg.nu0 = sw.nu0;
+        amg.nuc = sw.nuc;
+        amg.blocks0 = sw.blocks0;
+        amg.fuse = sw.fuse;
+        amg.progress = sw.progress;
+        amg.kdepth = (flags & SSRS_SOLVE_K_CYCLE) ? (((flags >> 12) & 15) ? ((flags >> 12) & 15) : 3) : 0;
+        amg.symmetric = (flags & SSRS_SOLVE_ONE_SIDED) == 0;
+        amg.strong_rounds = ((flags >> 8) & 15) ? ((flags >> 8) & 15) : 4;
+        ws_used = static_cast<size_t>(11 * vec_bytes(n)) + 512;
+    }
+    ~SolveRun() { amg_release(amg); }      // the captured graph is host state: freed on every exit
+    SolveRun(const SolveRun &) = delete;
+    SolveRun &operator=(const SolveRun &) = delete;
+
+    int setup_amg();
+    int start();
+    int pcg(double tol, int cap, double &reached);
+    int pcg_phase();
+    int report_pcg();
+    int bicgstab();
+    int fall_back();
+    int finish(void *stats_out);
+};
+
+// The hierarchy, in the workspace behind the solver's vectors
+int SolveRun::setup_amg()
+{
+    SSRS_HIP_CHECK(hipEventCreate(&ev.setup0));
+    SSRS_HIP_CHECK(hipEventCreate(&ev.setup1));
+    SSRS_HIP_CHECK(hipEventRecord(ev.setup0, st));
+    char *amg_base = base + 11 * vec_bytes(n);
+    amg_base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(amg_base) + 255) / 256 * 256);
+    const size_t amg_bytes = static_cast<size_t>(static_cast<char *>(workspace) + workspace_bytes - amg_base);
+    const int rc = amg_setup(amg, cond, fixed, rows, cols, amg_base, amg_bytes, st);
+    (void)hipEventRecord(ev.setup1, st);
+    (void)hipEventSynchronize(ev.setup1);
+    (void)hipEventElapsedTime(&setup_ms, ev.setup0, ev.setup1);
+    if (rc != SSRS_OK) return rc;
+    ws_used += amg.workspace_used;
+    return SSRS_OK;
+}
+
+// |b| (the stopping criterion is |r| <= rel_tol |b|, independent of the start) and the start field with its residual
+int SolveRun::start()
+{
+    a = StencilArgs{cond, use_amg ? amg.l0_rinv : nullptr, fixed, rows, cols, use_amg ? 1 : 0, 1, make_tile_walk(rows, cols)};
+    as = a;
+    as.quirk = 0;
+    nb = static_cast<int>((n + kBlock - 1) / kBlock);
+    if (nb > kRedBlocks) nb = kRedBlocks;
+    SSRS_HIP_CHECK(hipEventCreate(&ev.first));
+    SSRS_HIP_CHECK(hipEventCreate(&ev.last));
+    SSRS_HIP_CHECK(hipEventRecord(ev.first, st));
+    SSRS_HIP_CHECK(hipMemsetAsync(sc, 0, sizeof(Scalars), st));
+    hipLaunchKernelGGL(k_init_x, dim3(nb), dim3(kBlock), 0, st, fixed, fixed_values,
+                       static_cast<const double *>(nullptr), 0.0, x, rows, cols);
+    hipLaunchKernelGGL(k_setup, dim3(nb), dim3(kBlock), 0, st, a, x, r, rhat, p, v, sc);
+    hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_BNORM, nb);
+    // start field: caller's guess, else the mid value 500
+    hipLaunchKernelGGL(k_init_x, dim3(nb), dim3(kBlock), 0, st, fixed, fixed_values, guess, 500.0, x, rows, cols);
+    hipLaunchKernelGGL(k_setup, dim3(nb), dim3(kBlock), 0, st, a, x, r, rhat, p, v, sc);
+    hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_INIT, nb);
+    SSRS_HIP_CHECK(hipGetLastError());
+    return SSRS_OK;
+}
+
+// Preconditioned (flexible) CG on the symmetric operator A_s from the carried residual r, until |r| <= tol |b| or
+// cg_iterations reaches `cap`; `reached` = the last |r| / |b| it saw.  Phase 1 of the AMG solve, and the engine of
+// phase 2's fall-back.
+int SolveRun::pcg(double tol, int cap, double &reached)
+{
+    double cg_best = 1e300, now = 1e300;
+    int stalled = 0;
+    while (cg_iterations < cap) {
+        for (int j = 0; j < 5; ++j, ++cg_iterations) {
+            // flexible CG(1): p is A-orthogonalised explicitly against the previous direction
+            amg_apply(amg, r, phat, st);                                                         // z = M r
+            hipLaunchKernelGGL(k_cg_dot_rz, dim3(nb), dim3(kBlock), 0, st, phat, v, n, sc);      // (z, q_prev)
+            hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_CG_RHO, nb);
+            hipLaunchKernelGGL(k_cg_p, dim3(nb), dim3(kBlock), 0, st, p, phat, n, sc, restart_dirs ? 1 : 0);
+            restart_dirs = false;
+            if (as.rinv)                                                                         // q = A p
+                hipLaunchKernelGGL(k_cg_apply_wave, dim3(nb), dim3(kBlock), 0, st, as, p, v, r, sc);
+            else
+                hipLaunchKernelGGL(k_cg_apply, dim3(nb), dim3(kBlock), 0, st, as, p, v, r, sc);
+            hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_CG_ALPHA, nb);
+            hipLaunchKernelGGL(k_cg_xr, dim3(nb), dim3(kBlock), 0, st, x, r, p, v, n, sc);
+            hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_CG_RR, nb);
+        }
+        if (hipGetLastError() != hipSuccess ||
+            hipMemcpyAsync(host, &sc->rnorm2, 2 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) return SSRS_ERR_HIP;
+        if (!(host[0] == host[0])) break;
+        now = host[1] > 0.0 ? std::sqrt(host[0] / host[1]) : 0.0;
+        if (sw.progress && (cg_iterations % 250 == 0 || sw.progress_every))
+            fprintf(stderr, "[ssrs_potential_solve] PCG it %d |r|/|b| %.3e\n", cg_iterations, now);
+        if (now <= tol) break;
+        if (now < 0.9 * cg_best) { cg_best = now; stalled = 0; }
+        else if (++stalled >= 100) break;          // 500 iterations without a 10 % gain
+    }
+    reached = now;
+    return SSRS_OK;
+}
+
+// ---- phase 1: PCG on the symmetric operator (natural weights).  One V-cycle + one operator application per iteration;
+// it delivers the solution up to the east-edge quirk, which phase 2 (BiCGStab on the exact operator, started from here)
+// removes in a few iterations.
+int SolveRun::pcg_phase()
+{
+    hipLaunchKernelGGL(k_setup, dim3(nb), dim3(kBlock), 0, st, as, x, r, rhat, p, v, sc);
+    hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_INIT, nb);
+    // where PCG hands over: the exact operator's residual of the symmetric problem's solution (the quirk's defect) is
+    // ~1e-6 of the right-hand side, so BiCGStab starts from there whatever PCG reached below it
+    double reached = 1e300;
+    if (pcg(rel_tol, max_iterations, reached) != SSRS_OK)
+        return set_error(SSRS_ERR_HIP, "ssrs_potential_solve: HIP error in the PCG phase");
+    pcg_ok = reached <= rel_tol;
+    SSRS_HIP_CHECK(hipMemcpyAsync(x_pcg, x, n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (sw.progress) {
+        const int rc = report_pcg();
+        if (rc != SSRS_OK) return rc;
+    }
+    // hand over to BiCGStab on the exact operator
+    hipLaunchKernelGGL(k_setup, dim3(nb), dim3(kBlock), 0, st, a, x, r, rhat, p, v, sc);
+    hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_INIT, nb);
+    SSRS_HIP_CHECK(hipGetLastError());
+    return SSRS_OK;
+}
+
+// SSRS_PROGRESS: what PCG's carried residual is worth -- recomputed with the symmetric and with the exact operator
+int SolveRun::report_pcg()
+{
+    for (int q = 0; q < 2; ++q) {
+        StencilArgs aq = a;
+        aq.quirk = q;
+        hipLaunchKernelGGL(k_setup, dim3(nb), dim3(kBlock), 0, st, aq, x, r, rhat, p, v, sc);
+        hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_INIT, nb);
+        SSRS_HIP_CHECK(hipMemcpyAsync(host, &sc->rnorm2, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+        SSRS_HIP_CHECK(hipStreamSynchronize(st));
+        fprintf(stderr, "[ssrs_potential_solve] after PCG (%d iterations): recomputed |r|/|b| %.3e with the %s operator\n", cg_iterations,
+                host[1] > 0.0 ? std::sqrt(host[0] / host[1]) : 0.0, q ? "exact (east-edge quirk)" : "symmetric");
+        double *dbg = nullptr;
+        if (hipMalloc(&dbg, 8 * sizeof(double)) == hipSuccess) {
+            (void)hipMemsetAsync(dbg, 0, 8 * sizeof(double), st);
+            hipLaunchKernelGGL(k_resid_breakdown, dim3(1024), dim3(kBlock), 0, st, aq, r, dbg);
+            double hb[8];
+            (void)hipMemcpyAsync(hb, dbg, sizeof(hb), hipMemcpyDeviceToHost, st);
+            (void)hipStreamSynchronize(st);
+            unsigned long long wcell;
+            memcpy(&wcell, &hb[4], sizeof(wcell));
+            fprintf(stderr, "    sum r^2: live cells %.3e, dead cells %.3e, east-edge column %.3e (|b|^2 %.3e); largest |r| %.3e at row %llu col %llu\n",
+                    hb[0], hb[1], hb[2], host[1], hb[3], wcell / a.cols, wcell % a.cols);
+            (void)hipFree(dbg);
+        }
+    }
+    return SSRS_OK;
+}
+
+// ---- phase 2 (or the whole solve without the AMG): BiCGStab on the exact operator; x ends as the best iterate
+int SolveRun::bicgstab()
+{
+    int restarts = 0;
+    const int check_every = use_amg ? 5 : 25, max_restarts = 50;
+    bool fresh = true;                     // p == r (no k_update_p on the first pass)
+    // after the PCG phase BiCGStab only has to remove the quirk's defect: it gets
+    // what is left of the iteration budget (at least 50)
+    int bicg_cap = max_iterations;
+    if (use_amg) bicg_cap = max_iterations - cg_iterations > 50 ? max_iterations - cg_iterations : 50;
+    // BiCGStab can stagnate under the V(1,1) cycle (snapshot 25 of configs[4]: the carried residual sat at 1.7e-11 for
+    // 1 700 iterations, profiles/r04_k5.md) where the V(2,2) cycle of rounds 1-3 converges: a healthy run gains a factor
+    // of ten every ~15 iterations, so 40 iterations without a factor of two switch the preconditioner to the
+    // robust cycle for the rest of the solve (no restart: x and r stay consistent, only the search directions change)
+    bool robust_cycle = false;
+    double gain_mark = 1e300;
+    int gain_it = 0;
+    while (it < bicg_cap) {
+        for (int j = 0; j < check_every && it < bicg_cap; ++j, ++it) {
+            if (!fresh) hipLaunchKernelGGL(k_update_p, dim3(nb), dim3(kBlock), 0, st, p, r, v, n, sc);
+            fresh = false;
+            const double *ph = p, *sh = sv;
+            if (use_amg) { amg_apply(amg, p, phat, st, robust_cycle); ph = phat; }
+            if (a.rinv) hipLaunchKernelGGL(k_apply_dot1_wave, dim3(nb), dim3(kBlock), 0, st, a, ph, v, rhat, sc);
+            else hipLaunchKernelGGL(k_apply_dot1, dim3(nb), dim3(kBlock), 0, st, a, ph, v, rhat, sc);
+            hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_ALPHA, nb);
+            hipLaunchKernelGGL(k_form_s, dim3(nb), dim3(kBlock), 0, st, r, v, sv, n, sc);
+            if (use_amg) { amg_apply(amg, sv, shat, st, robust_cycle); sh = shat; }
+            if (a.rinv) hipLaunchKernelGGL(k_apply_dot2_wave, dim3(nb), dim3(kBlock), 0, st, a, sh, t, sv, sc);
+            else hipLaunchKernelGGL(k_apply_dot2, dim3(nb), dim3(kBlock), 0, st, a, sh, t, sv, sc);
+            hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_OMEGA, nb);
+            hipLaunchKernelGGL(k_update_xr, dim3(nb), dim3(kBlock), 0, st, x, r, ph, sh, sv, t, rhat, n, sc);
+            hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_RHO, nb);
+        }
+        SSRS_HIP_CHECK(hipGetLastError());
+        SSRS_HIP_CHECK(hipMemcpyAsync(host, &sc->rnorm2, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+        SSRS_HIP_CHECK(hipStreamSynchronize(st));
+        const bool finite = host[0] == host[0] && host[0] < 1e300;
+        const double now = finite && host[1] > 0.0 ? std::sqrt(host[0] / host[1]) : (finite ? 0.0 : 1e300);
+        if (sw.progress && (it % 250 == 0 || sw.progress_every))
+            fprintf(stderr, "[ssrs_potential_solve] BiCGStab it %d |r|/|b| %.3e\n", it, now);
+        if (finite && now < best) {
+            best = now;
+            rel = now;
+            SSRS_HIP_CHECK(hipMemcpyAsync(xbest, x, n * sizeof(double), hipMemcpyDeviceToDevice, st));
+            if (rel <= rel_tol) { converged = 1; break; }
+        }
+        if (finite && now < 0.5 * gain_mark) { gain_mark = now; gain_it = it; }
+        else if (use_amg && !robust_cycle && it - gain_it >= 40) {
+            robust_cycle = true;
+            robust_from = it;
+            gain_it = it;
+            if (sw.progress) fprintf(stderr, "[ssrs_potential_solve] BiCGStab it %d: no factor of two in 40 iterations (|r|/|b| %.3e): V(2,2) from here on\n", it, now);
+        } else if (use_amg && robust_cycle && pcg_ok && it - gain_it >= 60 && sw.fallback) {
+            // stagnation under the robust cycle too (snapshot 25 of configs[4] with the sliced-ELL sweeps' rounding: the
+            // residual sat at 5.9e-11 from iteration 200 to the cap at 1 695): no point in waiting for the cap -- the
+            // fall-back below takes ~400 PCG iterations from where PCG stood
+            if (sw.progress) fprintf(stderr, "[ssrs_potential_solve] BiCGStab it %d: no factor of two in 60 iterations under V(2,2) either (|r|/|b| %.3e)\n", it, now);
+            break;
+        }
+        // BiCGStab breakdown (rho or omega -> 0) or a residual that ran away:
+        // restart from the best iterate with a fresh shadow residual
+        if (!finite || now > 1e3 * best) {
+            if (++restarts > max_restarts) break;
+            SSRS_HIP_CHECK(hipMemcpyAsync(x, xbest, n * sizeof(double), hipMemcpyDeviceToDevice, st));
+            hipLaunchKernelGGL(k_setup, dim3(nb), dim3(kBlock), 0, st, a, x, r, rhat, p, v, sc);
+            hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_INIT, nb);
+            fresh = true;
+        }
+    }
+    if (best < 1e300) SSRS_HIP_CHECK(hipMemcpyAsync(x, xbest, n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    return SSRS_OK;
+}
+
+// ---- fall-back of phase 2: BiCGStab did not get there (breakdowns, stagnation).  Back to PCG's iterate -- its symmetric
+// residual is below rel_tol |b|: taken as zero -- and through the quirk's defect correction (k_quirk_defect) with the
+// same PCG: slower than a healthy BiCGStab, but monotone.
+int SolveRun::fall_back()
+{
+    if (sw.progress) fprintf(stderr, "[ssrs_potential_solve] BiCGStab stopped at |r|/|b| %.3e after %d iterations: defect correction from PCG's iterate\n", rel, it);
+    SSRS_HIP_CHECK(hipMemcpyAsync(x, x_pcg, n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    SSRS_HIP_CHECK(hipMemsetAsync(r, 0, n * sizeof(double), st));
+    double *e_prev = rhat;
+    SSRS_HIP_CHECK(hipMemsetAsync(e_prev, 0, sizeof(double) * static_cast<size_t>(rows), st));
+    const int budget = cg_iterations + max_iterations;           // the fall-back gets an iteration budget of its own
+    double dc_last = 1e300;
+    for (int dc_rounds = 0; dc_rounds < 40; ++dc_rounds) {
+        hipLaunchKernelGGL(k_quirk_defect, dim3((rows + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a, x, e_prev, r);
+        hipLaunchKernelGGL(k_norm2, dim3(nb), dim3(kBlock), 0, st, r, n, sc);
+        hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_CG_RR, nb);
+        SSRS_HIP_CHECK(hipGetLastError());
+        SSRS_HIP_CHECK(hipMemcpyAsync(host, &sc->rnorm2, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+        SSRS_HIP_CHECK(hipStreamSynchronize(st));
+        const double now = host[1] > 0.0 ? std::sqrt(host[0] / host[1]) : 0.0;
+        if (sw.progress) fprintf(stderr, "[ssrs_potential_solve] quirk update %d after %d PCG iterations: |r|/|b| %.3e (exact operator)\n", dc_rounds, cg_iterations, now);
+        dc_last = now;
+        if (now <= rel_tol) { converged = 1; rel = now; break; }
+        restart_dirs = true;
+        // an update only gains the contraction factor of A_s^-1 E (~0.1): a round solves to a tenth of where it stands
+        const double target = now * 0.05 > rel_tol ? now * 0.05 : rel_tol;
+        double reached = 1e300;
+        if (pcg(target, budget, reached) != SSRS_OK)
+            return set_error(SSRS_ERR_HIP, "ssrs_potential_solve: HIP error in the fall-back");
+        if (!(reached <= target) || cg_iterations >= budget) break;
+    }
+    if (!converged) {                      // keep the better of the two unfinished answers
+        if (dc_last < rel) rel = dc_last;
+        else if (best < 1e300) SSRS_HIP_CHECK(hipMemcpyAsync(x, xbest, n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    }
+    return SSRS_OK;
+}
+
+// The f32 potential and the stats
+int SolveRun::finish(void *stats_out)
+{
+    if (sw.progress) {
+        // the residual the iteration carried along against the one recomputed from x
+        hipLaunchKernelGGL(k_setup, dim3(nb), dim3(kBlock), 0, st, a, x, r, rhat, p, v, sc);
+        hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_INIT, nb);
+        SSRS_HIP_CHECK(hipMemcpyAsync(host, &sc->rnorm2, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+        SSRS_HIP_CHECK(hipStreamSynchronize(st));
+        fprintf(stderr, "[ssrs_potential_solve] done: carried |r|/|b| %.3e, recomputed %.3e (PCG %d + BiCGStab %d iterations%s)\n", rel,
+                host[1] > 0.0 ? std::sqrt(host[0] / host[1]) : 0.0, cg_iterations, it, robust_from >= 0 ? ", the last of them under V(2,2)" : "");
+    }
+    hipLaunchKernelGGL(k_to_f32, dim3(nb), dim3(kBlock), 0, st, x, potential, n);
+    SSRS_HIP_CHECK(hipGetLastError());
+    SSRS_HIP_CHECK(hipEventRecord(ev.last, st));
+    SSRS_HIP_CHECK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, ev.first, ev.last);
+    if (stats_out) {
+        auto *so = static_cast<SsrsSolveStatsInternal *>(stats_out);
+        so->iterations = it + cg_iterations;
+        so->converged = converged;
+        so->residual = rel;
+        so->kernel_ms = ms;
+        so->amg_levels = use_amg ? static_cast<int32_t>(amg.levels.size()) : 0;
+        so->amg_coarsest = use_amg ? amg.levels.back().n : 0;
+        so->setup_ms = setup_ms;
+        so->workspace_used = ws_used;
+    }
+    return SSRS_OK;
+}
+
+}  // namespace
 
 extern "C" int ssrs_potential_solve(const double *conductivity, const uint8_t *fixed_mask,
                                     const double *fixed_values, const double *initial_guess,
@@ -588,298 +984,13 @@ extern "C" int ssrs_potential_solve(const double *conductivity, const uint8_t *f
             st = own;
         }
     }
-    const size_t n = static_cast<size_t>(rows) * cols;
-    char *base = static_cast<char *>(workspace);
-    Scalars *sc = reinterpret_cast<Scalars *>(base);
-    base += (sizeof(Scalars) + 255) / 256 * 256;
-    double *vec[11];
-    for (int i = 0; i < 11; ++i) vec[i] = reinterpret_cast<double *>(base + i * vec_bytes(n));
-    double *x = vec[0], *r = vec[1], *rhat = vec[2], *p = vec[3], *v = vec[4], *sv = vec[5], *t = vec[6];
-    double *xbest = vec[7], *phat = vec[8], *shat = vec[9];
-    double *x_pcg = vec[10];               // PCG's iterate, kept for the fall-back of phase 2
-    // right-preconditioned BiCGStab: M = one AMG V-cycle of the symmetric operator
-    const bool use_amg = (flags & SSRS_SOLVE_NO_AMG) == 0;
-    AmgHierarchy amg;
-    struct AmgGuard {            // the captured graph is host state: free it on every exit
-        AmgHierarchy &h;
-        ~AmgGuard() { amg_release(h); }
-    } amg_guard{amg};
-    amg.sweeps = 1 + ((flags >> 4) & 7);
-    if (const char *e = std::getenv("SSRS_AMG_OMEGAS")) {
-        double a0 = 0.7, a1 = 0.7;
-        if (std::sscanf(e, "%lf,%lf", &a0, &a1) == 2 && a0 > 0.0 && a1 > 0.0) { amg.om[0] = a0; amg.om[1] = a1; }
-    }
-    if (const char *e = std::getenv("SSRS_AMG_NU")) {
-        int a0 = 2, a1 = 2;
-        if (std::sscanf(e, "%d,%d", &a0, &a1) == 2) { amg.nu0 = a0 == 1 ? 1 : 2; amg.nuc = a1 == 1 ? 1 : 2; }
-    }
-    if (const char *e = std::getenv("SSRS_AMG_K")) {
-        int a0 = 0, a1 = 0;
-        if (std::sscanf(e, "%d,%d", &a0, &a1) == 2 && a0 >= 1 && a0 <= 40 && a1 >= 1 && a1 <= 16) { amg.klevel = a0; amg.kinner = a1; }
-    }
-    amg.kdepth = (flags & SSRS_SOLVE_K_CYCLE) ? (((flags >> 12) & 15) ? ((flags >> 12) & 15) : 3) : 0;
-    amg.symmetric = (flags & SSRS_SOLVE_ONE_SIDED) == 0;
-    amg.strong_rounds = ((flags >> 8) & 15) ? ((flags >> 8) & 15) : 4;
-    float setup_ms = 0.f;
-    size_t ws_used = static_cast<size_t>(11 * vec_bytes(n)) + 512;
-    if (use_amg) {
-        hipEvent_t s0, s1;
-        SSRS_HIP_CHECK(hipEventCreate(&s0));
-        SSRS_HIP_CHECK(hipEventCreate(&s1));
-        SSRS_HIP_CHECK(hipEventRecord(s0, st));
-        char *amg_base = base + 11 * vec_bytes(n);
-        amg_base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(amg_base) + 255) / 256 * 256);
-        const size_t amg_bytes = static_cast<size_t>(static_cast<char *>(workspace) + workspace_bytes - amg_base);
-        const int rc = amg_setup(amg, conductivity, fixed_mask, rows, cols, amg_base, amg_bytes, st);
-        (void)hipEventRecord(s1, st);
-        (void)hipEventSynchronize(s1);
-        (void)hipEventElapsedTime(&setup_ms, s0, s1);
-        (void)hipEventDestroy(s0);
-        (void)hipEventDestroy(s1);
-        if (rc != SSRS_OK) return rc;
-        ws_used += amg.workspace_used;
-    }
-    StencilArgs a{conductivity, use_amg ? amg.l0_rinv : nullptr, fixed_mask, rows, cols, use_amg ? 1 : 0, 1,
-                  make_tile_walk(rows, cols)};
-    int nb = static_cast<int>((n + kBlock - 1) / kBlock);
-    if (nb > kRedBlocks) nb = kRedBlocks;
-    hipEvent_t e0, e1;
-    SSRS_HIP_CHECK(hipEventCreate(&e0));
-    SSRS_HIP_CHECK(hipEventCreate(&e1));
-    SSRS_HIP_CHECK(hipEventRecord(e0, st));
-    SSRS_HIP_CHECK(hipMemsetAsync(sc, 0, sizeof(Scalars), st));
-    // |b| (stopping criterion is |r| <= rel_tol |b|, independent of the start)
-    hipLaunchKernelGGL(k_init_x, dim3(nb), dim3(kBlock), 0, st, fixed_mask, fixed_values,
-                       static_cast<const double *>(nullptr), 0.0, x, rows, cols);
-    hipLaunchKernelGGL(k_setup, dim3(nb), dim3(kBlock), 0, st, a, x, r, rhat, p, v, sc);
-    hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_BNORM, nb);
-    // start field: caller's guess, else the mid value 500
-    hipLaunchKernelGGL(k_init_x, dim3(nb), dim3(kBlock), 0, st, fixed_mask, fixed_values,
-                       initial_guess, 500.0, x, rows, cols);
-    hipLaunchKernelGGL(k_setup, dim3(nb), dim3(kBlock), 0, st, a, x, r, rhat, p, v, sc);
-    hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_INIT, nb);
-    SSRS_HIP_CHECK(hipGetLastError());
-    double host[2] = {0.0, 0.0};
-    int cg_iterations = 0;
-    const bool progress = std::getenv("SSRS_PROGRESS") != nullptr;   // long solves: heartbeat on stderr
-    // preconditioned (flexible) CG on the symmetric operator A_s from the carried residual r, until |r| <= tol |b|; returns the
-    // last |r| / |b| it saw.  Phase 1 of the AMG solve, and the engine of phase 2's fall-back.
-    StencilArgs as = a;
-    as.quirk = 0;
-    bool restart_dirs = true;
-    int rc_pcg = SSRS_OK;
-    auto pcg_run = [&](double tol, int cap) -> double {
-        double cg_best = 1e300, now = 1e300;
-        int stalled = 0;
-        while (cg_iterations < cap) {
-            for (int j = 0; j < 5; ++j, ++cg_iterations) {
-                // flexible CG(1): p is A-orthogonalised explicitly against the previous direction
-                amg_apply(amg, r, phat, &sc->rnorm2, st);                                        // z = M r
-                hipLaunchKernelGGL(k_cg_dot_rz, dim3(nb), dim3(kBlock), 0, st, phat, v, n, sc);      // (z, q_prev)
-                hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_CG_RHO, nb);
-                hipLaunchKernelGGL(k_cg_p, dim3(nb), dim3(kBlock), 0, st, p, phat, n, sc, restart_dirs ? 1 : 0);
-                restart_dirs = false;
-                if (as.rinv)                                                                     // q = A p
-                    hipLaunchKernelGGL(k_cg_apply_wave, dim3(nb), dim3(kBlock), 0, st, as, p, v, r, sc);
-                else
-                    hipLaunchKernelGGL(k_cg_apply, dim3(nb), dim3(kBlock), 0, st, as, p, v, r, sc);
-                hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_CG_ALPHA, nb);
-                hipLaunchKernelGGL(k_cg_xr, dim3(nb), dim3(kBlock), 0, st, x, r, p, v, n, sc);
-                hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_CG_RR, nb);
-            }
-            if (hipGetLastError() != hipSuccess ||
-                hipMemcpyAsync(host, &sc->rnorm2, 2 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess) { rc_pcg = SSRS_ERR_HIP; break; }
-            if (!(host[0] == host[0])) break;
-            now = host[1] > 0.0 ? std::sqrt(host[0] / host[1]) : 0.0;
-            if (progress && (cg_iterations % 250 == 0 || std::atoi(std::getenv("SSRS_PROGRESS")) >= 2))   // (=2: every check)
-                fprintf(stderr, "[ssrs_potential_solve] PCG it %d |r|/|b| %.3e\n", cg_iterations, now);
-            if (now <= tol) break;
-            if (now < 0.9 * cg_best) { cg_best = now; stalled = 0; }
-            else if (++stalled >= 100) break;          // 500 iterations without a 10 % gain
-        }
-        return now;
-    };
-    bool pcg_ok = false;
-    if (use_amg) {
-        // ---- phase 1: PCG on the symmetric operator (natural weights).  One
-        // V-cycle + one operator application per iteration; it delivers the
-        // solution up to the east-edge quirk, which phase 2 (BiCGStab on the
-        // exact operator, started from here) removes in a few iterations.
-        hipLaunchKernelGGL(k_setup, dim3(nb), dim3(kBlock), 0, st, as, x, r, rhat, p, v, sc);
-        hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_INIT, nb);
-        // where PCG hands over: the exact operator's residual of the symmetric problem's solution (the quirk's
-        // defect) is ~1e-6 of the right-hand side, so BiCGStab starts from there whatever PCG reached below it
-        double pcg_tol = rel_tol;
-        if (const char *e = std::getenv("SSRS_SOLVE_PCG_TOL")) { const double vv = std::atof(e); if (vv > rel_tol) pcg_tol = vv; }
-        const double reached = pcg_run(pcg_tol, max_iterations);
-        if (rc_pcg != SSRS_OK) return set_error(SSRS_ERR_HIP, "ssrs_potential_solve: HIP error in the PCG phase");
-        pcg_ok = reached <= rel_tol;
-        SSRS_HIP_CHECK(hipMemcpyAsync(x_pcg, x, n * sizeof(double), hipMemcpyDeviceToDevice, st));
-        if (progress) {
-            // what PCG's carried residual is worth: recomputed with the symmetric and with the exact operator
-            for (int q = 0; q < 2; ++q) {
-                StencilArgs aq = a;
-                aq.quirk = q;
-                hipLaunchKernelGGL(k_setup, dim3(nb), dim3(kBlock), 0, st, aq, x, r, rhat, p, v, sc);
-                hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_INIT, nb);
-                SSRS_HIP_CHECK(hipMemcpyAsync(host, &sc->rnorm2, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-                SSRS_HIP_CHECK(hipStreamSynchronize(st));
-                fprintf(stderr, "[ssrs_potential_solve] after PCG (%d iterations): recomputed |r|/|b| %.3e with the %s operator\n", cg_iterations,
-                        host[1] > 0.0 ? std::sqrt(host[0] / host[1]) : 0.0, q ? "exact (east-edge quirk)" : "symmetric");
-                {
-                    double *dbg = nullptr;
-                    if (hipMalloc(&dbg, 8 * sizeof(double)) == hipSuccess) {
-                        (void)hipMemsetAsync(dbg, 0, 8 * sizeof(double), st);
-                        hipLaunchKernelGGL(k_resid_breakdown, dim3(1024), dim3(kBlock), 0, st, aq, r, dbg);
-                        double hb[8];
-                        (void)hipMemcpyAsync(hb, dbg, sizeof(hb), hipMemcpyDeviceToHost, st);
-                        (void)hipStreamSynchronize(st);
-                        unsigned long long wcell;
-                        memcpy(&wcell, &hb[4], sizeof(wcell));
-                        fprintf(stderr, "    sum r^2: live cells %.3e, dead cells %.3e, east-edge column %.3e (|b|^2 %.3e); largest |r| %.3e at row %llu col %llu\n",
-                                hb[0], hb[1], hb[2], host[1], hb[3], wcell / a.cols, wcell % a.cols);
-                        (void)hipFree(dbg);
-                    }
-                }
-            }
-        }
-        // hand over to BiCGStab on the exact operator
-        hipLaunchKernelGGL(k_setup, dim3(nb), dim3(kBlock), 0, st, a, x, r, rhat, p, v, sc);
-        hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_INIT, nb);
-        SSRS_HIP_CHECK(hipGetLastError());
-    }
-    int it = 0, converged = 0, restarts = 0;
-    const int check_every = use_amg ? 5 : 25, max_restarts = 50;
-    double rel = 1.0, best = 1e300;
-    bool fresh = true;                     // p == r (no k_update_p on the first pass)
-    // after the PCG phase BiCGStab only has to remove the quirk's defect: it gets
-    // what is left of the iteration budget (at least 50)
-    int bicg_cap = max_iterations;
-    if (use_amg) bicg_cap = max_iterations - cg_iterations > 50 ? max_iterations - cg_iterations : 50;
-    // BiCGStab can stagnate under the V(1,1) cycle (snapshot 25 of configs[4]: the carried residual sat at 1.7e-11 for
-    // 1 700 iterations, profiles/r04_k5.md) where the V(2,2) cycle of rounds 1-3 converges: a healthy run gains a factor
-    // of ten every ~15 iterations, so 40 iterations without a factor of two switch the preconditioner to the
-    // robust cycle for the rest of the solve (no restart: x and r stay consistent, only the search directions change)
-    bool robust_cycle = false;
-    double gain_mark = 1e300;
-    int gain_it = 0, robust_from = -1;
-    while (it < bicg_cap) {
-        for (int j = 0; j < check_every && it < bicg_cap; ++j, ++it) {
-            if (!fresh) hipLaunchKernelGGL(k_update_p, dim3(nb), dim3(kBlock), 0, st, p, r, v, n, sc);
-            fresh = false;
-            const double *ph = p, *sh = sv;
-            if (use_amg) { amg_apply(amg, p, phat, &sc->rnorm2, st, robust_cycle); ph = phat; }
-            if (a.rinv) hipLaunchKernelGGL(k_apply_dot1_wave, dim3(nb), dim3(kBlock), 0, st, a, ph, v, rhat, sc);
-            else hipLaunchKernelGGL(k_apply_dot1, dim3(nb), dim3(kBlock), 0, st, a, ph, v, rhat, sc);
-            hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_ALPHA, nb);
-            hipLaunchKernelGGL(k_form_s, dim3(nb), dim3(kBlock), 0, st, r, v, sv, n, sc);
-            if (use_amg) { amg_apply(amg, sv, shat, &sc->rnorm2, st, robust_cycle); sh = shat; }
-            if (a.rinv) hipLaunchKernelGGL(k_apply_dot2_wave, dim3(nb), dim3(kBlock), 0, st, a, sh, t, sv, sc);
-            else hipLaunchKernelGGL(k_apply_dot2, dim3(nb), dim3(kBlock), 0, st, a, sh, t, sv, sc);
-            hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_OMEGA, nb);
-            hipLaunchKernelGGL(k_update_xr, dim3(nb), dim3(kBlock), 0, st, x, r, ph, sh, sv, t, rhat, n, sc);
-            hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_RHO, nb);
-        }
-        SSRS_HIP_CHECK(hipGetLastError());
-        SSRS_HIP_CHECK(hipMemcpyAsync(host, &sc->rnorm2, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-        SSRS_HIP_CHECK(hipStreamSynchronize(st));
-        const bool finite = host[0] == host[0] && host[0] < 1e300;
-        const double now = finite && host[1] > 0.0 ? std::sqrt(host[0] / host[1]) : (finite ? 0.0 : 1e300);
-        if (progress && (it % 250 == 0 || std::atoi(std::getenv("SSRS_PROGRESS")) >= 2))
-            fprintf(stderr, "[ssrs_potential_solve] BiCGStab it %d |r|/|b| %.3e\n", it, now);
-        if (finite && now < best) {
-            best = now;
-            rel = now;
-            SSRS_HIP_CHECK(hipMemcpyAsync(xbest, x, n * sizeof(double), hipMemcpyDeviceToDevice, st));
-            if (rel <= rel_tol) { converged = 1; break; }
-        }
-        if (finite && now < 0.5 * gain_mark) { gain_mark = now; gain_it = it; }
-        else if (use_amg && !robust_cycle && it - gain_it >= 40) {
-            robust_cycle = true;
-            robust_from = it;
-            gain_it = it;
-            if (progress) fprintf(stderr, "[ssrs_potential_solve] BiCGStab it %d: no factor of two in 40 iterations (|r|/|b| %.3e): V(2,2) from here on\n", it, now);
-        } else if (use_amg && robust_cycle && pcg_ok && it - gain_it >= 60 && std::getenv("SSRS_SOLVE_NO_FALLBACK") == nullptr) {
-            // stagnation under the robust cycle too (snapshot 25 of configs[4] with the sliced-ELL sweeps' rounding: the
-            // residual sat at 5.9e-11 from iteration 200 to the cap at 1 695): no point in waiting for the cap -- the
-            // fall-back below takes ~400 PCG iterations from where PCG stood
-            if (progress) fprintf(stderr, "[ssrs_potential_solve] BiCGStab it %d: no factor of two in 60 iterations under V(2,2) either (|r|/|b| %.3e)\n", it, now);
-            break;
-        }
-        // BiCGStab breakdown (rho or omega -> 0) or a residual that ran away:
-        // restart from the best iterate with a fresh shadow residual
-        if (!finite || now > 1e3 * best) {
-            if (++restarts > max_restarts) break;
-            SSRS_HIP_CHECK(hipMemcpyAsync(x, xbest, n * sizeof(double), hipMemcpyDeviceToDevice, st));
-            hipLaunchKernelGGL(k_setup, dim3(nb), dim3(kBlock), 0, st, a, x, r, rhat, p, v, sc);
-            hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_INIT, nb);
-            fresh = true;
-        }
-    }
-    if (best < 1e300) SSRS_HIP_CHECK(hipMemcpyAsync(x, xbest, n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    int dc_rounds = 0;
-    if (use_amg && !converged && pcg_ok && std::getenv("SSRS_SOLVE_NO_FALLBACK") == nullptr) {
-        // ---- fall-back of phase 2: BiCGStab did not get there (breakdowns, stagnation).  Back to PCG's iterate -- its
-        // symmetric residual is below rel_tol |b|: taken as zero -- and through the quirk's defect correction
-        // (k_quirk_defect) with the same PCG: slower than a healthy BiCGStab, but monotone.
-        if (progress) fprintf(stderr, "[ssrs_potential_solve] BiCGStab stopped at |r|/|b| %.3e after %d iterations: defect correction from PCG's iterate\n", rel, it);
-        SSRS_HIP_CHECK(hipMemcpyAsync(x, x_pcg, n * sizeof(double), hipMemcpyDeviceToDevice, st));
-        SSRS_HIP_CHECK(hipMemsetAsync(r, 0, n * sizeof(double), st));
-        double *e_prev = rhat;
-        SSRS_HIP_CHECK(hipMemsetAsync(e_prev, 0, sizeof(double) * static_cast<size_t>(rows), st));
-        const int budget = cg_iterations + max_iterations;           // the fall-back gets an iteration budget of its own
-        double dc_last = 1e300;
-        for (; dc_rounds < 40; ++dc_rounds) {
-            hipLaunchKernelGGL(k_quirk_defect, dim3((rows + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a, x, e_prev, r);
-            hipLaunchKernelGGL(k_norm2, dim3(nb), dim3(kBlock), 0, st, r, n, sc);
-            hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_CG_RR, nb);
-            SSRS_HIP_CHECK(hipGetLastError());
-            SSRS_HIP_CHECK(hipMemcpyAsync(host, &sc->rnorm2, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-            SSRS_HIP_CHECK(hipStreamSynchronize(st));
-            const double now = host[1] > 0.0 ? std::sqrt(host[0] / host[1]) : 0.0;
-            if (progress) fprintf(stderr, "[ssrs_potential_solve] quirk update %d after %d PCG iterations: |r|/|b| %.3e (exact operator)\n", dc_rounds, cg_iterations, now);
-            dc_last = now;
-            if (now <= rel_tol) { converged = 1; rel = now; break; }
-            restart_dirs = true;
-            // an update only gains the contraction factor of A_s^-1 E (~0.1): a round solves to a tenth of where it stands
-            const double target = now * 0.05 > rel_tol ? now * 0.05 : rel_tol;
-            const double reached = pcg_run(target, budget);
-            if (rc_pcg != SSRS_OK) return set_error(SSRS_ERR_HIP, "ssrs_potential_solve: HIP error in the fall-back");
-            if (!(reached <= target) || cg_iterations >= budget) break;
-        }
-        if (!converged) {                      // keep the better of the two unfinished answers
-            if (dc_last < rel) rel = dc_last;
-            else if (best < 1e300) SSRS_HIP_CHECK(hipMemcpyAsync(x, xbest, n * sizeof(double), hipMemcpyDeviceToDevice, st));
-        }
-    }
-    if (progress) {
-        // the residual the iteration carried along against the one recomputed from x
-        hipLaunchKernelGGL(k_setup, dim3(nb), dim3(kBlock), 0, st, a, x, r, rhat, p, v, sc);
-        hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, st, sc, FIN_INIT, nb);
-        SSRS_HIP_CHECK(hipMemcpyAsync(host, &sc->rnorm2, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-        SSRS_HIP_CHECK(hipStreamSynchronize(st));
-        fprintf(stderr, "[ssrs_potential_solve] done: carried |r|/|b| %.3e, recomputed %.3e (PCG %d + BiCGStab %d iterations%s)\n", rel,
-                host[1] > 0.0 ? std::sqrt(host[0] / host[1]) : 0.0, cg_iterations, it, robust_from >= 0 ? ", the last of them under V(2,2)" : "");
-    }
-    hipLaunchKernelGGL(k_to_f32, dim3(nb), dim3(kBlock), 0, st, x, potential, n);
-    SSRS_HIP_CHECK(hipGetLastError());
-    SSRS_HIP_CHECK(hipEventRecord(e1, st));
-    SSRS_HIP_CHECK(hipStreamSynchronize(st));
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (stats_out) {
-        auto *so = static_cast<SsrsSolveStatsInternal *>(stats_out);
-        so->iterations = it + cg_iterations;
-        so->converged = converged;
-        so->residual = rel;
-        so->kernel_ms = ms;
-        so->amg_levels = use_amg ? static_cast<int32_t>(amg.levels.size()) : 0;
-        so->amg_coarsest = use_amg ? amg.levels.back().n : 0;
-        so->setup_ms = setup_ms;
-        so->workspace_used = ws_used;
-    }
-    return SSRS_OK;
+    SolveRun run(conductivity, fixed_mask, fixed_values, initial_guess, potential, rows, cols, rel_tol, max_iterations, flags,
+                 workspace, workspace_bytes, st);
+    int rc;
+    if (run.use_amg && (rc = run.setup_amg()) != SSRS_OK) return rc;
+    if ((rc = run.start()) != SSRS_OK) return rc;
+    if (run.use_amg && (rc = run.pcg_phase()) != SSRS_OK) return rc;
+    if ((rc = run.bicgstab()) != SSRS_OK) return rc;
+    if (run.use_amg && !run.converged && run.pcg_ok && run.sw.fallback && (rc = run.fall_back()) != SSRS_OK) return rc;
+    return run.finish(stats_out);
 }

@@ -250,8 +250,8 @@ def test_potential_workspace_tight_first_try_and_exhaustion(gpu, golden):
 
 def test_potential_cycle_switches_agree(gpu):
     """The solver's A/B switches on one small two-phase raster: the fused level 0 of the V(1,1) cycle is bit-identical to the
-    unfused kernels (SSRS_AMG_NO_FUSE), and the V(2,2) cycle of rounds 1-3 (SSRS_AMG_NU=2,2) converges to the same field
-    within the solver's own uncertainty."""
+    unfused kernels (SSRS_AMG_NO_FUSE), and the V(2,2) cycle of rounds 1-3 (SSRS_AMG_NU=2,2) and the pairwise first level
+    (SSRS_AMG_NO_BLOCKS) converge to the same field within the solver's own uncertainty."""
     import os
     from ssrs_amd.potential import solve_potential
     rng = np.random.default_rng(5)
@@ -260,7 +260,7 @@ def test_potential_cycle_switches_agree(gpu):
     cond[100:160, 50:300] = 0.0
     base, st = solve_potential(cond, 0., return_stats=True)
     assert st['converged']
-    for env, val, exact in (('SSRS_AMG_NO_FUSE', '1', True), ('SSRS_AMG_NU', '2,2', False)):
+    for env, val, exact in (('SSRS_AMG_NO_FUSE', '1', True), ('SSRS_AMG_NU', '2,2', False), ('SSRS_AMG_NO_BLOCKS', '1', False)):
         os.environ[env] = val
         try:
             alt, st2 = solve_potential(cond, 0., return_stats=True)

@@ -1,11 +1,11 @@
 #!/bin/bash
-# two-row level-0 passes (+ sliced-ELL sweeps) against the one-row / unfused / CSR variants: solver tests, C2 under both, kernel stats
+# fused two-row level-0 passes (+ sliced-ELL sweeps) against the unfused kernels: solver tests, C2 under both, kernel stats
 cd "${GRAFT_REPO_ROOT:-$PWD}" || exit 1
 export TMPDIR=/tmp
 OUT=gpurun_out/r04_l0two; mkdir -p "$OUT"
 timeout -k 10 600 python -m pytest tests -x -q -m gpu -k "potential or g10 or full_chain" > "$OUT/tests.log" 2>&1; rc=$?
 tail -4 "$OUT/tests.log"; [ $rc -eq 0 ] || echo "TESTS FAILED (going on: measurements)"
-python tools/dev/probe_k5.py 5000x6000 "default;one row;no fuse;no sell" > "$OUT/c2.txt" 2>&1 || { tail "$OUT/c2.txt"; exit 1; }
+python tools/dev/probe_k5.py 5000x6000 "default;no fuse" > "$OUT/c2.txt" 2>&1 || { tail "$OUT/c2.txt"; exit 1; }
 grep -v amdgpu "$OUT/c2.txt"
 python tools/dev/probe_k5_snapshot.py 25 > "$OUT/snap25.txt" 2>&1 || exit 1
 head -2 "$OUT/snap25.txt"

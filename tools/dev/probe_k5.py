@@ -1,4 +1,4 @@
-"""K5 at C2 (5000 x 6000 @10 m, the bench's field) under the solver's experiment switches: iterations, seconds,
+"""K5 at C2 (5000 x 6000 @10 m, the bench's field) under the solver's A/B switches: iterations, seconds,
 workspace.  usage: python tools/dev/probe_k5.py [ROWSxCOLS] -- variants are (label, env, kwargs) below."""
 import os, sys, time, warnings
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -20,14 +20,9 @@ variants = [
     ('nu 1,2', {'SSRS_AMG_NU': '1,2'}, {}),
     ('nu 1,1', {'SSRS_AMG_NU': '1,1'}, {}),
     ('nu 2,1', {'SSRS_AMG_NU': '2,1'}, {}),
-    ('no sell', {'SSRS_AMG_NO_SELL': '1'}, {}),
-    ('one row', {'SSRS_AMG_L0_ONE_ROW': '1'}, {}),
     ('ramp guess', {}, {'initial_guess': ramp}),
     ('nu 1,1 + ramp', {'SSRS_AMG_NU': '1,1'}, {'initial_guess': ramp}),
 ]
-# single-level K-cycle: SSRS_AMG_K=level,inner
-for lev, inner in ((1, 1), (4, 1), (4, 2), (2, 2), (3, 2), (3, 4), (4, 2), (4, 4), (5, 4), (4, 8), (5, 8), (6, 8)):
-    variants.append((f'K {lev},{inner}', {'SSRS_AMG_K': f'{lev},{inner}'}, {}))
 ref = None
 for label, env, kw in variants:
     if only and label not in only:
