@@ -143,6 +143,41 @@ int ssrs_wind_from_triangles(const double *points, const int32_t *triangles, con
                              double cell_size, double *wspeed, double *wdirn, int rows, int cols,
                              int batch, void *workspace, size_t workspace_bytes, void *stream);
 
+/* griddata's method='nearest' (NearestNDInterpolator -> cKDTree, Euclidean, no rescaling), in two steps.
+ * ssrs_wind_nearest_index: `points` as above -> index (rows, cols) int32, per cell the sample nearest to its centre,
+ * d^2 = dx * dx + dy * dy in f64.  A cell equally far from several samples takes the LOWEST sample index (cKDTree picks
+ * either), so the raster equals cKDTree's wherever the nearest sample is unique.  It depends on the points only: build
+ * it once per wind geometry.  Samples are culled per 64 x 32 cell tile by the triangle inequality; the cull never
+ * decides a result (a tile with too many candidates scans all samples).
+ * workspace: ssrs_wind_nearest_workspace_bytes(npts, rows, cols) bytes of device scratch; on return its first int32
+ * holds the number of tiles that scanned all samples.
+ * ssrs_wind_from_nearest: speed / dirn (batch, npts) f64 -> per sample the u/v recipe of simulator.py:778-792
+ * (speed = sqrt(e^2 + n^2), direction = mod(atan2(e, n) + 2 pi, 2 pi) in degrees) -> wspeed / wdirn (batch, rows, cols)
+ * f64 gathered through `index`.  No NaN (nearest has no hull), except for an index outside [0, npts). */
+size_t ssrs_wind_nearest_workspace_bytes(int npts, int rows, int cols);
+int ssrs_wind_nearest_index(const double *points, int npts, double cell_size, int32_t *index, int rows,
+                            int cols, void *workspace, size_t workspace_bytes, void *stream);
+int ssrs_wind_from_nearest(const int32_t *index, const double *speed, const double *dirn, int npts,
+                           double *wspeed, double *wdirn, int rows, int cols, int batch, void *stream);
+
+/* griddata's method='cubic' (CloughTocher2DInterpolator: a C1 piecewise cubic on the Delaunay triangulation).
+ * The caller's, from scipy: points / triangles / transform as for ssrs_wind_from_triangles, `neighbors` (ntri, 3) int32
+ * = Delaunay.neighbors (-1 on the hull), the east / north components (batch, npts) f64 of the samples and their
+ * gradients at the vertices grad_east / grad_north (batch, npts, 2) f64 as scipy estimates them
+ * (CloughTocher2DInterpolator(tri, values, tol=1e-6, maxiter=400).grad: a global iteration over the vertices).
+ * The device's: the 19 Bezier ordinates of every macro-triangle and field (a table [triangle][2 batch][19] in the
+ * workspace), cell ownership exactly as ssrs_wind_from_triangles (scipy's eps, lowest triangle index on a shared edge,
+ * NaN outside the hull), the cubic in the four shifted barycentric coordinates, and the u/v recipe -> wspeed / wdirn
+ * (batch, rows, cols) f64.  The interpolant is C1 across edges, so the triangle chosen on an edge changes a value by
+ * rounding only; sums are taken in scipy's order but agreement with griddata is to rounding, not bit for bit.
+ * workspace: ssrs_wind_cubic_workspace_bytes(npts, ntri, rows, cols, batch) bytes of device scratch. */
+size_t ssrs_wind_cubic_workspace_bytes(int npts, int ntri, int rows, int cols, int batch);
+int ssrs_wind_from_triangles_cubic(const double *points, const int32_t *triangles, const int32_t *neighbors,
+                                   const double *transform, const double *east, const double *north,
+                                   const double *grad_east, const double *grad_north, int npts, int ntri,
+                                   double cell_size, double *wspeed, double *wdirn, int rows, int cols,
+                                   int batch, void *workspace, size_t workspace_bytes, void *stream);
+
 /* compute_thermals (ssrs/layers.py:188-214), split in its two stages.
  * ssrs_thermal_seeds: per-cell seeding inside the 10 % border with probability
  * 1/(int(wt)-1), wt = 1000 + |aspect-180|/180*2000, amplitude

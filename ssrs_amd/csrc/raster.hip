@@ -846,3 +846,355 @@ extern "C" int ssrs_wind_from_triangles(const double *points, const int32_t *tri
     SSRS_HIP_CHECK(hipGetLastError());
     return SSRS_OK;
 }
+
+// ---------------------------------------------------------------------------
+// K6, the other two griddata methods (simulator.py:774-775 hands wtk_interp_type to scipy):
+//   'nearest'  NearestNDInterpolator: every cell takes the sample nearest to its centre.  The index raster depends on
+//              the points only (k_nearest_index, built once per geometry); per snapshot k_wind_nearest is two table
+//              look-ups and two stores per cell.
+//   'cubic'    CloughTocher2DInterpolator: a C1 piecewise cubic on the Delaunay triangulation.  The vertex gradients are
+//              scipy's (a global iteration over a few thousand vertices, done on the host); k_ct_coefficients turns
+//              values + gradients into the 19 Bezier ordinates of every macro-triangle, k_wind_cubic evaluates them
+//              per cell.  Cell ownership is k_tri_owner, as for 'linear'.
+namespace ssrs {
+
+// simulator.py:784-785,790-791 on one sample
+__device__ __forceinline__ void wind_recipe(double s, double a_deg, double &spd, double &dir)
+{
+    const double a = a_deg * kPi / 180.0;
+    const double e = s * sin(a), n = s * cos(a);
+    spd = sqrt(e * e + n * n);
+    dir = fmod(atan2(e, n) + 2.0 * kPi, 2.0 * kPi) * 180.0 / kPi;
+}
+
+__device__ __forceinline__ double wave_min(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
+    return v;
+}
+
+// One block per TW x TH tile.  With c the tile's centre, h its half diagonal and dmin the distance from c to its
+// nearest sample, the nearest sample p of ANY cell x of the tile has |c - p| <= |c - x| + |x - p| <= h + (|x - c| +
+// dmin) <= dmin + 2h: two passes over the samples collect those candidates in LDS and every lane scans the candidates
+// only.  A list that does not fit falls back to all samples, so the cull never decides a result; a lane keeps
+// (d^2, index) lexicographically smallest, so neither does the order in which candidates were collected.
+constexpr int kNearCand = 1024;
+static_assert(kBlock == 4 * 64 && kBlock % TW == 0 && TH % (kBlock / TW) == 0, "k_nearest_index: four waves over a TW x TH tile");
+
+__global__ __launch_bounds__(kBlock) void k_nearest_index(const double *__restrict__ pts, int npts, double cell, int rows,
+                                                         int cols, int tiles_x, int32_t *__restrict__ index,
+                                                         int32_t *__restrict__ full_scans)
+{
+    __shared__ double cand_x[kNearCand], cand_y[kNearCand];
+    __shared__ int32_t cand_i[kNearCand];
+    __shared__ double wave_dmin[kBlock / 64];
+    __shared__ int ncand;
+    const int tid = threadIdx.x;
+    const int r0 = (blockIdx.x / tiles_x) * TH, c0 = (blockIdx.x % tiles_x) * TW;
+    const double xc = (c0 + 0.5 * (TW - 1)) * cell, yc = (r0 + 0.5 * (TH - 1)) * cell;
+    const double h = 0.5 * sqrt(static_cast<double>((TW - 1) * (TW - 1) + (TH - 1) * (TH - 1))) * cell;
+    if (tid == 0) ncand = 0;
+    double dmin = __longlong_as_double(0x7FF0000000000000ll);
+    for (int p = tid; p < npts; p += kBlock) {
+        const double dx = pts[2 * p] - xc, dy = pts[2 * p + 1] - yc;
+        dmin = fmin(dmin, dx * dx + dy * dy);
+    }
+    dmin = wave_min(dmin);
+    if ((tid & 63) == 0) wave_dmin[tid >> 6] = dmin;
+    __syncthreads();
+    dmin = fmin(fmin(wave_dmin[0], wave_dmin[1]), fmin(wave_dmin[2], wave_dmin[3]));
+    const double reach = sqrt(dmin) + 2.0 * h;
+    const double lim = reach * reach * (1.0 + 1e-9);                // (rounding of d^2 is 1e-16 relative)
+    for (int p = tid; p < npts; p += kBlock) {
+        const double px = pts[2 * p], py = pts[2 * p + 1];
+        const double dx = px - xc, dy = py - yc;
+        if (dx * dx + dy * dy <= lim) {
+            const int k = atomicAdd(&ncand, 1);
+            if (k < kNearCand) {
+                cand_x[k] = px;
+                cand_y[k] = py;
+                cand_i[k] = p;
+            }
+        }
+    }
+    __syncthreads();
+    const int n = ncand;
+    const bool culled = n <= kNearCand;
+    if (!culled && tid == 0) atomicAdd(full_scans, 1);
+
+    constexpr int kRowsPerLane = TH / (kBlock / TW);
+    const int c = c0 + tid % TW, rl = tid / TW;
+    const double x = static_cast<double>(c) * cell;
+    double y[kRowsPerLane], best[kRowsPerLane];
+    int32_t who[kRowsPerLane];
+#pragma unroll
+    for (int j = 0; j < kRowsPerLane; ++j) {
+        y[j] = static_cast<double>(r0 + rl + j * (kBlock / TW)) * cell;
+        best[j] = __longlong_as_double(0x7FF0000000000000ll);
+        who[j] = 0;
+    }
+    auto visit = [&](double px, double py, int32_t id) {
+        const double dx = x - px, dxx = dx * dx;
+#pragma unroll
+        for (int j = 0; j < kRowsPerLane; ++j) {
+            const double dy = y[j] - py, d2 = dxx + dy * dy;
+            if (d2 < best[j] || (d2 == best[j] && id < who[j])) {
+                best[j] = d2;
+                who[j] = id;
+            }
+        }
+    };
+    if (culled)
+        for (int k = 0; k < n; ++k) visit(cand_x[k], cand_y[k], cand_i[k]);
+    else
+        for (int p = 0; p < npts; ++p) visit(pts[2 * p], pts[2 * p + 1], p);
+    if (c < cols) {
+#pragma unroll
+        for (int j = 0; j < kRowsPerLane; ++j) {
+            const int r = r0 + rl + j * (kBlock / TW);
+            if (r < rows) index[static_cast<size_t>(r) * cols + c] = who[j];
+        }
+    }
+}
+
+// Snapshot blockIdx.y.  The recipe runs once per sample and block into LDS (the value set is npts wide, the raster
+// 30 M cells); `table` == 0 (more samples than the LDS table holds) applies it per cell instead, same function, same
+// bits.  An index outside [0, npts) gives NaN.
+__global__ __launch_bounds__(kBlock) void k_wind_nearest(const int32_t *__restrict__ index, const double *__restrict__ speed,
+                                                        const double *__restrict__ dirn, int npts, double *__restrict__ wspeed,
+                                                        double *__restrict__ wdirn, size_t ncell, int table)
+{
+    extern __shared__ double sample_table[];                           // speed[npts], direction[npts]
+    const size_t b = blockIdx.y;
+    const double *s = speed + b * npts, *d = dirn + b * npts;
+    if (table) {
+        for (int p = threadIdx.x; p < npts; p += kBlock) wind_recipe(s[p], d[p], sample_table[p], sample_table[npts + p]);
+        __syncthreads();
+    }
+    double *os = wspeed + b * ncell, *od = wdirn + b * ncell;
+    for (size_t i = blockIdx.x * static_cast<size_t>(kBlock) + threadIdx.x; i < ncell; i += static_cast<size_t>(gridDim.x) * kBlock) {
+        const int32_t k = index[i];
+        double spd = __longlong_as_double(0x7FF8000000000000ll), dir = spd;
+        if (static_cast<uint32_t>(k) < static_cast<uint32_t>(npts)) {
+            if (table) {
+                spd = sample_table[k];
+                dir = sample_table[npts + k];
+            } else {
+                wind_recipe(s[k], d[k], spd, dir);
+            }
+        }
+        os[i] = spd;
+        od[i] = dir;
+    }
+}
+
+// The 19 Bezier ordinates of the Clough-Tocher macro-triangle t for field f = 2 * snapshot + (0 east | 1 north), as
+// scipy's _clough_tocher_2d_single computes them on every evaluation; they do not depend on the evaluation point.
+// Order: c3000 c2100 c2010 c2001 c1200 c1101 c1020 c1011 c1002 c0300 c0210 c0201 c0120 c0111 c0102 c0030 c0021 c0012
+// c0003 (the order of the cubic's terms).  No guard scipy does not have: a neighbour whose centroid makes a
+// denominator of g vanish gives what IEEE gives.
+constexpr int kCT = 19;
+
+__global__ __launch_bounds__(kBlock) void k_ct_coefficients(const double *__restrict__ pts, const int32_t *__restrict__ tri,
+                                                           const int32_t *__restrict__ nbr, const double *__restrict__ transform,
+                                                           const double *__restrict__ east, const double *__restrict__ north,
+                                                           const double *__restrict__ grad_east, const double *__restrict__ grad_north,
+                                                           int npts, int ntri, int batch, double *__restrict__ coef)
+{
+    const int nfield = 2 * batch;
+    const size_t q = blockIdx.x * static_cast<size_t>(kBlock) + threadIdx.x;
+    if (q >= static_cast<size_t>(ntri) * nfield) return;
+    const int t = static_cast<int>(q / nfield), f = static_cast<int>(q % nfield);
+    const size_t b = f >> 1;
+    const double *val = ((f & 1) ? north : east) + b * npts;
+    const double *grad = ((f & 1) ? grad_north : grad_east) + b * npts * 2;
+    const int32_t v0 = tri[3 * t], v1 = tri[3 * t + 1], v2 = tri[3 * t + 2];
+    const double x0 = pts[2 * v0], y0 = pts[2 * v0 + 1], x1 = pts[2 * v1], y1 = pts[2 * v1 + 1], x2 = pts[2 * v2], y2 = pts[2 * v2 + 1];
+    const double e12x = x1 - x0, e12y = y1 - y0, e23x = x2 - x1, e23y = y2 - y1, e31x = x0 - x2, e31y = y0 - y2;
+    const double f1 = val[v0], f2 = val[v1], f3 = val[v2];
+    const double g0x = grad[2 * v0], g0y = grad[2 * v0 + 1], g1x = grad[2 * v1], g1y = grad[2 * v1 + 1];
+    const double g2x = grad[2 * v2], g2y = grad[2 * v2 + 1];
+    const double df12 = +(g0x * e12x + g0y * e12y), df21 = -(g1x * e12x + g1y * e12y);
+    const double df23 = +(g1x * e23x + g1y * e23y), df32 = -(g2x * e23x + g2y * e23y);
+    const double df31 = +(g2x * e31x + g2y * e31y), df13 = -(g0x * e31x + g0y * e31y);
+    const double c3000 = f1, c2100 = (df12 + 3 * f1) / 3, c2010 = (df13 + 3 * f1) / 3;
+    const double c0300 = f2, c1200 = (df21 + 3 * f2) / 3, c0210 = (df23 + 3 * f2) / 3;
+    const double c0030 = f3, c1020 = (df31 + 3 * f3) / 3, c0120 = (df32 + 3 * f3) / 3;
+    const double c2001 = (c2100 + c2010 + c3000) / 3;
+    const double c0201 = (c1200 + c0300 + c0210) / 3;
+    const double c0021 = (c1020 + c0120 + c0030) / 3;
+    const double *T = transform + 6 * static_cast<size_t>(t);
+    double g[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int32_t n = nbr[3 * t + k];
+        if (n < 0) {
+            g[k] = -1.0 / 2;
+            continue;
+        }
+        const int32_t n0 = tri[3 * n], n1 = tri[3 * n + 1], n2 = tri[3 * n + 2];
+        const double yx = (pts[2 * n0] + pts[2 * n1] + pts[2 * n2]) / 3;          // the neighbour's centroid ...
+        const double yy = (pts[2 * n0 + 1] + pts[2 * n1 + 1] + pts[2 * n2 + 1]) / 3;
+        const double dx = yx - T[4], dy = yy - T[5];                                // ... in this triangle's coordinates
+        double c[3];
+        c[0] = T[0] * dx + T[1] * dy;
+        c[1] = T[2] * dx + T[3] * dy;
+        c[2] = 1.0 - c[0] - c[1];
+        const double a = c[(k + 2) % 3], bb = c[(k + 1) % 3];
+        g[k] = (2 * a + bb - 1) / (2 - 3 * a - 3 * bb);
+    }
+    const double c0111 = (g[0] * (-c0300 + 3 * c0210 - 3 * c0120 + c0030) + (-c0300 + 2 * c0210 - c0120 + c0021 + c0201)) / 2;
+    const double c1011 = (g[1] * (-c0030 + 3 * c1020 - 3 * c2010 + c3000) + (-c0030 + 2 * c1020 - c2010 + c2001 + c0021)) / 2;
+    const double c1101 = (g[2] * (-c3000 + 3 * c2100 - 3 * c1200 + c0300) + (-c3000 + 2 * c2100 - c1200 + c2001 + c0201)) / 2;
+    const double c1002 = (c1101 + c1011 + c2001) / 3;
+    const double c0102 = (c1101 + c0111 + c0201) / 3;
+    const double c0012 = (c1011 + c0111 + c0021) / 3;
+    const double c0003 = (c1002 + c0102 + c0012) / 3;
+    double *o = coef + q * kCT;
+    o[0] = c3000;  o[1] = c2100;  o[2] = c2010;  o[3] = c2001;  o[4] = c1200;  o[5] = c1101;  o[6] = c1020;
+    o[7] = c1011;  o[8] = c1002;  o[9] = c0300;  o[10] = c0210; o[11] = c0201; o[12] = c0120; o[13] = c0111;
+    o[14] = c0102; o[15] = c0030; o[16] = c0021; o[17] = c0012; o[18] = c0003;
+}
+
+// (east, north) of every snapshot at one cell from its 19 monomials; cf: the owner's [field][19] block
+__device__ __forceinline__ void ct_store(const double *__restrict__ cf, const double (&mono)[kCT], int batch, size_t ncell,
+                                         size_t i, double *__restrict__ wspeed, double *__restrict__ wdirn)
+{
+    for (int b = 0; b < batch; ++b, cf += 2 * kCT) {
+        double e = mono[0] * cf[0], n = mono[0] * cf[kCT];
+#pragma unroll
+        for (int k = 1; k < kCT; ++k) {
+            e += mono[k] * cf[k];
+            n += mono[k] * cf[kCT + k];
+        }
+        wspeed[b * ncell + i] = sqrt(e * e + n * n);
+        wdirn[b * ncell + i] = fmod(atan2(e, n) + 2.0 * kPi, 2.0 * kPi) * 180.0 / kPi;
+    }
+}
+
+// One thread per cell, all snapshots: owner -> barycentric coordinates -> the 19 monomials of the four shifted
+// coordinates, once; then 2 x 19 multiply-adds per snapshot and the u/v recipe.  A triangle of a 2 km lattice covers
+// some 20 000 cells at 10 m, so nearly every wave has ONE owner: its transform and coefficients are then read through
+// a wave-uniform pointer (scalar loads); a wave that straddles an edge takes the same code with per-lane pointers.
+__global__ __launch_bounds__(kBlock) void k_wind_cubic(const int32_t *__restrict__ owner, const double *__restrict__ transform,
+                                                      const double *__restrict__ coef, double cell,
+                                                      double *__restrict__ wspeed, double *__restrict__ wdirn, int rows,
+                                                      int cols, int batch)
+{
+    const size_t ncell = static_cast<size_t>(rows) * cols;
+    const size_t stride = static_cast<size_t>(2 * batch) * kCT;
+    const int lane = threadIdx.x & 63;
+    for (size_t base = blockIdx.x * static_cast<size_t>(kBlock) + (threadIdx.x - lane); base < ncell;
+         base += static_cast<size_t>(gridDim.x) * kBlock) {
+        const size_t i = base + lane;
+        if (i >= ncell) continue;
+        const int32_t t = owner[i];
+        if (t == 0x7f7f7f7f) {                                        // outside the hull: griddata's fill value
+            const double nan = __longlong_as_double(0x7FF8000000000000ll);
+            for (int b = 0; b < batch; ++b) {
+                wspeed[b * ncell + i] = nan;
+                wdirn[b * ncell + i] = nan;
+            }
+            continue;
+        }
+        // (readfirstlane and __ballot see the lanes that reached this point: those with an owner)
+        const int32_t t0 = __builtin_amdgcn_readfirstlane(t);
+        const bool uniform = __ballot(t != t0) == 0ull;
+        const size_t tt = static_cast<size_t>(uniform ? t0 : t);
+        const int r = static_cast<int>(i / cols), c = static_cast<int>(i % cols);
+        const double *T = transform + 6 * tt;
+        const double dx = static_cast<double>(c) * cell - T[4], dy = static_cast<double>(r) * cell - T[5];
+        const double b0 = T[0] * dx + T[1] * dy, b1 = T[2] * dx + T[3] * dy, b2 = 1.0 - b0 - b1;
+        const double m = fmin(b0, fmin(b1, b2));
+        const double a1 = b0 - m, a2 = b1 - m, a3 = b2 - m, a4 = 3 * m;
+        const double a11 = a1 * a1, a22 = a2 * a2, a33 = a3 * a3, a44 = a4 * a4;
+        const double mono[kCT] = {
+            a11 * a1,      3 * a11 * a2,      3 * a11 * a3,      3 * a11 * a4, 3 * a1 * a22, 6 * a1 * a2 * a4, 3 * a1 * a33,
+            6 * a1 * a3 * a4, 3 * a1 * a44,   a22 * a2,          3 * a22 * a3, 3 * a22 * a4, 3 * a2 * a33,     6 * a2 * a3 * a4,
+            3 * a2 * a44,  a33 * a3,          3 * a33 * a4,      3 * a3 * a44, a44 * a4};
+        if (uniform)
+            ct_store(coef + static_cast<size_t>(t0) * stride, mono, batch, ncell, i, wspeed, wdirn);
+        else
+            ct_store(coef + static_cast<size_t>(t) * stride, mono, batch, ncell, i, wspeed, wdirn);
+    }
+}
+
+static inline size_t align256(size_t n) { return (n + 255) / 256 * 256; }
+constexpr int kNearestTable = 3072;                                    // samples whose (speed, direction) fit 48 KB of LDS
+
+}  // namespace ssrs
+
+extern "C" size_t ssrs_wind_nearest_workspace_bytes(int npts, int rows, int cols)
+{
+    if (npts <= 0 || rows <= 0 || cols <= 0) return 0;
+    return 256;
+}
+
+extern "C" int ssrs_wind_nearest_index(const double *points, int npts, double cell_size, int32_t *index, int rows, int cols,
+                                       void *workspace, size_t workspace_bytes, void *stream)
+{
+    SSRS_REQUIRE(points && index, "ssrs_wind_nearest_index: NULL pointer");
+    SSRS_REQUIRE(npts >= 1 && rows > 0 && cols > 0, "ssrs_wind_nearest_index: bad sizes");
+    SSRS_REQUIRE(cell_size > 0.0, "ssrs_wind_nearest_index: cell_size must be > 0");
+    SSRS_REQUIRE(workspace && workspace_bytes >= ssrs_wind_nearest_workspace_bytes(npts, rows, cols),
+                 "ssrs_wind_nearest_index: workspace too small");
+    const int tiles_x = (cols + TW - 1) / TW, tiles_y = (rows + TH - 1) / TH;
+    hipStream_t st = as_stream(stream);
+    SSRS_HIP_CHECK(hipMemsetAsync(workspace, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_nearest_index, dim3(static_cast<unsigned>(tiles_x) * tiles_y), dim3(kBlock), 0, st, points, npts,
+                       cell_size, rows, cols, tiles_x, index, static_cast<int32_t *>(workspace));
+    SSRS_HIP_CHECK(hipGetLastError());
+    return SSRS_OK;
+}
+
+extern "C" int ssrs_wind_from_nearest(const int32_t *index, const double *speed, const double *dirn, int npts,
+                                      double *wspeed, double *wdirn, int rows, int cols, int batch, void *stream)
+{
+    SSRS_REQUIRE(index && speed && dirn && wspeed && wdirn, "ssrs_wind_from_nearest: NULL pointer");
+    SSRS_REQUIRE(npts >= 1 && rows > 0 && cols > 0 && batch > 0 && batch <= 65535, "ssrs_wind_from_nearest: bad sizes");
+    const size_t ncell = static_cast<size_t>(rows) * cols;
+    const int table = npts <= kNearestTable;
+    int nbx = kMaxStreamBlocks / batch;
+    nbx = nbx < 64 ? 64 : nbx;
+    const size_t need = (ncell + kBlock - 1) / kBlock;
+    if (static_cast<size_t>(nbx) > need) nbx = static_cast<int>(need);
+    hipLaunchKernelGGL(k_wind_nearest, dim3(nbx, batch), dim3(kBlock), table ? 2 * sizeof(double) * npts : 0, as_stream(stream),
+                       index, speed, dirn, npts, wspeed, wdirn, ncell, table);
+    SSRS_HIP_CHECK(hipGetLastError());
+    return SSRS_OK;
+}
+
+extern "C" size_t ssrs_wind_cubic_workspace_bytes(int npts, int ntri, int rows, int cols, int batch)
+{
+    if (npts < 3 || ntri <= 0 || rows <= 0 || cols <= 0 || batch <= 0) return 0;
+    return align256(static_cast<size_t>(rows) * cols * sizeof(int32_t)) +
+           static_cast<size_t>(ntri) * 2 * batch * kCT * sizeof(double) + 512;
+}
+
+extern "C" int ssrs_wind_from_triangles_cubic(const double *points, const int32_t *triangles, const int32_t *neighbors,
+                                              const double *transform, const double *east, const double *north,
+                                              const double *grad_east, const double *grad_north, int npts, int ntri,
+                                              double cell_size, double *wspeed, double *wdirn, int rows, int cols, int batch,
+                                              void *workspace, size_t workspace_bytes, void *stream)
+{
+    SSRS_REQUIRE(points && triangles && neighbors && transform && east && north && grad_east && grad_north && wspeed && wdirn,
+                 "ssrs_wind_from_triangles_cubic: NULL pointer");
+    SSRS_REQUIRE(npts >= 3 && ntri >= 1 && rows > 0 && cols > 0 && batch > 0, "ssrs_wind_from_triangles_cubic: bad sizes");
+    SSRS_REQUIRE(cell_size > 0.0, "ssrs_wind_from_triangles_cubic: cell_size must be > 0");
+    SSRS_REQUIRE(workspace && workspace_bytes >= ssrs_wind_cubic_workspace_bytes(npts, ntri, rows, cols, batch),
+                 "ssrs_wind_from_triangles_cubic: workspace too small");
+    hipStream_t st = as_stream(stream);
+    const size_t ncell = static_cast<size_t>(rows) * cols, ncoef = static_cast<size_t>(ntri) * 2 * batch;
+    int32_t *owner = static_cast<int32_t *>(workspace);
+    double *coef = reinterpret_cast<double *>(static_cast<char *>(workspace) + align256(ncell * sizeof(int32_t)));
+    SSRS_HIP_CHECK(hipMemsetAsync(owner, 0x7f, ncell * sizeof(int32_t), st));      // 0x7f7f7f7f: above any index
+    hipLaunchKernelGGL(k_ct_coefficients, dim3(static_cast<unsigned>((ncoef + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, points,
+                       triangles, neighbors, transform, east, north, grad_east, grad_north, npts, ntri, batch, coef);
+    hipLaunchKernelGGL(k_tri_owner, dim3(static_cast<unsigned>(ntri), 64), dim3(kBlock), 0, st, points, triangles, transform, ntri,
+                       cell_size, rows, cols, owner);
+    hipLaunchKernelGGL(k_wind_cubic, dim3(stream_grid(ncell)), dim3(kBlock), 0, st, owner, transform, coef, cell_size, wspeed,
+                       wdirn, rows, cols, batch);
+    SSRS_HIP_CHECK(hipGetLastError());
+    return SSRS_OK;
+}

@@ -51,7 +51,10 @@ class Simulator(Config):
         'Elevation' and optionally 'Slope', 'Aspect' | callable(gridsize, res).
         wind (snapshot / seasonal): list of dicts, each with 'datetime'
         (datetime or 4-tuple) or 'case_id', and 'wspeed', 'wdirn' given either as
-        (rows, cols) rasters or as lattice samples with 'x_km', 'y_km'.
+        (rows, cols) rasters or as lattice samples with 'x_km', 'y_km' (or samples at
+        scattered points: x_km[npts], y_km[npts], arrays (npts,)).  Samples are
+        interpolated as `wtk_interp_type` says ('nearest' | 'linear' | 'cubic', scipy
+        griddata's methods as in the reference); rasters are taken as they are.
         origin: projected (west, south) of cell (0, 0); the reference derives it
         from southwest_lonlat through GDAL (simulator.py:77-85)."""
         if in_config is None:
@@ -165,13 +168,12 @@ class Simulator(Config):
                 item['case_id'] = dt.strftime(self.time_format)       # simulator.py:126
             item['datetime'] = dt
             out.append(item)
-        if any('x_km' in it for it in out) and str(self.wtk_interp_type).lower() != 'linear':
+        if any('x_km' in it for it in out):
             # the reference hands wtk_interp_type to scipy's griddata ('nearest' | 'linear' | 'cubic',
-            # simulator.py:774-775); the device interpolation is the linear one only
-            raise NotImplementedError(
-                f"wtk_interp_type = {self.wtk_interp_type!r}: wind samples are interpolated linearly on the "
-                "device (lattice: bilinear; scattered points: Delaunay + barycentric = griddata 'linear'); "
-                "interpolate with scipy yourself and inject (rows, cols) rasters for 'nearest' / 'cubic'")
+            # simulator.py:774-775), which raises ValueError for anything else
+            from .wind import METHODS
+            if str(self.wtk_interp_type).lower() not in METHODS:
+                raise ValueError(f'wtk_interp_type = {self.wtk_interp_type!r}: expected one of {METHODS}')
         if self.sim_mode.lower() == 'snapshot' and len(out) != 1:
             raise ValueError('snapshot mode takes exactly one wind entry')
         return out
@@ -233,7 +235,8 @@ class Simulator(Config):
         # per batch, no per-cell wind rasters, no slope / aspect rasters)
         mine = set(self._cases_written_here())
         wind = [it for it in self._wind if it['case_id'] in mine]
-        lattice = len(wind) > 0 and all('x_km' in it and np.ndim(it['wspeed']) == 2 for it in wind) and \
+        lattice = len(wind) > 0 and str(self.wtk_interp_type).lower() == 'linear' and \
+            all('x_km' in it and np.ndim(it['wspeed']) == 2 for it in wind) and \
             not ('Slope' in self._terrain or 'Aspect' in self._terrain) and \
             all(np.array_equal(it['x_km'], wind[0]['x_km']) and
                 np.array_equal(it['y_km'], wind[0]['y_km']) for it in wind)
@@ -263,24 +266,44 @@ class Simulator(Config):
             for item, o in zip(chunk, oro):
                 fname = self._get_orograph_fname(item['case_id'], self.mode_data_dir)
                 np.save(f'{fname}.npy', o.cpu().numpy())
+        self._nearest_index = (None, None)        # ('nearest': 4 B per cell of device memory, needed no longer)
         print(f'took {_elapsed(start_time)}', flush=True)
 
     def _wind_rasters(self, item):
         """Per-cell wind speed / direction (f64 device tensors) of one case."""
         ws, wd = item['wspeed'], item['wdirn']
         if 'x_km' in item:
-            from .wind import interpolate_wind_lattice, interpolate_wind_scattered
+            from .wind import interpolate_wind_lattice, interpolate_wind_scattered, nearest_sample_index
             # samples on a regular lattice (x_km[nx], y_km[ny], arrays (ny, nx)) or at scattered points
             # (x_km[npts], y_km[npts], arrays (npts,)): the reference's griddata, simulator.py:765-776
-            if np.ndim(ws) == 1 and np.size(item['x_km']) == np.size(ws) == np.size(item['y_km']):
-                ws_d, wd_d = interpolate_wind_scattered(item['x_km'], item['y_km'], ws, wd,
-                                                        self.gridsize, self.resolution)
-                if bool(torch.isnan(ws_d).any()):
+            method = str(self.wtk_interp_type).lower()
+            x_km, y_km = item['x_km'], item['y_km']
+            if method != 'linear' and np.ndim(ws) == 2:
+                # the reference triangulates whatever points it gets: a lattice is its meshgrid points
+                if np.shape(ws) != (np.size(y_km), np.size(x_km)) or np.shape(wd) != np.shape(ws):
+                    raise ValueError(f'lattice arrays must be (ny, nx) = {(np.size(y_km), np.size(x_km))}')
+                x_km, y_km = (a.ravel() for a in np.meshgrid(np.asarray(x_km, dtype=np.float64).ravel(),
+                                                             np.asarray(y_km, dtype=np.float64).ravel()))
+                ws, wd = np.asarray(ws, dtype=np.float64).ravel(), np.asarray(wd, dtype=np.float64).ravel()
+            if np.ndim(ws) == 1 and np.size(x_km) == np.size(ws) == np.size(y_km):
+                index = None
+                if method == 'nearest':
+                    # the index raster depends on the points only: one per wind geometry, not one per case
+                    key = (np.asarray(x_km, dtype=np.float64).tobytes(), np.asarray(y_km, dtype=np.float64).tobytes())
+                    if getattr(self, '_nearest_index', (None, None))[0] != key:
+                        self._nearest_index = (key, nearest_sample_index(x_km, y_km, self.gridsize, self.resolution))
+                    index = self._nearest_index[1]
+                ws_d, wd_d = interpolate_wind_scattered(x_km, y_km, ws, wd, self.gridsize, self.resolution,
+                                                        method=method, index=index)
+                if method != 'nearest' and bool(torch.isnan(ws_d).any()):
                     # griddata's behaviour (cells outside the samples' convex hull are NaN); the reference
                     # prints rather than raises when NaNs turn up (simulator.py:286)
                     print(f"{item['case_id']}: NANs in the interpolated wind (raster cells outside the convex "
                           'hull of the wind samples); their updraft is 0')
                 return ws_d, wd_d
+            if method != 'linear':
+                raise ValueError("wind samples must be (npts,) at x_km[npts], y_km[npts] or (ny, nx) on a lattice "
+                                 'x_km[nx], y_km[ny]')
             return interpolate_wind_lattice(item['x_km'], item['y_km'], ws, wd,
                                             self.gridsize, self.resolution)
         ws = to_dev(ws, torch.float64)

@@ -39,13 +39,32 @@ def interpolate_wind_lattice(x_km, y_km, wspeed, wdirn, gridsize, resolution):
     return (out_s[0], out_d[0]) if single else (out_s, out_d)
 
 
-def interpolate_wind_scattered(x_km, y_km, wspeed, wdirn, gridsize, resolution):
+METHODS = ('nearest', 'linear', 'cubic')                       # scipy griddata's (reference: ssrs/config.py:44)
+
+
+def check_method(method):
+    """Lower-cased interpolation method; ValueError for anything griddata does not know (as griddata)."""
+    name = str(method).lower()
+    if name not in METHODS:
+        raise ValueError(f"unknown interpolation method {method!r}: expected one of {METHODS}")
+    return name
+
+
+def interpolate_wind_scattered(x_km, y_km, wspeed, wdirn, gridsize, resolution, method='linear', index=None):
     """The reference's general case (/root/reference/ssrs/simulator.py:765-792): wind samples at SCATTERED points
     x_km[npts], y_km[npts] (relative to the raster's south-west cell centre), wspeed / wdirn (npts,) or (B, npts).
     `scipy.interpolate.griddata(..., method='linear')` is a Delaunay triangulation + barycentric interpolation: the
     triangulation is built here on the host by the same scipy class griddata uses (a few thousand points), the
     30 M cells are interpolated by the HIP kernels behind `ssrs_wind_from_triangles`.  Returns (wspeed, wdirn) f64
-    CUDA tensors (rows, cols) or (B, rows, cols); NaN outside the convex hull of the points, as griddata."""
+    CUDA tensors (rows, cols) or (B, rows, cols); NaN outside the convex hull of the points, as griddata.
+    method: griddata's 'nearest' | 'linear' | 'cubic' (any case).  'nearest' has no hull and no NaN; `index` is its
+    optional prebuilt `nearest_sample_index` raster (it depends on the points only).  'cubic' takes the vertex
+    gradients from scipy's own estimator and evaluates the Clough-Tocher patches on the device."""
+    method = check_method(method)
+    if method == 'nearest':
+        return _scattered_nearest(x_km, y_km, wspeed, wdirn, gridsize, resolution, index)
+    if method == 'cubic':
+        return _scattered_cubic(x_km, y_km, wspeed, wdirn, gridsize, resolution)
     from scipy.spatial import Delaunay
     x = np.asarray(x_km, dtype=np.float64).ravel()
     y = np.asarray(y_km, dtype=np.float64).ravel()
@@ -74,5 +93,91 @@ def interpolate_wind_scattered(x_km, y_km, wspeed, wdirn, gridsize, resolution):
     nat.check(L.ssrs_wind_from_triangles(
         nat.ptr(d_pts), nat.ptr(d_tri), nat.ptr(d_tr), nat.ptr(ws.contiguous()), nat.ptr(wd.contiguous()),
         int(x.size), int(d_tri.shape[0]), C.c_double(resolution / 1000.), nat.ptr(out_s), nat.ptr(out_d), rows, cols, batch,
+        nat.ptr(scratch), C.c_size_t(nbytes), stream_ptr()))
+    return (out_s[0], out_d[0]) if single else (out_s, out_d)
+
+
+def _samples(x_km, y_km, wspeed, wdirn, least):
+    """points (npts, 2), wspeed / wdirn as (B, npts) numpy f64, and whether the caller gave one snapshot."""
+    x = np.asarray(x_km, dtype=np.float64).ravel()
+    y = np.asarray(y_km, dtype=np.float64).ravel()
+    if x.size != y.size or x.size < least:
+        raise ValueError(f'scattered wind samples need x_km, y_km of equal length >= {least}')
+    ws = np.asarray(wspeed.cpu() if isinstance(wspeed, torch.Tensor) else wspeed, dtype=np.float64)
+    wd = np.asarray(wdirn.cpu() if isinstance(wdirn, torch.Tensor) else wdirn, dtype=np.float64)
+    single = ws.ndim == 1
+    if single:
+        ws, wd = ws[None], wd[None]
+    if ws.ndim != 2 or ws.shape[1] != x.size or ws.shape != wd.shape:
+        raise ValueError(f'scattered wind arrays must be (npts,) or (B, npts) with npts = {x.size}')
+    return np.ascontiguousarray(np.stack([x, y], 1)), np.ascontiguousarray(ws), np.ascontiguousarray(wd), single
+
+
+def nearest_sample_index(x_km, y_km, gridsize, resolution):
+    """(rows, cols) int32 CUDA raster: per cell the index of the sample nearest to its centre (Euclidean, the lowest
+    index among equally near ones) -- what griddata's 'nearest' looks up through cKDTree.  It depends on the points
+    only: build it once and hand it to `interpolate_wind_scattered(..., method='nearest', index=...)`."""
+    x = np.asarray(x_km, dtype=np.float64).ravel()
+    y = np.asarray(y_km, dtype=np.float64).ravel()
+    if x.size != y.size or x.size < 1:
+        raise ValueError('scattered wind samples need x_km, y_km of equal length >= 1')
+    rows, cols = int(gridsize[0]), int(gridsize[1])
+    d_pts = to_dev(np.ascontiguousarray(np.stack([x, y], 1)), torch.float64)
+    index = torch.empty((rows, cols), dtype=torch.int32, device=d_pts.device)
+    L = nat.lib()
+    nbytes = int(L.ssrs_wind_nearest_workspace_bytes(int(x.size), rows, cols))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=d_pts.device)
+    nat.check(L.ssrs_wind_nearest_index(nat.ptr(d_pts), int(x.size), C.c_double(resolution / 1000.), nat.ptr(index),
+                                        rows, cols, nat.ptr(scratch), C.c_size_t(nbytes), stream_ptr()))
+    return index
+
+
+def _scattered_nearest(x_km, y_km, wspeed, wdirn, gridsize, resolution, index):
+    pts, ws, wd, single = _samples(x_km, y_km, wspeed, wdirn, 1)
+    rows, cols = int(gridsize[0]), int(gridsize[1])
+    if index is None:
+        index = nearest_sample_index(pts[:, 0], pts[:, 1], gridsize, resolution)
+    if not (isinstance(index, torch.Tensor) and index.is_cuda and index.dtype == torch.int32 and
+            tuple(index.shape) == (rows, cols)):
+        raise ValueError(f'index must be an int32 CUDA tensor of shape {(rows, cols)} (nearest_sample_index)')
+    d_ws, d_wd = to_dev(ws, torch.float64), to_dev(wd, torch.float64)
+    batch = int(ws.shape[0])
+    out_s = torch.empty((batch, rows, cols), dtype=torch.float64, device=index.device)
+    out_d = torch.empty_like(out_s)
+    nat.check(nat.lib().ssrs_wind_from_nearest(nat.ptr(index.contiguous()), nat.ptr(d_ws), nat.ptr(d_wd), int(pts.shape[0]),
+                                               nat.ptr(out_s), nat.ptr(out_d), rows, cols, batch, stream_ptr()))
+    return (out_s[0], out_d[0]) if single else (out_s, out_d)
+
+
+def _scattered_cubic(x_km, y_km, wspeed, wdirn, gridsize, resolution):
+    from scipy.interpolate import CloughTocher2DInterpolator
+    from scipy.spatial import Delaunay
+    pts, ws, wd, single = _samples(x_km, y_km, wspeed, wdirn, 3)
+    batch, npts = ws.shape
+    tri = Delaunay(pts)                                        # what griddata -> CloughTocher2DInterpolator builds
+    east = ws * np.sin(wd * np.pi / 180.)                      # simulator.py:784-785
+    north = ws * np.cos(wd * np.pi / 180.)
+    # the vertex gradients: scipy's estimator with griddata's parameters, every field in one call (column by column
+    # the same bits as the single-field calls griddata makes)
+    values = np.ascontiguousarray(np.concatenate([east, north], 0).T)             # (npts, 2 B)
+    grad = CloughTocher2DInterpolator(tri, values, tol=1e-6, maxiter=400).grad     # (npts, 2 B, 2)
+    grad = np.ascontiguousarray(np.transpose(grad, (1, 0, 2)))                     # (2 B, npts, 2)
+    rows, cols = int(gridsize[0]), int(gridsize[1])
+    d_pts = to_dev(pts, torch.float64)
+    dev = d_pts.device
+    d_tri = torch.from_numpy(np.ascontiguousarray(tri.simplices.astype(np.int32))).to(dev)
+    d_nbr = torch.from_numpy(np.ascontiguousarray(tri.neighbors.astype(np.int32))).to(dev)
+    d_tr = torch.from_numpy(np.ascontiguousarray(tri.transform.astype(np.float64))).to(dev)
+    d_east, d_north = torch.from_numpy(np.ascontiguousarray(east)).to(dev), torch.from_numpy(np.ascontiguousarray(north)).to(dev)
+    d_ge, d_gn = torch.from_numpy(grad[:batch].copy()).to(dev), torch.from_numpy(grad[batch:].copy()).to(dev)
+    out_s = torch.empty((batch, rows, cols), dtype=torch.float64, device=dev)
+    out_d = torch.empty_like(out_s)
+    L = nat.lib()
+    ntri = int(d_tri.shape[0])
+    nbytes = int(L.ssrs_wind_cubic_workspace_bytes(int(npts), ntri, rows, cols, int(batch)))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    nat.check(L.ssrs_wind_from_triangles_cubic(
+        nat.ptr(d_pts), nat.ptr(d_tri), nat.ptr(d_nbr), nat.ptr(d_tr), nat.ptr(d_east), nat.ptr(d_north), nat.ptr(d_ge),
+        nat.ptr(d_gn), int(npts), ntri, C.c_double(resolution / 1000.), nat.ptr(out_s), nat.ptr(out_d), rows, cols, int(batch),
         nat.ptr(scratch), C.c_size_t(nbytes), stream_ptr()))
     return (out_s[0], out_d[0]) if single else (out_s, out_d)
