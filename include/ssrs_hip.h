@@ -191,6 +191,20 @@ size_t ssrs_blur_workspace_bytes(int rows, int cols, double sigma);
 int ssrs_gaussian_blur(const double *in, double *out, double sigma, int rows, int cols,
                        void *workspace, size_t workspace_bytes, void *stream);
 
+/* compute_thermals as ONE call for `count` realisations: out[k] = blur(seeds(aspect, scale, seeds[k]), sigma),
+ * bit for bit what the two calls above give in f64 (the same Philox key per cell, the same sum in the same order),
+ * rounded once to f32 when out_is_f32 (what the <case>_r<k>_thermals.npy files hold).  One launch per 32
+ * realisations; a block draws the seeds of a 32 x 64 tile and its halo into LDS and blurs there, so neither the
+ * seed raster nor the axis-0 result reaches HBM.  No workspace; asynchronous on `stream`.
+ * aspect: device, (rows, cols) f64.  seeds: HOST array of `count` keys (read before the call returns).
+ * out: device, (count, rows, cols) f32 or f64.  sigma: the reference's 4 is what ssrs_amd passes; a sigma whose
+ * radius int(4 sigma + 0.5) exceeds 16 does not fit the tile and takes the chain above per realisation through
+ * stream-ordered scratch (hipMallocAsync, 16 bytes per cell; that path synchronises `stream` once).
+ * NULL pointers, count / rows / cols <= 0 or sigma <= 0 -> SSRS_ERR_INVALID before any GPU work. */
+int ssrs_thermal_fields(const double *aspect, double thermal_intensity_scale, double sigma,
+                        const uint64_t *seeds, int count, void *out, int out_is_f32,
+                        int rows, int cols, void *stream);
+
 /* ----------------------------------------------------------------- stepper */
 
 /* Per-run constants of generate_simulated_tracks (ssrs/movmodel.py:264-318).

@@ -29,7 +29,7 @@ EXPORTS = (
     'ssrs_wind_from_lattice', 'ssrs_wind_triangles_workspace_bytes', 'ssrs_wind_from_triangles',
     'ssrs_wind_nearest_workspace_bytes', 'ssrs_wind_nearest_index', 'ssrs_wind_from_nearest',
     'ssrs_wind_cubic_workspace_bytes', 'ssrs_wind_from_triangles_cubic', 'ssrs_thermal_seeds', 'ssrs_blur_workspace_bytes',
-    'ssrs_gaussian_blur', 'ssrs_track_params_init', 'ssrs_transition_table_build',
+    'ssrs_gaussian_blur', 'ssrs_thermal_fields', 'ssrs_track_params_init', 'ssrs_transition_table_build',
     'ssrs_transition_ring_bytes', 'ssrs_transition_ring_build',
     'ssrs_transition_thr_bytes', 'ssrs_transition_thr_build',
     'ssrs_tracks_workspace_bytes', 'ssrs_tracks_workspace_bytes_ex', 'ssrs_tracks_simulate', 'ssrs_uniform_selftest',
@@ -125,6 +125,8 @@ def lib():
         if hasattr(L, 'ssrs_blur_workspace_bytes'):
             L.ssrs_blur_workspace_bytes.restype = C.c_size_t
             L.ssrs_blur_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_double]
+        L.ssrs_thermal_fields.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_uint64), C.c_int,
+                                          C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         if hasattr(L, 'ssrs_potential_workspace_bytes'):
             L.ssrs_potential_workspace_bytes.restype = C.c_size_t
             L.ssrs_potential_workspace_bytes.argtypes = [C.c_int, C.c_int]

@@ -315,7 +315,7 @@ class Simulator(Config):
     def compute_thermal_updrafts(self, case_id: str):
         """simulator.py:217-228."""
         if self.thermals_realization_count > 0:
-            from .thermals import compute_thermals
+            from .thermals import compute_thermals_batch
             print('Computing thermal updrafts...', flush=True)
             aspect = self.get_terrain_aspect()
             # the reference draws every case / realisation from one advancing numpy stream
@@ -324,11 +324,16 @@ class Simulator(Config):
             base = (self.sim_seed if self.sim_seed >= 0 else
                     int.from_bytes(os.urandom(4), 'little'))
             case_no = self.case_ids.index(case_id) if case_id in self.case_ids else 0
-            for real_id in range(self.thermals_realization_count):
-                seed = base + 7919 * (real_id + 1) + 104729 * case_no
-                thermals = compute_thermals(aspect, 2.0, seed=seed)
-                fname = self._get_thermal_fname(case_id, real_id, self.mode_data_dir)
-                np.save(f'{fname}.npy', np.asarray(thermals, dtype=np.float32))
+            seeds = [base + 7919 * (real_id + 1) + 104729 * case_no
+                     for real_id in range(self.thermals_realization_count)]
+            # one fused call per case, in the f32 the files hold; at most 1 GiB of fields at a time
+            chunk = max(1, (1 << 30) // (4 * aspect.shape[0] * aspect.shape[1]))
+            aspect = to_dev(aspect, torch.float64)
+            for first in range(0, len(seeds), chunk):
+                fields = compute_thermals_batch(aspect, 2.0, seeds[first:first + chunk], dtype=torch.float32)
+                for k, field in enumerate(fields.cpu().numpy()):
+                    fname = self._get_thermal_fname(case_id, first + k, self.mode_data_dir)
+                    np.save(f'{fname}.npy', field)
         else:
             print('No thermals requested!', flush=True)
 

@@ -31,7 +31,24 @@ def thermal_seeds(aspect, thermal_intensity_scale, seed=0):
     return like_input(out, aspect)
 
 
+def compute_thermals_batch(aspect, thermal_intensity_scale, seeds, dtype=torch.float64, sigma=4.0):
+    """One field of smoothed random thermals per entry of `seeds`, (len(seeds), rows, cols) in
+    `dtype` (f64, or f32 = the f64 field rounded once), from one fused device call: field k is
+    bit for bit gaussian_blur(thermal_seeds(aspect, scale, seeds[k]), sigma)."""
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError('compute_thermals_batch: dtype must be torch.float32 or torch.float64')
+    a = to_dev(aspect, torch.float64)
+    if a.dim() != 2:
+        raise ValueError('compute_thermals_batch: aspect must be a (rows, cols) raster')
+    rows, cols = int(a.shape[0]), int(a.shape[1])
+    keys = [int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds]
+    out = torch.empty((len(keys), rows, cols), dtype=dtype, device=a.device)
+    nat.check(nat.lib().ssrs_thermal_fields(nat.ptr(a), C.c_double(thermal_intensity_scale), C.c_double(sigma),
+                                            (C.c_uint64 * len(keys))(*keys), len(keys), nat.ptr(out),
+                                            int(dtype == torch.float32), rows, cols, stream_ptr()))
+    return like_input(out, aspect)
+
+
 def compute_thermals(aspect, thermal_intensity_scale, seed=0):
     """Field of smoothed random thermals (f64), one realisation per `seed`."""
-    a = to_dev(aspect, torch.float64)
-    return like_input(gaussian_blur(thermal_seeds(a, thermal_intensity_scale, seed), 4.0), aspect)
+    return compute_thermals_batch(aspect, thermal_intensity_scale, [seed])[0]
