@@ -90,13 +90,16 @@ void orc_slope_aspect(const double *z, int rows, int cols, double res,
             double z7 = zm[-1], z8 = z0[-1], z9 = zp[-1];
             double dzdx = ((z3 + 2 * z6 + z9) - (z1 + 2 * z4 + z7)) / (8 * res);
             double dzdy = ((z1 + 2 * z2 + z3) - (z7 + 2 * z8 + z9)) / (8 * res);
-            if (slope)
-                slope[i] = atan(sqrt(dzdx * dzdx + dzdy * dzdy)) * r2d;
+            if (slope) {
+                double sl = atan(sqrt(dzdx * dzdx + dzdy * dzdy)) * r2d;
+                slope[i] = sl != sl ? 0.0 : sl;          /* np.nan_to_num, layers.py:93 */
+            }
             if (aspect) {
                 double dx = dzdx == 0.0 ? 1e-10 : dzdx;
                 double ang = atan(dzdy / dx) * r2d;
                 double mod = 90.0 * (dx / fabs(dx));
-                aspect[i] = 180.0 - ang + mod;
+                double as = 180.0 - ang + mod;
+                aspect[i] = as != as ? 0.0 : as;         /* np.nan_to_num, layers.py:128 */
             }
         }
     }

@@ -57,17 +57,26 @@ def _horn_gradients(z_mat, res):
     return dz_dx, dz_dy
 
 
+def _nan_to_zero(a):
+    """The part of the reference's closing np.nan_to_num (layers.py:93, :128) that a nodata (NaN)
+    elevation reaches: NaN -> 0.  nan_to_num also replaces +-inf by the largest finite double;
+    +-inf elevations are out of scope and are not restated here."""
+    a[np.isnan(a)] = 0.
+    return a
+
+
 def compute_slope_degrees(z_mat, res):
-    """layers.py:63-93 -- border cells are 0 (NaN -> nan_to_num)."""
+    """layers.py:63-93 -- border cells are 0 (NaN -> nan_to_num), and so is every cell whose
+    3 x 3 stencil touches a NaN elevation (see _nan_to_zero; +-inf elevations out of scope)."""
     z_mat = np.asarray(z_mat)
     slope = np.zeros_like(z_mat)
     dz_dx, dz_dy = _horn_gradients(z_mat, res)
     slope[1:-1, 1:-1] = np.degrees(np.arctan(np.sqrt(dz_dx**2 + dz_dy**2)))
-    return slope
+    return _nan_to_zero(slope)
 
 
 def compute_aspect_degrees(z_mat, res):
-    """layers.py:96-128."""
+    """layers.py:96-128, NaN -> 0 as compute_slope_degrees (+-inf elevations out of scope)."""
     z_mat = np.asarray(z_mat)
     aspect = np.zeros_like(z_mat)
     dz_dx, dz_dy = _horn_gradients(z_mat, res)
@@ -76,7 +85,7 @@ def compute_aspect_degrees(z_mat, res):
     angle = np.degrees(np.arctan(np.divide(dz_dy, dz_dx)))
     angle_mod = 90. * np.divide(dz_dx, np.absolute(dz_dx))
     aspect[1:-1, 1:-1] = 180. - angle + angle_mod
-    return aspect
+    return _nan_to_zero(aspect)
 
 
 def compute_orographic_updraft(wspeed, wdirn, slope, aspect, min_updraft_val=0.):

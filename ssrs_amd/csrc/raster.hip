@@ -108,6 +108,10 @@ __global__ __launch_bounds__(kBlock) void k_slope_aspect(
             const double dx = dzdx == 0.0 ? 1e-10 : dzdx;
             const double ang = atan(dzdy / dx) * r2d;
             a = 180.0 - ang + 90.0 * (dx / fabs(dx));
+            // a nodata (NaN) elevation in the stencil: the reference closes with np.nan_to_num
+            // (layers.py:93, :128), so both layers are 0 there (+-inf elevations: out of scope)
+            s = s != s ? 0.0 : s;
+            a = a != a ? 0.0 : a;
         }
         const size_t i = static_cast<size_t>(r) * cols + c;
         if (slope) slope[i] = static_cast<Tout>(s);

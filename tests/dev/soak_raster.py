@@ -6,12 +6,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import numpy as np
 from ssrs_amd import layers
 from oracle import ssrs_oracle as orc
-
-
-def ulp_diff_f32(a, b):
-    a = np.ascontiguousarray(a, dtype=np.float32).view(np.int32).astype(np.int64)
-    b = np.ascontiguousarray(b, dtype=np.float32).view(np.int32).astype(np.int64)
-    return np.abs(a - b)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from raster_checks import ulp_diff_f32
 
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.

@@ -54,6 +54,50 @@ def test_g2_raster(golden):
                                rtol=1e-12, atol=1e-15)
 
 
+def test_g14_raster_edges(golden):
+    """Plateau, ridge and nodata DEMs (generate_g14_raster_edges.py): the oracle's dz_dx == 0 branch
+    with values that show, and the reference's nan_to_num on a NaN stencil."""
+    from raster_checks import branch_share, nan_stencil_cells
+    g = golden('g14_raster_edges.npz')
+    res, thr = float(g['res']), float(g['threshold'])
+    # the fixture holds what it was made for: shares of interior cells with dz_dx == 0 != dz_dy
+    least = dict(integer=0.02, terraced=0.10, ridge_cols=0.90, nodata=0.02)
+    for name in ('integer', 'terraced', 'ridge_cols', 'ridge_rows', 'nodata'):
+        dem = g[f'{name}_dem']
+        assert dem.shape == (97, 161) and dem.dtype == (np.float32 if name == 'nodata' else np.int16)
+        z = dem.astype(np.float64)
+        share = branch_share(z, res, orc)
+        assert share >= least.get(name, 0.), (name, share)
+        gx, gy = orc._horn_gradients(z, res)
+        if name == 'ridge_rows':
+            assert share == 0. and ((gy == 0) & (gx != 0)).mean() >= 0.8
+        slope, aspect = orc.compute_slope_degrees(z, res), orc.compute_aspect_degrees(z, res)
+        assert np.array_equal(slope, g[f'{name}_slope']) and np.array_equal(aspect, g[f'{name}_aspect'])
+        hit = nan_stencil_cells(z)
+        if name == 'nodata':
+            cells = g['nodata_cells']
+            assert np.isnan(dem[cells[:, 0], cells[:, 1]]).all() and np.isnan(dem).sum() == len(cells) == 12
+            assert hit.sum() == 8 + 25 + 1 + 5  # round one cell, the block and its ring, (1, 1), round (1, 120)
+        else:
+            assert not hit.any()
+        assert (slope[hit] == 0).all() and (aspect[hit] == 0).all()
+        s, a = c_oracle.slope_aspect(z, res)
+        np.testing.assert_allclose(s, slope, rtol=1e-13, atol=1e-14)
+        np.testing.assert_allclose(a, aspect, rtol=1e-13, atol=1e-12)
+        assert (s[hit] == 0).all() and (a[hit] == 0).all()
+        assert len(g['cases']) == 5
+        for j, (ws, wd, mn) in enumerate(g['cases']):
+            oro = orc.compute_orographic_updraft(ws, wd, slope, aspect, mn)
+            oro32 = g[f'{name}_oro{j}']
+            assert oro32.dtype == np.float32 and np.array_equal(oro.astype(np.float32), oro32)
+            assert (oro32[hit] == np.float32(mn)).all()
+            np.testing.assert_allclose(orc.get_above_threshold_speed(oro32, thr), g[f'{name}_use{j}'],
+                                       rtol=1e-14, atol=0)
+            o64, o32 = c_oracle.orographic(slope, aspect, float(ws), float(wd), float(mn))
+            np.testing.assert_allclose(o64, oro, rtol=1e-13, atol=1e-15)
+            np.testing.assert_allclose(c_oracle.threshold(oro32, thr), g[f'{name}_use{j}'], rtol=1e-12, atol=1e-15)
+
+
 def test_g3_threshold(golden):
     g = golden('g3_threshold.npz')
     for thr in (0.75, 0.5, 1.2):
