@@ -205,6 +205,59 @@ int ssrs_thermal_fields(const double *aspect, double thermal_intensity_scale, do
                         const uint64_t *seeds, int count, void *out, int out_is_f32,
                         int rows, int cols, void *stream);
 
+/* The physical thermal model: the WTK layers pressure / temperature at wtk_thermal_height, boundary-layer height and
+ * surface heat flux -> thermal updraft at height z.  Three elementwise f64 calls over n values, each the reference's
+ * expression in the reference's operation order:
+ * ssrs_potential_temperature (ssrs/layers.py:40-48): (T + 273.15) * pow(1e5 / p, 0.2857) - 273.15, degrees Celsius.
+ * ssrs_deardorff_velocity (ssrs/layers.py:25-37): max(min, pow(9.8 / 1216 * (max(zi, 100) * max(q, 0) /
+ *   (theta + 273.15)), 1/3)).
+ * ssrs_thermal_updraft (ssrs/layers.py:51-60): x = clip(z / zi, 0, 1); max(min, w* * (0.85 * (pow(x, 1/3) * (1.3 - x))));
+ *   z = zmat[i], or z0 everywhere when zmat is NULL; zi is not clipped here (the reference does not).
+ * max / clip are numpy's: a NaN argument gives NaN (fmax / fmin would drop it).  The IEEE specials follow from plain
+ * division: zi = 0 with z > 0 gives x = 1, zi < 0 gives x = 0 and so the floor `min`, p = 0 gives theta = inf and so
+ * the floor, p < 0 gives NaN.  NULL pointers (zmat excepted) or n == 0 -> SSRS_ERR_INVALID before any GPU work. */
+int ssrs_potential_temperature(const double *pressure, const double *temperature, double *out, size_t n,
+                               void *stream);
+int ssrs_deardorff_velocity(const double *pot_temperature, const double *blayer_height,
+                            const double *surface_heat_flux, double min_updraft_val, double *out, size_t n,
+                            void *stream);
+int ssrs_thermal_updraft(const double *zmat, double z0, const double *deardorff_vel, const double *blayer_height,
+                         double min_updraft_val, double *out, size_t n, void *stream);
+
+/* _interpolate_wtk_vardata (ssrs/simulator.py:765-776): scipy griddata of ANY scalar samples, method 'nearest' |
+ * 'linear' | 'cubic'.  values (nfields, npts) f64 -> out (nfields, rows, cols) f64.  The geometry is the wind calls':
+ * 'nearest' reads `index`, the raster of ssrs_wind_nearest_index (the other geometry pointers may be NULL); 'linear'
+ * and 'cubic' take points / triangles / transform of scipy.spatial.Delaunay and find cell ownership exactly as
+ * ssrs_wind_from_triangles does (scipy's eps, lowest triangle index on a shared edge, NaN outside the hull); 'cubic'
+ * also takes `neighbors` and `grad` (nfields, npts, 2), the vertex gradients of scipy's estimator, and builds the
+ * ordinate table of ssrs_wind_from_triangles_cubic, [triangle][nfields][19].  A cell is evaluated by the very
+ * expressions of the wind kernels.  workspace: ssrs_scalar_interp_workspace_bytes(method, ntri, rows, cols, nfields)
+ * bytes of device scratch (ntri is ignored for 'nearest'); 0 for arguments the call would refuse. */
+#define SSRS_INTERP_NEAREST 0
+#define SSRS_INTERP_LINEAR 1
+#define SSRS_INTERP_CUBIC 2
+size_t ssrs_scalar_interp_workspace_bytes(int method, int ntri, int rows, int cols, int nfields);
+int ssrs_scalar_from_samples(int method, const double *points, const int32_t *triangles, const int32_t *neighbors,
+                             const double *transform, const int32_t *index, const double *values,
+                             const double *grad, int npts, int ntri, double cell_size, double *out, int rows,
+                             int cols, int nfields, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The two above as ONE call for `batch` snapshots (what compute_thermal_updraft would make of the four WTK layers the
+ * reference downloads, ssrs/simulator.py:107-115).  layers (4, batch, npts) f64: pressure, temperature, blheight,
+ * surfheatflux at the sample points; grad (4, batch, npts, 2), 'cubic' only.  Per cell the sample geometry is located
+ * once for the whole batch; per snapshot the four values are interpolated, run through the three functions in
+ * registers and stored: out (batch, rows, cols), f64 or -- out_is_f32 -- that result rounded once to f32 (what
+ * <case>_r<k>_thermals.npy holds).  zmat: (rows, cols) f64 heights, or NULL for z0 everywhere.  Bit for bit the chain
+ * ssrs_scalar_from_samples -> ssrs_potential_temperature -> ssrs_deardorff_velocity -> ssrs_thermal_updraft, none of
+ * whose 4 + 3 rasters per snapshot reaches memory: 4 B read per cell (owner or index), 4-8 B written per cell and
+ * snapshot.  A lane owns four consecutive cells of a row (one 16-byte f32 store when cols % 4 == 0).
+ * workspace: ssrs_scalar_interp_workspace_bytes(method, ntri, rows, cols, 4 * batch). */
+int ssrs_wtk_thermal_fields(int method, const double *points, const int32_t *triangles, const int32_t *neighbors,
+                            const double *transform, const int32_t *index, const double *layers,
+                            const double *grad, int npts, int ntri, double cell_size, const double *zmat,
+                            double z0, double min_updraft_val, void *out, int out_is_f32, int rows, int cols,
+                            int batch, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ----------------------------------------------------------------- stepper */
 
 /* Per-run constants of generate_simulated_tracks (ssrs/movmodel.py:264-318).

@@ -21,6 +21,7 @@ SSRS_TRACKS_SCATTERED = 32
 SSRS_TRACKS_NO_SCATTERED = 64
 SSRS_TRACKS_THR_TABLE = 128
 SSRS_SOLVE_NO_AMG = 1
+SSRS_INTERP = {'nearest': 0, 'linear': 1, 'cubic': 2}          # SSRS_INTERP_NEAREST / _LINEAR / _CUBIC
 
 EXPORTS = (
     'ssrs_version', 'ssrs_build_flags', 'ssrs_last_error', 'ssrs_device_info', 'ssrs_slope_aspect',
@@ -29,7 +30,9 @@ EXPORTS = (
     'ssrs_wind_from_lattice', 'ssrs_wind_triangles_workspace_bytes', 'ssrs_wind_from_triangles',
     'ssrs_wind_nearest_workspace_bytes', 'ssrs_wind_nearest_index', 'ssrs_wind_from_nearest',
     'ssrs_wind_cubic_workspace_bytes', 'ssrs_wind_from_triangles_cubic', 'ssrs_thermal_seeds', 'ssrs_blur_workspace_bytes',
-    'ssrs_gaussian_blur', 'ssrs_thermal_fields', 'ssrs_track_params_init', 'ssrs_transition_table_build',
+    'ssrs_gaussian_blur', 'ssrs_thermal_fields', 'ssrs_potential_temperature', 'ssrs_deardorff_velocity',
+    'ssrs_thermal_updraft', 'ssrs_scalar_interp_workspace_bytes', 'ssrs_scalar_from_samples', 'ssrs_wtk_thermal_fields',
+    'ssrs_track_params_init', 'ssrs_transition_table_build',
     'ssrs_transition_ring_bytes', 'ssrs_transition_ring_build',
     'ssrs_transition_thr_bytes', 'ssrs_transition_thr_build',
     'ssrs_tracks_workspace_bytes', 'ssrs_tracks_workspace_bytes_ex', 'ssrs_tracks_simulate', 'ssrs_uniform_selftest',
@@ -127,6 +130,17 @@ def lib():
             L.ssrs_blur_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_double]
         L.ssrs_thermal_fields.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_uint64), C.c_int,
                                           C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.ssrs_potential_temperature.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.ssrs_deardorff_velocity.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.ssrs_thermal_updraft.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_size_t,
+                                           C.c_void_p]
+        L.ssrs_scalar_interp_workspace_bytes.restype = C.c_size_t
+        L.ssrs_scalar_interp_workspace_bytes.argtypes = [C.c_int] * 5
+        L.ssrs_scalar_from_samples.argtypes = [C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int,
+                                                                             C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.ssrs_wtk_thermal_fields.argtypes = [C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_double,
+                                                                            C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                                            C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
         if hasattr(L, 'ssrs_potential_workspace_bytes'):
             L.ssrs_potential_workspace_bytes.restype = C.c_size_t
             L.ssrs_potential_workspace_bytes.argtypes = [C.c_int, C.c_int]

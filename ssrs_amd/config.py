@@ -29,7 +29,8 @@ _SECTIONS = (
                            'track_dirn_restrict')),
     ('Plotting and wind turbines', ('turbine_minimum_hubheight', 'turbine_mrkr_size',
                                     'fig_height', 'fig_dpi')),
-    ('MI355X build', ('save_tracks', 'stepper_path', 'steps_per_launch', 'max_tracks_file_gb', 'hist_safe_tracks')),
+    ('MI355X build', ('save_tracks', 'stepper_path', 'steps_per_launch', 'max_tracks_file_gb', 'hist_safe_tracks',
+                      'thermal_model')),
 )
 
 
@@ -105,6 +106,10 @@ class Config:
     #                                     CU: 250 000 tracks = ~105 000 roaming at first, one round of 512-lane blocks, later
     #                                     ~78 000 in 256-lane blocks: 2.0 s per pass = 1.27e5 tracks/s against 1.0e5 for 140 000
     #                                     (rounds 3-4) and 1.15e5 for 300 000 (a second round of blocks; profiles/r04_roam_fill.txt)
+    thermal_model: str = 'random'       # random | wtk.  'random': the reference's compute_thermals, one field of smoothed random
+    #                                     blobs per realisation.  'wtk' (snapshot / seasonal, thermals_realization_count = 1): the
+    #                                     Deardorff-velocity updraft at wtk_thermal_height from the case's own WTK layers
+    #                                     (pressure, temperature, blheight, surfheatflux in every wind entry)
 
     def __str__(self):
         known = {f.name for f in fields(self)}

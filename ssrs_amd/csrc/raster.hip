@@ -14,6 +14,7 @@
 //                      Horn gradients -> updraft with no trig at all
 // Built with -ffp-contract=off (see build.py).
 #include "common.h"
+#include "interp.h"
 
 namespace ssrs {
 
@@ -344,14 +345,6 @@ __global__ __launch_bounds__(kBlock) void k_threshold(const float *__restrict__ 
     }
 }
 
-static inline int stream_grid(size_t nthreads_needed)
-{
-    size_t b = (nthreads_needed + kBlock - 1) / kBlock;
-    if (b < 1) b = 1;
-    if (b > static_cast<size_t>(kMaxStreamBlocks)) b = kMaxStreamBlocks;
-    return static_cast<int>(b);
-}
-
 static inline bool aligned16(const void *p)
 {   // NULL counts as aligned (optional arrays); 32 B covers Pack<double, 4>
     return (reinterpret_cast<uintptr_t>(p) & 31u) == 0;
@@ -648,15 +641,14 @@ __global__ __launch_bounds__(kBlock) void k_wind_triangles(const int32_t *__rest
         const size_t c0 = i - static_cast<size_t>(b) * ncell;
         const int r = static_cast<int>(c0 / cols), c = static_cast<int>(c0 % cols);
         const int32_t t = owner[c0];
-        double spd = __longlong_as_double(0x7FF8000000000000ll), ang = spd;
-        if (t != 0x7f7f7f7f) {
-            const double *T = transform + 6 * static_cast<size_t>(t);
-            const double dx = static_cast<double>(c) * cell - T[4], dy = static_cast<double>(r) * cell - T[5];
-            const double b0 = T[0] * dx + T[1] * dy, b1 = T[2] * dx + T[3] * dy, b2 = 1.0 - b0 - b1;
+        double spd = quiet_nan(), ang = spd;
+        if (t != kNoOwner) {
+            double b0, b1, b2;
+            tri_barycentric(transform + 6 * static_cast<size_t>(t), r, c, cell, b0, b1, b2);
             const double *e = east + static_cast<size_t>(b) * npts, *nn = north + static_cast<size_t>(b) * npts;
             const int32_t v0 = tri[3 * t], v1 = tri[3 * t + 1], v2 = tri[3 * t + 2];
-            const double ee = b0 * e[v0] + b1 * e[v1] + b2 * e[v2];     // (left to right, as scipy sums them)
-            const double en = b0 * nn[v0] + b1 * nn[v1] + b2 * nn[v2];
+            const double ee = tri_linear(b0, b1, b2, e, v0, v1, v2);
+            const double en = tri_linear(b0, b1, b2, nn, v0, v1, v2);
             spd = sqrt(ee * ee + en * en);
             ang = fmod(atan2(ee, en) + 2.0 * kPi, 2.0 * kPi) * 180.0 / kPi;
         }
@@ -841,10 +833,8 @@ extern "C" int ssrs_wind_from_triangles(const double *points, const int32_t *tri
     int32_t *owner = static_cast<int32_t *>(workspace);
     double *east = reinterpret_cast<double *>(static_cast<char *>(workspace) + ((ncell * sizeof(int32_t) + 255) / 256) * 256);
     double *north = east + nval;
-    SSRS_HIP_CHECK(hipMemsetAsync(owner, 0x7f, ncell * sizeof(int32_t), st));      // 0x7f7f7f7f: above any index
     hipLaunchKernelGGL(k_lattice_components, dim3(stream_grid(nval)), dim3(kBlock), 0, st, speed, dirn, nval, east, north);
-    hipLaunchKernelGGL(k_tri_owner, dim3(static_cast<unsigned>(ntri), 64), dim3(kBlock), 0, st, points, triangles, transform, ntri,
-                       cell_size, rows, cols, owner);
+    if (int rc = launch_tri_owner(points, triangles, transform, ntri, cell_size, rows, cols, owner, st)) return rc;
     hipLaunchKernelGGL(k_wind_triangles, dim3(stream_grid(ncell * batch)), dim3(kBlock), 0, st, owner, triangles, transform, east,
                        north, npts, cell_size, wspeed, wdirn, rows, cols, batch);
     SSRS_HIP_CHECK(hipGetLastError());
@@ -993,20 +983,18 @@ __global__ __launch_bounds__(kBlock) void k_wind_nearest(const int32_t *__restri
     }
 }
 
-// The 19 Bezier ordinates of the Clough-Tocher macro-triangle t for field f = 2 * snapshot + (0 east | 1 north), as
+// The 19 Bezier ordinates of the Clough-Tocher macro-triangle t for field f (the wind: f = 2 * snapshot + (0 east |
+// 1 north); in general the pairing of interp.h's launch_ct_coefficients), as
 // scipy's _clough_tocher_2d_single computes them on every evaluation; they do not depend on the evaluation point.
 // Order: c3000 c2100 c2010 c2001 c1200 c1101 c1020 c1011 c1002 c0300 c0210 c0201 c0120 c0111 c0102 c0030 c0021 c0012
 // c0003 (the order of the cubic's terms).  No guard scipy does not have: a neighbour whose centroid makes a
 // denominator of g vanish gives what IEEE gives.
-constexpr int kCT = 19;
-
 __global__ __launch_bounds__(kBlock) void k_ct_coefficients(const double *__restrict__ pts, const int32_t *__restrict__ tri,
                                                            const int32_t *__restrict__ nbr, const double *__restrict__ transform,
                                                            const double *__restrict__ east, const double *__restrict__ north,
                                                            const double *__restrict__ grad_east, const double *__restrict__ grad_north,
-                                                           int npts, int ntri, int batch, double *__restrict__ coef)
+                                                           size_t npts, int ntri, int nfield, double *__restrict__ coef)
 {
-    const int nfield = 2 * batch;
     const size_t q = blockIdx.x * static_cast<size_t>(kBlock) + threadIdx.x;
     if (q >= static_cast<size_t>(ntri) * nfield) return;
     const int t = static_cast<int>(q / nfield), f = static_cast<int>(q % nfield);
@@ -1066,12 +1054,7 @@ __device__ __forceinline__ void ct_store(const double *__restrict__ cf, const do
                                          size_t i, double *__restrict__ wspeed, double *__restrict__ wdirn)
 {
     for (int b = 0; b < batch; ++b, cf += 2 * kCT) {
-        double e = mono[0] * cf[0], n = mono[0] * cf[kCT];
-#pragma unroll
-        for (int k = 1; k < kCT; ++k) {
-            e += mono[k] * cf[k];
-            n += mono[k] * cf[kCT + k];
-        }
+        const double e = ct_eval(mono, cf), n = ct_eval(mono, cf + kCT);
         wspeed[b * ncell + i] = sqrt(e * e + n * n);
         wdirn[b * ncell + i] = fmod(atan2(e, n) + 2.0 * kPi, 2.0 * kPi) * 180.0 / kPi;
     }
@@ -1094,8 +1077,8 @@ __global__ __launch_bounds__(kBlock) void k_wind_cubic(const int32_t *__restrict
         const size_t i = base + lane;
         if (i >= ncell) continue;
         const int32_t t = owner[i];
-        if (t == 0x7f7f7f7f) {                                        // outside the hull: griddata's fill value
-            const double nan = __longlong_as_double(0x7FF8000000000000ll);
+        if (t == kNoOwner) {                                          // outside the hull: griddata's fill value
+            const double nan = quiet_nan();
             for (int b = 0; b < batch; ++b) {
                 wspeed[b * ncell + i] = nan;
                 wdirn[b * ncell + i] = nan;
@@ -1107,16 +1090,9 @@ __global__ __launch_bounds__(kBlock) void k_wind_cubic(const int32_t *__restrict
         const bool uniform = __ballot(t != t0) == 0ull;
         const size_t tt = static_cast<size_t>(uniform ? t0 : t);
         const int r = static_cast<int>(i / cols), c = static_cast<int>(i % cols);
-        const double *T = transform + 6 * tt;
-        const double dx = static_cast<double>(c) * cell - T[4], dy = static_cast<double>(r) * cell - T[5];
-        const double b0 = T[0] * dx + T[1] * dy, b1 = T[2] * dx + T[3] * dy, b2 = 1.0 - b0 - b1;
-        const double m = fmin(b0, fmin(b1, b2));
-        const double a1 = b0 - m, a2 = b1 - m, a3 = b2 - m, a4 = 3 * m;
-        const double a11 = a1 * a1, a22 = a2 * a2, a33 = a3 * a3, a44 = a4 * a4;
-        const double mono[kCT] = {
-            a11 * a1,      3 * a11 * a2,      3 * a11 * a3,      3 * a11 * a4, 3 * a1 * a22, 6 * a1 * a2 * a4, 3 * a1 * a33,
-            6 * a1 * a3 * a4, 3 * a1 * a44,   a22 * a2,          3 * a22 * a3, 3 * a22 * a4, 3 * a2 * a33,     6 * a2 * a3 * a4,
-            3 * a2 * a44,  a33 * a3,          3 * a33 * a4,      3 * a3 * a44, a44 * a4};
+        double b0, b1, b2, mono[kCT];
+        tri_barycentric(transform + 6 * tt, r, c, cell, b0, b1, b2);
+        ct_monomials(b0, b1, b2, mono);
         if (uniform)
             ct_store(coef + static_cast<size_t>(t0) * stride, mono, batch, ncell, i, wspeed, wdirn);
         else
@@ -1124,8 +1100,27 @@ __global__ __launch_bounds__(kBlock) void k_wind_cubic(const int32_t *__restrict
     }
 }
 
-static inline size_t align256(size_t n) { return (n + 255) / 256 * 256; }
 constexpr int kNearestTable = 3072;                                    // samples whose (speed, direction) fit 48 KB of LDS
+
+int launch_tri_owner(const double *points, const int32_t *triangles, const double *transform, int ntri, double cell,
+                     int rows, int cols, int32_t *owner, hipStream_t st)
+{
+    SSRS_HIP_CHECK(hipMemsetAsync(owner, 0x7f, static_cast<size_t>(rows) * cols * sizeof(int32_t), st));   // kNoOwner: above any index
+    hipLaunchKernelGGL(k_tri_owner, dim3(static_cast<unsigned>(ntri), 64), dim3(kBlock), 0, st, points, triangles, transform, ntri,
+                       cell, rows, cols, owner);
+    return SSRS_OK;
+}
+
+int launch_ct_coefficients(const double *points, const int32_t *triangles, const int32_t *neighbors,
+                           const double *transform, const double *val_even, const double *val_odd,
+                           const double *grad_even, const double *grad_odd, size_t pair_stride, int ntri, int nfield,
+                           double *coef, hipStream_t st)
+{
+    const size_t ncoef = static_cast<size_t>(ntri) * nfield;
+    hipLaunchKernelGGL(k_ct_coefficients, dim3(static_cast<unsigned>((ncoef + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, points,
+                       triangles, neighbors, transform, val_even, val_odd, grad_even, grad_odd, pair_stride, ntri, nfield, coef);
+    return SSRS_OK;
+}
 
 }  // namespace ssrs
 
@@ -1189,14 +1184,12 @@ extern "C" int ssrs_wind_from_triangles_cubic(const double *points, const int32_
     SSRS_REQUIRE(workspace && workspace_bytes >= ssrs_wind_cubic_workspace_bytes(npts, ntri, rows, cols, batch),
                  "ssrs_wind_from_triangles_cubic: workspace too small");
     hipStream_t st = as_stream(stream);
-    const size_t ncell = static_cast<size_t>(rows) * cols, ncoef = static_cast<size_t>(ntri) * 2 * batch;
+    const size_t ncell = static_cast<size_t>(rows) * cols;
     int32_t *owner = static_cast<int32_t *>(workspace);
     double *coef = reinterpret_cast<double *>(static_cast<char *>(workspace) + align256(ncell * sizeof(int32_t)));
-    SSRS_HIP_CHECK(hipMemsetAsync(owner, 0x7f, ncell * sizeof(int32_t), st));      // 0x7f7f7f7f: above any index
-    hipLaunchKernelGGL(k_ct_coefficients, dim3(static_cast<unsigned>((ncoef + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, points,
-                       triangles, neighbors, transform, east, north, grad_east, grad_north, npts, ntri, batch, coef);
-    hipLaunchKernelGGL(k_tri_owner, dim3(static_cast<unsigned>(ntri), 64), dim3(kBlock), 0, st, points, triangles, transform, ntri,
-                       cell_size, rows, cols, owner);
+    launch_ct_coefficients(points, triangles, neighbors, transform, east, north, grad_east, grad_north,
+                           static_cast<size_t>(npts), ntri, 2 * batch, coef, st);
+    if (int rc = launch_tri_owner(points, triangles, transform, ntri, cell_size, rows, cols, owner, st)) return rc;
     hipLaunchKernelGGL(k_wind_cubic, dim3(stream_grid(ncell)), dim3(kBlock), 0, st, owner, transform, coef, cell_size, wspeed,
                        wdirn, rows, cols, batch);
     SSRS_HIP_CHECK(hipGetLastError());

@@ -191,3 +191,52 @@ def updraft_from_dem_lattice(z_mat, res, x_km, y_km, wspeed, wdirn, threshold=No
         oro = None if oro is None else oro[0]
         use = None if use is None else use[0]
     return oro, use
+
+
+def _elementwise_f64(arrays):
+    """The arguments as contiguous f64 device tensors of their common (broadcast) shape, and whether any was a tensor."""
+    devs = [to_dev(a, torch.float64) for a in arrays]
+    shape = torch.broadcast_shapes(*[tuple(d.shape) for d in devs])
+    return [d.expand(shape).contiguous() for d in devs], any(is_tensor(a) for a in arrays)
+
+
+def _elementwise_out(out, tensor_in):
+    return out if tensor_in else out.cpu().numpy()
+
+
+def compute_potential_temperature(pressure, temperature):
+    """layers.py:40-48: potential temperature in degrees Celsius from pressure (Pa) and temperature (deg C), f64."""
+    (p, t), tensor_in = _elementwise_f64((pressure, temperature))
+    out = torch.empty_like(p)
+    if out.numel():
+        nat.check(nat.lib().ssrs_potential_temperature(nat.ptr(p), nat.ptr(t), nat.ptr(out), C.c_size_t(out.numel()),
+                                                       stream_ptr()))
+    return _elementwise_out(out, tensor_in)
+
+
+def deardoff_velocity_function(pot_temperature, blayer_height, surface_heat_flux, min_updraft_val=1e-5):
+    """layers.py:25-37 (the reference's spelling): the convective velocity scale w*, f64.  NaN in, NaN out, as
+    np.maximum / ndarray.clip."""
+    (th, zi, q), tensor_in = _elementwise_f64((pot_temperature, blayer_height, surface_heat_flux))
+    out = torch.empty_like(th)
+    if out.numel():
+        nat.check(nat.lib().ssrs_deardorff_velocity(nat.ptr(th), nat.ptr(zi), nat.ptr(q), C.c_double(min_updraft_val),
+                                                    nat.ptr(out), C.c_size_t(out.numel()), stream_ptr()))
+    return _elementwise_out(out, tensor_in)
+
+
+def compute_thermal_updraft(zmat, deardoff_vel, blayer_height, min_updraft_val=1e-5):
+    """layers.py:51-60: thermal updraft at height `zmat` (a scalar or an array like the others), f64."""
+    scalar_z = not is_tensor(zmat) and np.ndim(zmat) == 0
+    if scalar_z:
+        (w, zi), tensor_in = _elementwise_f64((deardoff_vel, blayer_height))
+        z, z0 = None, float(zmat)
+    else:
+        (z, w, zi), tensor_in = _elementwise_f64((zmat, deardoff_vel, blayer_height))
+        z0 = 0.
+    out = torch.empty_like(w)
+    if out.numel():
+        nat.check(nat.lib().ssrs_thermal_updraft(nat.ptr(z), C.c_double(z0), nat.ptr(w), nat.ptr(zi),
+                                                 C.c_double(min_updraft_val), nat.ptr(out), C.c_size_t(out.numel()),
+                                                 stream_ptr()))
+    return _elementwise_out(out, tensor_in)

@@ -55,12 +55,16 @@ class Simulator(Config):
         scattered points: x_km[npts], y_km[npts], arrays (npts,)).  Samples are
         interpolated as `wtk_interp_type` says ('nearest' | 'linear' | 'cubic', scipy
         griddata's methods as in the reference); rasters are taken as they are.
+        With thermal_model='wtk' every entry also carries 'pressure', 'temperature',
+        'blheight' and 'surfheatflux' (the keys of `wtk_layers`), all four as (rows, cols)
+        rasters, as samples (npts,) at x_km / y_km, or on the lattice (ny, nx).
         origin: projected (west, south) of cell (0, 0); the reference derives it
         from southwest_lonlat through GDAL (simulator.py:77-85)."""
         if in_config is None:
             super().__init__(**kwargs)
         else:
             super().__init__(**asdict(in_config))
+        self._check_thermal_model()
         print(f'\n---- SSRS in {self.sim_mode} mode')
         print(f'Run name: {self.run_name}')
         if self.sim_seed >= 0:                                    # simulator.py:50-52
@@ -116,8 +120,11 @@ class Simulator(Config):
             print(f'Uniform mode: Wind dirn = {self.uniform_winddirn} deg(cw)')
             self.case_ids = [self._get_uniform_id()]
             self.compute_orographic_updraft_uniform()
-        for case_id in self._cases_written_here():
-            self.compute_thermal_updrafts(case_id)
+        if self._wtk_thermals():
+            self.compute_thermal_updrafts_using_wtk()
+        else:
+            for case_id in self._cases_written_here():
+                self.compute_thermal_updrafts(case_id)
         self._barrier()
 
         fig_aspect = self.region_width_km[0] / self.region_width_km[1]
@@ -176,7 +183,65 @@ class Simulator(Config):
                 raise ValueError(f'wtk_interp_type = {self.wtk_interp_type!r}: expected one of {METHODS}')
         if self.sim_mode.lower() == 'snapshot' and len(out) != 1:
             raise ValueError('snapshot mode takes exactly one wind entry')
+        if self._wtk_thermals():
+            for item in out:
+                item['_wtk_thermal'] = self._resolve_wtk_layers(item)
         return out
+
+    THERMAL_LAYERS = ('pressure', 'temperature', 'blheight', 'surfheatflux')      # keys of wtk_layers
+
+    def _wtk_thermals(self):
+        return str(self.thermal_model).lower() == 'wtk'
+
+    def _check_thermal_model(self):
+        if str(self.thermal_model).lower() not in ('random', 'wtk'):
+            raise ValueError(f"thermal_model = {self.thermal_model!r}: expected 'random' or 'wtk'")
+        if self._wtk_thermals():
+            if str(self.sim_mode).lower() not in ('snapshot', 'seasonal'):
+                raise ValueError("thermal_model = 'wtk' needs the WTK layers of a wind case: sim_mode must be 'snapshot' or "
+                                 f"'seasonal', not {self.sim_mode!r}")
+            if int(self.thermals_realization_count) != 1:
+                raise ValueError("thermal_model = 'wtk' gives ONE thermal field per case: thermals_realization_count must "
+                                 f'be 1, not {self.thermals_realization_count!r}')
+
+    def _resolve_wtk_layers(self, item):
+        """The four thermal layers of one wind entry, host side only: ('raster', None, None, (4, rows, cols)) or
+        ('samples', x_km[npts], y_km[npts], (4, npts)) -- a lattice (ny, nx) becomes its meshgrid points, the
+        reference triangulates whatever points it gets.  ValueError names the field that does not fit."""
+        case = item['case_id']
+        arrays, forms = [], set()
+        has_xy = 'x_km' in item and 'y_km' in item
+        x = np.asarray(item['x_km'], dtype=np.float64).ravel() if has_xy else None
+        y = np.asarray(item['y_km'], dtype=np.float64).ravel() if has_xy else None
+        for name in self.THERMAL_LAYERS:
+            if item.get(name) is None:
+                raise ValueError(f"{case}: thermal_model = 'wtk' needs the layer {name!r} ({self.wtk_layers[name]}) in "
+                                 'every wind entry')
+            val = item[name]
+            arr = np.asarray(val.cpu() if isinstance(val, torch.Tensor) else val, dtype=np.float64)
+            if has_xy and arr.ndim == 1 and arr.size == x.size == y.size:
+                forms.add('scattered')
+            elif has_xy and arr.ndim == 2 and arr.shape == (y.size, x.size):
+                forms.add('lattice')
+            elif arr.shape == tuple(self.gridsize):
+                forms.add('raster')
+            else:
+                raise ValueError(
+                    f'{case}: layer {name!r} has shape {arr.shape}: expected a raster {tuple(self.gridsize)}' +
+                    (f', samples ({x.size},) at x_km / y_km or a lattice {(y.size, x.size)}' if has_xy else
+                     ' (samples need x_km and y_km)'))
+            arrays.append(arr)
+            if len(forms) > 1:
+                raise ValueError(f'{case}: layer {name!r} is given as {forms - {form0}} but {self.THERMAL_LAYERS[0]!r} as '
+                                 f'{form0}: the four thermal layers must come in one form')
+            form0 = next(iter(forms))
+        if form0 == 'raster':
+            return ('raster', None, None, np.stack(arrays))
+        if form0 == 'lattice':
+            x, y = (a.ravel() for a in np.meshgrid(x, y))
+        if x.size < 3 and str(self.wtk_interp_type).lower() != 'nearest':
+            raise ValueError(f"{case}: layer 'pressure' has {x.size} samples: 'linear' and 'cubic' need at least 3")
+        return ('samples', x, y, np.stack([a.ravel() for a in arrays]))
 
     # -------------------------------------------------------------- terrain
     def get_terrain_elevation(self):
@@ -312,8 +377,48 @@ class Simulator(Config):
             raise ValueError('wind rasters must have the terrain grid shape')
         return ws, wd
 
+    def compute_thermal_updrafts_using_wtk(self) -> None:
+        """thermal_model = 'wtk': `<case>_r0_thermals.npy` (f32) of every case this rank writes.  Cases that share
+        their sample points go through the fused call in chunks of up to 8 (the sample geometry is located once per
+        cell for the whole chunk), like the orographic updrafts of compute_orographic_updrafts_using_wtk."""
+        print('Computing thermal updrafts from the WTK layers..', end="")
+        start_time = time.time()
+        mine = set(self._cases_written_here())
+        todo = [it for it in self._wind if it['case_id'] in mine]
+        while todo:
+            form, x, y, _ = todo[0]['_wtk_thermal']
+            same = [it for it in todo if form == 'samples' and it['_wtk_thermal'][0] == form and
+                    np.array_equal(it['_wtk_thermal'][1], x) and np.array_equal(it['_wtk_thermal'][2], y)][:8] or todo[:1]
+            self._write_wtk_thermals(same)
+            todo = [it for it in todo if not any(it is s for s in same)]
+        print(f'took {_elapsed(start_time)}', flush=True)
+
+    def _write_wtk_thermals(self, items):
+        """One device call for `items` (wind entries with the same form and sample points) -> their thermal files."""
+        from .thermals import compute_wtk_thermals
+        height = float(self.wtk_thermal_height)
+        form, x, y, _ = items[0]['_wtk_thermal']
+        if form == 'raster':
+            p, t, zi, q = (to_dev(a, torch.float64) for a in items[0]['_wtk_thermal'][3])
+            wstar = layers.deardoff_velocity_function(layers.compute_potential_temperature(p, t), zi, q)
+            fields = layers.compute_thermal_updraft(height, wstar, zi).to(torch.float32)[None].cpu().numpy()
+        else:
+            stacked = np.stack([it['_wtk_thermal'][3] for it in items], 1)              # (4, B, npts)
+            fields = compute_wtk_thermals(x, y, *stacked, self.gridsize, self.resolution, height,
+                                          method=str(self.wtk_interp_type).lower(), dtype=torch.float32)
+        for item, field in zip(items, fields):
+            if np.isnan(field).any():
+                # griddata's behaviour, as for the wind (cells outside the samples' convex hull are NaN)
+                print(f"{item['case_id']}: NANs in the interpolated thermal layers (raster cells outside the convex "
+                      'hull of the samples); their updraft is 0')
+            fname = self._get_thermal_fname(item['case_id'], 0, self.mode_data_dir)
+            np.save(f'{fname}.npy', field)
+
     def compute_thermal_updrafts(self, case_id: str):
-        """simulator.py:217-228."""
+        """simulator.py:217-228; with thermal_model = 'wtk' the one field of the physical model instead."""
+        if self._wtk_thermals():
+            self._write_wtk_thermals([it for it in self._wind if it['case_id'] == case_id])
+            return
         if self.thermals_realization_count > 0:
             from .thermals import compute_thermals_batch
             print('Computing thermal updrafts...', flush=True)

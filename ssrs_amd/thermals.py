@@ -1,6 +1,8 @@
 """Thermal updraft realisations (a5) on the device, behind the reference's
 `compute_thermals(aspect, thermal_intensity_scale)` (/root/reference/ssrs/
-layers.py:188-214).  Statistical parity only: see csrc/thermals.hip."""
+layers.py:188-214).  Statistical parity only: see csrc/thermals.hip.
+`compute_wtk_thermals` is the other thermal model (Config.thermal_model = 'wtk'): the Deardorff-velocity updraft of
+ssrs/layers.py:25-60 from a snapshot's own WTK layers, deterministic; see csrc/wtk_thermals.hip."""
 import ctypes as C
 
 import torch
@@ -52,3 +54,40 @@ def compute_thermals_batch(aspect, thermal_intensity_scale, seeds, dtype=torch.f
 def compute_thermals(aspect, thermal_intensity_scale, seed=0):
     """Field of smoothed random thermals (f64), one realisation per `seed`."""
     return compute_thermals_batch(aspect, thermal_intensity_scale, [seed])[0]
+
+
+def compute_wtk_thermals(x_km, y_km, pressure, temperature, blheight, surfheatflux, gridsize, resolution, height,
+                         method='linear', dtype=torch.float32, min_updraft_val=1e-5, index=None):
+    """Thermal updraft at `height` from the four WIND Toolkit layers of a snapshot, sampled at x_km[npts], y_km[npts]
+    (relative to the raster's south-west cell centre): the reference's `_interpolate_wtk_vardata` of each layer, then
+    `compute_potential_temperature`, `deardoff_velocity_function` and `compute_thermal_updraft`
+    (ssrs/layers.py:25-60), as ONE device call in which no interpolated raster is written.
+    pressure / temperature / blheight / surfheatflux: (npts,) or (B, npts); height: a scalar or a (rows, cols) raster.
+    Returns (rows, cols) or (B, rows, cols) in `dtype`: f64, bit for bit `wind.interpolate_scalar_scattered` followed
+    by the three `layers` functions, or f32 = that result rounded once; NaN outside the samples' convex hull for
+    'linear' and 'cubic'.  method, index: as `wind.interpolate_wind_scattered`."""
+    import numpy as np
+    from .wind import check_method, _host_f64, _scalar_geometry
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError('compute_wtk_thermals: dtype must be torch.float32 or torch.float64')
+    method = check_method(method)
+    given = (pressure, temperature, blheight, surfheatflux)
+    fields = [_host_f64(a) for a in given]
+    single = fields[0].ndim == 1
+    fields = [a[None] if a.ndim == 1 else a for a in fields]
+    if any(a.ndim != 2 or a.shape != fields[0].shape for a in fields):
+        raise ValueError('compute_wtk_thermals: the four layers must share one shape, (npts,) or (B, npts)')
+    batch, npts = fields[0].shape
+    rows, cols = int(gridsize[0]), int(gridsize[1])
+    raster_z = isinstance(height, torch.Tensor) or np.ndim(height) != 0
+    if raster_z and tuple(np.shape(height)) != (rows, cols):
+        raise ValueError(f'compute_wtk_thermals: height must be a scalar or a raster of shape {(rows, cols)}')
+    head, tail, keep = _scalar_geometry(x_km, y_km, np.stack(fields).reshape(4 * batch, npts), gridsize, resolution, method,
+                                        index, 'compute_wtk_thermals')
+    zmat = to_dev(height, torch.float64) if raster_z else None
+    z0 = 0. if raster_z else float(height)
+    out = torch.empty((batch, rows, cols), dtype=dtype, device=keep['values'].device)
+    nat.check(nat.lib().ssrs_wtk_thermal_fields(*head, nat.ptr(zmat), C.c_double(z0), C.c_double(min_updraft_val),
+                                                nat.ptr(out), int(dtype == torch.float32), rows, cols, int(batch), *tail))
+    out = out[0] if single else out
+    return out if any(isinstance(a, torch.Tensor) for a in given) else out.cpu().numpy()

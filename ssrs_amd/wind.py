@@ -181,3 +181,74 @@ def _scattered_cubic(x_km, y_km, wspeed, wdirn, gridsize, resolution):
         nat.ptr(d_gn), int(npts), ntri, C.c_double(resolution / 1000.), nat.ptr(out_s), nat.ptr(out_d), rows, cols, int(batch),
         nat.ptr(scratch), C.c_size_t(nbytes), stream_ptr()))
     return (out_s[0], out_d[0]) if single else (out_s, out_d)
+
+
+def _scalar_geometry(x_km, y_km, values, gridsize, resolution, method, index, what):
+    """Host side of a scalar interpolation: what scipy builds from the points (the triangulation, for 'cubic' the
+    vertex gradients of every field) or the nearest-index raster, as device tensors.  values: numpy (F, npts) f64.
+    Returns the leading arguments of ssrs_scalar_from_samples / ssrs_wtk_thermal_fields up to cell_size, the tensors
+    that back them, and the workspace."""
+    x = np.asarray(x_km, dtype=np.float64).ravel()
+    y = np.asarray(y_km, dtype=np.float64).ravel()
+    least = 1 if method == 'nearest' else 3
+    if x.size != y.size or x.size < least:
+        raise ValueError(f'{what}: samples need x_km, y_km of equal length >= {least}')
+    if values.ndim != 2 or values.shape[1] != x.size:
+        raise ValueError(f'{what}: sample arrays must be (npts,) or (F, npts) with npts = {x.size}')
+    rows, cols = int(gridsize[0]), int(gridsize[1])
+    npts, nfield = int(x.size), int(values.shape[0])
+    pts = np.ascontiguousarray(np.stack([x, y], 1))
+    keep = {'values': to_dev(np.ascontiguousarray(values), torch.float64)}
+    dev = keep['values'].device
+    ntri = 0
+    if method == 'nearest':
+        if index is None:
+            index = nearest_sample_index(x, y, gridsize, resolution)
+        if not (isinstance(index, torch.Tensor) and index.is_cuda and index.dtype == torch.int32 and
+                tuple(index.shape) == (rows, cols)):
+            raise ValueError(f'index must be an int32 CUDA tensor of shape {(rows, cols)} (nearest_sample_index)')
+        keep['index'] = index.contiguous()
+    else:
+        from scipy.spatial import Delaunay
+        tri = Delaunay(pts)                                    # what griddata builds for 'linear' and 'cubic'
+        keep['pts'] = torch.from_numpy(pts).to(dev)
+        keep['tri'] = torch.from_numpy(np.ascontiguousarray(tri.simplices.astype(np.int32))).to(dev)
+        keep['tr'] = torch.from_numpy(np.ascontiguousarray(tri.transform.astype(np.float64))).to(dev)
+        ntri = int(keep['tri'].shape[0])
+        if method == 'cubic':
+            from scipy.interpolate import CloughTocher2DInterpolator
+            # scipy's gradient estimator with griddata's parameters, every field in one call (column by column the
+            # same bits as the single-field calls griddata makes)
+            grad = CloughTocher2DInterpolator(tri, np.ascontiguousarray(values.T), tol=1e-6, maxiter=400).grad
+            keep['grad'] = torch.from_numpy(np.ascontiguousarray(np.transpose(grad, (1, 0, 2)))).to(dev)   # (F, npts, 2)
+            keep['nbr'] = torch.from_numpy(np.ascontiguousarray(tri.neighbors.astype(np.int32))).to(dev)
+    code = nat.SSRS_INTERP[method]
+    nbytes = int(nat.lib().ssrs_scalar_interp_workspace_bytes(code, ntri, rows, cols, nfield))
+    keep['scratch'] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    head = [code, nat.ptr(keep.get('pts')), nat.ptr(keep.get('tri')), nat.ptr(keep.get('nbr')), nat.ptr(keep.get('tr')),
+            nat.ptr(keep.get('index')), nat.ptr(keep['values']), nat.ptr(keep.get('grad')), npts, ntri,
+            C.c_double(resolution / 1000.)]
+    tail = [nat.ptr(keep['scratch']), C.c_size_t(nbytes), stream_ptr()]
+    return head, tail, keep
+
+
+def _host_f64(a):
+    return np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+
+
+def interpolate_scalar_scattered(x_km, y_km, values, gridsize, resolution, method='linear', index=None):
+    """The reference's `_interpolate_wtk_vardata` (ssrs/simulator.py:765-776): scipy griddata of
+    scalar samples at SCATTERED points x_km[npts], y_km[npts] (relative to the raster's south-west cell centre) onto
+    the raster's cell centres.  values: (npts,) or (F, npts) for F fields on the same points.  Returns an f64 CUDA
+    tensor (rows, cols) or (F, rows, cols); NaN outside the convex hull for 'linear' and 'cubic', as griddata.
+    method, index: as `interpolate_wind_scattered`.  The cells are evaluated by the expressions of the wind kernels."""
+    method = check_method(method)
+    vals = _host_f64(values)
+    single = vals.ndim == 1
+    if single:
+        vals = vals[None]
+    head, tail, keep = _scalar_geometry(x_km, y_km, vals, gridsize, resolution, method, index, 'interpolate_scalar_scattered')
+    rows, cols = int(gridsize[0]), int(gridsize[1])
+    out = torch.empty((vals.shape[0], rows, cols), dtype=torch.float64, device=keep['values'].device)
+    nat.check(nat.lib().ssrs_scalar_from_samples(*head, nat.ptr(out), rows, cols, int(vals.shape[0]), *tail))
+    return out[0] if single else out
