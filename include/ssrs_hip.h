@@ -520,6 +520,47 @@ int ssrs_presence_normalise_add(const void *src, int src_type, double *acc, size
 int ssrs_presence_normalise_f32(const double *src, float *out, size_t n,
                                 void *scratch8, void *stream);
 
+/* --------------------------------------------------------------- turbines */
+
+/* Which tracks came within `radius_cells` of which turbine (what the reference's get_turbine_presence,
+ * ssrs/simulator.py:594-607, was after), from the trajectories on the device.
+ * Geometry: a turbine is (xt, yt) f64 in CELL units relative to the centre of cell (0, 0), x along columns, y along
+ * rows; a trajectory point (r, c) encounters it iff dx * dx + dy * dy <= radius_cells * radius_cells with
+ * dx = (double)c - xt, dy = (double)r - yt, each product and the sum rounded on their own, `<=`: a point exactly on
+ * the circle counts.  NumPy's (c - xt)**2 + (r - yt)**2 <= R * R gives the same answer bit for bit.
+ *   traj, traj_offsets  as ssrs_tracks_simulate / ssrs_tracks_gather leave them: int16 (row, col) pairs, track t at
+ *                       [traj_offsets[t], traj_offsets[t + 1]) (int64, ntracks + 1; the first need not be 0); equal
+ *                       consecutive offsets are an empty track, which has no encounters.  A point outside the raster
+ *                       encounters nothing.  traj is 4-byte aligned (16-byte aligned buffers are read 16 bytes a lane)
+ *   turbines            (nturb, 2) f64 [xt, yt], 1 <= nturb <= SSRS_TURBINE_MAX
+ *   bin_start, bin_items  the CALLER's cull, as the Delaunay triangulation is for the wind calls: a CSR over bins of
+ *                       SSRS_TURBINE_BIN x SSRS_TURBINE_BIN cells, bin (r / 32) * nbc + c / 32 with nbr =
+ *                       ceil(rows / 32), nbc = ceil(cols / 32); bin_start int32 (nbr * nbc + 1), bin_items int32
+ *                       (bin_start[nbr * nbc]) the turbines whose disk can reach the bin.  The lists only cull: the
+ *                       test above decides every hit, and a list that OMITS a turbine loses its hits in that bin.
+ *                       Items outside [0, nturb) are skipped
+ *   hits                uint32 (ntracks, words), words = ceil(nturb / 32): bit t % 32 of word t / 32 of row k is set
+ *                       iff track k encountered turbine t.  ACCUMULATED by OR (zero it for a fresh count)
+ *   first_step          int32 (ntracks) or NULL: the index within the track of its first point inside any turbine's
+ *                       disk, combined by UNSIGNED minimum with what is there: the caller's initial -1 (0xFFFFFFFF)
+ *                       means "none"
+ * One streaming pass, asynchronous on `stream`; OR and min of integers: the same result from run to run.  The
+ * occupied-bin mask lives in LDS for rasters of up to 262 144 bins (16 384 x 16 384 cells); beyond, bin_start is read
+ * per point.  NULL pointers (first_step excepted), ntracks outside [0, 2^31), nturb outside [1, SSRS_TURBINE_MAX],
+ * rows / cols outside [1, 32767], a negative or NaN radius -> SSRS_ERR_INVALID before any GPU work. */
+#define SSRS_TURBINE_BIN 32
+#define SSRS_TURBINE_MAX 8192
+int ssrs_turbine_encounters(const int16_t *traj, const int64_t *traj_offsets, int64_t ntracks,
+                            const double *turbines, int nturb, double radius_cells,
+                            const int32_t *bin_start, const int32_t *bin_items, int rows, int cols,
+                            uint32_t *hits, int32_t *first_step, void *stream);
+
+/* Popcounts of that bitmap: tracks_per_turbine int64 (nturb) = the tracks whose bit t is set, turbines_per_track
+ * int32 (ntracks) = the bits of row k (may be NULL).  Both are OVERWRITTEN; bits at and above nturb are ignored.
+ * Asynchronous on `stream`. */
+int ssrs_turbine_encounter_counts(const uint32_t *hits, int64_t ntracks, int nturb,
+                                  int64_t *tracks_per_turbine, int32_t *turbines_per_track, void *stream);
+
 /* -------------------------------------------------------------- potential */
 
 typedef struct SsrsSolveStats {

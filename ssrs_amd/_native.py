@@ -21,6 +21,7 @@ SSRS_TRACKS_SCATTERED = 32
 SSRS_TRACKS_NO_SCATTERED = 64
 SSRS_TRACKS_THR_TABLE = 128
 SSRS_SOLVE_NO_AMG = 1
+SSRS_TURBINE_BIN, SSRS_TURBINE_MAX = 32, 8192
 SSRS_INTERP = {'nearest': 0, 'linear': 1, 'cubic': 2}          # SSRS_INTERP_NEAREST / _LINEAR / _CUBIC
 
 EXPORTS = (
@@ -42,6 +43,7 @@ EXPORTS = (
     'ssrs_presence_smooth_u64',
     'ssrs_presence_normalise_add', 'ssrs_presence_normalise_f32',
     'ssrs_potential_workspace_bytes', 'ssrs_potential_solve',
+    'ssrs_turbine_encounters', 'ssrs_turbine_encounter_counts',
 )
 
 
@@ -144,6 +146,11 @@ def lib():
         if hasattr(L, 'ssrs_potential_workspace_bytes'):
             L.ssrs_potential_workspace_bytes.restype = C.c_size_t
             L.ssrs_potential_workspace_bytes.argtypes = [C.c_int, C.c_int]
+        if hasattr(L, 'ssrs_turbine_encounters'):
+            L.ssrs_turbine_encounters.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_double,
+                                                  C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]
+            L.ssrs_turbine_encounter_counts.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 

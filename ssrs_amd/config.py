@@ -30,7 +30,7 @@ _SECTIONS = (
     ('Plotting and wind turbines', ('turbine_minimum_hubheight', 'turbine_mrkr_size',
                                     'fig_height', 'fig_dpi')),
     ('MI355X build', ('save_tracks', 'stepper_path', 'steps_per_launch', 'max_tracks_file_gb', 'hist_safe_tracks',
-                      'thermal_model')),
+                      'thermal_model', 'turbine_encounter_radius')),
 )
 
 
@@ -97,6 +97,11 @@ class Config:
     steps_per_launch: int = 0           # 0 = library default
     max_tracks_file_gb: float = 64.     # refuse a <id>_tracks.pkl larger than this (tracks that wander to
     #                                     max_moves: 1 TB per 100k tracks on a solved 10 m field)
+    turbine_encounter_radius: float = 0.  # metres; 0 = off.  > 0 (needs Simulator(turbines=...)): simulate_tracks also finds, per
+    #                                     turbine, the tracks that came within this distance of it and after how many moves, from
+    #                                     the trajectories on the device (produced even with save_tracks=False):
+    #                                     <id>_turbine_encounters.npy, Simulator.compute_turbine_encounters().  Listed last in
+    #                                     _SECTIONS; as a field it stands here because tests pin the last two
     hist_safe_tracks: int = 250_000     # tracks per sub-batch of a case: (i) histograms of several sub-batches are added up in 64
     #                                     bits; a sub-batch of more than 100 000 tracks is counted in 64 bits inside the library (a trap
     #                                     cell of the solved 10 m field takes 1.7e4 visits per track: 2^32 from ~245 000 tracks on;

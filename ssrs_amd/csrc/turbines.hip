@@ -1,0 +1,405 @@
+// K8 -- turbine encounters for gfx950 (MI355X).
+//
+// Which simulated tracks came within R of which turbine, and after how many moves: the per-turbine number the
+// reference's half-written get_turbine_presence (ssrs/simulator.py:594-607) was after, from the trajectories
+// the stepper leaves on the device.  One streaming pass over the int16 (row, col) points, 4 B each:
+//   - a wave owns a contiguous run of 256-point spans; a lane takes four consecutive points (one 16-byte load
+//     when the buffer is 16-byte aligned), and the next span's load is issued before this one is worked on;
+//   - the common point has no turbine near it: one lookup in a bit-per-bin mask in LDS (bins of 32 x 32 cells,
+//     3.7 KB at 5000 x 6000) and nothing else.  Only points of occupied bins walk the bin's turbine list;
+//   - a wave finds the track of its first point by ONE binary search, then advances along traj_offsets: a span
+//     inside one track is one scalar load; a span that crosses track ends marks the starts of the tracks that
+//     begin in it in LDS and takes a running maximum (any number of tracks per span, empty ones included);
+//   - hits are ORed and first steps min-ed, both order-independent integers.  A track that sits in a disk for
+//     millions of moves costs neither: every lane remembers the last bitmap word / first step it knows to be
+//     settled, an unknown one is tested with a load (bits are only ever set and steps only ever fall, so a stale
+//     read costs a redundant atomic, never a wrong result), and the lanes of a wave that still have news for
+//     the same word combine it before ONE atomic.
+#include <climits>
+
+#include "common.h"
+
+namespace ssrs {
+
+constexpr int kTurbWaves = kBlock / 64;
+constexpr int kTurbSpan = 256;                // points per wave and iteration: 64 lanes x 4
+constexpr long long kTurbMinSpans = 4;        // spans per wave at least: small inputs advance the track cursor too
+// Six blocks per CU.  With the mask of a 5000 x 6000 raster (8 KB of LDS a block, 70 VGPRs: 7 waves per SIMD) all of them
+// are resident at once; a mask near the 32 KB limit leaves room for four per CU and the rest run as a second round.
+// Nothing but speed depends on it: the blocks do not talk to each other.
+constexpr int kTurbBlocks = 256 * 6;
+constexpr int kTurbMaskWords = 8192;          // 32 KB of LDS: rasters of up to 262 144 bins keep the mask there
+
+__device__ __forceinline__ int wave_or(int v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v |= __shfl_xor(v, off);
+    return v;
+}
+
+__device__ __forceinline__ unsigned wave_min(unsigned v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned o = static_cast<unsigned>(__shfl_xor(static_cast<int>(v), off));
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
+// a load that is served by L2, where the atomics land (the vector L1 would keep handing out the stale line)
+__device__ __forceinline__ uint32_t load_l2(const uint32_t *p)
+{
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+struct TurbArgs {
+    const uint32_t *traj;          // one int16 (row, col) pair per dword
+    const long long *off;
+    long long ntracks;
+    const double *turb;
+    int nturb;
+    double r2;
+    const int *bin_start, *bin_items;
+    int rows, cols, nbc, nbins, words;
+    uint32_t *hits, *first_step;
+};
+
+// kVec: 16-byte loads (traj is 16-byte aligned).  kMask: the occupied-bin mask fits LDS.
+template <bool kVec, bool kMask>
+__global__ __launch_bounds__(kBlock) void k_turbine_encounters(const TurbArgs a)
+{
+    extern __shared__ uint32_t s_mask[];
+    __shared__ alignas(16) int s_mark[kTurbWaves][kTurbSpan];       // (read and zeroed 16 bytes a lane)
+
+    const long long p0 = a.off[0], p1 = a.off[a.ntracks];
+    if (p0 < 0 || p1 <= p0) return;
+    // spans are cut at multiples of four points of the BUFFER, so that a lane's four points are one aligned load
+    const long long a0 = p0 & ~3LL;
+    const long long nspans = (p1 - a0 + kTurbSpan - 1) / kTurbSpan;
+    const long long nwaves = static_cast<long long>(gridDim.x) * kTurbWaves;
+    long long per_wave = (nspans + nwaves - 1) / nwaves;
+    per_wave = per_wave < kTurbMinSpans ? kTurbMinSpans : per_wave;
+    if (static_cast<long long>(blockIdx.x) * kTurbWaves * per_wave >= nspans) return;      // (the whole block)
+
+    if (kMask) {
+        for (int w = threadIdx.x; w < (a.nbins + 31) / 32; w += kBlock) {
+            uint32_t bits = 0;
+            const int b0 = w * 32, b1 = b0 + 32 < a.nbins ? b0 + 32 : a.nbins;
+            int lo = a.bin_start[b0];
+            for (int b = b0; b < b1; ++b) {
+                const int hi = a.bin_start[b + 1];
+                bits |= hi > lo ? 1u << (b - b0) : 0u;
+                lo = hi;
+            }
+            s_mask[w] = bits;
+        }
+        __syncthreads();
+    }
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
+    int *mark = s_mark[wave];
+    const long long u0 = (static_cast<long long>(blockIdx.x) * kTurbWaves + wave) * per_wave;
+    const long long u1 = u0 + per_wave < nspans ? u0 + per_wave : nspans;
+    if (u0 >= u1) return;                        // (no barrier below this line)
+
+    // the last track that starts at or before the wave's first point: the one that holds it
+    long long t;
+    {
+        const long long first = a0 + u0 * kTurbSpan;
+        const long long key = first > p0 ? first : p0;
+        long long lo = 0, hi = a.ntracks;
+        while (hi - lo > 1) {
+            const long long mid = lo + (hi - lo) / 2;
+            if (a.off[mid] <= key) lo = mid; else hi = mid;
+        }
+        t = lo;
+    }
+
+    // A lane's four points of span u.  fetch: one 16-byte load without a branch around it, for spans that end at or
+    // before p1 (points in front of p0 belong to the buffer: a0 >= 0; they are masked later).  fetch_edge: point by point.
+    auto fetch = [&](long long u) {
+        return *reinterpret_cast<const uint4 *>(a.traj + (a0 + u * kTurbSpan + 4 * lane));
+    };
+    auto fetch_edge = [&](long long u) {
+        const long long i0 = a0 + u * kTurbSpan + 4 * lane;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (i0 + 0 >= p0 && i0 + 0 < p1) v.x = a.traj[i0 + 0];
+        if (i0 + 1 >= p0 && i0 + 1 < p1) v.y = a.traj[i0 + 1];
+        if (i0 + 2 >= p0 && i0 + 2 < p1) v.z = a.traj[i0 + 2];
+        if (i0 + 3 >= p0 && i0 + 3 < p1) v.w = a.traj[i0 + 3];
+        return v;
+    };
+
+    // what this lane knows to be settled: the bits of one bitmap word, the first step of one track
+    long long known_word = -1, known_track = -1, known_start = 0;
+    uint32_t known_bits = 0, known_step = 0xFFFFFFFFu;
+
+    // one span: `cur` its points, `t_end` = off[t + 1]
+    auto span = [&](const long long u, const uint4 cur, const long long t_end) {
+        const long long s = a0 + u * kTurbSpan, s_end = s + kTurbSpan;
+        const long long i0 = s + 4 * lane;
+        const uint32_t pts[4] = {cur.x, cur.y, cur.z, cur.w};
+
+        // ---- the track of every point: off[t] <= max(s, p0), and every later track starts at or after s
+        int rel[4] = {0, 0, 0, 0};
+        int span_rel = 0;
+        if (t_end < s_end) {
+            *reinterpret_cast<int4 *>(mark + 4 * lane) = make_int4(0, 0, 0, 0);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            // a track that is not empty and starts inside the span marks its first point (starts are distinct)
+            for (long long tb = t + 1;; tb += 64) {
+                const long long tt = tb + lane;
+                long long o = LLONG_MAX;
+                if (tt < a.ntracks) {
+                    o = a.off[tt];
+                    if (o >= s && o < s_end && a.off[tt + 1] > o) mark[o - s] = static_cast<int>(tt - t);
+                }
+                const long long last = __shfl(o, 63);
+                if (last >= s_end) break;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            const int4 m = *reinterpret_cast<const int4 *>(mark + 4 * lane);
+            rel[0] = m.x;
+            rel[1] = m.y > rel[0] ? m.y : rel[0];
+            rel[2] = m.z > rel[1] ? m.z : rel[1];
+            rel[3] = m.w > rel[2] ? m.w : rel[2];
+            int incl = rel[3];                    // inclusive running maximum over the lanes
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int o = __shfl_up(incl, d);
+                if (lane >= d) incl = o > incl ? o : incl;
+            }
+            int excl = __shfl_up(incl, 1);
+            excl = lane == 0 ? 0 : excl;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) rel[j] = rel[j] > excl ? rel[j] : excl;
+            span_rel = __shfl(incl, 63);
+            __builtin_amdgcn_wave_barrier();      // (the next span's zeroing comes after every lane's read)
+        }
+
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long long i = i0 + j;
+            const int r = static_cast<int16_t>(pts[j] & 0xFFFF), c = static_cast<int16_t>(pts[j] >> 16);
+            const bool inside_raster = i >= p0 && i < p1 && r >= 0 && c >= 0 && r < a.rows && c < a.cols;
+            const int bin = inside_raster ? (r >> 5) * a.nbc + (c >> 5) : 0;
+            // (no global load on this side of the branch: what waits for one would wait for the span in flight too)
+            bool occupied = inside_raster;
+            if (kMask) occupied = occupied && (s_mask[bin >> 5] >> (bin & 31) & 1u);
+            if (__ballot(occupied) == 0) continue;
+            int k0 = 0, k1 = 0;
+            if (occupied) {
+                k0 = a.bin_start[bin];
+                k1 = a.bin_start[bin + 1];
+            }
+            const long long track = t + rel[j];
+            bool in_any = false;
+            while (__ballot(k0 < k1) != 0) {
+                bool hit = false;
+                int tb = 0;
+                if (k0 < k1) {
+                    tb = a.bin_items[k0++];
+                    if (static_cast<unsigned>(tb) < static_cast<unsigned>(a.nturb)) {
+                        const double dx = static_cast<double>(c) - a.turb[2 * tb];
+                        const double dy = static_cast<double>(r) - a.turb[2 * tb + 1];
+                        hit = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)) <= a.r2;
+                    }
+                }
+                in_any |= hit;
+                // ---- hits: bit tb of the track's row
+                const long long word = track * a.words + (tb >> 5);
+                const uint32_t bit = 1u << (tb & 31);
+                bool news = hit && !(word == known_word && (known_bits & bit));
+                if (__ballot(news) == 0) continue;
+                if (news) {
+                    const uint32_t seen = load_l2(a.hits + word);
+                    known_word = word;
+                    known_bits = seen;
+                    news = !(seen & bit);
+                }
+                unsigned long long todo;
+                while ((todo = __ballot(news)) != 0) {
+                    const int leader = __ffsll(static_cast<long long>(todo)) - 1;
+                    const bool mine = news && word == __shfl(word, leader);
+                    const uint32_t bits = static_cast<uint32_t>(wave_or(mine ? static_cast<int>(bit) : 0));
+                    if (lane == leader) atomicOr(a.hits + word, bits);
+                    if (mine) {
+                        known_bits |= bits;
+                        news = false;
+                    }
+                }
+            }
+            // ---- first_step: the earliest point of the track inside any disk
+            if (a.first_step == nullptr || __ballot(in_any) == 0) continue;
+            uint32_t step = 0;
+            bool news = false;
+            if (in_any) {
+                if (track != known_track) {
+                    known_track = track;
+                    known_start = a.off[track];
+                    known_step = 0xFFFFFFFFu;
+                }
+                step = static_cast<uint32_t>(i - known_start);
+                news = step < known_step;
+            }
+            if (__ballot(news) == 0) continue;
+            if (news) {
+                const uint32_t seen = load_l2(a.first_step + track);
+                known_step = seen;
+                news = step < seen;
+            }
+            unsigned long long todo;
+            while ((todo = __ballot(news)) != 0) {
+                const int leader = __ffsll(static_cast<long long>(todo)) - 1;
+                const bool mine = news && track == __shfl(track, leader);
+                const uint32_t first = wave_min(mine ? step : 0xFFFFFFFFu);
+                if (lane == leader) atomicMin(a.first_step + track, first);
+                if (mine) {
+                    known_step = first;
+                    news = false;
+                }
+            }
+        }
+        t += span_rel;
+    };
+
+    // Spans that end at or before p1 stream through 16-byte loads, one span ahead and nothing but straight-line code
+    // between a load and its use; off[t + 1] is asked for BEFORE the next span (loads return in order: waiting for it
+    // leaves the span in flight).  The last span of the data, and every span of an unaligned buffer, go point by point.
+    long long u = u0;
+    if (kVec) {
+        const long long whole = (p1 - a0) / kTurbSpan;
+        const long long u_vec = u1 < whole ? u1 : whole;
+        if (u < u_vec) {
+            uint4 next = fetch(u);
+            for (; u < u_vec; ++u) {
+                const uint4 cur = next;
+                const long long t_end = a.off[t + 1];
+                next = fetch(u + 1 < u_vec ? u + 1 : u);
+                span(u, cur, t_end);
+            }
+        }
+    }
+    for (; u < u1; ++u) span(u, fetch_edge(u), a.off[t + 1]);
+}
+
+// turbines_per_track[k] = popcount of row k (bits at and above nturb are not counted)
+__global__ __launch_bounds__(kBlock) void k_turbines_per_track(const uint32_t *__restrict__ hits, long long ntracks,
+                                                              int nturb, int words, int32_t *__restrict__ out)
+{
+    const uint32_t tail = nturb & 31 ? (1u << (nturb & 31)) - 1u : 0xFFFFFFFFu;
+    for (long long k = blockIdx.x * static_cast<long long>(kBlock) + threadIdx.x; k < ntracks;
+         k += static_cast<long long>(gridDim.x) * kBlock) {
+        int n = 0;
+        for (int w = 0; w < words; ++w) n += __popc(hits[k * words + w] & (w == words - 1 ? tail : 0xFFFFFFFFu));
+        out[k] = n;
+    }
+}
+
+// tracks_per_turbine[t] += the set bits of column t: counted per block in LDS, then one 64-bit add per turbine
+__global__ __launch_bounds__(kBlock) void k_tracks_per_turbine(const uint32_t *__restrict__ hits, long long ntracks,
+                                                              int nturb, int words,
+                                                              unsigned long long *__restrict__ out)
+{
+    extern __shared__ uint32_t s_count[];
+    for (int t = threadIdx.x; t < words * 32; t += kBlock) s_count[t] = 0;
+    __syncthreads();
+    const long long n = ntracks * words;
+    for (long long i = blockIdx.x * static_cast<long long>(kBlock) + threadIdx.x; i < n;
+         i += static_cast<long long>(gridDim.x) * kBlock) {
+        uint32_t bits = hits[i];
+        const int w = static_cast<int>(i % words);
+        while (bits) {
+            const int b = __ffs(static_cast<int>(bits)) - 1;
+            bits &= bits - 1;
+            atomicAdd(&s_count[w * 32 + b], 1u);
+        }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < nturb; t += kBlock)
+        if (s_count[t]) atomicAdd(&out[t], static_cast<unsigned long long>(s_count[t]));
+}
+
+}  // namespace ssrs
+
+using namespace ssrs;
+
+extern "C" int ssrs_turbine_encounters(const int16_t *traj, const int64_t *traj_offsets, int64_t ntracks,
+                                       const double *turbines, int nturb, double radius_cells,
+                                       const int32_t *bin_start, const int32_t *bin_items, int rows, int cols,
+                                       uint32_t *hits, int32_t *first_step, void *stream)
+{
+    SSRS_REQUIRE(traj && traj_offsets && turbines && bin_start && bin_items && hits,
+                 "ssrs_turbine_encounters: NULL pointer");
+    // (beyond the issue's `ntracks < 0`: the kernel keeps track numbers relative to a wave's cursor as int, in LDS and in
+    // registers, and a bitmap of 2^31 rows would be 8 GB a word column)
+    SSRS_REQUIRE(ntracks >= 0 && ntracks <= INT32_MAX, "ssrs_turbine_encounters: ntracks = %lld outside [0, 2^31)",
+                 static_cast<long long>(ntracks));
+    SSRS_REQUIRE(nturb >= 1 && nturb <= SSRS_TURBINE_MAX, "ssrs_turbine_encounters: nturb = %d outside [1, %d]", nturb,
+                 SSRS_TURBINE_MAX);
+    SSRS_REQUIRE(rows >= 1 && rows <= 32767 && cols >= 1 && cols <= 32767,
+                 "ssrs_turbine_encounters: a %d x %d raster (int16 points: 1..32767 either way)", rows, cols);
+    SSRS_REQUIRE(radius_cells >= 0.0, "ssrs_turbine_encounters: radius_cells is negative or NaN");
+    SSRS_REQUIRE((reinterpret_cast<uintptr_t>(traj) & 3u) == 0, "ssrs_turbine_encounters: traj must be 4-byte aligned");
+    if (ntracks == 0) return SSRS_OK;
+    TurbArgs a;
+    a.traj = reinterpret_cast<const uint32_t *>(traj);
+    a.off = reinterpret_cast<const long long *>(traj_offsets);
+    a.ntracks = ntracks;
+    a.turb = turbines;
+    a.nturb = nturb;
+    a.r2 = radius_cells * radius_cells;
+    a.bin_start = bin_start;
+    a.bin_items = bin_items;
+    a.rows = rows;
+    a.cols = cols;
+    a.nbc = (cols + SSRS_TURBINE_BIN - 1) / SSRS_TURBINE_BIN;
+    a.nbins = (rows + SSRS_TURBINE_BIN - 1) / SSRS_TURBINE_BIN * a.nbc;
+    a.words = (nturb + 31) / 32;
+    a.hits = hits;
+    a.first_step = reinterpret_cast<uint32_t *>(first_step);
+    const bool vec = (reinterpret_cast<uintptr_t>(traj) & 15u) == 0;
+    const int mask_words = (a.nbins + 31) / 32;
+    const bool mask = mask_words <= kTurbMaskWords;
+    const size_t lds = mask ? static_cast<size_t>(mask_words) * 4 : 0;
+    hipStream_t st = as_stream(stream);
+    const dim3 grid(kTurbBlocks), block(kBlock);
+    if (vec && mask) hipLaunchKernelGGL((k_turbine_encounters<true, true>), grid, block, lds, st, a);
+    else if (vec) hipLaunchKernelGGL((k_turbine_encounters<true, false>), grid, block, lds, st, a);
+    else if (mask) hipLaunchKernelGGL((k_turbine_encounters<false, true>), grid, block, lds, st, a);
+    else hipLaunchKernelGGL((k_turbine_encounters<false, false>), grid, block, lds, st, a);
+    SSRS_HIP_CHECK(hipGetLastError());
+    return SSRS_OK;
+}
+
+extern "C" int ssrs_turbine_encounter_counts(const uint32_t *hits, int64_t ntracks, int nturb,
+                                             int64_t *tracks_per_turbine, int32_t *turbines_per_track, void *stream)
+{
+    SSRS_REQUIRE(hits && tracks_per_turbine, "ssrs_turbine_encounter_counts: NULL pointer");
+    // (the same limit as ssrs_turbine_encounters, whose bitmap this is)
+    SSRS_REQUIRE(ntracks >= 0 && ntracks <= INT32_MAX, "ssrs_turbine_encounter_counts: ntracks = %lld outside [0, 2^31)",
+                 static_cast<long long>(ntracks));
+    SSRS_REQUIRE(nturb >= 1 && nturb <= SSRS_TURBINE_MAX, "ssrs_turbine_encounter_counts: nturb = %d outside [1, %d]",
+                 nturb, SSRS_TURBINE_MAX);
+    hipStream_t st = as_stream(stream);
+    const int words = (nturb + 31) / 32;
+    SSRS_HIP_CHECK(hipMemsetAsync(tracks_per_turbine, 0, static_cast<size_t>(nturb) * 8, st));
+    if (ntracks == 0) return SSRS_OK;
+    size_t blocks = (static_cast<size_t>(ntracks) * words + kBlock - 1) / kBlock;
+    blocks = blocks > 1024 ? 1024 : blocks;
+    hipLaunchKernelGGL(k_tracks_per_turbine, dim3(static_cast<unsigned>(blocks)), dim3(kBlock),
+                       static_cast<size_t>(words) * 32 * 4, st, hits, static_cast<long long>(ntracks), nturb, words,
+                       reinterpret_cast<unsigned long long *>(tracks_per_turbine));
+    if (turbines_per_track) {
+        size_t b2 = (static_cast<size_t>(ntracks) + kBlock - 1) / kBlock;
+        b2 = b2 > static_cast<size_t>(kMaxStreamBlocks) ? kMaxStreamBlocks : b2;
+        hipLaunchKernelGGL(k_turbines_per_track, dim3(static_cast<unsigned>(b2)), dim3(kBlock), 0, st, hits,
+                           static_cast<long long>(ntracks), nturb, words, turbines_per_track);
+    }
+    SSRS_HIP_CHECK(hipGetLastError());
+    return SSRS_OK;
+}

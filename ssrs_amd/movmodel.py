@@ -213,24 +213,20 @@ class TrackBatch:
         self.traj = traj              # int16 (sum lengths, 2) or None
         self.offsets = offsets        # int64 (n + 1) or None
         self.stats = stats            # dict(total_steps, launches, kernel_ms, wall_ms)
-        self._replay = replay         # chunked trajectories: callable(t0, t1) -> int16 (points, 2) host array
+        self._replay = replay         # chunked trajectories: callable(t0, t1) -> device (int16 (points, 2), int64 offsets)
 
     @property
     def total_points(self):
         """Sum of the trajectory lengths (4 bytes each as int16 pairs)."""
         return int(self.lengths.sum(dtype=torch.int64).item())
 
-    def iter_tracks(self):
-        """The tracks one by one, int16 (n_i, 2) each, in track order.  When the trajectories did not fit
-        the device budget (Sum lengths x 4 B: 1 TB for 100k tracks on the solved 10 m field, where a
-        third of them take max_moves = 7.5e6) they are produced range by range: the lengths of the
-        finished pass give the ranges, and each range is stepped again with the generic kernel writing
-        every point at its offset (the same counter-based streams: the same tracks)."""
+    def iter_device_chunks(self):
+        """(t0, t1, traj, offsets) with the trajectories of tracks [t0, t1) ON THE DEVICE: traj int16 (points, 2) and
+        offsets int64 (t1 - t0 + 1) from 0, in track order.  One chunk when the batch holds its trajectory tensor;
+        otherwise one per replay range (see iter_tracks), each handed over before anything is copied to the host --
+        a consumer on the device (turbines.turbine_encounters) and the pickle are served by ONE replay."""
         if self.traj is not None:
-            traj = self.traj.cpu().numpy()
-            off = self.offsets.cpu().numpy()
-            for i in range(off.size - 1):
-                yield traj[off[i]:off[i + 1]]
+            yield 0, int(self.lengths.numel()), self.traj, self.offsets
             return
         if self._replay is None:
             raise ValueError('simulate_tracks was called with want_tracks=False')
@@ -242,11 +238,26 @@ class TrackBatch:
             while t1 < n and (t1 == t0 or pts + lengths[t1] <= budget_points):
                 pts += lengths[t1]
                 t1 += 1
-            traj = self._replay(t0, t1)
-            off = np.concatenate(([0], np.cumsum(lengths[t0:t1])))
-            for i in range(t1 - t0):
-                yield traj[off[i]:off[i + 1]]
+            traj, off = self._replay(t0, t1)
+            yield t0, t1, traj, off
             t0 = t1
+
+    @staticmethod
+    def host_tracks(traj, offsets):
+        """The tracks of one device chunk one by one, int16 (n_i, 2) host arrays."""
+        traj = traj.cpu().numpy()
+        off = offsets.cpu().numpy()
+        for i in range(off.size - 1):
+            yield traj[off[i]:off[i + 1]]
+
+    def iter_tracks(self):
+        """The tracks one by one, int16 (n_i, 2) each, in track order.  When the trajectories did not fit
+        the device budget (Sum lengths x 4 B: 1 TB for 100k tracks on the solved 10 m field, where a
+        third of them take max_moves = 7.5e6) they are produced range by range: the lengths of the
+        finished pass give the ranges, and each range is stepped again with the generic kernel writing
+        every point at its offset (the same counter-based streams: the same tracks)."""
+        for _, _, traj, off in self.iter_device_chunks():
+            yield from self.host_tracks(traj, off)
 
     def tracks(self, max_bytes=64 << 30):
         """List[int16 (n_i, 2)] like the reference's pool.map result (iter_tracks() streams them)."""
@@ -441,7 +452,7 @@ def simulate_tracks(move_dirn, starts, grid_shape, memory_parameter=1,
                     nat.ptr(out), nat.ptr(off), nat.ptr(wss), C.c_size_t(wsb), C.byref(st2), stream_ptr()))
                 if not torch.equal(sub_len, lengths[t0:t1]):
                     raise RuntimeError('trajectory replay: a track changed its length between the passes')
-                return out.cpu().numpy()
+                return out, off
     elif hist64:
         nat.check(nat.lib().ssrs_tracks_simulate_h64(
             C.byref(p), nat.ptr(upd), nat.ptr(pot), nat.ptr(table), nat.ptr(st),

@@ -66,6 +66,12 @@ def presence_kernel_radius(radius_m, resolution, gridsize):
     return int(round(krad))
 
 
+def windplant_kernel_radius(radius_m, resolution, gridsize):
+    """plot_windplant_presence_map hands the same `krad` on UNROUNDED (simulator.py:571, :580) and
+    compute_smooth_presence_counts truncates it with int() (movmodel.py:431): 270 m at 100 m is 2 cells here, 3 above."""
+    return int(min(max(radius_m / resolution, 2), min(gridsize) / 2))
+
+
 def normalise_add(src, acc):
     """acc += src / max(src) on the device (simulator.py:531-532, :538-539)."""
     s = to_dev(src)

@@ -26,6 +26,7 @@ import torch
 
 from .config import Config
 from . import layers, movmodel, presence
+from . import turbines as turbines_mod
 from . import potential as potential_mod
 from ._device import to_dev
 
@@ -46,7 +47,7 @@ class Simulator(Config):
     time_format = 'y%Ym%md%dh%H'
 
     def __init__(self, in_config: Config = None, *, terrain=None, wind=None,
-                 origin=(0.0, 0.0), **kwargs) -> None:
+                 origin=(0.0, 0.0), turbines=None, **kwargs) -> None:
         """terrain: 'synthetic' | elevation array (rows, cols) | dict with keys
         'Elevation' and optionally 'Slope', 'Aspect' | callable(gridsize, res).
         wind (snapshot / seasonal): list of dicts, each with 'datetime'
@@ -59,12 +60,17 @@ class Simulator(Config):
         'blheight' and 'surfheatflux' (the keys of `wtk_layers`), all four as (rows, cols)
         rasters, as samples (npts,) at x_km / y_km, or on the lattice (ny, nx).
         origin: projected (west, south) of cell (0, 0); the reference derives it
-        from southwest_lonlat through GDAL (simulator.py:77-85)."""
+        from southwest_lonlat through GDAL (simulator.py:77-85).
+        turbines: a `Turbines`, a dict of columns or a DataFrame with `x`, `y` in the projected frame of
+        `origin` (optionally `p_name`, `t_hh`, `t_rd`): the stand-in for the reference's USWTDB download
+        (simulator.py:101-105), filtered to `bounds` and `turbine_minimum_hubheight` like it."""
         if in_config is None:
             super().__init__(**kwargs)
         else:
             super().__init__(**asdict(in_config))
         self._check_thermal_model()
+        if not float(self.turbine_encounter_radius) >= 0.:
+            raise ValueError(f'turbine_encounter_radius = {self.turbine_encounter_radius!r}: expected metres >= 0 (0 = off)')
         print(f'\n---- SSRS in {self.sim_mode} mode')
         print(f'Run name: {self.run_name}')
         if self.sim_seed >= 0:                                    # simulator.py:50-52
@@ -96,7 +102,8 @@ class Simulator(Config):
         self.terrain_layers = {'Elevation': 'DEM', 'Slope': 'Slope Degrees',
                                'Aspect': 'Aspect Degrees'}
         self._terrain = self._resolve_terrain(terrain)
-        self.turbines = None
+        self.turbines = self._resolve_turbines(turbines)
+        self.turbine_encounters = {}      # (case_id, real_id) -> dict(tracks_per_turbine, turbines_per_track, first_step)
         self.wtk_layers = {
             'wspeed': f'windspeed_{str(int(self.wtk_orographic_height))}m',
             'wdirn': f'winddirection_{str(int(self.wtk_orographic_height))}m',
@@ -159,6 +166,26 @@ class Simulator(Config):
         if 'Elevation' not in out:
             raise ValueError("terrain needs an 'Elevation' layer")
         return out
+
+    def _resolve_turbines(self, turbines):
+        """The injected turbines inside `bounds` at or above `turbine_minimum_hubheight` (None stays None); with
+        turbine_encounter_radius > 0 also their cell coordinates and the cull lists of the encounter kernel."""
+        radius = float(self.turbine_encounter_radius)
+        if turbines is not None:
+            turbines = turbines_mod.Turbines(turbines, self.bounds, float(self.turbine_minimum_hubheight),
+                                             bool(self.print_verbose))
+        if radius > 0.:
+            if turbines is None or len(turbines) == 0:
+                raise ValueError(f'turbine_encounter_radius = {radius:g} m needs turbines: ' +
+                                 ('none were given (Simulator(..., turbines=...))' if turbines is None else
+                                  'none of those given lies inside the bounds at or above turbine_minimum_hubheight'))
+            if len(turbines) > turbines_mod.MAX_TURBINES:
+                raise ValueError(f'{len(turbines)} turbines inside the bounds: encounters are counted for at most '
+                                 f'{turbines_mod.MAX_TURBINES}')
+            self._turbine_cells = turbines.cell_coordinates(self.bounds, self.resolution)
+            self._turbine_bins = turbines_mod.build_bins(self._turbine_cells, radius / float(self.resolution),
+                                                         self.gridsize)
+        return turbines
 
     def _resolve_wind(self, wind):
         if isinstance(wind, dict):
@@ -531,6 +558,17 @@ class Simulator(Config):
         dist.broadcast(t, src=src)
         return t.cpu().numpy()
 
+    def _allreduce_sum_f64(self, values):
+        """Sum over the ranks of an f64 vector, on every rank."""
+        import torch.distributed as dist
+        arr = np.asarray(values, dtype=np.float64)
+        if not (self._dist_on() and dist.get_world_size() > 1):
+            return arr
+        dev = torch.device('cuda', torch.cuda.current_device()) if dist.get_backend() == 'nccl' else torch.device('cpu')
+        t = torch.from_numpy(arr.copy()).to(dev)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        return t.cpu().numpy()
+
     def _allreduce_sum_int64(self, values):
         """Sum over the ranks of an int64 vector, on every rank."""
         import torch.distributed as dist
@@ -631,6 +669,12 @@ class Simulator(Config):
                         else (None, None)
                     yield (case_id, real_id, fields, self._stream_seed(real_id))
 
+        encounters = float(self.turbine_encounter_radius) > 0.
+        if encounters:
+            # (one upload for all cases: the kernel reads the turbines and their cull lists from the device)
+            enc_geometry = (to_dev(self._turbine_cells, torch.float64),
+                            tuple(to_dev(a, torch.int32) for a in self._turbine_bins))
+
         def run(item):
             case_id, real_id, fields, seed = item
             self.last_seeds[(case_id, real_id)] = seed
@@ -641,6 +685,14 @@ class Simulator(Config):
                 torch.cuda.current_stream().synchronize()
                 print(f'{id_str}: Simulating {hi - lo} tracks..took {_elapsed(start_time)}',
                       flush=True)
+                chunks = None
+                if encounters:
+                    # every device chunk of the trajectories goes through the encounter kernel, then (save_tracks) on
+                    # to the pickle: a replay range is stepped ONCE for both
+                    nturb = int(enc_geometry[0].shape[0])
+                    hits = torch.zeros((hi - lo, (nturb + 31) // 32), dtype=torch.int32, device=my_starts.device)
+                    first_step = torch.full((hi - lo,), -1, dtype=torch.int32, device=my_starts.device)
+                    chunks = self._encounter_chunks(batch, enc_geometry, hits, first_step)
                 if self.save_tracks:
                     # (inside the stream's scope: long trajectories are stepped again range by range while written)
                     need = sum(b.total_points for b in batch.parts) * 4
@@ -654,8 +706,18 @@ class Simulator(Config):
                             f'(Sum lengths x 4 B; max_tracks_file_gb = {self.max_tracks_file_gb:g}): on fields where '
                             'tracks wander to max_moves run with save_tracks=False, or raise max_tracks_file_gb')
                     fname = self._get_tracks_fname(case_id, real_id, self.mode_data_dir)
-                    self._write_tracks(fname, (t for b in batch.parts for t in b.iter_tracks()), sharded)
+                    tracks = (t for b in batch.parts for t in b.iter_tracks()) if chunks is None else \
+                        (t for traj, off in chunks for t in movmodel.TrackBatch.host_tracks(traj, off))
+                    self._write_tracks(fname, tracks, sharded)
                     torch.cuda.current_stream().synchronize()
+                elif chunks is not None:
+                    for _ in chunks:
+                        pass
+                if encounters:
+                    per_turbine, per_track = turbines_mod.encounter_counts(hits, nturb)
+                    # (track-sharded: the sum over the ranks is a collective, issued here in item order like the rest)
+                    self._store_encounters(case_id, real_id, per_turbine.cpu().numpy(), per_track.cpu().numpy(),
+                                           first_step.cpu().numpy(), sharded)
             if sharded:
                 from .distributed import reduce_histogram
                 batch.hist = reduce_histogram(batch.hist, all_ranks=True)
@@ -689,6 +751,34 @@ class Simulator(Config):
                         collect(f.result() for f in done)
                 collect(f.result() for f in pending)
 
+    def _encounter_chunks(self, batch, geometry, hits, first_step):
+        """The device chunks (traj, offsets) of every part of `batch` in track order, each one run through the encounter
+        kernel into its rows of `hits` / `first_step` before it is handed on."""
+        xy, bins = geometry
+        radius_cells = float(self.turbine_encounter_radius) / float(self.resolution)
+        base = 0
+        for part in batch.parts:
+            for t0, t1, traj, off in part.iter_device_chunks():
+                turbines_mod.turbine_encounters(traj, off, xy, radius_cells, self.gridsize, bins=bins,
+                                                hits=hits[base + t0:base + t1], first_step=first_step[base + t0:base + t1])
+                yield traj, off
+            base += int(part.lengths.numel())
+
+    def _store_encounters(self, case_id, real_id, tracks_per_turbine, turbines_per_track, first_step, sharded):
+        """Keeps the encounters of one (case, realisation) and writes <id>_turbine_encounters.npy (int64 (nturb,): the
+        tracks that came within turbine_encounter_radius of each turbine).  Track-sharded runs sum the per-turbine
+        counts over the ranks (every rank must call this, in the same item order) and rank 0 writes; otherwise the
+        rank that owns the case does.  turbines_per_track / first_step stay this rank's tracks."""
+        per_turbine = np.asarray(tracks_per_turbine, dtype=np.int64)
+        if sharded:
+            per_turbine = np.asarray(self._allreduce_sum_int64(per_turbine), dtype=np.int64)
+        self.turbine_encounters[(case_id, real_id)] = dict(
+            tracks_per_turbine=per_turbine, turbines_per_track=np.asarray(turbines_per_track, dtype=np.int32),
+            first_step=np.asarray(first_step, dtype=np.int32))
+        if not sharded or self._rank() == 0:
+            fname = os.path.join(self.mode_data_dir, f'{self._get_id_string(case_id, real_id)}_turbine_encounters')
+            np.save(f'{fname}.npy', per_turbine)
+
     _MIN_SPLIT_TRACKS = 64          # a wrapped sub-batch smaller than twice this is an error, not a split
     _HIST64_FROM_TRACKS = 100_000   # sub-batches larger than this count in 64 bits (when no trajectories are asked for)
 
@@ -707,6 +797,8 @@ class Simulator(Config):
         # short last sub-batch would cost a full pass's time for a fraction of the work
         step = max(1, -(-n // max(1, -(-n // safe))))
         parts, wide, stats = [], None, None
+        # trajectories: for the pickle, or for the turbine encounters (which read them on the device)
+        want_tracks = bool(self.save_tracks) or float(self.turbine_encounter_radius) > 0.
         # (start, length) of the sub-batches still to step, in track-id order; one whose uint32 counts wrapped is stepped
         # again as two halves, added up in 64 bits like the rest
         todo = [(t0, min(step, n - t0)) for t0 in range(0, max(n, 1), step)]
@@ -715,11 +807,11 @@ class Simulator(Config):
             sub = my_starts[t0:t0 + m]
             # large sub-batches without trajectories count in 64 bits inside the library (the trap cells of a solved 10 m field
             # pass 2^32 visits from ~250 000 tracks on: ssrs_tracks_simulate_h64); the others keep the uint32 raster
-            use64 = not self.save_tracks and m > self._HIST64_FROM_TRACKS
+            use64 = not want_tracks and m > self._HIST64_FROM_TRACKS
             b = movmodel.simulate_tracks(
                 self.track_direction, sub, self.gridsize, self.track_dirn_restrict,
                 self.track_stochastic_nu, fields[0], fields[1], seed=seed, track_id_base=lo + t0,
-                use_table=use_table, want_tracks=bool(self.save_tracks),
+                use_table=use_table, want_tracks=want_tracks,
                 steps_per_launch=self.steps_per_launch, hist64=use64)
             if b.hist.dtype == torch.int64:
                 widen = True
@@ -818,13 +910,12 @@ class Simulator(Config):
         flat = np.concatenate(tracks) if len(tracks) else np.zeros((0, 2), dtype=np.int16)
         return presence.compute_presence_counts(torch.from_numpy(flat).cuda(), self.gridsize)
 
-    def compute_presence_map(self, radius: float = 1000.):
-        """The numeric part of plot_presence_map (simulator.py:518-546): returns
-        the f32 summary map and writes summary_presence.npy."""
-        krad = presence.presence_kernel_radius(radius, self.resolution, self.gridsize)
+    def _presence_summary(self, krad):
+        """The normalisation ladder of plot_presence_map / plot_windplant_presence_map (simulator.py:521-546, :572-586)
+        with a disk of `krad` cells: (the f32 summary map, the same on every rank; this rank's per-case maps)."""
         dev = self._presence_device()
         summary = torch.zeros(self.gridsize, dtype=torch.float64, device=dev)
-        self.case_presence = {}
+        case_presence = {}
         for case_id in self.my_case_ids():
             nreal = 1 + int(self.thermals_realization_count)
             case_prob = torch.zeros(self.gridsize, dtype=torch.float64, device=dev)
@@ -833,13 +924,61 @@ class Simulator(Config):
                 prprob = presence.smooth_presence_counts(counts, krad)
                 presence.normalise_add(prprob, case_prob)       # prprob /= amax; case += prprob
             presence.normalise_add(case_prob, summary)          # case /= amax; summary += case
-            self.case_presence[case_id] = case_prob
+            case_presence[case_id] = case_prob
         if not self._shards_tracks():
             from .distributed import reduce_presence_sum
             reduce_presence_sum(summary)                        # cases of the other ranks
-        out = presence.normalise_to_f32(summary).cpu().numpy()  # summary /= amax -> f32
+        return presence.normalise_to_f32(summary).cpu().numpy(), case_presence  # summary /= amax -> f32
+
+    def compute_presence_map(self, radius: float = 1000.):
+        """The numeric part of plot_presence_map (simulator.py:518-546): returns
+        the f32 summary map and writes summary_presence.npy."""
+        out, self.case_presence = self._presence_summary(
+            presence.presence_kernel_radius(radius, self.resolution, self.gridsize))
         if self._rank() == 0:
             np.save(os.path.join(self.mode_data_dir, 'summary_presence.npy'), out)
+        self._barrier()
+        return out
+
+    def compute_windplant_presence_map(self, pname, radius: float = 100., pad: float = 2000.):
+        """The numeric part of plot_windplant_presence_map (simulator.py:557-592): the same ladder with this method's
+        radius -- handed on unrounded there, so int() truncates it (presence.windplant_kernel_radius) -- cropped to the
+        axis limits of :589-590.  Returns (window, (r0, r1, c0, c1)): the f32 summary over the cells whose centres lie within
+        `pad` of the project's turbines in x and in y, window = summary[r0:r1, c0:c1], clipped to the raster; writes
+        presence_<pname>.npy.  ValueError for an unknown project or a window without cells."""
+        if self.turbines is None:
+            raise ValueError('compute_windplant_presence_map needs turbines (Simulator(..., turbines=...))')
+        xloc, yloc = self.turbines.get_locations_for_this_project(pname)
+        if len(xloc) == 0:
+            raise ValueError(f'no turbines of a project {pname!r} inside the bounds '
+                             f'(projects: {list(self.turbines.get_project_names())})')
+        window = turbines_mod.windplant_window(xloc, yloc, float(pad), self.bounds, self.resolution, self.gridsize)
+        r0, r1, c0, c1 = window
+        summary, _ = self._presence_summary(presence.windplant_kernel_radius(radius, self.resolution, self.gridsize))
+        out = np.ascontiguousarray(summary[r0:r1, c0:c1])
+        if self._rank() == 0:
+            np.save(os.path.join(self.mode_data_dir, f'presence_{pname}.npy'), out)
+        self._barrier()
+        return out, window
+
+    def compute_turbine_encounters(self):
+        """Per turbine, the share of the simulated tracks that came within turbine_encounter_radius of it: the mean over
+        all (case, realisation) items of tracks_per_turbine / track_count, f64 (nturb,) in the order of
+        `turbines.get_locations()`; case-sharded runs take the mean over every rank's items.  Writes
+        summary_turbine_encounters.npy.  ValueError when simulate_tracks computed no encounters."""
+        if not self.turbine_encounters:
+            raise ValueError('no turbine encounters were computed: run simulate_tracks() with turbine_encounter_radius > 0 '
+                             'and turbines')
+        items = [self.turbine_encounters[key] for key in sorted(self.turbine_encounters)]
+        total = np.zeros(items[0]['tracks_per_turbine'].size + 1, dtype=np.float64)        # [..., number of items]
+        for enc in items:
+            total[:-1] += enc['tracks_per_turbine'] / float(self.track_count)
+            total[-1] += 1.
+        if self._world() > 1 and not self._shards_tracks():
+            total = self._allreduce_sum_f64(total)                  # the cases of the other ranks
+        out = total[:-1] / total[-1]
+        if self._rank() == 0:
+            np.save(os.path.join(self.mode_data_dir, 'summary_turbine_encounters.npy'), out)
         self._barrier()
         return out
 
@@ -911,5 +1050,15 @@ class Simulator(Config):
     def plot_updrafts(self, *a, **k): self._no_plot('plot_updrafts')
     def plot_directional_potentials(self, *a, **k): self._no_plot('plot_directional_potentials')
     def plot_simulated_tracks(self, *a, **k): self._no_plot('plot_simulated_tracks')
-    def plot_windplant_presence_map(self, *a, **k): self._no_plot('plot_windplant_presence_map')
+
+    def plot_windplant_presence_map(self, pname, radius: float = 100., plot_turbs=True, show=False, minval=0.05,
+                                    pad: float = 2000., **k) -> None:
+        """simulator.py:557-592 up to the summary map and its crop (presence_<pname>.npy); the figure is out of scope.
+        Without injected turbines there is nothing to crop to: the no-op line of the other plotting methods."""
+        if getattr(self, 'turbines', None) is None:
+            self._no_plot('plot_windplant_presence_map')
+            return
+        print('Plotting presence density map..')
+        self.compute_windplant_presence_map(pname, radius=radius, pad=pad)
+
     def plot_updraft_threshold_function(self, *a, **k): self._no_plot('plot_updraft_threshold_function')

@@ -1,0 +1,231 @@
+"""Wind turbines (K8 host side): `Turbines`, the injected stand-in for the reference's TurbinesUSWTB
+(ssrs/turbines.py there; the USWTDB download and the CRS transform stay out of scope), and the
+encounter pass of the trajectories against them -- which simulated tracks came within R of which turbine, and
+after how many moves (include/ssrs_hip.h "turbines").
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _native as nat
+from ._device import device, stream_ptr, to_dev, is_tensor
+
+BIN = nat.SSRS_TURBINE_BIN
+MAX_TURBINES = nat.SSRS_TURBINE_MAX
+
+
+class Turbines:
+    """Turbine table with the query methods of TurbinesUSWTB.
+
+    data: dict of equally long columns, a pandas DataFrame or another `Turbines`.  Columns `x`, `y` are projected
+    metres in the frame of `Simulator(origin=...)`; `p_name` (project), `t_hh` (hub height, m) and `t_rd` (rotor
+    diameter, m) are optional, anything else is carried along.  The constructor filters like turbines.py:68-71:
+    x within [bounds[0], bounds[2]] and y within [bounds[1], bounds[3]], both ends included, and -- when `t_hh` is
+    given -- min_hubheight <= t_hh < 10000.  bounds=None keeps every position.  pandas is never imported
+    unless `dframe` is asked for."""
+
+    def __init__(self, data, bounds=None, min_hubheight: float = 50., print_verbose: bool = False):
+        if isinstance(data, Turbines):
+            cols = dict(data.columns)
+        elif hasattr(data, 'columns') and hasattr(data, 'to_numpy'):            # a DataFrame, without importing pandas
+            cols = {str(name): data[name].to_numpy() for name in data.columns}
+        elif isinstance(data, dict):
+            cols = {str(name): np.asarray(val) for name, val in data.items()}
+        else:
+            raise TypeError(f'turbines: expected a dict of columns, a DataFrame or a Turbines, not {type(data).__name__}')
+        for name in ('x', 'y'):
+            if name not in cols:
+                raise ValueError(f"turbines: column {name!r} is missing (projected metres, the frame of origin=)")
+            cols[name] = np.asarray(cols[name], dtype=np.float64).reshape(-1)
+        n = cols['x'].size
+        for name, val in cols.items():
+            if np.ndim(val) != 1 or np.shape(val)[0] != n:
+                raise ValueError(f'turbines: column {name!r} has shape {np.shape(val)}, expected ({n},)')
+        keep = np.ones(n, dtype=bool)
+        if bounds is not None:
+            keep &= (cols['x'] >= bounds[0]) & (cols['x'] <= bounds[2])         # between(..., 'both')
+            keep &= (cols['y'] >= bounds[1]) & (cols['y'] <= bounds[3])
+        if 't_hh' in cols:
+            hh = np.asarray(cols['t_hh'], dtype=np.float64)
+            keep &= (hh >= float(min_hubheight)) & (hh < 10000.)                # between(min, 10000., 'left')
+        self.columns = {name: val[keep] for name, val in cols.items()}
+        if print_verbose:
+            self.print_details()
+
+    def __len__(self):
+        return int(self.columns['x'].size)
+
+    @property
+    def dframe(self):
+        """The table as a pandas DataFrame (the reference's attribute)."""
+        import pandas as pd
+        return pd.DataFrame(self.columns)
+
+    def get_locations(self):
+        """(x, y) of every turbine (turbines.py:80-83)."""
+        return self.columns['x'], self.columns['y']
+
+    def _project(self, pname):
+        if 'p_name' not in self.columns:
+            raise KeyError('p_name')
+        return self.columns['p_name'] == pname
+
+    def get_locations_for_this_project(self, pname: str):
+        """(x, y) of the turbines of one project (turbines.py:85-91); empty arrays for an unknown name."""
+        sel = self._project(pname)
+        return self.columns['x'][sel], self.columns['y'][sel]
+
+    def get_project_names(self):
+        """Project names in order of first appearance (pandas' unique(), turbines.py:93-95)."""
+        if 'p_name' not in self.columns:
+            raise KeyError('p_name')
+        names = self.columns['p_name']
+        _, first = np.unique(names, return_index=True)
+        return names[np.sort(first)]
+
+    def cell_coordinates(self, bounds, resolution):
+        """(n, 2) f64 [x, y] in cell units relative to the centre of cell (0, 0): x along columns, y along rows."""
+        x, y = self.get_locations()
+        return np.stack([(x - float(bounds[0])) / float(resolution), (y - float(bounds[1])) / float(resolution)], 1)
+
+    def print_details(self):
+        if len(self) == 0:
+            print('Turbines: No wind turbines found within the bounds!')
+            return
+        if 'p_name' in self.columns:
+            print(f'Number of projects: {self.get_project_names().size}')
+        print(f'Number of turbines: {len(self)}')
+        for name, label in (('t_hh', 'Hub height'), ('t_rd', 'Rotor Dia')):
+            if name in self.columns:
+                v = np.asarray(self.columns[name], dtype=np.float64)
+                print(f'{label} (min,median,max): {v.min()}, {np.median(v)}, {v.max()}')
+
+
+def windplant_window(xloc, yloc, pad, bounds, resolution, gridsize):
+    """(r0, r1, c0, c1), ends exclusive: the cells whose centres (bounds[0] + c * res, bounds[1] + r * res) lie in
+    [min(x) - pad, max(x) + pad] x [min(y) - pad, max(y) + pad] (the axis limits of simulator.py:589-590), clipped
+    to the raster by construction.  ValueError when there is no such cell."""
+    xloc, yloc = np.asarray(xloc, dtype=np.float64), np.asarray(yloc, dtype=np.float64)
+    if xloc.size == 0:
+        raise ValueError('windplant window: no turbine locations')
+    out = []
+    for origin, n, loc in ((bounds[1], gridsize[0], yloc), (bounds[0], gridsize[1], xloc)):
+        centres = float(origin) + np.arange(int(n)) * float(resolution)
+        inside = np.nonzero((centres >= loc.min() - pad) & (centres <= loc.max() + pad))[0]
+        if inside.size == 0:
+            raise ValueError('windplant window: it holds no cell of the raster')
+        out += [int(inside[0]), int(inside[-1]) + 1]
+    return tuple(out)
+
+
+def build_bins(xy_cells, radius_cells, gridshape):
+    """The cull lists of ssrs_turbine_encounters: (bin_start int32 (nbr * nbc + 1), bin_items int32), a CSR over bins
+    of 32 x 32 cells listing, in ascending order, the turbines whose disk can reach a cell of the bin.
+    Conservative: the disk's bounding box, one cell wider on every side than the real numbers ask for (the exact
+    test rounds c - xt before it squares), against the bin's cells.  A turbine with a NaN coordinate is in no list."""
+    rows, cols = int(gridshape[0]), int(gridshape[1])
+    xy = np.asarray(xy_cells, dtype=np.float64).reshape(-1, 2)
+    radius = float(radius_cells)
+    if not radius >= 0.:
+        raise ValueError(f'radius_cells = {radius_cells!r}: expected a number >= 0')
+    nbr, nbc = -(-rows // BIN), -(-cols // BIN)
+    bins, items = [], []
+    # first / last cell of the widened box, clipped to the raster (in floats first: coordinates may be huge)
+    c_lo = np.clip(np.floor(xy[:, 0] - radius) - 1, 0, cols)
+    c_hi = np.clip(np.ceil(xy[:, 0] + radius) + 1, -1, cols - 1)
+    r_lo = np.clip(np.floor(xy[:, 1] - radius) - 1, 0, rows)
+    r_hi = np.clip(np.ceil(xy[:, 1] + radius) + 1, -1, rows - 1)
+    ok = ~(np.isnan(c_lo) | np.isnan(c_hi) | np.isnan(r_lo) | np.isnan(r_hi))
+    for t in np.nonzero(ok)[0]:
+        c0, c1, r0, r1 = int(c_lo[t]), int(c_hi[t]), int(r_lo[t]), int(r_hi[t])
+        if c0 > c1 or r0 > r1:
+            continue
+        br = np.arange(r0 // BIN, r1 // BIN + 1, dtype=np.int64)
+        bc = np.arange(c0 // BIN, c1 // BIN + 1, dtype=np.int64)
+        b = (br[:, None] * nbc + bc[None, :]).ravel()
+        bins.append(b)
+        items.append(np.full(b.size, t, dtype=np.int32))
+    bins = np.concatenate(bins) if bins else np.zeros(0, dtype=np.int64)
+    items = np.concatenate(items) if items else np.zeros(0, dtype=np.int32)
+    if bins.size >= 2 ** 31:
+        raise ValueError(f'build_bins: {bins.size} list entries do not fit int32 (radius_cells = {radius})')
+    order = np.argsort(bins, kind='stable')                # turbines were appended in ascending order
+    bin_start = np.zeros(nbr * nbc + 1, dtype=np.int64)
+    np.cumsum(np.bincount(bins, minlength=nbr * nbc), out=bin_start[1:])
+    return bin_start.astype(np.int32), np.ascontiguousarray(items[order], dtype=np.int32)
+
+
+def _check_bins(bin_start, bin_items, nbins, nturb):
+    bs, bi = np.asarray(bin_start), np.asarray(bin_items)
+    if bs.shape != (nbins + 1,) or bi.ndim != 1:
+        raise ValueError(f'bins: bin_start has shape {bs.shape}, expected ({nbins + 1},) for this raster')
+    if bs[0] != 0 or bs[-1] != bi.size or (np.diff(bs) < 0).any():
+        raise ValueError('bins: bin_start must ascend from 0 to len(bin_items)')
+    if bi.size and (bi.min() < 0 or bi.max() >= nturb):
+        raise ValueError(f'bins: bin_items outside [0, {nturb})')
+
+
+def turbine_encounters(traj, offsets, xy_cells, radius_cells, gridshape, bins=None, hits=None, first_step=None):
+    """ssrs_turbine_encounters on device tensors.  traj int16 (points, 2) and offsets int64 (ntracks + 1) as
+    movmodel.simulate_tracks / TrackBatch.iter_device_chunks() give them (`offsets` may be a slice of a longer
+    vector: its first entry need not be 0); xy_cells (nturb, 2) f64 in cell units (Turbines.cell_coordinates).
+    bins: (bin_start, bin_items) of build_bins, numpy (checked) or int32 device tensors (trusted); built here when
+    None.  hits: int32 tensor (ntracks, ceil(nturb / 32)) holding the uint32 bitmap, ORed into when given;
+    first_step: int32 (ntracks), min-ed into when given (-1 = none).  Returns (hits, first_step)."""
+    rows, cols = int(gridshape[0]), int(gridshape[1])
+    xy = xy_cells if is_tensor(xy_cells) else np.asarray(xy_cells, dtype=np.float64).reshape(-1, 2)
+    xy = to_dev(xy, torch.float64).reshape(-1, 2)
+    nturb = int(xy.shape[0])
+    if not 1 <= nturb <= MAX_TURBINES:
+        raise ValueError(f'turbine_encounters: {nturb} turbines, expected 1 to {MAX_TURBINES}')
+    off = to_dev(offsets, torch.int64).reshape(-1)
+    ntracks = int(off.numel()) - 1
+    if ntracks < 0:
+        raise ValueError('turbine_encounters: offsets needs at least one entry')
+    pts = to_dev(traj, torch.int16).reshape(-1, 2)
+    words = (nturb + 31) // 32
+    dev = device()
+    if hits is None:
+        hits = torch.zeros((ntracks, words), dtype=torch.int32, device=dev)
+    if first_step is None:
+        first_step = torch.full((ntracks,), -1, dtype=torch.int32, device=dev)
+    if hits.dtype != torch.int32 or tuple(hits.shape) != (ntracks, words) or not hits.is_contiguous() or not hits.is_cuda:
+        raise ValueError(f'turbine_encounters: hits must be a contiguous int32 device tensor ({ntracks}, {words})')
+    if first_step.dtype != torch.int32 or tuple(first_step.shape) != (ntracks,) or not first_step.is_contiguous() \
+            or not first_step.is_cuda:
+        raise ValueError(f'turbine_encounters: first_step must be a contiguous int32 device tensor ({ntracks},)')
+    nbins = -(-rows // BIN) * -(-cols // BIN)
+    if bins is None:
+        bins = build_bins(xy.cpu().numpy(), radius_cells, gridshape)
+    if not is_tensor(bins[0]):
+        _check_bins(bins[0], bins[1], nbins, nturb)
+    bin_start, bin_items = to_dev(bins[0], torch.int32), to_dev(bins[1], torch.int32)
+    if int(bin_start.numel()) != nbins + 1:
+        raise ValueError(f'bins: bin_start has {bin_start.numel()} entries, expected {nbins + 1} for this raster')
+    if ntracks == 0 or pts.numel() == 0 or bin_items.numel() == 0:
+        # nothing to read, or no disk reaches the raster (empty tensors have no address to hand over); the radius
+        # is still the library's to judge
+        if not float(radius_cells) >= 0.:
+            raise ValueError(f'radius_cells = {radius_cells!r}: expected a number >= 0')
+        return hits, first_step
+    nat.check(nat.lib().ssrs_turbine_encounters(
+        nat.ptr(pts), nat.ptr(off), C.c_int64(ntracks), nat.ptr(xy), nturb, C.c_double(float(radius_cells)),
+        nat.ptr(bin_start), nat.ptr(bin_items), rows, cols, nat.ptr(hits), nat.ptr(first_step), stream_ptr()))
+    return hits, first_step
+
+
+def encounter_counts(hits, nturb):
+    """ssrs_turbine_encounter_counts: (tracks_per_turbine int64 (nturb), turbines_per_track int32 (ntracks)),
+    device tensors, from the bitmap of turbine_encounters."""
+    h = to_dev(hits, torch.int32)
+    nturb = int(nturb)
+    ntracks = int(h.shape[0])
+    if h.dim() != 2 or int(h.shape[1]) != (nturb + 31) // 32:
+        raise ValueError(f'encounter_counts: hits has shape {tuple(h.shape)}, expected (ntracks, {(nturb + 31) // 32})')
+    per_turbine = torch.zeros(nturb, dtype=torch.int64, device=h.device)
+    per_track = torch.zeros(ntracks, dtype=torch.int32, device=h.device)
+    if ntracks:
+        nat.check(nat.lib().ssrs_turbine_encounter_counts(
+            nat.ptr(h), C.c_int64(ntracks), nturb, nat.ptr(per_turbine), nat.ptr(per_track), stream_ptr()))
+    return per_turbine, per_track

@@ -2,9 +2,12 @@
 // table builder's mix (12 B read, 8 x 4 B written to eight planes per element), 16-byte and 4-byte
 // accesses per lane.  The write-heavy kernels of this repo (K1, K2a) are priced against these, and
 // v_cvt_pknorm_u16_f32's rounding is checked against round(65535 x) on the way.
+// `stream [GiB]`: the size of each of the two buffers (default 1; the read-only kernels of this repo that stream several
+// GB, K8's trajectory pass, are priced with 4).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cmath>
+#include <cstdlib>
 #include <vector>
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); return 1; } } while (0)
 template <typename T> __global__ void k_read(const T *a, T *sink, size_t n)
@@ -51,9 +54,11 @@ template <typename F> static float timed(F f, int reps = 10)
     hipEventRecord(a); for (int i = 0; i < reps; ++i) f(); hipEventRecord(b); hipEventSynchronize(b);
     float ms; hipEventElapsedTime(&ms, a, b); return ms / reps;
 }
-int main()
+int main(int argc, char **argv)
 {
-    const size_t bytes = size_t(1) << 30, cells = 30000000;
+    const size_t gib = argc > 1 && std::atoi(argv[1]) > 0 ? static_cast<size_t>(std::atoi(argv[1])) : 1;
+    const size_t bytes = gib << 30, cells = 30000000;
+    printf("buffers of %zu GiB\n", gib);
     char *a, *b; CK(hipMalloc(&a, bytes)); CK(hipMalloc(&b, bytes + 4096));
     CK(hipMemset(a, 1, bytes)); CK(hipMemset(b, 0, bytes));
     for (int grid : {2048, 8192, 65536}) {
