@@ -561,6 +561,61 @@ int ssrs_turbine_encounters(const int16_t *traj, const int64_t *traj_offsets, in
 int ssrs_turbine_encounter_counts(const uint32_t *hits, int64_t ntracks, int nturb,
                                   int64_t *tracks_per_turbine, int32_t *turbines_per_track, void *stream);
 
+/* ---------------------------------------------------------------- shelter */
+
+/* K9 -- the terrain-shelter angle Sx (Winstral et al. 2002) and the orographic updraft adjusted by it and by a
+ * flight-height factor.  Per cell (r0, c0) of the DEM z, with K = floor(dmax / res) >= 1 samples along the upwind ray:
+ *   upwind unit step (ur, uc) in (row, col): SSRS_RAY_ROW_NORTH (cos A, sin A), SSRS_RAY_ROW_EAST (sin A, cos A), A the
+ *       direction the wind comes from in degrees clockwise from north.  SSRS_RAY_ROW_EAST is the frame of the Horn
+ *       aspect that ssrs_slope_aspect / ssrs_updraft_from_dem compute from a DEM alone
+ *   for k = 1..K and both axes: o = (double)k * u, io = floor(o), fo = o - io; fo < 1e-9 -> fo = 0;
+ *       fo > 1 - 1e-9 -> io += 1, fo = 0.  Sample cell (i, j) = (r0 + io_r, c0 + io_c); valid iff 0 <= i and
+ *       (i + 1 <= rows - 1 or (fo_r == 0 and i <= rows - 1)), the same for j.  Invalid samples are skipped
+ *   zs = (z[i,j] (1 - fo_c) + z[i,j+1] fo_c) (1 - fo_r) + (z[i+1,j] (1 - fo_c) + z[i+1,j+1] fo_c) fo_r, no
+ *       contraction; a neighbour of weight 0 is not read and enters as 0.0
+ *   T_k = (zs - z0) * (1.0 / ((double)k * res)); NaN skipped; T = max_k T_k (a T_k replaces T iff T_k > T); T = 0
+ *       when no sample is valid, z0 is NaN or the ray direction is NaN.  tan_sx = T, sx_deg = atan(T) 180 / pi.
+ * Wind direction: EITHER ray_ur / ray_uc, `batch` HOST doubles each (uniform wind: the caller's cos / sin), OR wdirn,
+ * a DEVICE f64 raster (batch, rows, cols) in degrees (the step comes from the device's sine / cosine of degrees).
+ * path: SSRS_SHELTER_AUTO stages the DEM tile and its upwind halo of K + 2 cells in LDS when that fits and reads
+ * global memory otherwise; _LDS / _GLOBAL force one (A/B; _LDS that does not fit is SSRS_ERR_INVALID).  Both give the
+ * same bits.  Outputs f64 (batch, rows, cols); either may be NULL.  Arguments are checked before any GPU work. */
+#define SSRS_RAY_ROW_NORTH 0
+#define SSRS_RAY_ROW_EAST 1
+#define SSRS_SHELTER_AUTO 0
+#define SSRS_SHELTER_LDS 1
+#define SSRS_SHELTER_GLOBAL 2
+int ssrs_shelter_sx(const void *dem, int dem_type, double res, const double *ray_ur, const double *ray_uc,
+                    const double *wdirn, double dmax, int ray_axes, int path, double *tan_sx, double *sx_deg,
+                    int rows, int cols, int batch, void *stream);
+
+typedef struct SsrsShelterParams {
+    double dmax;      /* metres; K = floor(dmax / res) */
+    int32_t ray_axes; /* SSRS_RAY_* */
+    int32_t path;     /* SSRS_SHELTER_* */
+    double height;    /* h, metres above ground */
+    double coef[7];   /* a, b, c, d, e, f, g */
+} SsrsShelterParams;
+
+/* The adjusted updraft, batched over `batch` wind cases with the terrain read once:
+ *   w0   = the orographic updraft before its clamp: with slope / aspect NULL from the Horn stencil of the DEM in the
+ *          arithmetic of ssrs_updraft_from_dem (wind direction wdirn0 in degrees), else from the slope / aspect DEVICE
+ *          rasters (sa_type SSRS_F32 / _F64, degrees) in the arithmetic of ssrs_orographic_updraft
+ *   F_h  = (a h^2 + b h + c) d^(e - cos(slope)) + f, cos(slope) = 8 res / sqrt((8 res)^2 + X^2 + Y^2) from the Horn
+ *          sums, or the cosine of the slope raster; d^x = exp(x ln d), d > 0
+ *   F_sx = max(0, 1 + g T)
+ *   w    = max(min_updraft_val, w0 F_sx / F_h) -> orograph f32; usable f64 = the threshold function of that f32
+ *          (threshold > 0 when usable is asked for); sx_deg as above.  Any output may be NULL.
+ * Uniform wind: ray_ur, ray_uc, wspeed0, wdirn0, `batch` HOST doubles each, and wspeed = wdirn = NULL.  Per-cell wind:
+ * wspeed, wdirn DEVICE f64 (batch, rows, cols), the four host arrays NULL.  Coefficients for which F_h <= 0 can occur
+ * (checked at cos(slope) = 0 and 1), d <= 0, height < 0, K < 1: SSRS_ERR_INVALID before any GPU work.  With
+ * coef = (0, 0, 1, 1, 0, 0, 0) the outputs equal those of the two calls named above bit for bit. */
+int ssrs_updraft_sheltered(const void *dem, int dem_type, double res, const double *ray_ur, const double *ray_uc,
+                           const double *wspeed0, const double *wdirn0, const double *wspeed, const double *wdirn,
+                           const void *slope, const void *aspect, int sa_type, const SsrsShelterParams *params,
+                           double min_updraft_val, double threshold, float *orograph, double *usable,
+                           double *sx_deg, int rows, int cols, int batch, void *stream);
+
 /* -------------------------------------------------------------- potential */
 
 typedef struct SsrsSolveStats {

@@ -22,6 +22,8 @@ SSRS_TRACKS_NO_SCATTERED = 64
 SSRS_TRACKS_THR_TABLE = 128
 SSRS_SOLVE_NO_AMG = 1
 SSRS_TURBINE_BIN, SSRS_TURBINE_MAX = 32, 8192
+SSRS_RAY_AXES = {'row_north': 0, 'row_east': 1}                  # SSRS_RAY_ROW_NORTH / _ROW_EAST
+SSRS_SHELTER_PATH = {'auto': 0, 'lds': 1, 'global': 2}           # SSRS_SHELTER_AUTO / _LDS / _GLOBAL
 SSRS_INTERP = {'nearest': 0, 'linear': 1, 'cubic': 2}          # SSRS_INTERP_NEAREST / _LINEAR / _CUBIC
 
 EXPORTS = (
@@ -44,6 +46,7 @@ EXPORTS = (
     'ssrs_presence_normalise_add', 'ssrs_presence_normalise_f32',
     'ssrs_potential_workspace_bytes', 'ssrs_potential_solve',
     'ssrs_turbine_encounters', 'ssrs_turbine_encounter_counts',
+    'ssrs_shelter_sx', 'ssrs_updraft_sheltered',
 )
 
 
@@ -71,6 +74,11 @@ class SsrsSolveStats(C.Structure):
                 ('residual', C.c_double), ('kernel_ms', C.c_float),
                 ('amg_levels', C.c_int32), ('amg_coarsest', C.c_int32),
                 ('setup_ms', C.c_float), ('workspace_used', C.c_uint64)]
+
+
+class SsrsShelterParams(C.Structure):
+    _fields_ = [('dmax', C.c_double), ('ray_axes', C.c_int32), ('path', C.c_int32), ('height', C.c_double),
+                ('coef', C.c_double * 7)]
 
 
 class SsrsError(RuntimeError):
@@ -151,6 +159,11 @@ def lib():
                                                   C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                   C.c_void_p]
             L.ssrs_turbine_encounter_counts.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ssrs_shelter_sx.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.ssrs_updraft_sheltered.argtypes = [C.c_void_p, C.c_int, C.c_double] + [C.c_void_p] * 8 + \
+            [C.c_int, C.POINTER(SsrsShelterParams), C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+             C.c_int, C.c_int, C.c_int, C.c_void_p]
         _lib = L
     return _lib
 

@@ -1,0 +1,439 @@
+// K9 -- terrain-shelter angle Sx (Winstral et al. 2002) and the orographic updraft adjusted by it and by a
+// flight-height factor, for gfx950 (MI355X).  The model is stated in include/ssrs_hip.h and DESIGN.md (K9).
+//
+// Per cell K = floor(dmax / res) bilinear samples of the DEM along the upwind ray: 4 K reads of 8 bytes against
+// 8 bytes of input, so the DEM tile and its upwind halo of K + 2 cells are staged in LDS once per block and every
+// sample is an LDS read.  One block of 512 threads per CU (8 waves share the one tile; the LDS bounds the residency,
+// and 512 threads leave each lane the 141-147 VGPRs the kernel takes without scratch: 1024 threads spilled):
+//   uniform wind   tile 64 x 32 cells, halo on the two upwind sides only (2 cells on the others: the Horn stencil
+//                  and the +1 neighbour of a sample).  K = 50: 118 x 86 f64 = 81 KB.  (io, fo) of a sample depend
+//                  on k alone, so the block tabulates them, 256 samples at a time, and every lane reads its entry
+//                  from LDS as a broadcast
+//   per-cell wind  the ray may point anywhere: tile 32 x 32, halo all round.  K = 50: 136 x 136 f64 = 148 KB
+// A halo that does not fit (uniform K > 85, per-cell K > 51) is read from global memory instead: the same
+// arithmetic on the same values, hence the same bits; the choice is the host's.
+// Several uniform cases in one launch re-stage the tile only when the upwind quadrant changes: the terrain comes
+// from HBM once.  Built with -ffp-contract=off like the rest (the sample is defined without contraction).
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+#include "common.h"
+#include "raster_math.h"
+
+namespace ssrs {
+
+constexpr int kShelterBlock = 512;
+constexpr int kShelterTH = 32;
+constexpr int kTileDoubles = 19200;              // 150 KB of the CU's 160 KB
+constexpr int kRayChunk = 256;                   // samples tabulated at a time
+constexpr int kMaxShelterBatch = 16;
+constexpr int kMaxK = 1 << 20;
+
+struct ShelterArgs {
+    const void *dem;
+    const double *wspeed_r, *wdirn_r;            // per-cell wind (batch, rows, cols) or NULL
+    const void *slope, *aspect;                  // NULL: Horn stencil of the DEM
+    double *tan_sx, *sx_deg, *usable;
+    float *orograph;
+    int rows, cols, K, batch;
+    int row_north, use_lds, sa_f64, want_updraft;
+    double res;
+    double d, d2, min_val, thr, inv_thr, scale, em1;   // as FusedArgs of K1 (+ e - 1 for the elementwise form)
+    double poly, ln_d, ce, cf, cg;                     // a h^2 + b h + c, ln d, e, f, g
+    double ur[kMaxShelterBatch], uc[kMaxShelterBatch]; // uniform wind
+    double wspeed[kMaxShelterBatch], wdirn[kMaxShelterBatch], cos_w[kMaxShelterBatch], sin_w[kMaxShelterBatch];
+};
+
+// offset of one ray sample along one axis: o = k u -> (io, fo) with the snap that keeps an axis wind on the lattice
+__device__ __forceinline__ void ray_offset(double k, double u, int &io, double &fo)
+{
+    const double o = k * u;
+    const double fl = floor(o);
+    io = static_cast<int>(fl);
+    fo = o - fl;
+    if (fo < 1e-9) {
+        fo = 0.0;
+    } else if (fo > 1.0 - 1e-9) {
+        io += 1;
+        fo = 0.0;
+    }
+}
+
+struct DemView {
+    const double *tile;       // LDS image of rows [tr0, tr0 + lh) x cols [tc0, tc0 + lw), or unused
+    int tr0, tc0, lh, lw;
+    bool lds;
+};
+
+// z[i, j] of a cell inside the raster: from the tile when it holds the cell, else from global memory
+template <typename Tin>
+__device__ __forceinline__ double dem_at(const Tin *__restrict__ dem, int cols, const DemView &v, int i, int j)
+{
+    const int li = i - v.tr0, lj = j - v.tc0;
+    if (v.lds && li >= 0 && li < v.lh && lj >= 0 && lj < v.lw) return v.tile[li * v.lw + lj];
+    return static_cast<double>(dem[static_cast<size_t>(i) * cols + j]);
+}
+
+// One sample: T <- T_k where valid and larger.  (i, j) the sample cell; neighbours of weight 0 are not read.
+template <typename Tin>
+__device__ __forceinline__ void shelter_sample(const Tin *__restrict__ dem, int rows, int cols, const DemView &v,
+                                               int i, int j, double fo_r, double fo_c, double z0, double inv_d,
+                                               double &T)
+{
+    const bool ok_r = i >= 0 && (i + 1 <= rows - 1 || (fo_r == 0.0 && i <= rows - 1));
+    const bool ok_c = j >= 0 && (j + 1 <= cols - 1 || (fo_c == 0.0 && j <= cols - 1));
+    if (!(ok_r && ok_c)) return;
+    const int li = i - v.tr0, lj = j - v.tc0;
+    double z00, z01 = 0.0, z10 = 0.0, z11 = 0.0;
+    if (v.lds && li >= 0 && li + 1 < v.lh && lj >= 0 && lj + 1 < v.lw) {   // the 2 x 2 footprint lies in the tile
+        const double *p = v.tile + li * v.lw + lj;
+        z00 = p[0];
+        z01 = fo_c != 0.0 ? p[1] : 0.0;
+        z10 = fo_r != 0.0 ? p[v.lw] : 0.0;
+        z11 = fo_r != 0.0 && fo_c != 0.0 ? p[v.lw + 1] : 0.0;
+    } else {
+        z00 = dem_at(dem, cols, v, i, j);
+        if (fo_c != 0.0) z01 = dem_at(dem, cols, v, i, j + 1);
+        if (fo_r != 0.0) {
+            z10 = dem_at(dem, cols, v, i + 1, j);
+            if (fo_c != 0.0) z11 = dem_at(dem, cols, v, i + 1, j + 1);
+        }
+    }
+    const double zs = (z00 * (1.0 - fo_c) + z01 * fo_c) * (1.0 - fo_r) + (z10 * (1.0 - fo_c) + z11 * fo_c) * fo_r;
+    const double tk = (zs - z0) * inv_d;
+    if (tk > T) T = tk;                          // false for a NaN: skipped
+}
+
+__device__ __forceinline__ double load_sa(const void *p, bool f64, size_t i)
+{
+    return f64 ? static_cast<const double *>(p)[i] : static_cast<double>(static_cast<const float *>(p)[i]);
+}
+
+template <typename Tin, bool UNIFORM>
+__global__ __launch_bounds__(kShelterBlock) void k_shelter(ShelterArgs a, int tiles_x, int ntiles)
+{
+    constexpr int TW = UNIFORM ? 64 : 32;
+    constexpr int TH = kShelterTH;
+    constexpr int CPT = TW * TH / kShelterBlock;                 // cells per thread: 4 or 2
+    __shared__ double s_tile[kTileDoubles];
+    __shared__ double s_inv_d[kRayChunk], s_fo_r[kRayChunk], s_fo_c[kRayChunk];
+    __shared__ int s_io_r[kRayChunk], s_io_c[kRayChunk];
+
+    const Tin *__restrict__ dem = static_cast<const Tin *>(a.dem);
+    const int rows = a.rows, cols = a.cols, K = a.K;
+    const int t = xcd_tile(blockIdx.x, ntiles);
+    const int r0 = (t / tiles_x) * TH, c0 = (t % tiles_x) * TW;
+    const size_t ncell = static_cast<size_t>(rows) * cols;
+    const int tid = threadIdx.x;
+
+    DemView v;
+    v.tile = s_tile;
+    v.lds = a.use_lds != 0;
+    v.tr0 = v.tc0 = v.lh = v.lw = 0;
+    int staged_mt = -1, staged_ml = -1;
+
+    for (int b = 0; b < a.batch; ++b) {
+        // ---- stage the tile and its halo: K + 2 cells on an upwind side, 2 on the others
+        if (v.lds) {
+            int mt = K + 2, ml = K + 2, mb = K + 2, mr = K + 2;
+            if (UNIFORM) {
+                if (a.ur[b] < 0.0) mb = 2; else mt = 2;
+                if (a.uc[b] < 0.0) mr = 2; else ml = 2;
+            }
+            if (mt != staged_mt || ml != staged_ml) {            // (block-uniform)
+                __syncthreads();
+                v.tr0 = r0 - mt;
+                v.tc0 = c0 - ml;
+                v.lh = TH + mt + mb;
+                v.lw = TW + ml + mr;                             // host: lh * lw <= kTileDoubles
+                for (int i = tid; i < v.lh * v.lw; i += kShelterBlock) {
+                    const int li = i / v.lw, lj = i - li * v.lw;
+                    const int gr = v.tr0 + li, gc = v.tc0 + lj;
+                    double z = 0.0;                              // outside the raster: never read (validity rule)
+                    if (gr >= 0 && gr < rows && gc >= 0 && gc < cols)
+                        z = static_cast<double>(dem[static_cast<size_t>(gr) * cols + gc]);
+                    s_tile[i] = z;
+                }
+                staged_mt = mt;
+                staged_ml = ml;
+                __syncthreads();
+            }
+        }
+
+        // ---- this thread's cells, one after the other (every thread takes part in every barrier)
+        const double ninf = -__builtin_huge_val();
+#pragma unroll 1
+        for (int q = 0; q < CPT; ++q) {
+            const int cell = tid + q * kShelterBlock;
+            const int r = r0 + cell / TW, c = c0 + cell % TW;
+            const bool inside = r < rows && c < cols;
+            const size_t i = static_cast<size_t>(r) * cols + c;
+            const size_t o = b * ncell + i;
+            bool live = inside;
+            double z0 = 0.0, T = ninf, ur = 0.0, uc = 0.0, sn_w = 0.0, cs_w = 0.0;
+            if (inside) {
+                z0 = dem_at(dem, cols, v, r, c);
+                if (!UNIFORM) {
+                    sincos_deg(a.wdirn_r[o], sn_w, cs_w);
+                    ur = a.row_north ? cs_w : sn_w;
+                    uc = a.row_north ? sn_w : cs_w;
+                    live = ur == ur && uc == uc;                 // NaN direction: no sample, T = 0
+                }
+            }
+
+            // ---- the K samples, tabulated kRayChunk at a time
+            for (int k0 = 0; k0 < K; k0 += kRayChunk) {
+                const int n = K - k0 < kRayChunk ? K - k0 : kRayChunk;
+                __syncthreads();                                 // the previous table is done with
+                if (tid < n) {
+                    const double k = static_cast<double>(k0 + tid + 1);
+                    s_inv_d[tid] = 1.0 / (k * a.res);
+                    if (UNIFORM) {
+                        int io;
+                        double fo;
+                        ray_offset(k, a.ur[b], io, fo);
+                        s_io_r[tid] = io;
+                        s_fo_r[tid] = fo;
+                        ray_offset(k, a.uc[b], io, fo);
+                        s_io_c[tid] = io;
+                        s_fo_c[tid] = fo;
+                    }
+                }
+                __syncthreads();
+                if (!live) continue;
+                for (int kk = 0; kk < n; ++kk) {
+                    int io_r, io_c;
+                    double fo_r, fo_c;
+                    if (UNIFORM) {
+                        io_r = s_io_r[kk];
+                        io_c = s_io_c[kk];
+                        fo_r = s_fo_r[kk];
+                        fo_c = s_fo_c[kk];
+                    } else {
+                        const double k = static_cast<double>(k0 + kk + 1);
+                        ray_offset(k, ur, io_r, fo_r);
+                        ray_offset(k, uc, io_c, fo_c);
+                    }
+                    shelter_sample(dem, rows, cols, v, r + io_r, c + io_c, fo_r, fo_c, z0, s_inv_d[kk], T);
+                }
+            }
+
+            // ---- outputs
+            if (!inside) continue;
+            const double Tq = (T == ninf || z0 != z0) ? 0.0 : T;
+            if (a.tan_sx) a.tan_sx[o] = Tq;
+            if (a.sx_deg) a.sx_deg[o] = atan(Tq) * (180.0 / kPi);
+            if (!a.want_updraft) continue;
+            double w0 = 0.0, cos_s = 1.0;
+            if (a.slope) {
+                // the arithmetic of k_orographic
+                const double spd = UNIFORM ? a.wspeed[b] : a.wspeed_r[o];
+                const double dir = UNIFORM ? a.wdirn[b] : a.wdirn_r[o];
+                double sin_s, ad, unused;
+                sincos_deg(load_sa(a.slope, a.sa_f64, i), sin_s, cos_s);
+                sincos_deg(load_sa(a.aspect, a.sa_f64, i) - dir, unused, ad);
+                ad = ad > 0.0 ? ad : 0.0;
+                w0 = spd * (sin_s * ad);
+            } else if (r > 0 && c > 0 && r < rows - 1 && c < cols - 1) {
+                // the arithmetic of k_updraft_from_dem: un-normalised Horn sums, "x" = row axis
+                const double spd = UNIFORM ? a.wspeed[b] : a.wspeed_r[o];
+                const double cw = UNIFORM ? a.cos_w[b] : cs_w;
+                const double sw = UNIFORM ? a.sin_w[b] : sn_w;
+                const double m_l = dem_at(dem, cols, v, r - 1, c - 1), m_c = dem_at(dem, cols, v, r - 1, c),
+                             m_r = dem_at(dem, cols, v, r - 1, c + 1);
+                const double z_l = dem_at(dem, cols, v, r, c - 1), z_r = dem_at(dem, cols, v, r, c + 1);
+                const double p_l = dem_at(dem, cols, v, r + 1, c - 1), p_c = dem_at(dem, cols, v, r + 1, c),
+                             p_r = dem_at(dem, cols, v, r + 1, c + 1);
+                const double X = (p_r + 2 * p_c + p_l) - (m_r + 2 * m_c + m_l);
+                const double Y = (m_r + 2 * z_r + p_r) - (m_l + 2 * z_l + p_l);
+                const double rs = rsqrt_pos(a.d2 + (X * X + Y * Y));
+                if (X != 0.0) {
+                    const double P = -(Y * cw + X * sw);
+                    if (P > 0.0) w0 = spd * (P * rs);
+                } else {
+                    const double dzdy = Y / a.d, dx = 1e-10;
+                    const double g2 = dzdy * dzdy, gp2 = dx * dx + g2;
+                    const double proj = -(dzdy * cw + dx * sw);
+                    if (proj > 0.0 && g2 > 0.0) w0 = spd * (proj * sqrt(g2 / (gp2 * (1.0 + g2))));
+                }
+                cos_s = a.d * rs;
+                cos_s = cos_s == cos_s ? cos_s : 1.0;            // NaN in the stencil: slope 0, as the layers
+            }
+            const double f_h = a.poly * exp((a.ce - cos_s) * a.ln_d) + a.cf;
+            double f_sx = 1.0 + a.cg * Tq;
+            f_sx = f_sx > 0.0 ? f_sx : 0.0;
+            double w = w0 * f_sx / f_h;
+            w = w > a.min_val ? w : a.min_val;
+            const float w32 = static_cast<float>(w);
+            if (a.orograph) a.orograph[o] = w32;
+            if (a.usable)
+                a.usable[o] = a.slope ? usable_updraft(static_cast<double>(w32), a.thr, a.em1)
+                                      : usable_updraft_fast(static_cast<double>(w32), a.thr, a.inv_thr, a.scale);
+        }
+    }
+}
+
+// LDS doubles the staged tile takes, or 0 when it does not fit
+static int shelter_tile_doubles(bool uniform, int K)
+{
+    const long long tw = uniform ? 64 : 32, th = kShelterTH;
+    const long long halo = uniform ? static_cast<long long>(K) + 4 : 2 * (static_cast<long long>(K) + 2);
+    const long long n = (tw + halo) * (th + halo);
+    return n <= kTileDoubles ? static_cast<int>(n) : 0;
+}
+
+static int shelter_launch(ShelterArgs &a, int dem_type, bool uniform, int path, const char *who, hipStream_t st)
+{
+    if (const char *e = std::getenv("SSRS_SHELTER_PATH")) {      // A/B switch: lds | global
+        if (!std::strcmp(e, "lds")) path = SSRS_SHELTER_LDS;
+        else if (!std::strcmp(e, "global")) path = SSRS_SHELTER_GLOBAL;
+    }
+    const bool fits = shelter_tile_doubles(uniform, a.K) > 0;
+    SSRS_REQUIRE(!(path == SSRS_SHELTER_LDS && !fits), "%s: the halo of K = %d samples does not fit the LDS tile", who, a.K);
+    a.use_lds = path == SSRS_SHELTER_GLOBAL ? 0 : (fits ? 1 : 0);
+    const int tw = uniform ? 64 : 32;
+    const int tx = (a.cols + tw - 1) / tw, ty = (a.rows + kShelterTH - 1) / kShelterTH, nt = tx * ty;
+    const bool f64 = dem_type == SSRS_F64;
+    if (uniform && f64) hipLaunchKernelGGL((k_shelter<double, true>), dim3(nt), dim3(kShelterBlock), 0, st, a, tx, nt);
+    else if (uniform) hipLaunchKernelGGL((k_shelter<float, true>), dim3(nt), dim3(kShelterBlock), 0, st, a, tx, nt);
+    else if (f64) hipLaunchKernelGGL((k_shelter<double, false>), dim3(nt), dim3(kShelterBlock), 0, st, a, tx, nt);
+    else hipLaunchKernelGGL((k_shelter<float, false>), dim3(nt), dim3(kShelterBlock), 0, st, a, tx, nt);
+    SSRS_HIP_CHECK(hipGetLastError());
+    return SSRS_OK;
+}
+
+// The checks the two calls share; fills the geometry of `a`.
+static int shelter_common(ShelterArgs &a, const char *who, const void *dem, int dem_type, double res,
+                          const double *ray_ur, const double *ray_uc, const double *wdirn, double dmax, int ray_axes,
+                          int path, int rows, int cols, int batch, int min_size)
+{
+    SSRS_REQUIRE(dem != nullptr, "%s: dem is NULL", who);
+    SSRS_REQUIRE(dem_type == SSRS_F32 || dem_type == SSRS_F64, "%s: bad element type", who);
+    SSRS_REQUIRE(rows >= min_size && cols >= min_size && batch >= 1,
+                 "%s: need rows, cols >= %d and batch >= 1 (got %d x %d, batch %d)", who, min_size, rows, cols, batch);
+    SSRS_REQUIRE(static_cast<long long>(rows) * cols < (1ll << 31), "%s: more than 2^31 - 1 cells", who);
+    SSRS_REQUIRE(res > 0.0 && std::isfinite(res), "%s: res must be > 0", who);
+    SSRS_REQUIRE(ray_axes == SSRS_RAY_ROW_NORTH || ray_axes == SSRS_RAY_ROW_EAST, "%s: bad ray_axes %d", who, ray_axes);
+    SSRS_REQUIRE(path == SSRS_SHELTER_AUTO || path == SSRS_SHELTER_LDS || path == SSRS_SHELTER_GLOBAL,
+                 "%s: bad path %d", who, path);
+    SSRS_REQUIRE(dmax > 0.0 && std::isfinite(dmax), "%s: dmax must be > 0", who);
+    const double k = floor(dmax / res);
+    SSRS_REQUIRE(k >= 1.0, "%s: dmax = %g is less than one cell of %g m (K = floor(dmax / res) < 1)", who, dmax, res);
+    SSRS_REQUIRE(k <= kMaxK, "%s: K = floor(dmax / res) exceeds %d", who, kMaxK);
+    SSRS_REQUIRE((ray_ur != nullptr) == (ray_uc != nullptr), "%s: give both ray_ur and ray_uc or neither", who);
+    SSRS_REQUIRE((ray_ur != nullptr) != (wdirn != nullptr),
+                 "%s: give the wind direction either as ray_ur / ray_uc or as a wdirn raster", who);
+    for (int j = 0; ray_ur && j < batch; ++j)
+        SSRS_REQUIRE(std::isfinite(ray_ur[j]) && std::isfinite(ray_uc[j]) && fabs(ray_ur[j]) <= 1.0 && fabs(ray_uc[j]) <= 1.0,
+                     "%s: ray step %d = (%g, %g) is not a unit step", who, j, ray_ur[j], ray_uc[j]);
+    a.dem = dem;
+    a.rows = rows;
+    a.cols = cols;
+    a.K = static_cast<int>(k);
+    a.res = res;
+    a.row_north = ray_axes == SSRS_RAY_ROW_NORTH;
+    a.wdirn_r = wdirn;
+    return SSRS_OK;
+}
+
+}  // namespace ssrs
+
+using namespace ssrs;
+
+extern "C" int ssrs_shelter_sx(const void *dem, int dem_type, double res, const double *ray_ur, const double *ray_uc,
+                               const double *wdirn, double dmax, int ray_axes, int path, double *tan_sx,
+                               double *sx_deg, int rows, int cols, int batch, void *stream)
+{
+    ShelterArgs a = {};
+    if (int rc = shelter_common(a, "ssrs_shelter_sx", dem, dem_type, res, ray_ur, ray_uc, wdirn, dmax, ray_axes, path,
+                                rows, cols, batch, 2))
+        return rc;
+    if (!tan_sx && !sx_deg) return SSRS_OK;
+    hipStream_t st = as_stream(stream);
+    const size_t ncell = static_cast<size_t>(rows) * cols;
+    const int step = ray_ur ? kMaxShelterBatch : batch;         // uniform cases travel in the kernel's arguments
+    for (int b0 = 0; b0 < batch; b0 += step) {
+        a.batch = batch - b0 < step ? batch - b0 : step;
+        for (int j = 0; ray_ur && j < a.batch; ++j) {
+            a.ur[j] = ray_ur[b0 + j];
+            a.uc[j] = ray_uc[b0 + j];
+        }
+        a.tan_sx = tan_sx ? tan_sx + b0 * ncell : nullptr;
+        a.sx_deg = sx_deg ? sx_deg + b0 * ncell : nullptr;
+        if (int rc = shelter_launch(a, dem_type, ray_ur != nullptr, path, "ssrs_shelter_sx", st)) return rc;
+    }
+    return SSRS_OK;
+}
+
+extern "C" int ssrs_updraft_sheltered(const void *dem, int dem_type, double res, const double *ray_ur,
+                                      const double *ray_uc, const double *wspeed0, const double *wdirn0,
+                                      const double *wspeed, const double *wdirn, const void *slope,
+                                      const void *aspect, int sa_type, const SsrsShelterParams *params,
+                                      double min_updraft_val, double threshold, float *orograph, double *usable,
+                                      double *sx_deg, int rows, int cols, int batch, void *stream)
+{
+    const char *who = "ssrs_updraft_sheltered";
+    SSRS_REQUIRE(params != nullptr, "%s: params is NULL", who);
+    ShelterArgs a = {};
+    if (int rc = shelter_common(a, who, dem, dem_type, res, ray_ur, ray_uc, wdirn, params->dmax, params->ray_axes,
+                                params->path, rows, cols, batch, 3))
+        return rc;
+    const bool uniform = ray_ur != nullptr;
+    SSRS_REQUIRE(uniform ? (wspeed0 && wdirn0 && !wspeed) : (wspeed && !wspeed0 && !wdirn0),
+                 "%s: uniform wind takes ray_ur, ray_uc, wspeed0, wdirn0 (host); per-cell wind takes wspeed, wdirn (device)", who);
+    SSRS_REQUIRE((slope == nullptr) == (aspect == nullptr), "%s: give both slope and aspect or neither", who);
+    SSRS_REQUIRE(!slope || sa_type == SSRS_F32 || sa_type == SSRS_F64, "%s: bad slope / aspect element type", who);
+    SSRS_REQUIRE(!(usable && !(threshold > 0.0)), "%s: usable requested without a positive threshold", who);
+    const double h = params->height;
+    const double *cf = params->coef;
+    for (int j = 0; j < 7; ++j) SSRS_REQUIRE(std::isfinite(cf[j]), "%s: coefficient %d is not finite", who, j);
+    SSRS_REQUIRE(h >= 0.0 && std::isfinite(h), "%s: height must be >= 0 (got %g)", who, h);
+    SSRS_REQUIRE(cf[3] > 0.0, "%s: coefficient d must be > 0 (got %g)", who, cf[3]);
+    const double poly = cf[0] * h * h + cf[1] * h + cf[2];
+    const double fh0 = poly * pow(cf[3], cf[4]) + cf[5], fh1 = poly * pow(cf[3], cf[4] - 1.0) + cf[5];
+    SSRS_REQUIRE(fh0 > 0.0 && fh1 > 0.0 && std::isfinite(fh0) && std::isfinite(fh1),
+                 "%s: these coefficients allow F_h <= 0 (F_h = %g on flat ground, %g on a vertical face)", who, fh1, fh0);
+    if (!orograph && !usable && !sx_deg) return SSRS_OK;
+    a.want_updraft = orograph || usable;
+    a.wspeed_r = wspeed;
+    a.slope = slope;
+    a.aspect = aspect;
+    a.sa_f64 = sa_type == SSRS_F64;
+    a.d = 8 * res;
+    a.d2 = a.d * a.d;
+    a.min_val = min_updraft_val;
+    a.thr = threshold;
+    a.inv_thr = threshold > 0.0 ? 1.0 / threshold : 0.0;
+    a.scale = threshold > 0.0 ? threshold / (exp(1.0) - 1.0) : 0.0;
+    a.em1 = exp(1.0) - 1.0;
+    a.poly = poly;
+    a.ln_d = log(cf[3]);
+    a.ce = cf[4];
+    a.cf = cf[5];
+    a.cg = cf[6];
+    hipStream_t st = as_stream(stream);
+    const size_t ncell = static_cast<size_t>(rows) * cols;
+    const int step = uniform ? kMaxShelterBatch : batch;
+    for (int b0 = 0; b0 < batch; b0 += step) {
+        a.batch = batch - b0 < step ? batch - b0 : step;
+        for (int j = 0; uniform && j < a.batch; ++j) {
+            a.ur[j] = ray_ur[b0 + j];
+            a.uc[j] = ray_uc[b0 + j];
+            a.wspeed[j] = wspeed0[b0 + j];
+            a.wdirn[j] = wdirn0[b0 + j];
+            const double w = wdirn0[b0 + j] * kPi / 180.0;      // as ssrs_updraft_from_dem
+            a.cos_w[j] = cos(w);
+            a.sin_w[j] = sin(w);
+        }
+        a.orograph = orograph ? orograph + b0 * ncell : nullptr;
+        a.usable = usable ? usable + b0 * ncell : nullptr;
+        a.sx_deg = sx_deg ? sx_deg + b0 * ncell : nullptr;
+        if (!uniform) {
+            a.wspeed_r = wspeed + b0 * ncell;
+            a.wdirn_r = wdirn + b0 * ncell;
+        }
+        if (int rc = shelter_launch(a, dem_type, uniform, params->path, who, st)) return rc;
+    }
+    return SSRS_OK;
+}

@@ -240,3 +240,140 @@ def compute_thermal_updraft(zmat, deardoff_vel, blayer_height, min_updraft_val=1
                                                  C.c_double(min_updraft_val), nat.ptr(out), C.c_size_t(out.numel()),
                                                  stream_ptr()))
     return _elementwise_out(out, tensor_in)
+
+
+# ---------------------------------------------------------------------------- K9: shelter angle, improved model
+IMPROVED_COEFFS = (4e-5, 2.8e-3, 0.8, 0.35, 0.095, -0.09, 1.0)     # (a, b, c, d, e, f, g): UNVERIFIED, see DESIGN.md K9
+
+
+def ray_step(wdirn, ray_axes='row_east'):
+    """Upwind unit step (ur, uc) in (row, col) of a wind from `wdirn` degrees (clockwise from north), f64 arrays:
+    'row_north' (+row = north, +col = east) -> (cos A, sin A); 'row_east' (the frame of the Horn aspect computed
+    from a DEM alone: +row = east, +col = north) -> (sin A, cos A)."""
+    if ray_axes not in nat.SSRS_RAY_AXES:
+        raise ValueError(f'ray_axes = {ray_axes!r}: expected one of {tuple(nat.SSRS_RAY_AXES)}')
+    rad = np.atleast_1d(np.asarray(wdirn, dtype=np.float64)) * np.pi / 180.
+    return (np.cos(rad), np.sin(rad)) if ray_axes == 'row_north' else (np.sin(rad), np.cos(rad))
+
+
+def check_improved_parameters(dmax, res, height, coeffs):
+    """ValueError unless K = floor(dmax / res) >= 1, height >= 0, seven finite coefficients with d > 0 and
+    F_h = (a h^2 + b h + c) d^(e - cos(slope)) + f > 0 at both ends cos(slope) = 0 and 1.  Host only."""
+    if not (float(dmax) > 0. and np.isfinite(dmax) and np.floor(float(dmax) / float(res)) >= 1.):
+        raise ValueError(f'orographic_sx_dmax = {dmax!r} m is less than one cell of {res!r} m')
+    if not (float(height) >= 0. and np.isfinite(height)):
+        raise ValueError(f'orographic_height = {height!r}: expected metres >= 0')
+    try:
+        cf = tuple(float(x) for x in coeffs)
+    except (TypeError, ValueError):
+        cf = ()
+    if len(cf) != 7 or not np.all(np.isfinite(cf)):
+        raise ValueError(f'orographic_coeffs = {coeffs!r}: expected 7 finite numbers (a, b, c, d, e, f, g)')
+    a, b, c, d, e, f, _ = cf
+    if not d > 0.:
+        raise ValueError(f'orographic_coeffs: d = {d!r} must be > 0')
+    poly = a * float(height) ** 2 + b * float(height) + c
+    ends = (poly * d ** e + f, poly * d ** (e - 1.) + f)
+    if not (np.all(np.isfinite(ends)) and min(ends) > 0.):
+        raise ValueError(f'orographic_coeffs = {coeffs!r} with height {height!r} allow F_h <= 0 '
+                         f'(F_h = {ends[1]:g} on flat ground, {ends[0]:g} on a vertical face)')
+    return cf
+
+
+def _wind_direction_args(wdirn, ray_axes, rows, cols):
+    """(batch, single, ur, uc, wdirn device raster | None) from scalars / a 1-D sequence (uniform) or rasters."""
+    if (wdirn.dim() if is_tensor(wdirn) else np.ndim(wdirn)) <= 1:
+        wd0 = np.asarray(wdirn.cpu() if is_tensor(wdirn) else wdirn, dtype=np.float64)
+        ur, uc = ray_step(wd0, ray_axes)
+        return ur.size, wd0.ndim == 0, np.ascontiguousarray(ur), np.ascontiguousarray(uc), None
+    wd = to_dev(wdirn, torch.float64)
+    single = wd.dim() == 2
+    if single:
+        wd = wd[None]
+    if wd.dim() != 3 or tuple(wd.shape[1:]) != (rows, cols):
+        raise ValueError('wind raster shape does not match the terrain')
+    return int(wd.shape[0]), single, None, None, wd.contiguous()
+
+
+def _dptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def compute_sx(z_mat, res, wdirn, dmax=500., ray_axes='row_east', want='deg', path='auto'):
+    """Winstral's terrain-shelter angle: per cell the steepest angle at which it sees terrain within `dmax` metres
+    upwind (K = floor(dmax / res) bilinear samples along the ray; DESIGN.md K9 states the sample exactly).
+    wdirn: a scalar or B scalars (uniform wind; the ray step is numpy's cos / sin, handed to the device), or a raster
+    (rows, cols) / (B, rows, cols) of degrees.  want: 'deg' -> Sx in degrees, 'tan' -> tan(Sx), 'both' -> (tan, deg);
+    f64, shaped (rows, cols) for a single case, else (B, rows, cols).  path: 'auto' | 'lds' | 'global' (A/B)."""
+    if want not in ('deg', 'tan', 'both'):
+        raise ValueError(f"want = {want!r}: expected 'deg', 'tan' or 'both'")
+    if ray_axes not in nat.SSRS_RAY_AXES or path not in nat.SSRS_SHELTER_PATH:
+        raise ValueError(f'ray_axes = {ray_axes!r} / path = {path!r}: expected one of {tuple(nat.SSRS_RAY_AXES)} / '
+                         f'{tuple(nat.SSRS_SHELTER_PATH)}')
+    dem = float_dev(z_mat)
+    rows, cols = _shape2(dem)
+    batch, single, ur, uc, wd = _wind_direction_args(wdirn, ray_axes, rows, cols)
+    tan = torch.empty((batch, rows, cols), dtype=torch.float64, device=dem.device) if want != 'deg' else None
+    deg = torch.empty((batch, rows, cols), dtype=torch.float64, device=dem.device) if want != 'tan' else None
+    nat.check(nat.lib().ssrs_shelter_sx(
+        nat.ptr(dem), ftype(dem), C.c_double(res), _dptr(ur), _dptr(uc), nat.ptr(wd), C.c_double(dmax),
+        nat.SSRS_RAY_AXES[ray_axes], nat.SSRS_SHELTER_PATH[path], nat.ptr(tan), nat.ptr(deg), rows, cols, batch,
+        stream_ptr()))
+    out = [None if t is None else like_input(t[0] if single else t, z_mat) for t in (tan, deg)]
+    return out[1] if want == 'deg' else out[0] if want == 'tan' else tuple(out)
+
+
+def orographic_updraft_improved(z_mat, res, wspeed, wdirn, slope=None, aspect=None, dmax=500., height=80.,
+                                coeffs=IMPROVED_COEFFS, ray_axes=None, min_updraft_val=0., threshold=None,
+                                want_orograph=True, want_sx=False, path='auto'):
+    """The orographic updraft sheltered by upwind terrain and scaled to a flight height:
+    w = max(min_updraft_val, w0 F_sx / F_h), w0 the value of updraft_from_dem (slope / aspect None: Horn stencil of
+    the DEM) or of orographic_updraft (slope / aspect rasters) before its clamp, F_sx = max(0, 1 + g tan Sx),
+    F_h = (a h^2 + b h + c) d^(e - cos(slope)) + f.  wspeed / wdirn: scalars or B scalars, or rasters (rows, cols) /
+    (B, rows, cols).  ray_axes: the frame of the shelter ray, by default that of the aspect it multiplies --
+    'row_east' for the DEM's own Horn aspect, 'row_north' for given layers.  Returns (orograph f32 | None,
+    usable f64 | None[, Sx degrees f64]) shaped (rows, cols) for a single case, else (B, rows, cols); numpy when
+    z_mat is numpy."""
+    if (slope is None) != (aspect is None):
+        raise ValueError('give both slope and aspect or neither')
+    if ray_axes is None:
+        ray_axes = 'row_east' if slope is None else 'row_north'
+    if ray_axes not in nat.SSRS_RAY_AXES or path not in nat.SSRS_SHELTER_PATH:
+        raise ValueError(f'ray_axes = {ray_axes!r} / path = {path!r}: expected one of {tuple(nat.SSRS_RAY_AXES)} / '
+                         f'{tuple(nat.SSRS_SHELTER_PATH)}')
+    cf = check_improved_parameters(dmax, res, height, coeffs)
+    dem = float_dev(z_mat)
+    rows, cols = _shape2(dem)
+    s = a = None
+    if slope is not None:
+        s = float_dev(slope)
+        a = float_dev(aspect)
+        if a.dtype != s.dtype:
+            a = a.to(s.dtype)
+        if tuple(s.shape) != (rows, cols) or tuple(a.shape) != (rows, cols):
+            raise ValueError('slope / aspect shapes do not match the terrain')
+    batch, single, ur, uc, wd = _wind_direction_args(wdirn, ray_axes, rows, cols)
+    ws = ws0 = wd0 = None
+    if wd is None:
+        ws0 = np.atleast_1d(np.asarray(wspeed.cpu() if is_tensor(wspeed) else wspeed, dtype=np.float64))
+        wd0 = np.atleast_1d(np.asarray(wdirn.cpu() if is_tensor(wdirn) else wdirn, dtype=np.float64))
+        if ws0.shape != wd0.shape:
+            raise ValueError('wspeed and wdirn lengths differ')
+        ws0, wd0 = np.ascontiguousarray(ws0), np.ascontiguousarray(wd0)
+    else:
+        ws = to_dev(wspeed, torch.float64)
+        ws = (ws[None] if ws.dim() == 2 else ws).contiguous()
+        if ws.shape != wd.shape:
+            raise ValueError('wspeed and wdirn shapes differ')
+    params = nat.SsrsShelterParams(float(dmax), nat.SSRS_RAY_AXES[ray_axes], nat.SSRS_SHELTER_PATH[path], float(height),
+                                   (C.c_double * 7)(*cf))
+    oro = torch.empty((batch, rows, cols), dtype=torch.float32, device=dem.device) if want_orograph else None
+    use = torch.empty((batch, rows, cols), dtype=torch.float64, device=dem.device) if threshold is not None else None
+    sx = torch.empty((batch, rows, cols), dtype=torch.float64, device=dem.device) if want_sx else None
+    nat.check(nat.lib().ssrs_updraft_sheltered(
+        nat.ptr(dem), ftype(dem), C.c_double(res), _dptr(ur), _dptr(uc), _dptr(ws0), _dptr(wd0), nat.ptr(ws),
+        nat.ptr(wd), nat.ptr(s), nat.ptr(a), nat.SSRS_F64 if s is None else ftype(s), C.byref(params),
+        C.c_double(min_updraft_val), C.c_double(-1. if threshold is None else threshold), nat.ptr(oro), nat.ptr(use),
+        nat.ptr(sx), rows, cols, batch, stream_ptr()))
+    out = tuple(None if t is None else like_input(t[0] if single else t, z_mat) for t in (oro, use, sx))
+    return out if want_sx else out[:2]

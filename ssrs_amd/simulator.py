@@ -69,6 +69,7 @@ class Simulator(Config):
         else:
             super().__init__(**asdict(in_config))
         self._check_thermal_model()
+        self._check_orographic_model()
         if not float(self.turbine_encounter_radius) >= 0.:
             raise ValueError(f'turbine_encounter_radius = {self.turbine_encounter_radius!r}: expected metres >= 0 (0 = off)')
         print(f'\n---- SSRS in {self.sim_mode} mode')
@@ -231,6 +232,33 @@ class Simulator(Config):
                 raise ValueError("thermal_model = 'wtk' gives ONE thermal field per case: thermals_realization_count must "
                                  f'be 1, not {self.thermals_realization_count!r}')
 
+    def _improved(self):
+        return str(self.orographic_model).lower() == 'improved'
+
+    def _check_orographic_model(self):
+        """The four orographic_* fields, on the host (no device work): ValueError names the one that does not fit."""
+        if str(self.orographic_model).lower() not in ('original', 'improved'):
+            raise ValueError(f"orographic_model = {self.orographic_model!r}: expected 'original' or 'improved'")
+        if self._improved():
+            layers.check_improved_parameters(self.orographic_sx_dmax, self.resolution, self.orographic_height,
+                                             self.orographic_coeffs)
+
+    def _improved_args(self):
+        """Keyword arguments of layers.orographic_updraft_improved for this run.  The shelter ray lives in the frame of
+        the aspect it multiplies: the Horn fallback computed from the DEM alone is transposed (+row = east, +col =
+        north: DESIGN.md K9), injected Slope / Aspect layers are geographic (+row = north, +col = east).  With one layer
+        injected and the other from the DEM, the aspect's frame decides."""
+        given = 'Aspect' in self._terrain
+        args = dict(dmax=float(self.orographic_sx_dmax), height=float(self.orographic_height),
+                    coeffs=tuple(self.orographic_coeffs), ray_axes='row_north' if given else 'row_east', want_sx=True)
+        if 'Slope' in self._terrain or 'Aspect' in self._terrain:
+            args.update(slope=to_dev(self.get_terrain_slope(), torch.float64),
+                        aspect=to_dev(self.get_terrain_aspect(), torch.float64))
+        return args
+
+    def _get_sx_fname(self, case_id: str, dirname: str = './'):
+        return os.path.join(dirname, f'{case_id}_sx')
+
     def _resolve_wtk_layers(self, item):
         """The four thermal layers of one wind entry, host side only: ('raster', None, None, (4, rows, cols)) or
         ('samples', x_km[npts], y_km[npts], (4, npts)) -- a lattice (ny, nx) becomes its meshgrid points, the
@@ -306,7 +334,12 @@ class Simulator(Config):
         print('Computing orographic updrafts..')
         if self.case_ids[0] not in self._cases_written_here():
             return
-        if 'Slope' in self._terrain or 'Aspect' in self._terrain:
+        if self._improved():
+            orograph, _, sx = layers.orographic_updraft_improved(
+                self.get_terrain_elevation(), self.resolution, float(self.uniform_windspeed),
+                float(self.uniform_winddirn), **self._improved_args())
+            np.save(f'{self._get_sx_fname(self.case_ids[0], self.mode_data_dir)}.npy', np.asarray(sx, dtype=np.float32))
+        elif 'Slope' in self._terrain or 'Aspect' in self._terrain:
             orograph = layers.compute_orographic_updraft(
                 float(self.uniform_windspeed), float(self.uniform_winddirn),
                 self.get_terrain_slope(), self.get_terrain_aspect())
@@ -327,7 +360,7 @@ class Simulator(Config):
         # per batch, no per-cell wind rasters, no slope / aspect rasters)
         mine = set(self._cases_written_here())
         wind = [it for it in self._wind if it['case_id'] in mine]
-        lattice = len(wind) > 0 and str(self.wtk_interp_type).lower() == 'linear' and \
+        lattice = not self._improved() and len(wind) > 0 and str(self.wtk_interp_type).lower() == 'linear' and \
             all('x_km' in it and np.ndim(it['wspeed']) == 2 for it in wind) and \
             not ('Slope' in self._terrain or 'Aspect' in self._terrain) and \
             all(np.array_equal(it['x_km'], wind[0]['x_km']) and
@@ -345,8 +378,13 @@ class Simulator(Config):
                     np.save(f'{fname}.npy', o.cpu().numpy())
             print(f'took {_elapsed(start_time)}', flush=True)
             return
-        slope = to_dev(self.get_terrain_slope(), torch.float64)
-        aspect = to_dev(self.get_terrain_aspect(), torch.float64)
+        if self._improved():
+            # the per-cell wind rasters, always (the fused lattice kernel has no shelter ray)
+            dem = to_dev(self.get_terrain_elevation(), torch.float64)
+            improved_args = self._improved_args()
+        else:
+            slope = to_dev(self.get_terrain_slope(), torch.float64)
+            aspect = to_dev(self.get_terrain_aspect(), torch.float64)
         for b0 in range(0, len(wind), batch):
             chunk = wind[b0:b0 + batch]
             ws, wd = [], []
@@ -354,7 +392,13 @@ class Simulator(Config):
                 s, d = self._wind_rasters(item)
                 ws.append(s)
                 wd.append(d)
-            oro, _ = layers.orographic_updraft(torch.stack(ws), torch.stack(wd), slope, aspect)
+            if self._improved():
+                oro, _, sx = layers.orographic_updraft_improved(dem, self.resolution, torch.stack(ws), torch.stack(wd),
+                                                                **improved_args)
+                for item, x in zip(chunk, sx):
+                    np.save(f"{self._get_sx_fname(item['case_id'], self.mode_data_dir)}.npy", x.to(torch.float32).cpu().numpy())
+            else:
+                oro, _ = layers.orographic_updraft(torch.stack(ws), torch.stack(wd), slope, aspect)
             for item, o in zip(chunk, oro):
                 fname = self._get_orograph_fname(item['case_id'], self.mode_data_dir)
                 np.save(f'{fname}.npy', o.cpu().numpy())
@@ -515,8 +559,12 @@ class Simulator(Config):
 
     def _get_id_string(self, case_id: str, real_id=None):
         """simulator.py:290-298: <case>_d<dir>_t<thr*100>_<model>[_r<k>]."""
+        model = self.movement_model
+        if self._improved():
+            # (a cached potential of the original model must never be picked up for the improved one)
+            model = f'{self.movement_model}-sx{int(self.orographic_sx_dmax)}h{int(self.orographic_height)}'
         out_str = (f'{case_id}_d{int(self.track_direction % 360)}'
-                   f'_t{int(self.updraft_threshold * 100)}_{self.movement_model}')
+                   f'_t{int(self.updraft_threshold * 100)}_{model}')
         if real_id is not None:
             out_str += f'_r{int(real_id)}'
         return out_str
