@@ -616,6 +616,67 @@ int ssrs_updraft_sheltered(const void *dem, int dem_type, double res, const doub
                            double min_updraft_val, double threshold, float *orograph, double *usable,
                            double *sx_deg, int rows, int cols, int batch, void *stream);
 
+/* ---------------------------------------------------------------- georef */
+
+/* K10 -- Albers Equal Area Conic on an ellipsoid (Snyder, USGS PP 1395, eqs. 14-12 ... 14-21, 3-12, 3-16) and the
+ * warp of a longitude / latitude raster onto the projected grid.  With e = sqrt(e2), angles in radians inside:
+ *   q(phi) = (1 - e2) (sin phi / (1 - e2 sin^2 phi) - (1 / (2 e)) ln((1 - e sin phi) / (1 + e sin phi)))
+ *   m(phi) = cos phi / sqrt(1 - e2 sin^2 phi)
+ *   n = (m1^2 - m2^2) / (q2 - q1) (sin lat_1 when lat_1 = lat_2),  C = m1^2 + n q1,  rho0 = a sqrt(C - n q0) / n
+ *   forward: rho = a sqrt(C - n q(phi)) / n, theta = n (lambda - lon_0), x = x_0 + rho sin theta,
+ *            y = y_0 + rho0 - rho cos theta
+ *   inverse: X = x - x_0, Y = rho0 - (y - y_0), rho = sqrt(X^2 + Y^2), theta = atan2(X, Y) (of -X, -Y for n < 0),
+ *            qv = (C - (rho n / a)^2) / n, lambda = lon_0 + theta / n, phi from asin(clamp(qv / 2, -1, 1)) by a FIXED
+ *            number of iterations of eq. 3-16 (ssrs_amd/csrc/georef.h), no contraction anywhere. */
+typedef struct SsrsProjection {
+    /* inputs */
+    double a;     /* semi-major axis, metres */
+    double e2;    /* eccentricity squared, in (0, 1) */
+    double lat_1; /* standard parallels, degrees */
+    double lat_2;
+    double lat_0; /* origin, degrees */
+    double lon_0;
+    double x_0; /* false easting / northing, metres */
+    double y_0;
+    /* derived: filled by the init call below */
+    double n;
+    double C;
+    double rho0;
+    double e;
+} SsrsProjection;
+
+/* [host] fills n, C, rho0, e.  a <= 0, e2 outside (0, 1), |n| < 1e-12 (lat_1 = -lat_2: the cylindrical limit) or a
+ * non-finite field -> SSRS_ERR_INVALID.  No GPU work. */
+int ssrs_projection_init_albers(SsrsProjection *proj);
+
+/* rasterio's reproject (bilinear) of the reference's get_raster_in_projected_crs (ssrs/raster.py:12-49) for a
+ * source on a regular longitude / latitude grid: every destination cell gets the exact inverse projection of its
+ * centre and one bilinear gather.
+ *   src, src_type   (src_rows, src_cols) SSRS_F32 / _F64; pixel (i, j) has its centre at (lon0 + j dlon, lat0 + i dlat)
+ *                   degrees.  dlon, dlat are signed: dlat < 0 is a north-up source (the GeoTIFF order), read in place.
+ *                   NULL is allowed when dst is NULL
+ *   nodata          source values equal to it count as missing, as NaN pixels always do; NaN = no such value
+ *   proj            [host] an initialised SsrsProjection (passed on to the kernel by value)
+ *   west, south, res  centre of destination cell (0, 0) and the cell size, metres; destination row 0 = south
+ *   dst, dst_type   (rows, cols) SSRS_F32 / _F64 or NULL
+ *   lon, lat        (rows, cols) f64 or NULL: the inverse projection of the cell centres itself, degrees
+ *   uncovered       uint64, 1 value, or NULL: ACCUMULATED count of the cells of dst that got NaN (zero it first)
+ * Cell (r, c): x = west + c res, y = south + r res, (lambda, phi) by the inverse above, fc = (lambda - lon0) / dlon,
+ * fr = (phi - lat0) / dlat.  Covered iff 0 <= fr <= src_rows - 1 and 0 <= fc <= src_cols - 1.  i = floor(fr),
+ * j = floor(fc), both lowered to src_rows - 2 / src_cols - 2 at the far edge; tr = fr - i, tc = fc - j;
+ *   v = (z[i,j] (1 - tc) + z[i,j+1] tc) (1 - tr) + (z[i+1,j] (1 - tc) + z[i+1,j+1] tc) tr
+ * in f64 (the order of zs above), then rounded to dst_type; a neighbour whose weight is exactly 0 is not read and
+ * enters as 0.0.  A neighbour of non-zero weight that is NaN or equals nodata makes the cell NaN, and so does a cell
+ * that is not covered; both count in *uncovered (one atomic per wave).  Nothing is counted when dst is NULL.
+ * Asynchronous on `stream`.  dst, lon and lat all NULL, src NULL with dst given, a NULL proj or one that was not
+ * initialised, rows / cols outside [1, 32767], src_rows / src_cols < 2, dlon or dlat 0, res <= 0, a type selector
+ * that is neither SSRS_F32 nor SSRS_F64, a non-finite lon0 / lat0 / dlon / dlat / west / south / res or an infinite
+ * nodata -> SSRS_ERR_INVALID before any GPU work. */
+int ssrs_warp_lonlat_raster(const void *src, int src_type, int src_rows, int src_cols, double lon0, double lat0,
+                            double dlon, double dlat, double nodata, const SsrsProjection *proj, double west,
+                            double south, double res, void *dst, int dst_type, double *lon, double *lat,
+                            unsigned long long *uncovered, int rows, int cols, void *stream);
+
 /* -------------------------------------------------------------- potential */
 
 typedef struct SsrsSolveStats {

@@ -6,6 +6,7 @@ from .config import Config
 from .simulator import Simulator
 from .layers import (compute_orographic_updraft, compute_slope_degrees,
                      compute_aspect_degrees, get_above_threshold_speed)
+from .georef import Projection, LonLatRaster, warp_to_grid
 
 __all__ = ['Config', 'Simulator', 'compute_orographic_updraft', 'compute_slope_degrees',
-           'compute_aspect_degrees', 'get_above_threshold_speed']
+           'compute_aspect_degrees', 'get_above_threshold_speed', 'Projection', 'LonLatRaster', 'warp_to_grid']

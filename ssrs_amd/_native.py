@@ -47,6 +47,7 @@ EXPORTS = (
     'ssrs_potential_workspace_bytes', 'ssrs_potential_solve',
     'ssrs_turbine_encounters', 'ssrs_turbine_encounter_counts',
     'ssrs_shelter_sx', 'ssrs_updraft_sheltered',
+    'ssrs_projection_init_albers', 'ssrs_warp_lonlat_raster',
 )
 
 
@@ -79,6 +80,11 @@ class SsrsSolveStats(C.Structure):
 class SsrsShelterParams(C.Structure):
     _fields_ = [('dmax', C.c_double), ('ray_axes', C.c_int32), ('path', C.c_int32), ('height', C.c_double),
                 ('coef', C.c_double * 7)]
+
+
+class SsrsProjection(C.Structure):
+    _fields_ = [(name, C.c_double) for name in ('a', 'e2', 'lat_1', 'lat_2', 'lat_0', 'lon_0', 'x_0', 'y_0',
+                                                'n', 'C', 'rho0', 'e')]
 
 
 class SsrsError(RuntimeError):
@@ -164,6 +170,10 @@ def lib():
         L.ssrs_updraft_sheltered.argtypes = [C.c_void_p, C.c_int, C.c_double] + [C.c_void_p] * 8 + \
             [C.c_int, C.POINTER(SsrsShelterParams), C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
              C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.ssrs_projection_init_albers.argtypes = [C.POINTER(SsrsProjection)]
+        L.ssrs_warp_lonlat_raster.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_double] * 5 + \
+            [C.POINTER(SsrsProjection)] + [C.c_double] * 3 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                             C.c_int, C.c_int, C.c_void_p]
         _lib = L
     return _lib
 

@@ -59,8 +59,12 @@ class Simulator(Config):
         With thermal_model='wtk' every entry also carries 'pressure', 'temperature',
         'blheight' and 'surfheatflux' (the keys of `wtk_layers`), all four as (rows, cols)
         rasters, as samples (npts,) at x_km / y_km, or on the lattice (ny, nx).
-        origin: projected (west, south) of cell (0, 0); the reference derives it
-        from southwest_lonlat through GDAL (simulator.py:77-85).
+        origin: projected (west, south) of cell (0, 0), or 'southwest_lonlat': the image of
+        `southwest_lonlat` under `projected_crs` (an Albers projection, ssrs_amd/georef.py), as the
+        reference derives it through GDAL (simulator.py:77-85); `projection` and `lonlat_bounds` are
+        then set, and inputs in degrees are accepted: terrain=LonLatRaster(...) (warped to the grid
+        on the device), turbines with the USWTDB columns `xlong`, `ylat` instead of `x`, `y`, and
+        wind entries with 'lon', 'lat' instead of 'x_km', 'y_km'.
         turbines: a `Turbines`, a dict of columns or a DataFrame with `x`, `y` in the projected frame of
         `origin` (optionally `p_name`, `t_hh`, `t_rd`): the stand-in for the reference's USWTDB download
         (simulator.py:101-105), filtered to `bounds` and `turbine_minimum_hubheight` like it."""
@@ -94,11 +98,25 @@ class Simulator(Config):
         ysize = int(round((self.region_width_km[1] * 1000. / self.resolution)))
         self.gridsize = (ysize, xsize)
         print(f'Terrain grid size = {self.gridsize}')
-        west, south = float(origin[0]), float(origin[1])
+        self.projection = None
+        if isinstance(origin, str):
+            if origin != 'southwest_lonlat':
+                raise ValueError(f"origin = {origin!r}: expected a pair (west, south) or 'southwest_lonlat'")
+            # simulator.py:77-82: the projected image of the south-west corner
+            from .georef import Projection
+            self.projection = Projection.from_crs(self.projected_crs)
+            west, south = (float(v) for v in self.projection.forward(*self.southwest_lonlat))
+        else:
+            west, south = float(origin[0]), float(origin[1])
         self.bounds = (west, south, west + (xsize - 1) * self.resolution,
                        south + (ysize - 1) * self.resolution)
         self.extent = (self.bounds[0], self.bounds[2], self.bounds[1], self.bounds[3])
-        self.lonlat_bounds = None          # needs GDAL/PROJ; out of scope
+        self.lonlat_bounds = None          # known only with origin='southwest_lonlat'
+        if self.projection is not None:
+            # transform_bounds, raster.py:52-84: the four corners, then min and max
+            lon, lat = self.projection.inverse([self.bounds[0], self.bounds[0], self.bounds[2], self.bounds[2]],
+                                               [self.bounds[1], self.bounds[3], self.bounds[1], self.bounds[3]])
+            self.lonlat_bounds = [float(lon.min()), float(lat.min()), float(lon.max()), float(lat.max())]
 
         self.terrain_layers = {'Elevation': 'DEM', 'Slope': 'Slope Degrees',
                                'Aspect': 'Aspect Degrees'}
@@ -147,6 +165,20 @@ class Simulator(Config):
                 'Terrain download (USGS 3DEP / SRTM, simulator.py:88-99) is outside the '
                 "hot-path scope: pass terrain='synthetic', an elevation array, a dict "
                 "{'Elevation': ..., 'Slope': ..., 'Aspect': ...} or a callable.")
+        from .georef import LonLatRaster
+        if isinstance(terrain, LonLatRaster):
+            # get_raster_in_projected_crs (raster.py:12-49) on the device; slope and aspect then come from the
+            # Horn path, as in the reference when only the elevation could be had (simulator.py:152-159)
+            from .georef import warp_to_grid
+            projection = self._need_projection('terrain=LonLatRaster(...)')
+            dem, uncovered = warp_to_grid(terrain, projection, self.bounds[0], self.bounds[1], self.gridsize,
+                                          self.resolution)
+            if uncovered > 0:
+                raise ValueError(
+                    f'terrain: {uncovered} of the {self.gridsize[0] * self.gridsize[1]} cells are not covered by the '
+                    f'longitude / latitude raster (its pixel centres span {terrain.lonlat_bounds}) or need a missing '
+                    f'pixel; the region needs lonlat_bounds = {self.lonlat_bounds}')
+            terrain = dem
         if isinstance(terrain, str):
             if terrain != 'synthetic':
                 raise ValueError(f'unknown terrain provider {terrain!r}')
@@ -168,10 +200,22 @@ class Simulator(Config):
             raise ValueError("terrain needs an 'Elevation' layer")
         return out
 
+    def _need_projection(self, what):
+        """The projection of a georeferenced run; ValueError for an input in degrees when the origin is numeric."""
+        if self.projection is None:
+            raise ValueError(f"{what} is given in longitude / latitude and needs the georeferenced origin: "
+                             "Simulator(..., origin='southwest_lonlat') places cell (0, 0) at the projected image "
+                             f'(projected_crs = {self.projected_crs!r}) of southwest_lonlat; a numeric origin says '
+                             'nothing about where the grid lies on the ellipsoid')
+        return self.projection
+
     def _resolve_turbines(self, turbines):
         """The injected turbines inside `bounds` at or above `turbine_minimum_hubheight` (None stays None); with
         turbine_encounter_radius > 0 also their cell coordinates and the cull lists of the encounter kernel."""
         radius = float(self.turbine_encounter_radius)
+        if turbines is not None and turbines_mod.has_lonlat_only(turbines):
+            # the USWTDB columns, projected as turbines.py:52-62 of the reference does
+            turbines = turbines_mod.with_projected_columns(turbines, self._need_projection('turbines= (xlong, ylat)'))
         if turbines is not None:
             turbines = turbines_mod.Turbines(turbines, self.bounds, float(self.turbine_minimum_hubheight),
                                              bool(self.print_verbose))
@@ -202,6 +246,8 @@ class Simulator(Config):
                     raise ValueError("each wind entry needs 'datetime' or 'case_id'")
                 item['case_id'] = dt.strftime(self.time_format)       # simulator.py:126
             item['datetime'] = dt
+            if 'lon' in item or 'lat' in item:
+                self._project_wind_samples(item)
             out.append(item)
         if any('x_km' in it for it in out):
             # the reference hands wtk_interp_type to scipy's griddata ('nearest' | 'linear' | 'cubic',
@@ -217,6 +263,33 @@ class Simulator(Config):
         return out
 
     THERMAL_LAYERS = ('pressure', 'temperature', 'blheight', 'surfheatflux')      # keys of wtk_layers
+
+    def _project_wind_samples(self, item):
+        """A wind entry whose samples sit at 'lon', 'lat' (degrees) instead of 'x_km', 'y_km': the WTK points as
+        they are delivered.  Scattered points (npts,) or the axes (nx,), (ny,) of a lattice whose arrays are
+        (ny, nx).  The points are projected and become scattered samples in kilometres from the centre of cell
+        (0, 0) -- a lattice in degrees is no lattice on the projected grid -- and `item` is rewritten in place."""
+        case = item['case_id']
+        if 'x_km' in item or 'y_km' in item:
+            raise ValueError(f"{case}: the wind samples have both 'lon' / 'lat' and 'x_km' / 'y_km': give one pair")
+        if 'lon' not in item or 'lat' not in item:
+            raise ValueError(f"{case}: wind samples in degrees need both 'lon' and 'lat'")
+        projection = self._need_projection(f"{case}: wind samples at 'lon', 'lat'")
+        lon = np.asarray(item.pop('lon'), dtype=np.float64).ravel()
+        lat = np.asarray(item.pop('lat'), dtype=np.float64).ravel()
+        fields = [name for name in ('wspeed', 'wdirn') + self.THERMAL_LAYERS if item.get(name) is not None]
+        if any(np.ndim(item[name]) == 2 and np.shape(item[name]) == (lat.size, lon.size) for name in fields):
+            for name in fields:
+                if np.shape(item[name]) == (lat.size, lon.size):
+                    val = item[name]
+                    item[name] = np.asarray(val.cpu() if isinstance(val, torch.Tensor) else val, dtype=np.float64).ravel()
+            lon, lat = (a.ravel() for a in np.meshgrid(lon, lat))
+        elif lon.size != lat.size:
+            raise ValueError(f"{case}: 'lon' has {lon.size} values and 'lat' {lat.size}: scattered samples need as many "
+                             'of each, a lattice arrays of shape (lat, lon)')
+        x, y = projection.forward(lon, lat)
+        item['x_km'] = (x - self.bounds[0]) / 1000.
+        item['y_km'] = (y - self.bounds[1]) / 1000.
 
     def _wtk_thermals(self):
         return str(self.thermal_model).lower() == 'wtk'

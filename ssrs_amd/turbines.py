@@ -1,5 +1,6 @@
 """Wind turbines (K8 host side): `Turbines`, the injected stand-in for the reference's TurbinesUSWTB
-(ssrs/turbines.py there; the USWTDB download and the CRS transform stay out of scope), and the
+(ssrs/turbines.py there; the USWTDB download stays out of scope, its `xlong` / `ylat` columns are projected by
+`with_projected_columns` in a georeferenced run), and the
 encounter pass of the trajectories against them -- which simulated tracks came within R of which turbine, and
 after how many moves (include/ssrs_hip.h "turbines").
 """
@@ -100,6 +101,34 @@ class Turbines:
             if name in self.columns:
                 v = np.asarray(self.columns[name], dtype=np.float64)
                 print(f'{label} (min,median,max): {v.min()}, {np.median(v)}, {v.max()}')
+
+
+def _column_names(data):
+    if isinstance(data, Turbines):
+        return list(data.columns)
+    if isinstance(data, dict) or (hasattr(data, 'columns') and hasattr(data, 'to_numpy')):
+        return [str(name) for name in (data if isinstance(data, dict) else data.columns)]
+    return []
+
+
+def has_lonlat_only(data):
+    """A table with the USWTDB position columns `xlong`, `ylat` (degrees) and neither `x` nor `y`."""
+    names = _column_names(data)
+    return 'xlong' in names and 'ylat' in names and 'x' not in names and 'y' not in names
+
+
+def with_projected_columns(data, projection):
+    """The columns of such a table plus `x`, `y` = projection.forward(xlong, ylat), as a dict (turbines.py:52-62 of
+    the reference); the degrees are carried along."""
+    if isinstance(data, Turbines):
+        data = data.columns
+    cols = {name: np.asarray(data[name].to_numpy() if hasattr(data[name], 'to_numpy') else data[name])
+            for name in _column_names(data)}
+    lon, lat = (np.asarray(cols[name], dtype=np.float64).reshape(-1) for name in ('xlong', 'ylat'))
+    if lon.shape != lat.shape:
+        raise ValueError(f'turbines: xlong has {lon.size} values, ylat {lat.size}')
+    cols['x'], cols['y'] = projection.forward(lon, lat)
+    return cols
 
 
 def windplant_window(xloc, yloc, pad, bounds, resolution, gridsize):

@@ -1,0 +1,202 @@
+"""K10 on the device: ssrs_warp_lonlat_raster against the NumPy restatement (tests/warp_ref.py, ssrs_amd/georef.py).
+
+Shapes: destinations 37 x 53 (scalar tail) and 40 x 64 (vector stores), sources 41 x 29 and 64 x 48, f32 and f64,
+south-up and north-up.  Three comparisons, from the sharpest to the widest:
+  * lon / lat against Projection.inverse: 1e-11 degrees (libm against the device's functions);
+  * dst against the bilinear rule evaluated at the DEVICE's own (fr, fc): one ulp of the output type -- the gather and
+    the weights alone;
+  * dst against the full CPU restatement: (1e-11 / |dlon| + 1e-11 / |dlat|) x (max - min of the four neighbours)
+    plus one output ulp, the 1e-11 degrees of the first comparison carried through a bilinear patch.
+Cells whose CPU (fr, fc) lies within 1e-6 px of the source's edge are left out of the last one and of the coverage
+counts (rounding may decide on which side they fall); they are at most 0.1 % of the cells, which the unmarked test
+checks without a GPU."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from ssrs_amd import _native as nat
+from ssrs_amd.georef import LonLatRaster, Projection, warp_to_grid
+from warp_ref import Geometry, bilinear_ref, geometries, pixel_coordinates
+
+DEG = 1e-11
+TORCH = {np.float32: torch.float32, np.float64: torch.float64}
+
+
+def _ulp(want, dtype):
+    return np.spacing(np.abs(want).astype(dtype)).astype(np.float64)
+
+
+def _warp(geo, raster, out_dtype=torch.float64, **kw):
+    return warp_to_grid(raster, geo.proj, geo.west, geo.south, geo.shape, geo.res, out_dtype=out_dtype, **kw)
+
+
+def test_geometries_keep_clear_of_the_source_edge():
+    """The CPU restatement alone: covered geometries are covered, overhanging ones are not, and the cells within
+    1e-6 px of the source's edge stay under 0.1 % in both."""
+    for holes in (False, True):
+        for geo in geometries(overhang=holes):
+            val, _, edge = geo.cpu(geo.raster())
+            assert edge.mean() <= 1e-3
+            assert bool(np.isnan(val).any()) == holes
+            if holes:
+                assert 0.1 < np.isnan(val).mean() < 0.9
+
+
+@pytest.mark.gpu
+def test_inverse_gather_and_full_chain(gpu):
+    for geo in geometries():
+        base = None
+        for src_dtype in (np.float64, np.float32):
+            for out_dtype in (np.float64, np.float32):
+                for north_up in (False, True):
+                    raster = geo.raster(src_dtype, north_up)
+                    dst, lon, lat, uncovered = _warp(geo, raster, TORCH[out_dtype], want_lonlat=True)
+                    assert dst.dtype == TORCH[out_dtype] and tuple(dst.shape) == geo.shape and uncovered == 0
+                    dst, lon, lat = dst.cpu().numpy(), lon.cpu().numpy(), lat.cpu().numpy()
+                    err = max(np.abs(lon - geo.lon).max(), np.abs(lat - geo.lat).max())
+                    print(f'{geo.shape} <- {raster.shape} {src_dtype.__name__}->{out_dtype.__name__} north_up={north_up}: '
+                          f'lon/lat {err:.2e} deg', end='')
+                    assert err <= DEG
+                    # the gather alone, at the device's own pixel coordinates
+                    want, _ = bilinear_ref(raster.data, *pixel_coordinates(raster, lon, lat))
+                    off = np.abs(dst.astype(np.float64) - want.astype(out_dtype).astype(np.float64))
+                    print(f', gather {np.max(off / _ulp(want, out_dtype)):.2f} ulp', end='')
+                    assert np.all(off <= _ulp(want, out_dtype))
+                    # the whole chain on the CPU
+                    cpu, spread, edge = geo.cpu(raster)
+                    tol = (DEG / abs(raster.dlon) + DEG / abs(raster.dlat)) * spread + _ulp(cpu, out_dtype)
+                    off = np.abs(dst.astype(np.float64) - cpu.astype(out_dtype).astype(np.float64))
+                    print(f', chain {np.max((off / tol)[~edge]):.2f} of its tolerance')
+                    assert edge.mean() <= 1e-3 and np.all(off[~edge] <= tol[~edge])
+                    # the north-up source is the same raster: the same bits
+                    if not north_up:
+                        base = dst
+                    else:
+                        assert np.array_equal(dst.view(np.uint8), base.view(np.uint8))
+
+
+@pytest.mark.gpu
+def test_outputs_may_be_left_out(gpu):
+    """dst alone, lon / lat alone (without a source): the same values as the call that asks for everything."""
+    geo = Geometry((37, 53), (41, 29))
+    raster, proj = geo.raster(np.float32), geo.proj.as_struct()
+    dst, lon, lat, _ = _warp(geo, raster, want_lonlat=True)
+    alone, _ = _warp(geo, raster)
+    assert torch.equal(alone, dst)
+    lon2, lat2 = torch.full_like(lon, -1.), torch.full_like(lat, -1.)
+    for a, b in ((lon2, None), (None, lat2)):
+        nat.check(nat.lib().ssrs_warp_lonlat_raster(
+            None, nat.SSRS_F32, 41, 29, raster.lon0, raster.lat0, raster.dlon, raster.dlat, float('nan'), C.byref(proj),
+            geo.west, geo.south, geo.res, None, nat.SSRS_F64, nat.ptr(a), nat.ptr(b), None, 37, 53, None))
+    torch.cuda.synchronize()
+    assert torch.equal(lon2, lon) and torch.equal(lat2, lat)
+
+
+@pytest.mark.gpu
+def test_overhang_is_nan_and_counted(gpu):
+    for geo in geometries(overhang=True):
+        for north_up in (False, True):
+            raster = geo.raster(np.float64, north_up)
+            cpu, _, edge = geo.cpu(raster)
+            counter = torch.zeros(1, dtype=torch.int64, device=gpu)
+            dst, count = _warp(geo, raster, torch.float32, uncovered=counter)
+            holes = torch.isnan(dst).cpu().numpy()
+            assert np.array_equal(holes[~edge], np.isnan(cpu)[~edge])
+            assert count == int(holes.sum()) and abs(count - int(np.isnan(cpu).sum())) <= int(edge.sum())
+            assert 0 < count < holes.size
+            _, again = _warp(geo, raster, torch.float32, uncovered=counter)          # accumulated, not overwritten
+            assert again == 2 * count and int(counter.item()) == 2 * count
+
+
+@pytest.mark.gpu
+def test_missing_pixels_poison_exactly_the_cells_that_read_them(gpu):
+    rng = np.random.default_rng(5)
+    for geo in geometries():
+        values = geo.values.copy()
+        lost = rng.random(values.shape) < 0.04
+        values[lost] = np.where(rng.random(int(lost.sum())) < 0.5, -9999., np.nan)
+        for dtype in (np.float32, np.float64):
+            raster = geo.raster(dtype, values=values, nodata=-9999.)
+            dst, lon, lat, count = _warp(geo, raster, TORCH[dtype], want_lonlat=True)
+            dst = dst.cpu().numpy()
+            want, _ = bilinear_ref(raster.data, *pixel_coordinates(raster, lon.cpu().numpy(), lat.cpu().numpy()), nodata=-9999.)
+            assert np.array_equal(np.isnan(dst), np.isnan(want))
+            assert 0 < count == int(np.isnan(want).sum()) < want.size
+            ok = ~np.isnan(want)
+            assert np.all(np.abs(dst.astype(np.float64) - want.astype(dtype))[ok] <= _ulp(want, dtype)[ok])
+            # without the nodata value only the NaN pixels are missing, and -9999 is a height like any other
+            plain, fewer = _warp(geo, geo.raster(dtype, values=values), TORCH[dtype])
+            assert 0 < fewer < count and int(torch.isnan(plain).sum()) == fewer
+
+
+@pytest.mark.gpu
+def test_a_missing_neighbour_of_weight_zero_is_not_read(gpu):
+    """Destination cell (0, 0) exactly on the centre of source pixel (2, 3): the device's own longitude / latitude of
+    that cell, minus whole dyadic steps, is the source's origin, so that fr = 2 and fc = 3 exactly.  Its three other
+    neighbours are missing and must not poison it; the cells around it, which do read them, are NaN."""
+    geo = Geometry((37, 53), (41, 29))
+    _, lon, lat, _ = _warp(geo, geo.raster(), want_lonlat=True)
+    lon00, lat00 = float(lon[0, 0]), float(lat[0, 0])
+    step = 1. / 256.                              # about 320 m x 430 m: finer than the 400 m cells
+    for north_up in (False, True):
+        for nodata, hole in ((None, np.nan), (-9999., -9999.)):
+            data = np.fromfunction(lambda i, j: 100. + 7. * i + 3. * j, (16, 16))
+            data[2, 4] = data[3, 3] = data[3, 4] = hole
+            raster = LonLatRaster(data, lon00 - 3 * step, lat00 - 2 * step, step, step, nodata)
+            assert pixel_coordinates(raster, lon00, lat00) == (2., 3.)
+            if north_up:
+                raster = LonLatRaster(np.ascontiguousarray(data[::-1]), raster.lon0, raster.lat0 + 15 * step, step, -step, nodata)
+                assert pixel_coordinates(raster, lon00, lat00) == (13., 3.)
+            dst, count = _warp(geo, raster, torch.float64)
+            assert float(dst[0, 0]) == data[2, 3] == 123. and count > 0
+            assert bool(torch.isnan(dst[0, 1])) and bool(torch.isnan(dst[1, 0]))
+
+
+def _refusals():
+    nan, inf = float('nan'), float('inf')
+    good = dict(src=1, src_type=nat.SSRS_F32, src_rows=41, src_cols=29, lon0=-106.5, lat0=42.5, dlon=1 / 64, dlat=1 / 64,
+                nodata=nan, proj=1, west=-8e5, south=3e5, res=400., dst=1, dst_type=nat.SSRS_F64, lon=1, lat=1,
+                uncovered=1, rows=37, cols=53)
+    cases = [(dict(proj=0), 'proj is NULL'), (dict(dst=0, lon=0, lat=0), 'all NULL'), (dict(src=0), 'src is NULL'),
+             (dict(rows=0), 'rows'), (dict(rows=32768), 'rows'), (dict(cols=0), 'cols'), (dict(cols=40000), 'cols'),
+             (dict(src_rows=1), 'source'), (dict(src_cols=1), 'source'), (dict(dlon=0.), 'dlon'), (dict(dlat=0.), 'dlat'),
+             (dict(res=0.), 'res'), (dict(res=-400.), 'res'), (dict(src_type=2), 'src_type'), (dict(dst_type=-1), 'dst_type'),
+             (dict(proj='raw'), 'not initialised')]
+    cases += [({name: bad}, 'non-finite') for name in ('lon0', 'lat0', 'dlon', 'dlat', 'west', 'south', 'res')
+              for bad in (nan, inf)]
+    cases += [(dict(nodata=inf), 'non-finite'), (dict(nodata=-inf), 'non-finite')]
+    return good, cases
+
+
+def test_refused_arguments_launch_nothing():
+    """Every refusal is SSRS_ERR_INVALID with a message, before any GPU work: this test runs without a GPU as well,
+    and with one the output buffers keep what was in them."""
+    lib = nat.lib()
+    on_gpu = torch.cuda.is_available()
+    proj = Projection.from_crs('ESRI:102008').as_struct()
+    raw = nat.SsrsProjection(*[getattr(proj, f) for f in Projection.FIELDS[:8]])         # derived fields left 0
+    if on_gpu:
+        src = torch.zeros((41, 29), dtype=torch.float32, device='cuda')
+        outs = [torch.full((37, 53), 7., dtype=torch.float64, device='cuda') for _ in range(3)]
+        counter = torch.zeros(1, dtype=torch.int64, device='cuda')
+        address = dict(src=src.data_ptr(), dst=outs[0].data_ptr(), lon=outs[1].data_ptr(), lat=outs[2].data_ptr(),
+                       uncovered=counter.data_ptr())
+    else:
+        # never dereferenced: the call is refused first (and without a device nothing could be launched)
+        address = dict(src=4096, dst=8192, lon=12288, lat=16384, uncovered=20480)
+    good, cases = _refusals()
+    for change, word in cases:
+        a = {**good, **change}
+        ptrs = {k: C.c_void_p(address[k] if a[k] else 0) for k in address}
+        p = {0: None, 1: C.byref(proj), 'raw': C.byref(raw)}[a['proj']]
+        rc = lib.ssrs_warp_lonlat_raster(ptrs['src'], a['src_type'], a['src_rows'], a['src_cols'], a['lon0'], a['lat0'],
+                                         a['dlon'], a['dlat'], a['nodata'], p, a['west'], a['south'], a['res'],
+                                         ptrs['dst'], a['dst_type'], ptrs['lon'], ptrs['lat'], ptrs['uncovered'],
+                                         a['rows'], a['cols'], None)
+        message = lib.ssrs_last_error().decode()
+        assert rc == nat.SSRS_ERR_INVALID and 'ssrs_warp_lonlat_raster' in message and word in message, (change, rc, message)
+    if on_gpu:
+        torch.cuda.synchronize()
+        assert all(bool((t == 7.).all()) for t in outs) and int(counter.item()) == 0
