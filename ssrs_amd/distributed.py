@@ -8,8 +8,48 @@ single-GPU run bit for bit.  The one exchange step is a sum-reduce of the
 uint32 presence histogram (120 MB at 5000 x 6000) -- RCCL over xGMI when the
 process group is 'nccl', gloo in the CPU tests.
 """
+import numpy as np
 import torch
 import torch.distributed as dist
+
+
+def is_on():
+    return dist.is_available() and dist.is_initialized()
+
+
+def rank():
+    return dist.get_rank() if is_on() else 0
+
+
+def world_size():
+    return dist.get_world_size() if is_on() else 1
+
+
+def barrier():
+    if world_size() > 1:
+        dist.barrier()
+
+
+def _collective(arr, call):
+    """`call(tensor)` on a copy of the numpy array `arr` (the device follows the backend: the GPU for 'nccl', else the
+    host); returns numpy of the same dtype.  Without a process group, or with one rank, `arr` as it is."""
+    arr = np.asarray(arr)
+    if world_size() == 1:
+        return arr
+    dev = torch.device('cuda', torch.cuda.current_device()) if dist.get_backend() == 'nccl' else torch.device('cpu')
+    t = torch.from_numpy(arr.copy()).to(dev)
+    call(t)
+    return t.cpu().numpy()
+
+
+def broadcast(arr, src=0):
+    """The numpy array `arr` of rank `src`, on every rank."""
+    return _collective(arr, lambda t: dist.broadcast(t, src=src))
+
+
+def all_reduce_sum(arr):
+    """Sum over the ranks of the numpy array `arr`, on every rank."""
+    return _collective(arr, lambda t: dist.all_reduce(t, op=dist.ReduceOp.SUM))
 
 
 def shard_range(ntracks, rank, world_size):
@@ -25,7 +65,7 @@ def shard_cases(case_ids, rank=None, world_size=None, group=None):
     tracks), and only the per-case normalised presence sums are exchanged.  Without a
     process group every case stays here."""
     if rank is None or world_size is None:
-        if not (dist.is_available() and dist.is_initialized()):
+        if not is_on():
             return list(case_ids)
         rank, world_size = dist.get_rank(group), dist.get_world_size(group)
     lo, hi = shard_range(len(case_ids), rank, world_size)
@@ -36,7 +76,7 @@ def reduce_presence_sum(summary, group=None):
     """Sum of the per-case normalised presence maps (f64) over ranks, on every rank:
     the one exchange step of seasonal mode (120-240 MB at 5000 x 6000).  The following
     /max of plot_presence_map (simulator.py:546) is then the same on all ranks."""
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+    if not is_on() or dist.get_world_size(group) == 1:
         return summary
     dist.all_reduce(summary, op=dist.ReduceOp.SUM, group=group)
     return summary
@@ -87,7 +127,7 @@ def reduce_histogram(hist, dst=0, group=None, all_ranks=False, async_op=False, g
     next batch's stepper launches; ``wait()`` orders the current stream after it and
     ``handle.result`` is the tensor that holds the sum (the caller must not touch `hist`
     before ``wait()``).  With guard=False every rank must pass the same dtype."""
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+    if not is_on() or dist.get_world_size(group) == 1:
         return None if async_op else hist
 
     def run(t, **kw):
@@ -123,7 +163,7 @@ def reduce_histogram(hist, dst=0, group=None, all_ranks=False, async_op=False, g
 
 def gather_track_summaries(lengths, ends, dst=0, group=None):
     """Optional: lengths/endpoints of every shard on `dst` (8 B per track)."""
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+    if not is_on() or dist.get_world_size(group) == 1:
         return [lengths], [ends]
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)

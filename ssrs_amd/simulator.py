@@ -19,13 +19,12 @@ import os
 import pickle
 import time
 from dataclasses import asdict
-from datetime import datetime
 
 import numpy as np
 import torch
 
 from .config import Config
-from . import layers, movmodel, presence
+from . import distributed, inputs, layers, movmodel, presence
 from . import turbines as turbines_mod
 from . import potential as potential_mod
 from ._device import to_dev
@@ -132,14 +131,16 @@ class Simulator(Config):
             'surfheatflux': 'surface_heat_flux',
         }
         self._presence_counts = {}        # (case_id, real_id) -> device histogram
+        self._nearest_index = (None, None)    # ('nearest': the sample points and their index raster, per wind geometry)
 
         if self.sim_mode.lower() != 'uniform':
             if wind is None:
                 raise ValueError(f'{self.sim_mode} mode needs injected wind data (wind=[...]); '
                                  'the WIND Toolkit download is out of scope')
-            self._wind = self._resolve_wind(wind)
-            self.dtimes = [w['datetime'] for w in self._wind]
-            self.case_ids = [w['case_id'] for w in self._wind]
+            self._wind = inputs.resolve_wind(wind, self.sim_mode, self.time_format, self.gridsize, self.wtk_interp_type,
+                                             self._wtk_thermals(), self.wtk_layers, self._wind_km)
+            self.dtimes = [w.datetime for w in self._wind]
+            self.case_ids = [w.case_id for w in self._wind]
             self.compute_orographic_updrafts_using_wtk()
         else:
             print(f'Uniform mode: Wind speed = {self.uniform_windspeed} m/s')
@@ -190,8 +191,7 @@ class Simulator(Config):
             terrain = {'Elevation': terrain}
         out = {}
         for key, val in terrain.items():
-            arr = np.asarray(val.cpu() if isinstance(val, torch.Tensor) else val,
-                             dtype=np.float64)
+            arr = inputs.host_f64(val)
             if arr.shape != tuple(self.gridsize):
                 raise ValueError(f'terrain layer {key} has shape {arr.shape}, '
                                  f'expected {tuple(self.gridsize)}')
@@ -232,64 +232,12 @@ class Simulator(Config):
                                                          self.gridsize)
         return turbines
 
-    def _resolve_wind(self, wind):
-        if isinstance(wind, dict):
-            wind = [dict(case_id=k, wspeed=v[0], wdirn=v[1]) for k, v in wind.items()]
-        out = []
-        for item in wind:
-            item = dict(item)
-            dt = item.get('datetime')
-            if dt is not None and not isinstance(dt, datetime):
-                dt = datetime(*dt)
-            if 'case_id' not in item:
-                if dt is None:
-                    raise ValueError("each wind entry needs 'datetime' or 'case_id'")
-                item['case_id'] = dt.strftime(self.time_format)       # simulator.py:126
-            item['datetime'] = dt
-            if 'lon' in item or 'lat' in item:
-                self._project_wind_samples(item)
-            out.append(item)
-        if any('x_km' in it for it in out):
-            # the reference hands wtk_interp_type to scipy's griddata ('nearest' | 'linear' | 'cubic',
-            # simulator.py:774-775), which raises ValueError for anything else
-            from .wind import METHODS
-            if str(self.wtk_interp_type).lower() not in METHODS:
-                raise ValueError(f'wtk_interp_type = {self.wtk_interp_type!r}: expected one of {METHODS}')
-        if self.sim_mode.lower() == 'snapshot' and len(out) != 1:
-            raise ValueError('snapshot mode takes exactly one wind entry')
-        if self._wtk_thermals():
-            for item in out:
-                item['_wtk_thermal'] = self._resolve_wtk_layers(item)
-        return out
+    THERMAL_LAYERS = inputs.THERMAL_LAYERS      # keys of wtk_layers
 
-    THERMAL_LAYERS = ('pressure', 'temperature', 'blheight', 'surfheatflux')      # keys of wtk_layers
-
-    def _project_wind_samples(self, item):
-        """A wind entry whose samples sit at 'lon', 'lat' (degrees) instead of 'x_km', 'y_km': the WTK points as
-        they are delivered.  Scattered points (npts,) or the axes (nx,), (ny,) of a lattice whose arrays are
-        (ny, nx).  The points are projected and become scattered samples in kilometres from the centre of cell
-        (0, 0) -- a lattice in degrees is no lattice on the projected grid -- and `item` is rewritten in place."""
-        case = item['case_id']
-        if 'x_km' in item or 'y_km' in item:
-            raise ValueError(f"{case}: the wind samples have both 'lon' / 'lat' and 'x_km' / 'y_km': give one pair")
-        if 'lon' not in item or 'lat' not in item:
-            raise ValueError(f"{case}: wind samples in degrees need both 'lon' and 'lat'")
-        projection = self._need_projection(f"{case}: wind samples at 'lon', 'lat'")
-        lon = np.asarray(item.pop('lon'), dtype=np.float64).ravel()
-        lat = np.asarray(item.pop('lat'), dtype=np.float64).ravel()
-        fields = [name for name in ('wspeed', 'wdirn') + self.THERMAL_LAYERS if item.get(name) is not None]
-        if any(np.ndim(item[name]) == 2 and np.shape(item[name]) == (lat.size, lon.size) for name in fields):
-            for name in fields:
-                if np.shape(item[name]) == (lat.size, lon.size):
-                    val = item[name]
-                    item[name] = np.asarray(val.cpu() if isinstance(val, torch.Tensor) else val, dtype=np.float64).ravel()
-            lon, lat = (a.ravel() for a in np.meshgrid(lon, lat))
-        elif lon.size != lat.size:
-            raise ValueError(f"{case}: 'lon' has {lon.size} values and 'lat' {lat.size}: scattered samples need as many "
-                             'of each, a lattice arrays of shape (lat, lon)')
-        x, y = projection.forward(lon, lat)
-        item['x_km'] = (x - self.bounds[0]) / 1000.
-        item['y_km'] = (y - self.bounds[1]) / 1000.
+    def _wind_km(self, lon, lat):
+        """Wind samples at lon / lat (degrees) in kilometres from the centre of cell (0, 0)."""
+        x, y = self._need_projection("wind samples at 'lon', 'lat'").forward(lon, lat)
+        return (x - self.bounds[0]) / 1000., (y - self.bounds[1]) / 1000.
 
     def _wtk_thermals(self):
         return str(self.thermal_model).lower() == 'wtk'
@@ -332,44 +280,12 @@ class Simulator(Config):
     def _get_sx_fname(self, case_id: str, dirname: str = './'):
         return os.path.join(dirname, f'{case_id}_sx')
 
-    def _resolve_wtk_layers(self, item):
-        """The four thermal layers of one wind entry, host side only: ('raster', None, None, (4, rows, cols)) or
-        ('samples', x_km[npts], y_km[npts], (4, npts)) -- a lattice (ny, nx) becomes its meshgrid points, the
-        reference triangulates whatever points it gets.  ValueError names the field that does not fit."""
-        case = item['case_id']
-        arrays, forms = [], set()
-        has_xy = 'x_km' in item and 'y_km' in item
-        x = np.asarray(item['x_km'], dtype=np.float64).ravel() if has_xy else None
-        y = np.asarray(item['y_km'], dtype=np.float64).ravel() if has_xy else None
-        for name in self.THERMAL_LAYERS:
-            if item.get(name) is None:
-                raise ValueError(f"{case}: thermal_model = 'wtk' needs the layer {name!r} ({self.wtk_layers[name]}) in "
-                                 'every wind entry')
-            val = item[name]
-            arr = np.asarray(val.cpu() if isinstance(val, torch.Tensor) else val, dtype=np.float64)
-            if has_xy and arr.ndim == 1 and arr.size == x.size == y.size:
-                forms.add('scattered')
-            elif has_xy and arr.ndim == 2 and arr.shape == (y.size, x.size):
-                forms.add('lattice')
-            elif arr.shape == tuple(self.gridsize):
-                forms.add('raster')
-            else:
-                raise ValueError(
-                    f'{case}: layer {name!r} has shape {arr.shape}: expected a raster {tuple(self.gridsize)}' +
-                    (f', samples ({x.size},) at x_km / y_km or a lattice {(y.size, x.size)}' if has_xy else
-                     ' (samples need x_km and y_km)'))
-            arrays.append(arr)
-            if len(forms) > 1:
-                raise ValueError(f'{case}: layer {name!r} is given as {forms - {form0}} but {self.THERMAL_LAYERS[0]!r} as '
-                                 f'{form0}: the four thermal layers must come in one form')
-            form0 = next(iter(forms))
-        if form0 == 'raster':
-            return ('raster', None, None, np.stack(arrays))
-        if form0 == 'lattice':
-            x, y = (a.ravel() for a in np.meshgrid(x, y))
-        if x.size < 3 and str(self.wtk_interp_type).lower() != 'nearest':
-            raise ValueError(f"{case}: layer 'pressure' has {x.size} samples: 'linear' and 'cubic' need at least 3")
-        return ('samples', x, y, np.stack([a.ravel() for a in arrays]))
+    @staticmethod
+    def _save_f32(fname, field):
+        """`<fname>.npy` in the f32 the files hold, from a tensor or an array."""
+        if isinstance(field, torch.Tensor):
+            field = field.to(torch.float32).cpu().numpy()
+        np.save(f'{fname}.npy', np.asarray(field, dtype=np.float32))
 
     # -------------------------------------------------------------- terrain
     def get_terrain_elevation(self):
@@ -411,7 +327,7 @@ class Simulator(Config):
             orograph, _, sx = layers.orographic_updraft_improved(
                 self.get_terrain_elevation(), self.resolution, float(self.uniform_windspeed),
                 float(self.uniform_winddirn), **self._improved_args())
-            np.save(f'{self._get_sx_fname(self.case_ids[0], self.mode_data_dir)}.npy', np.asarray(sx, dtype=np.float32))
+            self._save_f32(self._get_sx_fname(self.case_ids[0], self.mode_data_dir), sx)
         elif 'Slope' in self._terrain or 'Aspect' in self._terrain:
             orograph = layers.compute_orographic_updraft(
                 float(self.uniform_windspeed), float(self.uniform_winddirn),
@@ -420,148 +336,115 @@ class Simulator(Config):
             orograph, _ = layers.updraft_from_dem(
                 self.get_terrain_elevation(), self.resolution,
                 float(self.uniform_windspeed), float(self.uniform_winddirn))
-        fname = self._get_orograph_fname(self.case_ids[0], self.mode_data_dir)
-        np.save(f'{fname}.npy', np.asarray(orograph, dtype=np.float32))
+        self._save_f32(self._get_orograph_fname(self.case_ids[0], self.mode_data_dir), orograph)
+
+    _CHUNK = 8          # wind cases per batched device call (the terrain, or the sample geometry, is read once for all)
 
     def compute_orographic_updrafts_using_wtk(self) -> None:
         """simulator.py:200-215: one orograph per wind case, batched so the
         terrain is read once for all cases."""
         print('Computing orographic updrafts..', end="")
         start_time = time.time()
-        batch = 8
+        mine = set(self._cases_written_here())
+        cases = [c for c in self._wind if c.case_id in mine]
+        injected = 'Slope' in self._terrain or 'Aspect' in self._terrain
         # DEM-only terrain and wind on one regular lattice: the fused kernel (DEM read once
         # per batch, no per-cell wind rasters, no slope / aspect rasters)
-        mine = set(self._cases_written_here())
-        wind = [it for it in self._wind if it['case_id'] in mine]
-        lattice = not self._improved() and len(wind) > 0 and str(self.wtk_interp_type).lower() == 'linear' and \
-            all('x_km' in it and np.ndim(it['wspeed']) == 2 for it in wind) and \
-            not ('Slope' in self._terrain or 'Aspect' in self._terrain) and \
-            all(np.array_equal(it['x_km'], wind[0]['x_km']) and
-                np.array_equal(it['y_km'], wind[0]['y_km']) for it in wind)
-        if lattice:
+        fused = not self._improved() and not injected and len(cases) > 0 and \
+            str(self.wtk_interp_type).lower() == 'linear' and \
+            all(c.wind.form == 'lattice' and c.wind.same_points(cases[0].wind) for c in cases)
+        if fused or self._improved():
+            # (improved: the per-cell wind rasters, always -- the fused lattice kernel has no shelter ray)
             dem = to_dev(self.get_terrain_elevation(), torch.float64)
-            for b0 in range(0, len(wind), batch):
-                chunk = wind[b0:b0 + batch]
-                oro, _ = layers.updraft_from_dem_lattice(
-                    dem, self.resolution, chunk[0]['x_km'], chunk[0]['y_km'],
-                    np.stack([np.asarray(it['wspeed'], dtype=np.float64) for it in chunk]),
-                    np.stack([np.asarray(it['wdirn'], dtype=np.float64) for it in chunk]))
-                for item, o in zip(chunk, oro):
-                    fname = self._get_orograph_fname(item['case_id'], self.mode_data_dir)
-                    np.save(f'{fname}.npy', o.cpu().numpy())
-            print(f'took {_elapsed(start_time)}', flush=True)
-            return
-        if self._improved():
-            # the per-cell wind rasters, always (the fused lattice kernel has no shelter ray)
-            dem = to_dev(self.get_terrain_elevation(), torch.float64)
-            improved_args = self._improved_args()
+            improved_args = self._improved_args() if self._improved() else None
         else:
             slope = to_dev(self.get_terrain_slope(), torch.float64)
             aspect = to_dev(self.get_terrain_aspect(), torch.float64)
-        for b0 in range(0, len(wind), batch):
-            chunk = wind[b0:b0 + batch]
-            ws, wd = [], []
-            for item in chunk:
-                s, d = self._wind_rasters(item)
-                ws.append(s)
-                wd.append(d)
-            if self._improved():
-                oro, _, sx = layers.orographic_updraft_improved(dem, self.resolution, torch.stack(ws), torch.stack(wd),
-                                                                **improved_args)
-                for item, x in zip(chunk, sx):
-                    np.save(f"{self._get_sx_fname(item['case_id'], self.mode_data_dir)}.npy", x.to(torch.float32).cpu().numpy())
+        for b0 in range(0, len(cases), self._CHUNK):
+            chunk = cases[b0:b0 + self._CHUNK]
+            if fused:
+                oro, _ = layers.updraft_from_dem_lattice(dem, self.resolution, chunk[0].wind.x_km, chunk[0].wind.y_km,
+                                                         np.stack([c.wind.values[0] for c in chunk]),
+                                                         np.stack([c.wind.values[1] for c in chunk]))
             else:
-                oro, _ = layers.orographic_updraft(torch.stack(ws), torch.stack(wd), slope, aspect)
-            for item, o in zip(chunk, oro):
-                fname = self._get_orograph_fname(item['case_id'], self.mode_data_dir)
-                np.save(f'{fname}.npy', o.cpu().numpy())
+                ws, wd = (torch.stack(rasters) for rasters in zip(*(self._wind_rasters(c) for c in chunk)))
+                if self._improved():
+                    oro, _, sx = layers.orographic_updraft_improved(dem, self.resolution, ws, wd, **improved_args)
+                    for case, x in zip(chunk, sx):
+                        self._save_f32(self._get_sx_fname(case.case_id, self.mode_data_dir), x)
+                else:
+                    oro, _ = layers.orographic_updraft(ws, wd, slope, aspect)
+            for case, o in zip(chunk, oro):
+                self._save_f32(self._get_orograph_fname(case.case_id, self.mode_data_dir), o)
         self._nearest_index = (None, None)        # ('nearest': 4 B per cell of device memory, needed no longer)
         print(f'took {_elapsed(start_time)}', flush=True)
 
-    def _wind_rasters(self, item):
-        """Per-cell wind speed / direction (f64 device tensors) of one case."""
-        ws, wd = item['wspeed'], item['wdirn']
-        if 'x_km' in item:
-            from .wind import interpolate_wind_lattice, interpolate_wind_scattered, nearest_sample_index
-            # samples on a regular lattice (x_km[nx], y_km[ny], arrays (ny, nx)) or at scattered points
-            # (x_km[npts], y_km[npts], arrays (npts,)): the reference's griddata, simulator.py:765-776
-            method = str(self.wtk_interp_type).lower()
-            x_km, y_km = item['x_km'], item['y_km']
-            if method != 'linear' and np.ndim(ws) == 2:
-                # the reference triangulates whatever points it gets: a lattice is its meshgrid points
-                if np.shape(ws) != (np.size(y_km), np.size(x_km)) or np.shape(wd) != np.shape(ws):
-                    raise ValueError(f'lattice arrays must be (ny, nx) = {(np.size(y_km), np.size(x_km))}')
-                x_km, y_km = (a.ravel() for a in np.meshgrid(np.asarray(x_km, dtype=np.float64).ravel(),
-                                                             np.asarray(y_km, dtype=np.float64).ravel()))
-                ws, wd = np.asarray(ws, dtype=np.float64).ravel(), np.asarray(wd, dtype=np.float64).ravel()
-            if np.ndim(ws) == 1 and np.size(x_km) == np.size(ws) == np.size(y_km):
-                index = None
-                if method == 'nearest':
-                    # the index raster depends on the points only: one per wind geometry, not one per case
-                    key = (np.asarray(x_km, dtype=np.float64).tobytes(), np.asarray(y_km, dtype=np.float64).tobytes())
-                    if getattr(self, '_nearest_index', (None, None))[0] != key:
-                        self._nearest_index = (key, nearest_sample_index(x_km, y_km, self.gridsize, self.resolution))
-                    index = self._nearest_index[1]
-                ws_d, wd_d = interpolate_wind_scattered(x_km, y_km, ws, wd, self.gridsize, self.resolution,
-                                                        method=method, index=index)
-                if method != 'nearest' and bool(torch.isnan(ws_d).any()):
-                    # griddata's behaviour (cells outside the samples' convex hull are NaN); the reference
-                    # prints rather than raises when NaNs turn up (simulator.py:286)
-                    print(f"{item['case_id']}: NANs in the interpolated wind (raster cells outside the convex "
-                          'hull of the wind samples); their updraft is 0')
-                return ws_d, wd_d
-            if method != 'linear':
-                raise ValueError("wind samples must be (npts,) at x_km[npts], y_km[npts] or (ny, nx) on a lattice "
-                                 'x_km[nx], y_km[ny]')
-            return interpolate_wind_lattice(item['x_km'], item['y_km'], ws, wd,
-                                            self.gridsize, self.resolution)
-        ws = to_dev(ws, torch.float64)
-        wd = to_dev(wd, torch.float64)
-        if tuple(ws.shape) != tuple(self.gridsize) or tuple(wd.shape) != tuple(self.gridsize):
-            raise ValueError('wind rasters must have the terrain grid shape')
-        return ws, wd
+    def _wind_rasters(self, entry):
+        """Per-cell wind speed / direction (f64 device tensors) of one resolved case: rasters as they are, samples
+        through the reference's griddata (simulator.py:765-776) as `wtk_interp_type` says."""
+        from .wind import interpolate_wind_lattice, interpolate_wind_scattered, nearest_sample_index
+        wind, method = entry.wind, str(self.wtk_interp_type).lower()
+        if wind.form == 'raster':
+            return tuple(to_dev(v, torch.float64) for v in wind.values)
+        if wind.form == 'lattice' and method == 'linear':
+            return interpolate_wind_lattice(wind.x_km, wind.y_km, *wind.values, self.gridsize, self.resolution)
+        pts = wind.as_points()        # the reference triangulates whatever points it gets: a lattice is its meshgrid points
+        index = None
+        if method == 'nearest':
+            # the index raster depends on the points only: one per wind geometry, not one per case
+            if self._nearest_index[0] is None or not pts.same_points(self._nearest_index[0]):
+                self._nearest_index = (pts, nearest_sample_index(pts.x_km, pts.y_km, self.gridsize, self.resolution))
+            index = self._nearest_index[1]
+        ws_d, wd_d = interpolate_wind_scattered(pts.x_km, pts.y_km, *pts.values, self.gridsize, self.resolution,
+                                                method=method, index=index)
+        if method != 'nearest' and bool(torch.isnan(ws_d).any()):
+            # griddata's behaviour (cells outside the samples' convex hull are NaN); the reference
+            # prints rather than raises when NaNs turn up (simulator.py:286)
+            print(f"{entry.case_id}: NANs in the interpolated wind (raster cells outside the convex "
+                  'hull of the wind samples); their updraft is 0')
+        return ws_d, wd_d
 
     def compute_thermal_updrafts_using_wtk(self) -> None:
         """thermal_model = 'wtk': `<case>_r0_thermals.npy` (f32) of every case this rank writes.  Cases that share
-        their sample points go through the fused call in chunks of up to 8 (the sample geometry is located once per
-        cell for the whole chunk), like the orographic updrafts of compute_orographic_updrafts_using_wtk."""
+        their sample points go through the fused call in chunks (the sample geometry is located once per cell for the
+        whole chunk), like the orographic updrafts of compute_orographic_updrafts_using_wtk."""
         print('Computing thermal updrafts from the WTK layers..', end="")
         start_time = time.time()
         mine = set(self._cases_written_here())
-        todo = [it for it in self._wind if it['case_id'] in mine]
+        todo = [(c.case_id, c.thermal.as_points()) for c in self._wind if c.case_id in mine]
         while todo:
-            form, x, y, _ = todo[0]['_wtk_thermal']
-            same = [it for it in todo if form == 'samples' and it['_wtk_thermal'][0] == form and
-                    np.array_equal(it['_wtk_thermal'][1], x) and np.array_equal(it['_wtk_thermal'][2], y)][:8] or todo[:1]
+            first = todo[0][1]
+            same = todo[:1] if first.form == 'raster' else \
+                [it for it in todo if it[1].form == first.form and it[1].same_points(first)][:self._CHUNK]
             self._write_wtk_thermals(same)
             todo = [it for it in todo if not any(it is s for s in same)]
         print(f'took {_elapsed(start_time)}', flush=True)
 
     def _write_wtk_thermals(self, items):
-        """One device call for `items` (wind entries with the same form and sample points) -> their thermal files."""
+        """One device call for `items` = [(case_id, thermal layers as points or rasters), ...] of one form and one set
+        of sample points -> their thermal files."""
         from .thermals import compute_wtk_thermals
         height = float(self.wtk_thermal_height)
-        form, x, y, _ = items[0]['_wtk_thermal']
-        if form == 'raster':
-            p, t, zi, q = (to_dev(a, torch.float64) for a in items[0]['_wtk_thermal'][3])
+        first = items[0][1]
+        if first.form == 'raster':
+            p, t, zi, q = (to_dev(a, torch.float64) for a in first.values)
             wstar = layers.deardoff_velocity_function(layers.compute_potential_temperature(p, t), zi, q)
             fields = layers.compute_thermal_updraft(height, wstar, zi).to(torch.float32)[None].cpu().numpy()
         else:
-            stacked = np.stack([it['_wtk_thermal'][3] for it in items], 1)              # (4, B, npts)
-            fields = compute_wtk_thermals(x, y, *stacked, self.gridsize, self.resolution, height,
+            stacked = np.stack([samples.values for _, samples in items], 1)            # (4, B, npts)
+            fields = compute_wtk_thermals(first.x_km, first.y_km, *stacked, self.gridsize, self.resolution, height,
                                           method=str(self.wtk_interp_type).lower(), dtype=torch.float32)
-        for item, field in zip(items, fields):
+        for (case_id, _), field in zip(items, fields):
             if np.isnan(field).any():
                 # griddata's behaviour, as for the wind (cells outside the samples' convex hull are NaN)
-                print(f"{item['case_id']}: NANs in the interpolated thermal layers (raster cells outside the convex "
+                print(f"{case_id}: NANs in the interpolated thermal layers (raster cells outside the convex "
                       'hull of the samples); their updraft is 0')
-            fname = self._get_thermal_fname(item['case_id'], 0, self.mode_data_dir)
-            np.save(f'{fname}.npy', field)
+            self._save_f32(self._get_thermal_fname(case_id, 0, self.mode_data_dir), field)
 
     def compute_thermal_updrafts(self, case_id: str):
         """simulator.py:217-228; with thermal_model = 'wtk' the one field of the physical model instead."""
         if self._wtk_thermals():
-            self._write_wtk_thermals([it for it in self._wind if it['case_id'] == case_id])
+            self._write_wtk_thermals([(c.case_id, c.thermal.as_points()) for c in self._wind if c.case_id == case_id])
             return
         if self.thermals_realization_count > 0:
             from .thermals import compute_thermals_batch
@@ -581,21 +464,22 @@ class Simulator(Config):
             for first in range(0, len(seeds), chunk):
                 fields = compute_thermals_batch(aspect, 2.0, seeds[first:first + chunk], dtype=torch.float32)
                 for k, field in enumerate(fields.cpu().numpy()):
-                    fname = self._get_thermal_fname(case_id, first + k, self.mode_data_dir)
-                    np.save(f'{fname}.npy', field)
+                    self._save_f32(self._get_thermal_fname(case_id, first + k, self.mode_data_dir), field)
         else:
             print('No thermals requested!', flush=True)
+
+    def _updraft_fields(self, case_id, load):
+        """The orograph of a case, then orograph + thermal_k of every realisation (simulator.py:230-243), read through
+        `load(file name)`."""
+        orograph = load(f'{self._get_orograph_fname(case_id, self.mode_data_dir)}.npy')
+        yield orograph
+        for real_id in range(int(self.thermals_realization_count)):
+            yield orograph + load(f'{self._get_thermal_fname(case_id, real_id, self.mode_data_dir)}.npy')
 
     def load_updrafts(self, case_id: str, apply_threshold=True):
         """simulator.py:230-243 -> [orograph] + [orograph + thermal_k], each
         passed through the threshold function (f64) when requested."""
-        fname = self._get_orograph_fname(case_id, self.mode_data_dir)
-        orograph = np.load(f'{fname}.npy')
-        updrafts = [orograph]
-        if self.thermals_realization_count > 0:
-            for real_id in range(self.thermals_realization_count):
-                fname = self._get_thermal_fname(case_id, real_id, self.mode_data_dir)
-                updrafts.append(orograph + np.load(f'{fname}.npy'))
+        updrafts = list(self._updraft_fields(case_id, np.load))
         if apply_threshold:
             updrafts = [layers.get_above_threshold_speed(ix, self.updraft_threshold)
                         for ix in updrafts]
@@ -611,23 +495,27 @@ class Simulator(Config):
     def get_directional_potential(self, updraft, case_id, real_id):
         """simulator.py:259-288: cached `<id>_potential.npy` when its shape
         matches, else the GPU solve; saved as f32."""
-        fname = self._get_potential_fname(case_id, real_id, self.mode_data_dir)
-        id_str = self._get_id_string(case_id, real_id)
-        try:
-            potential = np.load(f'{fname}.npy')
-            if potential.shape != self.gridsize:
-                raise FileNotFoundError
-            if (self.sim_seed < 0) & (real_id != 0):
-                raise FileNotFoundError
-            print(f'{id_str}: Found saved potential')
-        except FileNotFoundError as _:
+        potential = self._cached_potential(case_id, real_id)
+        if potential is None:
             start_time = time.time()
-            print(f'{id_str}: Computing potential..', end="", flush=True)
+            print(f'{self._get_id_string(case_id, real_id)}: Computing potential..', end="", flush=True)
             potential = potential_mod.solve_potential(np.asarray(updraft), self.track_direction)
             print(f'took {_elapsed(start_time)}', flush=True)
-            np.save(f'{fname}.npy', potential.astype(np.float32))
+            np.save(f'{self._get_potential_fname(case_id, real_id, self.mode_data_dir)}.npy', potential.astype(np.float32))
         if np.isnan(potential).any():
             print('NANs found in potential!')
+        return potential
+
+    def _cached_potential(self, case_id, real_id):
+        """The saved `<id>_potential.npy` (f32) when it fits this run, else None: its shape must be the grid's, and an
+        unseeded run keeps only realisation 0 (simulator.py:262-270)."""
+        try:
+            potential = np.load(f'{self._get_potential_fname(case_id, real_id, self.mode_data_dir)}.npy')
+        except FileNotFoundError:
+            return None
+        if potential.shape != self.gridsize or (self.sim_seed < 0) & (real_id != 0):
+            return None
+        print(f'{self._get_id_string(case_id, real_id)}: Found saved potential')
         return potential
 
     def _get_id_string(self, case_id: str, real_id=None):
@@ -665,73 +553,29 @@ class Simulator(Config):
         if self._shards_tracks():
             # the shards of one case are ONE batch: every rank steps under rank 0's key (the items
             # are prepared in the same order on every rank, so the broadcasts pair up)
-            seed = int(self._broadcast_int64([seed])[0])
+            seed = int(distributed.broadcast(np.array([seed], dtype=np.int64))[0])
         return seed
-
-    def _broadcast_int64(self, values, src=0):
-        """`values` of rank `src` on every rank (an int64 array; the device follows the backend)."""
-        import torch.distributed as dist
-        arr = np.asarray(values, dtype=np.int64)
-        if not (self._dist_on() and dist.get_world_size() > 1):
-            return arr
-        dev = torch.device('cuda', torch.cuda.current_device()) if dist.get_backend() == 'nccl' else torch.device('cpu')
-        t = torch.from_numpy(arr.copy()).to(dev)
-        dist.broadcast(t, src=src)
-        return t.cpu().numpy()
-
-    def _allreduce_sum_f64(self, values):
-        """Sum over the ranks of an f64 vector, on every rank."""
-        import torch.distributed as dist
-        arr = np.asarray(values, dtype=np.float64)
-        if not (self._dist_on() and dist.get_world_size() > 1):
-            return arr
-        dev = torch.device('cuda', torch.cuda.current_device()) if dist.get_backend() == 'nccl' else torch.device('cpu')
-        t = torch.from_numpy(arr.copy()).to(dev)
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)
-        return t.cpu().numpy()
-
-    def _allreduce_sum_int64(self, values):
-        """Sum over the ranks of an int64 vector, on every rank."""
-        import torch.distributed as dist
-        arr = np.asarray(values, dtype=np.int64)
-        if not (self._dist_on() and dist.get_world_size() > 1):
-            return arr
-        dev = torch.device('cuda', torch.cuda.current_device()) if dist.get_backend() == 'nccl' else torch.device('cpu')
-        t = torch.from_numpy(arr.copy()).to(dev)
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)
-        return t.cpu().numpy()
 
     # device-resident forms of load_updrafts / get_directional_potential: the public methods
     # keep the reference's numpy-in / numpy-out contract, the stepper takes these
     def _load_updrafts_dev(self, case_id):
-        fname = self._get_orograph_fname(case_id, self.mode_data_dir)
-        orograph = to_dev(np.load(f'{fname}.npy'), torch.float32)
-        fields = [orograph]
-        for real_id in range(int(self.thermals_realization_count)):
-            fname = self._get_thermal_fname(case_id, real_id, self.mode_data_dir)
-            fields.append(orograph + to_dev(np.load(f'{fname}.npy'), torch.float32))
+        fields = self._updraft_fields(case_id, lambda fname: to_dev(np.load(fname), torch.float32))
         return [layers.get_above_threshold_speed(f, self.updraft_threshold) for f in fields]
 
     def _potential_dev(self, updraft, case_id, real_id):
         """get_directional_potential on device tensors: the cached .npy when valid, else
         the GPU solve (written to the cache by the rank that owns the case)."""
         fname = self._get_potential_fname(case_id, real_id, self.mode_data_dir)
-        id_str = self._get_id_string(case_id, real_id)
         sharded = self._shards_tracks()
         if sharded and self._rank() != 0:
             self._barrier()                       # rank 0 solves (or finds the cache) and saves
             return to_dev(np.load(f'{fname}.npy'), torch.float32)
-        try:
-            potential = np.load(f'{fname}.npy')
-            if potential.shape != self.gridsize:
-                raise FileNotFoundError
-            if (self.sim_seed < 0) & (real_id != 0):
-                raise FileNotFoundError
-            print(f'{id_str}: Found saved potential')
+        potential = self._cached_potential(case_id, real_id)
+        if potential is not None:
             pot = to_dev(potential, torch.float32)
-        except FileNotFoundError as _:
+        else:
             start_time = time.time()
-            print(f'{id_str}: Computing potential..', end="", flush=True)
+            print(f'{self._get_id_string(case_id, real_id)}: Computing potential..', end="", flush=True)
             pot = potential_mod.solve_potential(updraft, self.track_direction)
             torch.cuda.current_stream().synchronize()
             print(f'took {_elapsed(start_time)}', flush=True)
@@ -762,11 +606,10 @@ class Simulator(Config):
         sharded = self._shards_tracks()
         if sharded and self.sim_seed < 0:
             # unseeded: every rank drew its own start cells; the batch is rank 0's
-            starts = self._broadcast_int64(starts).astype(np.int32)
+            starts = distributed.broadcast(starts)
         lo, hi = 0, len(starts)
         if sharded:
-            from .distributed import shard_range
-            lo, hi = shard_range(len(starts), self._rank(), self._world())
+            lo, hi = distributed.shard_range(len(starts), self._rank(), self._world())
         my_starts = to_dev(starts[lo:hi], torch.int32)
         # the largest share of any rank (shard sizes differ by one): whether the counts are kept in 64 bits
         # must not depend on the rank, or the ranks would meet in the reduce with different dtypes
@@ -820,7 +663,7 @@ class Simulator(Config):
                     if sharded:
                         # the limit is the merged file's, and every rank must reach the same verdict (a rank
                         # that raised alone would leave the others waiting in _write_tracks' barrier)
-                        need = int(self._allreduce_sum_int64([need])[0])
+                        need = int(self._allreduce_sum(np.array([need], dtype=np.int64))[0])
                     if need > float(self.max_tracks_file_gb) * 2 ** 30:
                         raise ValueError(
                             f'{id_str}: the trajectories of these {len(starts)} tracks are {need / 2 ** 30:.1f} GiB '
@@ -840,8 +683,7 @@ class Simulator(Config):
                     self._store_encounters(case_id, real_id, per_turbine.cpu().numpy(), per_track.cpu().numpy(),
                                            first_step.cpu().numpy(), sharded)
             if sharded:
-                from .distributed import reduce_histogram
-                batch.hist = reduce_histogram(batch.hist, all_ranks=True)
+                batch.hist = distributed.reduce_histogram(batch.hist, all_ranks=True)
             return (case_id, real_id), batch
 
         nitems = max(1, len(self.my_case_ids())) * (1 + int(self.thermals_realization_count))
@@ -892,7 +734,7 @@ class Simulator(Config):
         rank that owns the case does.  turbines_per_track / first_step stay this rank's tracks."""
         per_turbine = np.asarray(tracks_per_turbine, dtype=np.int64)
         if sharded:
-            per_turbine = np.asarray(self._allreduce_sum_int64(per_turbine), dtype=np.int64)
+            per_turbine = np.asarray(self._allreduce_sum(per_turbine), dtype=np.int64)
         self.turbine_encounters[(case_id, real_id)] = dict(
             tracks_per_turbine=per_turbine, turbines_per_track=np.asarray(turbines_per_track, dtype=np.int32),
             first_step=np.asarray(first_step, dtype=np.int32))
@@ -910,7 +752,6 @@ class Simulator(Config):
         histograms are added up in 64 bits (K4 takes that form), and every sub-batch is checked by its
         checksum -- the counts must add up to the points of its tracks; a wrapped cell leaves 2^32 missing, and that
         sub-batch is stepped again as two halves (HistogramOverflow only below _MIN_SPLIT_TRACKS tracks)."""
-        from .distributed import HistogramOverflow
         n = int(my_starts.shape[0])
         safe = max(1, int(self.hist_safe_tracks))
         widen = max(n, int(widest_share or 0)) > safe
@@ -941,7 +782,7 @@ class Simulator(Config):
                 counted = int((b.hist.view(torch.int32).to(torch.int64) & 0xFFFFFFFF).sum().item())
             if counted != b.total_points:
                 if m < 2 * self._MIN_SPLIT_TRACKS:
-                    raise HistogramOverflow(
+                    raise distributed.HistogramOverflow(
                         f'presence histogram: {b.total_points - counted} visits are missing from the uint32 counts of '
                         f'{m} tracks (a cell passed 2^32 - 1)')
                 import warnings
@@ -950,7 +791,7 @@ class Simulator(Config):
                               f'(Config.hist_safe_tracks = {self.hist_safe_tracks} is too many for this field)', RuntimeWarning)
                 todo[:0] = [(t0, m // 2), (t0 + m // 2, m - m // 2)]
                 if not widen and parts:                       # (cannot happen: without `widen` there is one sub-batch)
-                    raise HistogramOverflow('presence histogram: sub-batch wrapped after others were kept in 32 bits')
+                    raise distributed.HistogramOverflow('presence histogram: sub-batch wrapped after others were kept in 32 bits')
                 widen = True
                 del b
                 continue
@@ -1047,8 +888,7 @@ class Simulator(Config):
             presence.normalise_add(case_prob, summary)          # case /= amax; summary += case
             case_presence[case_id] = case_prob
         if not self._shards_tracks():
-            from .distributed import reduce_presence_sum
-            reduce_presence_sum(summary)                        # cases of the other ranks
+            distributed.reduce_presence_sum(summary)                        # cases of the other ranks
         return presence.normalise_to_f32(summary).cpu().numpy(), case_presence  # summary /= amax -> f32
 
     def compute_presence_map(self, radius: float = 1000.):
@@ -1096,7 +936,7 @@ class Simulator(Config):
             total[:-1] += enc['tracks_per_turbine'] / float(self.track_count)
             total[-1] += 1.
         if self._world() > 1 and not self._shards_tracks():
-            total = self._allreduce_sum_f64(total)                  # the cases of the other ranks
+            total = self._allreduce_sum(total)                      # the cases of the other ranks
         out = total[:-1] / total[-1]
         if self._rank() == 0:
             np.save(os.path.join(self.mode_data_dir, 'summary_turbine_encounters.npy'), out)
@@ -1108,26 +948,11 @@ class Simulator(Config):
         return torch.device('cuda', torch.cuda.current_device())
 
     # ---------------------------------------------------------- multi-GPU
-    @staticmethod
-    def _dist_on():
-        import torch.distributed as dist
-        return dist.is_available() and dist.is_initialized()
-
-    @classmethod
-    def _rank(cls):
-        import torch.distributed as dist
-        return dist.get_rank() if cls._dist_on() else 0
-
-    @classmethod
-    def _world(cls):
-        import torch.distributed as dist
-        return dist.get_world_size() if cls._dist_on() else 1
-
-    @classmethod
-    def _barrier(cls):
-        import torch.distributed as dist
-        if cls._dist_on() and dist.get_world_size() > 1:
-            dist.barrier()
+    # (host tests replace these four on an instance to stand in for the ranks of a group)
+    _rank = staticmethod(distributed.rank)
+    _world = staticmethod(distributed.world_size)
+    _barrier = staticmethod(distributed.barrier)
+    _allreduce_sum = staticmethod(distributed.all_reduce_sum)
 
     def _shards_tracks(self):
         """Fewer wind cases than ranks (uniform / snapshot mode: one case): the tracks of
@@ -1141,8 +966,7 @@ class Simulator(Config):
         ranks every rank takes every case and a share of its tracks (simulate_tracks)."""
         if self._shards_tracks():
             return list(self.case_ids)
-        from .distributed import shard_cases
-        return shard_cases(self.case_ids)
+        return distributed.shard_cases(self.case_ids)
 
     def _cases_written_here(self):
         """Cases whose rasters (orograph, thermals) this rank computes and saves: its own

@@ -67,12 +67,13 @@ def compute_wtk_thermals(x_km, y_km, pressure, temperature, blheight, surfheatfl
     by the three `layers` functions, or f32 = that result rounded once; NaN outside the samples' convex hull for
     'linear' and 'cubic'.  method, index: as `wind.interpolate_wind_scattered`."""
     import numpy as np
-    from .wind import check_method, _host_f64, _scalar_geometry
+    from .inputs import host_f64
+    from .wind import check_method, _scalar_geometry
     if dtype not in (torch.float32, torch.float64):
         raise ValueError('compute_wtk_thermals: dtype must be torch.float32 or torch.float64')
     method = check_method(method)
     given = (pressure, temperature, blheight, surfheatflux)
-    fields = [_host_f64(a) for a in given]
+    fields = [host_f64(a) for a in given]
     single = fields[0].ndim == 1
     fields = [a[None] if a.ndim == 1 else a for a in fields]
     if any(a.ndim != 2 or a.shape != fields[0].shape for a in fields):

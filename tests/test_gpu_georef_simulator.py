@@ -130,7 +130,7 @@ def test_wind_samples_in_degrees_give_the_same_rasters(gpu, tmp_path):
     files = [np.load(s._get_orograph_fname(s.case_ids[0], s.mode_data_dir) + '.npy') for s in (a, b)]
     assert np.array_equal(files[0], files[1]) and files[0].max() > 0.
     # a lattice in degrees (axes and (ny, nx) arrays) is its meshgrid points
-    ws, wd = (np.asarray(a._wind[0][k]).reshape(5, 5) for k in ('wspeed', 'wdirn'))
+    ws, wd = (np.asarray(v).reshape(5, 5) for v in a._wind[0].wind.values)
     c = Simulator(replace(cfg, run_name='c'), terrain='synthetic', origin='southwest_lonlat',
                   wind=[dict(datetime=cfg.snapshot_datetime, wspeed=ws, wdirn=wd, lon=glon[:5], lat=glat[::5])])
     assert np.array_equal(np.load(c._get_orograph_fname(c.case_ids[0], c.mode_data_dir) + '.npy'), files[0])

@@ -189,7 +189,7 @@ def test_track_sharded_runs_sum_the_per_turbine_counts_once_per_item(tmp_path):
     def fake_sum(values):
         calls.append(np.array(values))
         return np.asarray(values, dtype=np.int64) * 4          # "four ranks with the same counts"
-    sim._allreduce_sum_int64 = fake_sum
+    sim._allreduce_sum = fake_sum
     sim._world = lambda: 4
     per_track, first = np.array([1, 0, 2], dtype=np.int32), np.array([5, -1, 0], dtype=np.int32)
     for rank in (1, 0):

@@ -187,3 +187,95 @@ def test_numpy_restatement_of_the_cubic_patch_vs_griddata(geometry):
         bound = 1e-12 * max(1., float(np.max(np.abs(ref[ok]))))
         print(f'{geometry[0]} field {f}: max |restatement - griddata| = {err:.3g} (bound {bound:.3g})')
         assert err <= bound
+
+
+CASE = 'y2010m06d17h13'
+_XY5 = dict(x_km=np.array([0., 1., 0., 1., .5]), y_km=np.array([0., 0., 1., 1., .4]))
+_AXES = dict(x_km=np.array([0., .5, 1.]), y_km=np.array([0., 1.]))
+MALFORMED = {                                       # name -> (entry, the field the message must name)
+    'rasters of the wrong shape': (dict(wspeed=np.full((10, 9), 5.), wdirn=np.full((10, 9), 270.)), 'wspeed'),
+    'samples shorter than their points': (dict(wspeed=np.full(4, 5.), wdirn=np.full(4, 270.), **_XY5), 'wspeed'),
+    'lattice arrays of the wrong shape': (dict(wspeed=np.full((3, 2), 5.), wdirn=np.full((3, 2), 270.), **_AXES), 'wspeed'),
+    'wdirn shorter than wspeed': (dict(wspeed=np.full(5, 5.), wdirn=np.full(4, 270.), **_XY5), 'wdirn'),
+    'rasters beside x_km': (dict(wspeed=np.full((10, 10), 5.), wdirn=np.full((10, 10), 270.), **_XY5), 'wspeed'),
+}
+
+
+@pytest.mark.parametrize('method', ['linear', 'cubic'])
+@pytest.mark.parametrize('fault', list(MALFORMED))
+def test_malformed_wind_pair_is_a_value_error_before_device_work(tmp_path, fault, method):
+    """Raised by the constructor from the resolver: this test runs without a GPU, where the first device call would be
+    a RuntimeError instead.  The message names the case and the field."""
+    from ssrs_amd import Config, Simulator
+    entry, field = MALFORMED[fault]
+    cfg = Config(run_name='bad', out_dir=str(tmp_path), region_width_km=(1., 1.), resolution=100., sim_mode='snapshot',
+                 snapshot_datetime=(2010, 6, 17, 13), track_count=1, sim_seed=1, wtk_interp_type=method)
+    with pytest.raises(ValueError) as err:
+        Simulator(cfg, terrain=np.zeros((10, 10)), wind=[dict(datetime=(2010, 6, 17, 13), **entry)])
+    assert CASE in str(err.value) and field in str(err.value)
+
+
+@pytest.mark.parametrize('tensor', [False, True], ids=['numpy', 'torch'])
+def test_classifier_on_the_wind_pair(tensor):
+    import torch
+    from ssrs_amd.inputs import classify
+    give = (lambda a: torch.from_numpy(a)) if tensor else (lambda a: a)
+    pair = lambda shape, dtype=np.float32: [('wspeed', give(np.full(shape, 5., dtype=dtype))),
+                                            ('wdirn', give(np.full(shape, 270., dtype=dtype)))]
+    fields = pair((10, 10))
+    got = classify(fields, None, None, (10, 10), CASE)
+    assert got.form == 'raster' and got.x_km is None and got.y_km is None
+    assert got.values[0] is fields[0][1] and got.values[1] is fields[1][1]            # neither copied nor moved
+    assert got.as_points() is got
+    got = classify(pair((2, 3)), _AXES['x_km'], _AXES['y_km'], (10, 10), CASE)
+    assert got.form == 'lattice' and isinstance(got.values, np.ndarray)
+    assert got.values.dtype == np.float64 and got.values.shape == (2, 2, 3)
+    assert got.x_km.shape == (3,) and got.y_km.shape == (2,)
+    pts = got.as_points()
+    gx, gy = np.meshgrid(_AXES['x_km'], _AXES['y_km'])
+    assert pts.form == 'scattered' and pts.values.shape == (2, 6)
+    assert np.array_equal(pts.x_km, gx.ravel()) and np.array_equal(pts.y_km, gy.ravel())
+    got = classify(pair((5,)), _XY5['x_km'], _XY5['y_km'], (10, 10), CASE)
+    assert got.form == 'scattered' and isinstance(got.values, np.ndarray)
+    assert got.values.dtype == np.float64 and got.values.shape == (2, 5)
+    assert got.x_km.dtype == np.float64 and got.as_points() is got
+    other = classify(pair((5,)), _XY5['x_km'][::-1].copy(), _XY5['y_km'], (10, 10), CASE)
+    assert got.same_points(got) and not got.same_points(other)                        # equal length, other points
+    with pytest.raises(ValueError, match='wdirn.*one form'):
+        classify([fields[0], pair((5,))[1]], _XY5['x_km'], _XY5['y_km'], (10, 10), CASE)
+
+
+def test_resolve_wind_projects_samples_in_degrees():
+    """Scattered points at lon / lat, and lattice axes with (lat, lon) arrays, both come back as scattered samples in
+    kilometres from the centre of cell (0, 0); a linear stand-in for the projection, so no device and no library."""
+    from ssrs_amd.inputs import resolve_wind
+    west, south = 2000., -3000.
+    forward = lambda lon, lat: (1000. * lon + 50. * lat, 700. * lat - 20. * lon)
+    project = lambda lon, lat: ((forward(lon, lat)[0] - west) / 1000., (forward(lon, lat)[1] - south) / 1000.)
+    names = dict(wspeed='windspeed_100m', wdirn='winddirection_100m')
+    lon, lat = np.array([1., 2., 4.]), np.array([10., 12.])
+    glon, glat = (a.ravel() for a in np.meshgrid(lon, lat))
+    ws, wd = np.arange(6.).reshape(2, 3) + 3., np.arange(6.).reshape(2, 3) + 250.
+    entries = [dict(datetime=(2010, 6, 17, 13), wspeed=ws.ravel(), wdirn=wd.ravel(), lon=glon, lat=glat),
+               dict(datetime=(2010, 6, 18, 13), wspeed=ws, wdirn=wd, lon=lon, lat=lat)]
+    cases = resolve_wind(entries, 'seasonal', 'y%Ym%md%dh%H', (10, 10), 'linear', False, names, project)
+    assert [c.case_id for c in cases] == [CASE, 'y2010m06d18h13'] and all(c.thermal is None for c in cases)
+    x, y = forward(glon, glat)
+    for case in cases:
+        assert case.wind.form == 'scattered' and case.wind.values.shape == (2, 6)
+        assert np.array_equal(case.wind.x_km, (x - west) / 1000.) and np.array_equal(case.wind.y_km, (y - south) / 1000.)
+        assert np.array_equal(case.wind.values, np.stack([ws.ravel(), wd.ravel()]))
+    assert cases[0].wind.same_points(cases[1].wind)
+    with pytest.raises(ValueError, match="both 'lon' / 'lat' and 'x_km' / 'y_km'"):
+        resolve_wind([dict(entries[0], x_km=glon, y_km=glat)], 'seasonal', 'y%Ym%md%dh%H', (10, 10), 'linear', False, names,
+                     project)
+
+
+@pytest.mark.parametrize('dtype', [np.int64, np.float64, np.int32])
+def test_collectives_without_a_process_group_return_their_input(dtype):
+    from ssrs_amd import distributed
+    assert not distributed.is_on() and distributed.rank() == 0 and distributed.world_size() == 1
+    distributed.barrier()
+    arr = np.arange(6, dtype=dtype).reshape(2, 3)
+    for got in (distributed.broadcast(arr), distributed.broadcast(arr, src=0), distributed.all_reduce_sum(arr)):
+        assert got.dtype == dtype and np.array_equal(got, arr)

@@ -190,25 +190,24 @@ def test_wtk_thermal_model_value_errors_need_no_gpu(tmp_path):
                   wind=[_entry(), _entry(datetime=(2010, 6, 18, 13), pressure=...)])
 
 
-def test_wtk_layer_forms_are_resolved_on_the_host(tmp_path):
+def test_wtk_layer_forms_are_resolved_on_the_host():
     """Rasters, scattered samples and a lattice (-> its meshgrid points) are all accepted; checked through the
-    resolver itself, which needs no device."""
+    classifier itself, which needs no device."""
     from ssrs_amd import Simulator
-    sim = Simulator.__new__(Simulator)
-    cfg = _wtk_config(tmp_path)
-    sim.__dict__.update(cfg.__dict__)
-    sim.gridsize = (10, 10)
-    sim.wtk_layers = dict(pressure='pressure_100m', temperature='temperature_100m', blheight='boundary_layer_height',
-                          surfheatflux='surface_heat_flux')
-    form, x, y, arr = sim._resolve_wtk_layers(dict(_entry(), case_id='c'))
-    assert form == 'samples' and arr.shape == (4, 5) and x.shape == (5,)
+    from ssrs_amd.inputs import classify
+    entry = _entry()
+    layers = lambda item: [(k, item[k]) for k in Simulator.THERMAL_LAYERS]
+    got = classify(layers(entry), entry['x_km'], entry['y_km'], (10, 10), 'c')
+    assert got.form == 'scattered' and got.values.shape == (4, 5) and got.x_km.shape == (5,) and got.as_points() is got
     xk, yk = np.array([0., .5, 1.]), np.array([0., 1.])
     lat = {k: np.arange(6.).reshape(2, 3) + i for i, k in enumerate(Simulator.THERMAL_LAYERS)}
-    form, x, y, arr = sim._resolve_wtk_layers(dict(case_id='c', x_km=xk, y_km=yk, **lat))
-    assert form == 'samples' and arr.shape == (4, 6)
+    got = classify(layers(lat), xk, yk, (10, 10), 'c')
+    assert got.form == 'lattice' and got.values.shape == (4, 2, 3)
+    pts = got.as_points()
+    assert pts.form == 'scattered' and pts.values.shape == (4, 6)
     gx, gy = np.meshgrid(xk, yk)
-    assert np.array_equal(x, gx.ravel()) and np.array_equal(y, gy.ravel())
-    assert np.array_equal(arr[2], lat['blheight'].ravel())
+    assert np.array_equal(pts.x_km, gx.ravel()) and np.array_equal(pts.y_km, gy.ravel())
+    assert np.array_equal(pts.values[2], lat['blheight'].ravel())
     ras = {k: np.full((10, 10), 1. + i) for i, k in enumerate(Simulator.THERMAL_LAYERS)}
-    form, x, y, arr = sim._resolve_wtk_layers(dict(case_id='c', **ras))
-    assert form == 'raster' and x is None and arr.shape == (4, 10, 10)
+    got = classify(layers(ras), None, None, (10, 10), 'c')
+    assert got.form == 'raster' and got.x_km is None and np.shape(got.values) == (4, 10, 10)
