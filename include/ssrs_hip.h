@@ -616,6 +616,36 @@ int ssrs_updraft_sheltered(const void *dem, int dem_type, double res, const doub
                            double min_updraft_val, double threshold, float *orograph, double *usable,
                            double *sx_deg, int rows, int cols, int batch, void *stream);
 
+/* Sx averaged over an upwind SECTOR of azimuths (Winstral's shelter parameter: typically 30 degrees wide in steps of 5),
+ * in one kernel: the tile is staged once for all rays of a cell, the mean stays in registers.  With a half-width
+ * W = sector_half_width >= 0 and a step S = sector_step > 0, both in degrees:
+ *   H = floor(W / S + 1e-9), M = 2 H + 1 azimuths A_m = A + (double)(m - H) S, m = 0 .. 2 H, A the direction the wind
+ *       comes from
+ *   T_m = the T of ssrs_shelter_sx for A_m: the same unit step per ray_axes, the same K = floor(dmax / res) samples,
+ *       snap, validity rule, unread weight-0 neighbour, NaN skipping and operation order; T_m = 0 without a valid sample,
+ *       for a NaN z0 or a NaN direction
+ *   sx_deg = Sx-bar = (sum_m atan(T_m) (180 / pi)) / (double)M, summed in ascending m in f64 (starting from 0.0)
+ *   tan_sx = T-bar  = tan(Sx-bar (pi / 180)).  For M = 1 (W < S): T-bar = T_0 and Sx-bar = atan(T_0) (180 / pi), no
+ *       division and no round trip, so the outputs of the single-ray calls are reproduced bit for bit
+ *   the updraft is that of ssrs_updraft_sheltered with T-bar for T: F_sx = max(0, 1 + g T-bar)
+ * Uniform wind: ray_ur / ray_uc hold `batch` x M HOST doubles, case-major (entry j M + m = the unit step of A_m of case
+ * j, the caller's cos / sin); wdirn0 stays the centre direction A.  Per-cell wind: the device forms A_m from the raster
+ * value and takes its sine / cosine of degrees.  Everything else is as in the single-ray calls, `path` included: the
+ * LDS halo of a uniform case is K |u| + 2 cells on every side one of its rays points to and 2 on the others, all round
+ * for per-cell wind, and a halo that does not fit reads global memory with the same bits.  W not finite or outside
+ * [0, 90], S not finite or not > 0, M > 61: SSRS_ERR_INVALID before anything else is looked at and before any GPU
+ * work. */
+int ssrs_shelter_sx_sector(const void *dem, int dem_type, double res, const double *ray_ur, const double *ray_uc,
+                           const double *wdirn, double dmax, int ray_axes, int path, double sector_half_width,
+                           double sector_step, double *tan_sx, double *sx_deg, int rows, int cols, int batch,
+                           void *stream);
+int ssrs_updraft_sheltered_sector(const void *dem, int dem_type, double res, const double *ray_ur, const double *ray_uc,
+                                  const double *wspeed0, const double *wdirn0, const double *wspeed,
+                                  const double *wdirn, const void *slope, const void *aspect, int sa_type,
+                                  const SsrsShelterParams *params, double sector_half_width, double sector_step,
+                                  double min_updraft_val, double threshold, float *orograph, double *usable,
+                                  double *sx_deg, int rows, int cols, int batch, void *stream);
+
 /* ---------------------------------------------------------------- georef */
 
 /* K10 -- Albers Equal Area Conic on an ellipsoid (Snyder, USGS PP 1395, eqs. 14-12 ... 14-21, 3-12, 3-16) and the

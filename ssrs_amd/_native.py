@@ -46,7 +46,7 @@ EXPORTS = (
     'ssrs_presence_normalise_add', 'ssrs_presence_normalise_f32',
     'ssrs_potential_workspace_bytes', 'ssrs_potential_solve',
     'ssrs_turbine_encounters', 'ssrs_turbine_encounter_counts',
-    'ssrs_shelter_sx', 'ssrs_updraft_sheltered',
+    'ssrs_shelter_sx', 'ssrs_updraft_sheltered', 'ssrs_shelter_sx_sector', 'ssrs_updraft_sheltered_sector',
     'ssrs_projection_init_albers', 'ssrs_warp_lonlat_raster',
 )
 
@@ -170,6 +170,12 @@ def lib():
         L.ssrs_updraft_sheltered.argtypes = [C.c_void_p, C.c_int, C.c_double] + [C.c_void_p] * 8 + \
             [C.c_int, C.POINTER(SsrsShelterParams), C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
              C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.ssrs_shelter_sx_sector.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                             C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_int, C.c_int, C.c_void_p]
+        L.ssrs_updraft_sheltered_sector.argtypes = [C.c_void_p, C.c_int, C.c_double] + [C.c_void_p] * 8 + \
+            [C.c_int, C.POINTER(SsrsShelterParams), C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+             C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.ssrs_projection_init_albers.argtypes = [C.POINTER(SsrsProjection)]
         L.ssrs_warp_lonlat_raster.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_double] * 5 + \
             [C.POINTER(SsrsProjection)] + [C.c_double] * 3 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -23,7 +23,8 @@ _SECTIONS = (
     ('WindToolKit settings', ('wtk_source', 'wtk_orographic_height', 'wtk_thermal_height',
                               'wtk_interp_type')),
     ('Updraft computation', ('thermals_realization_count', 'updraft_threshold',
-                             'movement_model', 'orographic_model', 'orographic_sx_dmax',
+                             'movement_model', 'orographic_sx_sector', 'orographic_sx_step',
+                             'orographic_model', 'orographic_sx_dmax',
                              'orographic_height', 'orographic_coeffs')),
     ('Simulating tracks', ('track_direction', 'track_count', 'track_start_region',
                            'track_start_type', 'track_stochastic_nu',
@@ -107,12 +108,17 @@ class Config:
     #                                     'improved': that value sheltered by the terrain upwind (Winstral's Sx within
     #                                     orographic_sx_dmax metres) and scaled to orographic_height metres above ground:
     #                                     w0 max(0, 1 + g tan Sx) / ((a h^2 + b h + c) d^(e - cos(slope)) + f), DESIGN.md K9;
-    #                                     also writes <case>_sx.npy, and the ids carry -sx<dmax>h<height>
+    #                                     also writes <case>_sx.npy, and the ids carry -sx<dmax>h<height>[a<sector>s<step>]
     orographic_sx_dmax: float = 500.    # metres upwind searched for sheltering terrain (>= resolution)
     orographic_height: float = 80.      # h, metres above ground
     orographic_coeffs: Tuple = (4e-5, 2.8e-3, 0.8, 0.35, 0.095, -0.09, 1.0)   # (a, b, c, d, e, f, g), recalled from the
     #                                     published improved model and NOT verified against it (the sign of g least of all):
     #                                     correct them here, no rebuild is needed
+    orographic_sx_sector: float = 0.    # 'improved' only: half-width in degrees of the upwind sector Sx is averaged over
+    #                                     (Winstral: 15 = a 30 degree sector).  0 = the single ray towards the wind.  > 0: the mean
+    #                                     of Sx over the azimuths wdirn + j orographic_sx_step within the sector, at most 61 of
+    #                                     them, in one device call; <case>_sx.npy holds the mean and the ids carry a<sector>s<step>
+    orographic_sx_step: float = 5.      # degrees between the rays of that sector (> 0)
     hist_safe_tracks: int = 250_000     # tracks per sub-batch of a case: (i) histograms of several sub-batches are added up in 64
     #                                     bits; a sub-batch of more than 100 000 tracks is counted in 64 bits inside the library (a trap
     #                                     cell of the solved 10 m field takes 1.7e4 visits per track: 2^32 from ~245 000 tracks on;

@@ -14,6 +14,7 @@
 // arithmetic on the same values, hence the same bits; the choice is the host's.
 // Several uniform cases in one launch re-stage the tile only when the upwind quadrant changes: the terrain comes
 // from HBM once.  Built with -ffp-contract=off like the rest (the sample is defined without contraction).
+// k_shelter_sector (below) averages Sx over M azimuths of an upwind sector on one staging of the tile.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -337,6 +338,369 @@ static int shelter_common(ShelterArgs &a, const char *who, const void *dem, int 
     return SSRS_OK;
 }
 
+// The checks and the fill of `a` that the two updraft calls share (everything but the wind cases of a launch).
+static int sheltered_common(ShelterArgs &a, const char *who, const void *dem, int dem_type, double res,
+                            const double *ray_ur, const double *ray_uc, const double *wspeed0, const double *wdirn0,
+                            const double *wspeed, const double *wdirn, const void *slope, const void *aspect,
+                            int sa_type, const SsrsShelterParams *params, double min_updraft_val, double threshold,
+                            bool want_usable, int rows, int cols, int batch)
+{
+    SSRS_REQUIRE(params != nullptr, "%s: params is NULL", who);
+    if (int rc = shelter_common(a, who, dem, dem_type, res, ray_ur, ray_uc, wdirn, params->dmax, params->ray_axes,
+                                params->path, rows, cols, batch, 3))
+        return rc;
+    const bool uniform = ray_ur != nullptr;
+    SSRS_REQUIRE(uniform ? (wspeed0 && wdirn0 && !wspeed) : (wspeed && !wspeed0 && !wdirn0),
+                 "%s: uniform wind takes ray_ur, ray_uc, wspeed0, wdirn0 (host); per-cell wind takes wspeed, wdirn (device)", who);
+    SSRS_REQUIRE((slope == nullptr) == (aspect == nullptr), "%s: give both slope and aspect or neither", who);
+    SSRS_REQUIRE(!slope || sa_type == SSRS_F32 || sa_type == SSRS_F64, "%s: bad slope / aspect element type", who);
+    SSRS_REQUIRE(!(want_usable && !(threshold > 0.0)), "%s: usable requested without a positive threshold", who);
+    const double h = params->height;
+    const double *cf = params->coef;
+    for (int j = 0; j < 7; ++j) SSRS_REQUIRE(std::isfinite(cf[j]), "%s: coefficient %d is not finite", who, j);
+    SSRS_REQUIRE(h >= 0.0 && std::isfinite(h), "%s: height must be >= 0 (got %g)", who, h);
+    SSRS_REQUIRE(cf[3] > 0.0, "%s: coefficient d must be > 0 (got %g)", who, cf[3]);
+    const double poly = cf[0] * h * h + cf[1] * h + cf[2];
+    const double fh0 = poly * pow(cf[3], cf[4]) + cf[5], fh1 = poly * pow(cf[3], cf[4] - 1.0) + cf[5];
+    SSRS_REQUIRE(fh0 > 0.0 && fh1 > 0.0 && std::isfinite(fh0) && std::isfinite(fh1),
+                 "%s: these coefficients allow F_h <= 0 (F_h = %g on flat ground, %g on a vertical face)", who, fh1, fh0);
+    a.wspeed_r = wspeed;
+    a.slope = slope;
+    a.aspect = aspect;
+    a.sa_f64 = sa_type == SSRS_F64;
+    a.d = 8 * res;
+    a.d2 = a.d * a.d;
+    a.min_val = min_updraft_val;
+    a.thr = threshold;
+    a.inv_thr = threshold > 0.0 ? 1.0 / threshold : 0.0;
+    a.scale = threshold > 0.0 ? threshold / (exp(1.0) - 1.0) : 0.0;
+    a.em1 = exp(1.0) - 1.0;
+    a.poly = poly;
+    a.ln_d = log(cf[3]);
+    a.ce = cf[4];
+    a.cf = cf[5];
+    a.cg = cf[6];
+    return SSRS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- the sector average
+// Sx averaged over M = 2 H + 1 azimuths A + (m - H) S (include/ssrs_hip.h): k_shelter's ray M times per cell on ONE
+// staging of the tile, the mean of the angles kept in registers, Sx-bar and T-bar written once.
+constexpr int kMaxSectorM = 61;
+constexpr int kMaxSectorRays = 128;              // ray steps in the arguments of one launch: min(16, 128 / M) uniform cases
+
+struct SectorArgs {
+    ShelterArgs s;                               // (s.ur / s.uc stay unused: the M rays of every case are below)
+    int M, H;
+    double step;                                 // S in degrees: per-cell wind forms A_m on the device
+    double ur[kMaxSectorRays], uc[kMaxSectorRays];                     // uniform wind: case-major, M per case
+    int mt[kMaxShelterBatch], ml[kMaxShelterBatch], mb[kMaxShelterBatch], mr[kMaxShelterBatch];   // its halo per side
+};
+static_assert(sizeof(SectorArgs) + 2 * sizeof(int) <= 4096, "the kernel's arguments must fit 4 KB");
+
+// The adjusted updraft of one cell from T = tan Sx: the epilogue of k_shelter, operation for operation.
+template <typename Tin, bool UNIFORM>
+__device__ __forceinline__ void sheltered_updraft(const ShelterArgs &a, const Tin *__restrict__ dem, const DemView &v,
+                                                  int b, int r, int c, size_t i, size_t o, double Tq, double sn_w,
+                                                  double cs_w)
+{
+    const int rows = a.rows, cols = a.cols;
+    double w0 = 0.0, cos_s = 1.0;
+    if (a.slope) {
+        // the arithmetic of k_orographic
+        const double spd = UNIFORM ? a.wspeed[b] : a.wspeed_r[o];
+        const double dir = UNIFORM ? a.wdirn[b] : a.wdirn_r[o];
+        double sin_s, ad, unused;
+        sincos_deg(load_sa(a.slope, a.sa_f64, i), sin_s, cos_s);
+        sincos_deg(load_sa(a.aspect, a.sa_f64, i) - dir, unused, ad);
+        ad = ad > 0.0 ? ad : 0.0;
+        w0 = spd * (sin_s * ad);
+    } else if (r > 0 && c > 0 && r < rows - 1 && c < cols - 1) {
+        // the arithmetic of k_updraft_from_dem: un-normalised Horn sums, "x" = row axis
+        const double spd = UNIFORM ? a.wspeed[b] : a.wspeed_r[o];
+        const double cw = UNIFORM ? a.cos_w[b] : cs_w;
+        const double sw = UNIFORM ? a.sin_w[b] : sn_w;
+        const double m_l = dem_at(dem, cols, v, r - 1, c - 1), m_c = dem_at(dem, cols, v, r - 1, c),
+                     m_r = dem_at(dem, cols, v, r - 1, c + 1);
+        const double z_l = dem_at(dem, cols, v, r, c - 1), z_r = dem_at(dem, cols, v, r, c + 1);
+        const double p_l = dem_at(dem, cols, v, r + 1, c - 1), p_c = dem_at(dem, cols, v, r + 1, c),
+                     p_r = dem_at(dem, cols, v, r + 1, c + 1);
+        const double X = (p_r + 2 * p_c + p_l) - (m_r + 2 * m_c + m_l);
+        const double Y = (m_r + 2 * z_r + p_r) - (m_l + 2 * z_l + p_l);
+        const double rs = rsqrt_pos(a.d2 + (X * X + Y * Y));
+        if (X != 0.0) {
+            const double P = -(Y * cw + X * sw);
+            if (P > 0.0) w0 = spd * (P * rs);
+        } else {
+            const double dzdy = Y / a.d, dx = 1e-10;
+            const double g2 = dzdy * dzdy, gp2 = dx * dx + g2;
+            const double proj = -(dzdy * cw + dx * sw);
+            if (proj > 0.0 && g2 > 0.0) w0 = spd * (proj * sqrt(g2 / (gp2 * (1.0 + g2))));
+        }
+        cos_s = a.d * rs;
+        cos_s = cos_s == cos_s ? cos_s : 1.0;                    // NaN in the stencil: slope 0, as the layers
+    }
+    const double f_h = a.poly * exp((a.ce - cos_s) * a.ln_d) + a.cf;
+    double f_sx = 1.0 + a.cg * Tq;
+    f_sx = f_sx > 0.0 ? f_sx : 0.0;
+    double w = w0 * f_sx / f_h;
+    w = w > a.min_val ? w : a.min_val;
+    const float w32 = static_cast<float>(w);
+    if (a.orograph) a.orograph[o] = w32;
+    if (a.usable)
+        a.usable[o] = a.slope ? usable_updraft(static_cast<double>(w32), a.thr, a.em1)
+                              : usable_updraft_fast(static_cast<double>(w32), a.thr, a.inv_thr, a.scale);
+}
+
+template <typename Tin, bool UNIFORM>
+__global__ __launch_bounds__(kShelterBlock) void k_shelter_sector(SectorArgs g, int tiles_x, int ntiles)
+{
+    constexpr int TW = UNIFORM ? 64 : 32;
+    constexpr int TH = kShelterTH;
+    constexpr int CPT = TW * TH / kShelterBlock;                 // cells per thread: 4 or 2
+    __shared__ double s_tile[kTileDoubles];
+    __shared__ double s_inv_d[kRayChunk], s_fo_r[kRayChunk], s_fo_c[kRayChunk];
+    __shared__ int s_io_r[kRayChunk], s_io_c[kRayChunk];
+
+    const ShelterArgs &a = g.s;
+    const Tin *__restrict__ dem = static_cast<const Tin *>(a.dem);
+    const int rows = a.rows, cols = a.cols, K = a.K, M = g.M;
+    const int MK = M * K;                                        // host: M K < 2^31
+    const int t = xcd_tile(blockIdx.x, ntiles);
+    const int r0 = (t / tiles_x) * TH, c0 = (t % tiles_x) * TW;
+    const size_t ncell = static_cast<size_t>(rows) * cols;
+    const int tid = threadIdx.x;
+
+    DemView v;
+    v.tile = s_tile;
+    v.lds = a.use_lds != 0;
+    v.tr0 = v.tc0 = v.lh = v.lw = 0;
+    int staged_mt = -1, staged_ml = -1, staged_mb = -1, staged_mr = -1;
+
+    for (int b = 0; b < a.batch; ++b) {
+        // ---- stage the tile and its halo once for the M rays: what the sector reaches on every side (uniform
+        //      wind, from the host) or K + 2 all round
+        if (v.lds) {
+            int mt = K + 2, ml = K + 2, mb = K + 2, mr = K + 2;
+            if (UNIFORM) {
+                mt = g.mt[b];
+                ml = g.ml[b];
+                mb = g.mb[b];
+                mr = g.mr[b];
+            }
+            if (mt != staged_mt || ml != staged_ml || mb != staged_mb || mr != staged_mr) {   // (block-uniform)
+                __syncthreads();
+                v.tr0 = r0 - mt;
+                v.tc0 = c0 - ml;
+                v.lh = TH + mt + mb;
+                v.lw = TW + ml + mr;                             // host: lh * lw <= kTileDoubles
+                for (int i = tid; i < v.lh * v.lw; i += kShelterBlock) {
+                    const int li = i / v.lw, lj = i - li * v.lw;
+                    const int gr = v.tr0 + li, gc = v.tc0 + lj;
+                    double z = 0.0;                              // outside the raster: never read (validity rule)
+                    if (gr >= 0 && gr < rows && gc >= 0 && gc < cols)
+                        z = static_cast<double>(dem[static_cast<size_t>(gr) * cols + gc]);
+                    s_tile[i] = z;
+                }
+                staged_mt = mt;
+                staged_ml = ml;
+                staged_mb = mb;
+                staged_mr = mr;
+                __syncthreads();
+            }
+        }
+
+        const double ninf = -__builtin_huge_val();
+#pragma unroll 1
+        for (int q = 0; q < CPT; ++q) {
+            const int cell = tid + q * kShelterBlock;
+            const int r = r0 + cell / TW, c = c0 + cell % TW;
+            const bool inside = r < rows && c < cols;
+            const size_t i = static_cast<size_t>(r) * cols + c;
+            const size_t o = b * ncell + i;
+            double z0 = 0.0, A = 0.0, sn_w = 0.0, cs_w = 0.0;
+            if (inside) {
+                z0 = dem_at(dem, cols, v, r, c);
+                if (!UNIFORM) {
+                    A = a.wdirn_r[o];
+                    sincos_deg(A, sn_w, cs_w);                   // the centre ray's, for the Horn projection below
+                }
+            }
+
+            // ---- the M K samples, ray after ray, tabulated kRayChunk at a time; (m, k) = the ray and the samples
+            //      of it already taken
+            double T = ninf, T0 = 0.0, acc = 0.0, ur = 0.0, uc = 0.0;
+            bool ray_live = UNIFORM;
+            int m = 0, k = 0;
+            for (int e0 = 0; e0 < MK; e0 += kRayChunk) {
+                const int n = MK - e0 < kRayChunk ? MK - e0 : kRayChunk;
+                __syncthreads();                                 // the previous table is done with
+                for (int me = e0 / K; me * K < e0 + n; ++me) {   // (block-uniform: the ray's step is a scalar load)
+                    const int ke = e0 + tid - me * K;            // entry tid is sample ke + 1 of ray me
+                    if (tid < n && ke >= 0 && ke < K) {
+                        const double kd = static_cast<double>(ke + 1);
+                        s_inv_d[tid] = 1.0 / (kd * a.res);
+                        if (UNIFORM) {
+                            int io;
+                            double fo;
+                            ray_offset(kd, g.ur[b * M + me], io, fo);
+                            s_io_r[tid] = io;
+                            s_fo_r[tid] = fo;
+                            ray_offset(kd, g.uc[b * M + me], io, fo);
+                            s_io_c[tid] = io;
+                            s_fo_c[tid] = fo;
+                        }
+                    }
+                }
+                __syncthreads();
+                if (!inside) continue;
+                for (int kk = 0; kk < n; ++kk) {
+                    if (!UNIFORM && k == 0) {
+                        double sn, cs;
+                        sincos_deg(A + static_cast<double>(m - g.H) * g.step, sn, cs);
+                        ur = a.row_north ? cs : sn;
+                        uc = a.row_north ? sn : cs;
+                        ray_live = ur == ur && uc == uc;         // NaN direction: no sample, T_m = 0
+                    }
+                    if (ray_live) {
+                        int io_r, io_c;
+                        double fo_r, fo_c;
+                        if (UNIFORM) {
+                            io_r = s_io_r[kk];
+                            io_c = s_io_c[kk];
+                            fo_r = s_fo_r[kk];
+                            fo_c = s_fo_c[kk];
+                        } else {
+                            const double kd = static_cast<double>(k + 1);
+                            ray_offset(kd, ur, io_r, fo_r);
+                            ray_offset(kd, uc, io_c, fo_c);
+                        }
+                        shelter_sample(dem, rows, cols, v, r + io_r, c + io_c, fo_r, fo_c, z0, s_inv_d[kk], T);
+                    }
+                    if (++k == K) {                              // ray m is complete: its angle joins the sum
+                        const double Tm = (T == ninf || z0 != z0) ? 0.0 : T;
+                        acc += atan(Tm) * (180.0 / kPi);
+                        if (m == 0) T0 = Tm;
+                        T = ninf;
+                        k = 0;
+                        ++m;
+                    }
+                }
+            }
+
+            // ---- outputs: one ray keeps its own T and angle (no round trip), M > 1 the mean angle and its tangent
+            if (!inside) continue;
+            double Tq = T0, sx = acc;
+            if (M > 1) {
+                sx = acc / static_cast<double>(M);
+                Tq = tan(sx * (kPi / 180.0));
+            }
+            if (a.tan_sx) a.tan_sx[o] = Tq;
+            if (a.sx_deg) a.sx_deg[o] = sx;
+            if (a.want_updraft) sheltered_updraft<Tin, UNIFORM>(a, dem, v, b, r, c, i, o, Tq, sn_w, cs_w);
+        }
+    }
+}
+
+// H and M of a sector of half-width W in steps of S degrees; refused before anything else is looked at
+static int sector_rays(const char *who, double W, double S, int &H, int &M)
+{
+    SSRS_REQUIRE(std::isfinite(W) && W >= 0.0 && W <= 90.0,
+                 "%s: sector_half_width = %g: expected degrees in [0, 90]", who, W);
+    SSRS_REQUIRE(std::isfinite(S) && S > 0.0, "%s: sector_step = %g: expected degrees > 0", who, S);
+    const double h = floor(W / S + 1e-9);
+    SSRS_REQUIRE(2.0 * h + 1.0 <= kMaxSectorM, "%s: a sector of +-%g degrees in steps of %g takes M = %.0f rays, more than %d",
+                 who, W, S, 2.0 * h + 1.0, kMaxSectorM);
+    H = static_cast<int>(h);
+    M = 2 * H + 1;
+    return SSRS_OK;
+}
+
+// Halo (top, left, bottom, right) that the M rays of one uniform case reach: K |u| + 2 on the side a ray points
+// to, 2 elsewhere.  True when the tile with it fits the LDS.
+static bool sector_halo(const double *ur, const double *uc, int M, int K, int halo[4])
+{
+    halo[0] = halo[1] = halo[2] = halo[3] = 2;
+    for (int m = 0; m < M; ++m) {
+        const int rr = static_cast<int>(ceil(K * fabs(ur[m]))) + 2, rc = static_cast<int>(ceil(K * fabs(uc[m]))) + 2;
+        int &side_r = ur[m] < 0.0 ? halo[0] : halo[2], &side_c = uc[m] < 0.0 ? halo[1] : halo[3];
+        side_r = rr > side_r ? rr : side_r;
+        side_c = rc > side_c ? rc : side_c;
+    }
+    const long long n = (64ll + halo[1] + halo[3]) * (kShelterTH + halo[0] + halo[2]);
+    return n <= kTileDoubles;
+}
+
+static int sector_path(int path)
+{
+    if (const char *e = std::getenv("SSRS_SHELTER_PATH")) {      // A/B switch: lds | global, as shelter_launch
+        if (!std::strcmp(e, "lds")) path = SSRS_SHELTER_LDS;
+        else if (!std::strcmp(e, "global")) path = SSRS_SHELTER_GLOBAL;
+    }
+    return path;
+}
+
+// The checks of a sector call beyond shelter_common's: every one of the batch x M ray steps, and a forced LDS path
+// (`path` as sector_path gives it)
+static int sector_common(const ShelterArgs &a, const char *who, const double *ray_ur, const double *ray_uc, int M,
+                         int path, int batch)
+{
+    SSRS_REQUIRE(static_cast<long long>(M) * a.K < (1ll << 31), "%s: M K = %d x %d samples per cell exceed 2^31 - 1", who, M, a.K);
+    int halo[4];
+    for (int j = 0; ray_ur && j < batch; ++j) {
+        for (int m = 0; m < M; ++m) {
+            const double u = ray_ur[j * M + m], w = ray_uc[j * M + m];
+            SSRS_REQUIRE(std::isfinite(u) && std::isfinite(w) && fabs(u) <= 1.0 && fabs(w) <= 1.0,
+                         "%s: ray step %d of case %d = (%g, %g) is not a unit step", who, m, j, u, w);
+        }
+        SSRS_REQUIRE(path != SSRS_SHELTER_LDS || sector_halo(ray_ur + j * M, ray_uc + j * M, M, a.K, halo),
+                     "%s: the halo of K = %d samples over the sector of case %d does not fit the LDS tile", who, a.K, j);
+    }
+    SSRS_REQUIRE(ray_ur || path != SSRS_SHELTER_LDS || shelter_tile_doubles(false, a.K) > 0,
+                 "%s: the halo of K = %d samples does not fit the LDS tile", who, a.K);
+    return SSRS_OK;
+}
+
+// The ray steps and halos of the uniform cases [b0, b0 + g.s.batch), the path, and the launch
+static int sector_launch(SectorArgs &g, int dem_type, const double *ray_ur, const double *ray_uc, int b0, int path,
+                         hipStream_t st)
+{
+    ShelterArgs &a = g.s;
+    const bool uniform = ray_ur != nullptr;
+    bool fits = uniform || shelter_tile_doubles(false, a.K) > 0;
+    for (int j = 0; uniform && j < a.batch; ++j) {
+        int halo[4];
+        const double *ur = ray_ur + static_cast<size_t>(b0 + j) * g.M, *uc = ray_uc + static_cast<size_t>(b0 + j) * g.M;
+        fits = sector_halo(ur, uc, g.M, a.K, halo) && fits;      // one case too wide: the launch reads global memory
+        g.mt[j] = halo[0];
+        g.ml[j] = halo[1];
+        g.mb[j] = halo[2];
+        g.mr[j] = halo[3];
+        for (int m = 0; m < g.M; ++m) {
+            g.ur[j * g.M + m] = ur[m];
+            g.uc[j * g.M + m] = uc[m];
+        }
+    }
+    a.use_lds = path != SSRS_SHELTER_GLOBAL && fits;
+    const int tw = uniform ? 64 : 32;
+    const int tx = (a.cols + tw - 1) / tw, ty = (a.rows + kShelterTH - 1) / kShelterTH, nt = tx * ty;
+    const bool f64 = dem_type == SSRS_F64;
+    if (uniform && f64) hipLaunchKernelGGL((k_shelter_sector<double, true>), dim3(nt), dim3(kShelterBlock), 0, st, g, tx, nt);
+    else if (uniform) hipLaunchKernelGGL((k_shelter_sector<float, true>), dim3(nt), dim3(kShelterBlock), 0, st, g, tx, nt);
+    else if (f64) hipLaunchKernelGGL((k_shelter_sector<double, false>), dim3(nt), dim3(kShelterBlock), 0, st, g, tx, nt);
+    else hipLaunchKernelGGL((k_shelter_sector<float, false>), dim3(nt), dim3(kShelterBlock), 0, st, g, tx, nt);
+    SSRS_HIP_CHECK(hipGetLastError());
+    return SSRS_OK;
+}
+
+// uniform cases per launch: their M ray steps each travel in the kernel's arguments
+static int sector_cases_per_launch(bool uniform, int M, int batch)
+{
+    if (!uniform) return batch;
+    const int n = kMaxSectorRays / M;
+    return n < kMaxShelterBatch ? n : kMaxShelterBatch;
+}
+
 }  // namespace ssrs
 
 using namespace ssrs;
@@ -374,44 +738,14 @@ extern "C" int ssrs_updraft_sheltered(const void *dem, int dem_type, double res,
                                       double *sx_deg, int rows, int cols, int batch, void *stream)
 {
     const char *who = "ssrs_updraft_sheltered";
-    SSRS_REQUIRE(params != nullptr, "%s: params is NULL", who);
     ShelterArgs a = {};
-    if (int rc = shelter_common(a, who, dem, dem_type, res, ray_ur, ray_uc, wdirn, params->dmax, params->ray_axes,
-                                params->path, rows, cols, batch, 3))
+    if (int rc = sheltered_common(a, who, dem, dem_type, res, ray_ur, ray_uc, wspeed0, wdirn0, wspeed, wdirn, slope,
+                                  aspect, sa_type, params, min_updraft_val, threshold, usable != nullptr, rows, cols,
+                                  batch))
         return rc;
     const bool uniform = ray_ur != nullptr;
-    SSRS_REQUIRE(uniform ? (wspeed0 && wdirn0 && !wspeed) : (wspeed && !wspeed0 && !wdirn0),
-                 "%s: uniform wind takes ray_ur, ray_uc, wspeed0, wdirn0 (host); per-cell wind takes wspeed, wdirn (device)", who);
-    SSRS_REQUIRE((slope == nullptr) == (aspect == nullptr), "%s: give both slope and aspect or neither", who);
-    SSRS_REQUIRE(!slope || sa_type == SSRS_F32 || sa_type == SSRS_F64, "%s: bad slope / aspect element type", who);
-    SSRS_REQUIRE(!(usable && !(threshold > 0.0)), "%s: usable requested without a positive threshold", who);
-    const double h = params->height;
-    const double *cf = params->coef;
-    for (int j = 0; j < 7; ++j) SSRS_REQUIRE(std::isfinite(cf[j]), "%s: coefficient %d is not finite", who, j);
-    SSRS_REQUIRE(h >= 0.0 && std::isfinite(h), "%s: height must be >= 0 (got %g)", who, h);
-    SSRS_REQUIRE(cf[3] > 0.0, "%s: coefficient d must be > 0 (got %g)", who, cf[3]);
-    const double poly = cf[0] * h * h + cf[1] * h + cf[2];
-    const double fh0 = poly * pow(cf[3], cf[4]) + cf[5], fh1 = poly * pow(cf[3], cf[4] - 1.0) + cf[5];
-    SSRS_REQUIRE(fh0 > 0.0 && fh1 > 0.0 && std::isfinite(fh0) && std::isfinite(fh1),
-                 "%s: these coefficients allow F_h <= 0 (F_h = %g on flat ground, %g on a vertical face)", who, fh1, fh0);
     if (!orograph && !usable && !sx_deg) return SSRS_OK;
     a.want_updraft = orograph || usable;
-    a.wspeed_r = wspeed;
-    a.slope = slope;
-    a.aspect = aspect;
-    a.sa_f64 = sa_type == SSRS_F64;
-    a.d = 8 * res;
-    a.d2 = a.d * a.d;
-    a.min_val = min_updraft_val;
-    a.thr = threshold;
-    a.inv_thr = threshold > 0.0 ? 1.0 / threshold : 0.0;
-    a.scale = threshold > 0.0 ? threshold / (exp(1.0) - 1.0) : 0.0;
-    a.em1 = exp(1.0) - 1.0;
-    a.poly = poly;
-    a.ln_d = log(cf[3]);
-    a.ce = cf[4];
-    a.cf = cf[5];
-    a.cg = cf[6];
     hipStream_t st = as_stream(stream);
     const size_t ncell = static_cast<size_t>(rows) * cols;
     const int step = uniform ? kMaxShelterBatch : batch;
@@ -434,6 +768,81 @@ extern "C" int ssrs_updraft_sheltered(const void *dem, int dem_type, double res,
             a.wdirn_r = wdirn + b0 * ncell;
         }
         if (int rc = shelter_launch(a, dem_type, uniform, params->path, who, st)) return rc;
+    }
+    return SSRS_OK;
+}
+
+extern "C" int ssrs_shelter_sx_sector(const void *dem, int dem_type, double res, const double *ray_ur,
+                                      const double *ray_uc, const double *wdirn, double dmax, int ray_axes, int path,
+                                      double sector_half_width, double sector_step, double *tan_sx, double *sx_deg,
+                                      int rows, int cols, int batch, void *stream)
+{
+    const char *who = "ssrs_shelter_sx_sector";
+    SectorArgs g = {};
+    ShelterArgs &a = g.s;
+    if (int rc = sector_rays(who, sector_half_width, sector_step, g.H, g.M)) return rc;
+    if (int rc = shelter_common(a, who, dem, dem_type, res, ray_ur, ray_uc, wdirn, dmax, ray_axes, path, rows, cols,
+                                batch, 2))
+        return rc;
+    path = sector_path(path);
+    if (int rc = sector_common(a, who, ray_ur, ray_uc, g.M, path, batch)) return rc;
+    if (!tan_sx && !sx_deg) return SSRS_OK;
+    g.step = sector_step;
+    hipStream_t st = as_stream(stream);
+    const size_t ncell = static_cast<size_t>(rows) * cols;
+    const int step = sector_cases_per_launch(ray_ur != nullptr, g.M, batch);
+    for (int b0 = 0; b0 < batch; b0 += step) {
+        a.batch = batch - b0 < step ? batch - b0 : step;
+        a.tan_sx = tan_sx ? tan_sx + b0 * ncell : nullptr;
+        a.sx_deg = sx_deg ? sx_deg + b0 * ncell : nullptr;
+        a.wdirn_r = wdirn ? wdirn + b0 * ncell : nullptr;
+        if (int rc = sector_launch(g, dem_type, ray_ur, ray_uc, b0, path, st)) return rc;
+    }
+    return SSRS_OK;
+}
+
+extern "C" int ssrs_updraft_sheltered_sector(const void *dem, int dem_type, double res, const double *ray_ur,
+                                             const double *ray_uc, const double *wspeed0, const double *wdirn0,
+                                             const double *wspeed, const double *wdirn, const void *slope,
+                                             const void *aspect, int sa_type, const SsrsShelterParams *params,
+                                             double sector_half_width, double sector_step, double min_updraft_val,
+                                             double threshold, float *orograph, double *usable, double *sx_deg,
+                                             int rows, int cols, int batch, void *stream)
+{
+    const char *who = "ssrs_updraft_sheltered_sector";
+    SectorArgs g = {};
+    ShelterArgs &a = g.s;
+    if (int rc = sector_rays(who, sector_half_width, sector_step, g.H, g.M)) return rc;
+    if (int rc = sheltered_common(a, who, dem, dem_type, res, ray_ur, ray_uc, wspeed0, wdirn0, wspeed, wdirn, slope,
+                                  aspect, sa_type, params, min_updraft_val, threshold, usable != nullptr, rows, cols,
+                                  batch))
+        return rc;
+    const int path = sector_path(params->path);
+    if (int rc = sector_common(a, who, ray_ur, ray_uc, g.M, path, batch)) return rc;
+    if (!orograph && !usable && !sx_deg) return SSRS_OK;
+    const bool uniform = ray_ur != nullptr;
+    a.want_updraft = orograph || usable;
+    g.step = sector_step;
+    hipStream_t st = as_stream(stream);
+    const size_t ncell = static_cast<size_t>(rows) * cols;
+    const int step = sector_cases_per_launch(uniform, g.M, batch);
+    for (int b0 = 0; b0 < batch; b0 += step) {
+        a.batch = batch - b0 < step ? batch - b0 : step;
+        for (int j = 0; uniform && j < a.batch; ++j) {
+            a.wspeed[j] = wspeed0[b0 + j];
+            a.wdirn[j] = wdirn0[b0 + j];
+            const double w = wdirn0[b0 + j] * kPi / 180.0;      // as ssrs_updraft_from_dem
+            a.cos_w[j] = cos(w);
+            a.sin_w[j] = sin(w);
+        }
+        a.orograph = orograph ? orograph + b0 * ncell : nullptr;
+        a.usable = usable ? usable + b0 * ncell : nullptr;
+        a.sx_deg = sx_deg ? sx_deg + b0 * ncell : nullptr;
+        if (!uniform) {
+            a.wspeed_r = wspeed + b0 * ncell;
+            a.wdirn_r = wdirn + b0 * ncell;
+        }
+        if (int rc = sector_launch(g, dem_type, ray_ur, ray_uc, b0, path, st)) return rc;
     }
     return SSRS_OK;
 }

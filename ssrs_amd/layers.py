@@ -280,10 +280,38 @@ def check_improved_parameters(dmax, res, height, coeffs):
     return cf
 
 
-def _wind_direction_args(wdirn, ray_axes, rows, cols):
-    """(batch, single, ur, uc, wdirn device raster | None) from scalars / a 1-D sequence (uniform) or rasters."""
+SECTOR_MAX_RAYS = 61
+
+
+def sector_rays(sector, sector_step):
+    """(H, M) of a shelter sector of half-width `sector` in steps of `sector_step` degrees: H = floor(W / S + 1e-9),
+    M = 2 H + 1 azimuths A + (m - H) S.  ValueError unless W is finite and in [0, 90], S finite and > 0, M <= 61.
+    Host only."""
+    try:
+        w, s = float(sector), float(sector_step)
+    except (TypeError, ValueError):
+        w = s = np.nan
+    if not (np.isfinite(w) and 0. <= w <= 90.):
+        raise ValueError(f'orographic_sx_sector = {sector!r}: expected a half-width in degrees in [0, 90]')
+    if not (np.isfinite(s) and s > 0.):
+        raise ValueError(f'orographic_sx_step = {sector_step!r}: expected degrees > 0')
+    h = np.floor(w / s + 1e-9)
+    if not 2. * h + 1. <= SECTOR_MAX_RAYS:
+        raise ValueError(f'orographic_sx_sector = {sector!r} in steps of orographic_sx_step = {sector_step!r} takes '
+                         f'M = {2. * h + 1.:.0f} rays, more than {SECTOR_MAX_RAYS}')
+    return int(h), 2 * int(h) + 1
+
+
+def _wind_direction_args(wdirn, ray_axes, rows, cols, sector=0., sector_step=5.):
+    """(batch, single, ur, uc, wdirn device raster | None) from scalars / a 1-D sequence (uniform) or rasters.  With a
+    sector, ur / uc hold the M steps of every case, case-major."""
     if (wdirn.dim() if is_tensor(wdirn) else np.ndim(wdirn)) <= 1:
         wd0 = np.asarray(wdirn.cpu() if is_tensor(wdirn) else wdirn, dtype=np.float64)
+        if sector > 0.:
+            half, count = sector_rays(sector, sector_step)
+            wd_m = np.atleast_1d(wd0)[:, None] + np.arange(-half, half + 1).astype(np.float64) * float(sector_step)
+            ur, uc = ray_step(wd_m.ravel(), ray_axes)
+            return ur.size // count, wd0.ndim == 0, np.ascontiguousarray(ur), np.ascontiguousarray(uc), None
         ur, uc = ray_step(wd0, ray_axes)
         return ur.size, wd0.ndim == 0, np.ascontiguousarray(ur), np.ascontiguousarray(uc), None
     wd = to_dev(wdirn, torch.float64)
@@ -299,39 +327,50 @@ def _dptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-def compute_sx(z_mat, res, wdirn, dmax=500., ray_axes='row_east', want='deg', path='auto'):
+def compute_sx(z_mat, res, wdirn, dmax=500., ray_axes='row_east', want='deg', path='auto', sector=0., sector_step=5.):
     """Winstral's terrain-shelter angle: per cell the steepest angle at which it sees terrain within `dmax` metres
     upwind (K = floor(dmax / res) bilinear samples along the ray; DESIGN.md K9 states the sample exactly).
     wdirn: a scalar or B scalars (uniform wind; the ray step is numpy's cos / sin, handed to the device), or a raster
     (rows, cols) / (B, rows, cols) of degrees.  want: 'deg' -> Sx in degrees, 'tan' -> tan(Sx), 'both' -> (tan, deg);
-    f64, shaped (rows, cols) for a single case, else (B, rows, cols).  path: 'auto' | 'lds' | 'global' (A/B)."""
+    f64, shaped (rows, cols) for a single case, else (B, rows, cols).  path: 'auto' | 'lds' | 'global' (A/B).
+    sector > 0: Winstral's sector average -- the mean of Sx over the azimuths wdirn + j sector_step within
+    +- sector degrees, in one fused device call (ssrs_shelter_sx_sector); 'deg' is that mean, 'tan' its tangent.
+    sector = 0 is the single ray."""
     if want not in ('deg', 'tan', 'both'):
         raise ValueError(f"want = {want!r}: expected 'deg', 'tan' or 'both'")
+    sector_rays(sector, sector_step)
     if ray_axes not in nat.SSRS_RAY_AXES or path not in nat.SSRS_SHELTER_PATH:
         raise ValueError(f'ray_axes = {ray_axes!r} / path = {path!r}: expected one of {tuple(nat.SSRS_RAY_AXES)} / '
                          f'{tuple(nat.SSRS_SHELTER_PATH)}')
     dem = float_dev(z_mat)
     rows, cols = _shape2(dem)
-    batch, single, ur, uc, wd = _wind_direction_args(wdirn, ray_axes, rows, cols)
+    batch, single, ur, uc, wd = _wind_direction_args(wdirn, ray_axes, rows, cols, sector, sector_step)
     tan = torch.empty((batch, rows, cols), dtype=torch.float64, device=dem.device) if want != 'deg' else None
     deg = torch.empty((batch, rows, cols), dtype=torch.float64, device=dem.device) if want != 'tan' else None
-    nat.check(nat.lib().ssrs_shelter_sx(
-        nat.ptr(dem), ftype(dem), C.c_double(res), _dptr(ur), _dptr(uc), nat.ptr(wd), C.c_double(dmax),
-        nat.SSRS_RAY_AXES[ray_axes], nat.SSRS_SHELTER_PATH[path], nat.ptr(tan), nat.ptr(deg), rows, cols, batch,
-        stream_ptr()))
+    if sector > 0.:
+        nat.check(nat.lib().ssrs_shelter_sx_sector(
+            nat.ptr(dem), ftype(dem), C.c_double(res), _dptr(ur), _dptr(uc), nat.ptr(wd), C.c_double(dmax),
+            nat.SSRS_RAY_AXES[ray_axes], nat.SSRS_SHELTER_PATH[path], C.c_double(sector), C.c_double(sector_step),
+            nat.ptr(tan), nat.ptr(deg), rows, cols, batch, stream_ptr()))
+    else:
+        nat.check(nat.lib().ssrs_shelter_sx(
+            nat.ptr(dem), ftype(dem), C.c_double(res), _dptr(ur), _dptr(uc), nat.ptr(wd), C.c_double(dmax),
+            nat.SSRS_RAY_AXES[ray_axes], nat.SSRS_SHELTER_PATH[path], nat.ptr(tan), nat.ptr(deg), rows, cols, batch,
+            stream_ptr()))
     out = [None if t is None else like_input(t[0] if single else t, z_mat) for t in (tan, deg)]
     return out[1] if want == 'deg' else out[0] if want == 'tan' else tuple(out)
 
 
 def orographic_updraft_improved(z_mat, res, wspeed, wdirn, slope=None, aspect=None, dmax=500., height=80.,
                                 coeffs=IMPROVED_COEFFS, ray_axes=None, min_updraft_val=0., threshold=None,
-                                want_orograph=True, want_sx=False, path='auto'):
+                                want_orograph=True, want_sx=False, path='auto', sector=0., sector_step=5.):
     """The orographic updraft sheltered by upwind terrain and scaled to a flight height:
     w = max(min_updraft_val, w0 F_sx / F_h), w0 the value of updraft_from_dem (slope / aspect None: Horn stencil of
     the DEM) or of orographic_updraft (slope / aspect rasters) before its clamp, F_sx = max(0, 1 + g tan Sx),
     F_h = (a h^2 + b h + c) d^(e - cos(slope)) + f.  wspeed / wdirn: scalars or B scalars, or rasters (rows, cols) /
     (B, rows, cols).  ray_axes: the frame of the shelter ray, by default that of the aspect it multiplies --
-    'row_east' for the DEM's own Horn aspect, 'row_north' for given layers.  Returns (orograph f32 | None,
+    'row_east' for the DEM's own Horn aspect, 'row_north' for given layers.  sector / sector_step: as compute_sx
+    (tan Sx becomes the tangent of the sector's mean angle, Sx that mean).  Returns (orograph f32 | None,
     usable f64 | None[, Sx degrees f64]) shaped (rows, cols) for a single case, else (B, rows, cols); numpy when
     z_mat is numpy."""
     if (slope is None) != (aspect is None):
@@ -342,6 +381,7 @@ def orographic_updraft_improved(z_mat, res, wspeed, wdirn, slope=None, aspect=No
         raise ValueError(f'ray_axes = {ray_axes!r} / path = {path!r}: expected one of {tuple(nat.SSRS_RAY_AXES)} / '
                          f'{tuple(nat.SSRS_SHELTER_PATH)}')
     cf = check_improved_parameters(dmax, res, height, coeffs)
+    sector_rays(sector, sector_step)
     dem = float_dev(z_mat)
     rows, cols = _shape2(dem)
     s = a = None
@@ -352,7 +392,7 @@ def orographic_updraft_improved(z_mat, res, wspeed, wdirn, slope=None, aspect=No
             a = a.to(s.dtype)
         if tuple(s.shape) != (rows, cols) or tuple(a.shape) != (rows, cols):
             raise ValueError('slope / aspect shapes do not match the terrain')
-    batch, single, ur, uc, wd = _wind_direction_args(wdirn, ray_axes, rows, cols)
+    batch, single, ur, uc, wd = _wind_direction_args(wdirn, ray_axes, rows, cols, sector, sector_step)
     ws = ws0 = wd0 = None
     if wd is None:
         ws0 = np.atleast_1d(np.asarray(wspeed.cpu() if is_tensor(wspeed) else wspeed, dtype=np.float64))
@@ -370,10 +410,13 @@ def orographic_updraft_improved(z_mat, res, wspeed, wdirn, slope=None, aspect=No
     oro = torch.empty((batch, rows, cols), dtype=torch.float32, device=dem.device) if want_orograph else None
     use = torch.empty((batch, rows, cols), dtype=torch.float64, device=dem.device) if threshold is not None else None
     sx = torch.empty((batch, rows, cols), dtype=torch.float64, device=dem.device) if want_sx else None
-    nat.check(nat.lib().ssrs_updraft_sheltered(
-        nat.ptr(dem), ftype(dem), C.c_double(res), _dptr(ur), _dptr(uc), _dptr(ws0), _dptr(wd0), nat.ptr(ws),
-        nat.ptr(wd), nat.ptr(s), nat.ptr(a), nat.SSRS_F64 if s is None else ftype(s), C.byref(params),
-        C.c_double(min_updraft_val), C.c_double(-1. if threshold is None else threshold), nat.ptr(oro), nat.ptr(use),
-        nat.ptr(sx), rows, cols, batch, stream_ptr()))
+    head = (nat.ptr(dem), ftype(dem), C.c_double(res), _dptr(ur), _dptr(uc), _dptr(ws0), _dptr(wd0), nat.ptr(ws),
+            nat.ptr(wd), nat.ptr(s), nat.ptr(a), nat.SSRS_F64 if s is None else ftype(s), C.byref(params))
+    tail = (C.c_double(min_updraft_val), C.c_double(-1. if threshold is None else threshold), nat.ptr(oro), nat.ptr(use),
+            nat.ptr(sx), rows, cols, batch, stream_ptr())
+    if sector > 0.:
+        nat.check(nat.lib().ssrs_updraft_sheltered_sector(*head, C.c_double(sector), C.c_double(sector_step), *tail))
+    else:
+        nat.check(nat.lib().ssrs_updraft_sheltered(*head, *tail))
     out = tuple(None if t is None else like_input(t[0] if single else t, z_mat) for t in (oro, use, sx))
     return out if want_sx else out[:2]

@@ -257,12 +257,13 @@ class Simulator(Config):
         return str(self.orographic_model).lower() == 'improved'
 
     def _check_orographic_model(self):
-        """The four orographic_* fields, on the host (no device work): ValueError names the one that does not fit."""
+        """The orographic_* fields, on the host (no device work): ValueError names the one that does not fit."""
         if str(self.orographic_model).lower() not in ('original', 'improved'):
             raise ValueError(f"orographic_model = {self.orographic_model!r}: expected 'original' or 'improved'")
         if self._improved():
             layers.check_improved_parameters(self.orographic_sx_dmax, self.resolution, self.orographic_height,
                                              self.orographic_coeffs)
+            layers.sector_rays(self.orographic_sx_sector, self.orographic_sx_step)
 
     def _improved_args(self):
         """Keyword arguments of layers.orographic_updraft_improved for this run.  The shelter ray lives in the frame of
@@ -271,7 +272,8 @@ class Simulator(Config):
         injected and the other from the DEM, the aspect's frame decides."""
         given = 'Aspect' in self._terrain
         args = dict(dmax=float(self.orographic_sx_dmax), height=float(self.orographic_height),
-                    coeffs=tuple(self.orographic_coeffs), ray_axes='row_north' if given else 'row_east', want_sx=True)
+                    coeffs=tuple(self.orographic_coeffs), ray_axes='row_north' if given else 'row_east', want_sx=True,
+                    sector=float(self.orographic_sx_sector), sector_step=float(self.orographic_sx_step))
         if 'Slope' in self._terrain or 'Aspect' in self._terrain:
             args.update(slope=to_dev(self.get_terrain_slope(), torch.float64),
                         aspect=to_dev(self.get_terrain_aspect(), torch.float64))
@@ -524,6 +526,8 @@ class Simulator(Config):
         if self._improved():
             # (a cached potential of the original model must never be picked up for the improved one)
             model = f'{self.movement_model}-sx{int(self.orographic_sx_dmax)}h{int(self.orographic_height)}'
+            if float(self.orographic_sx_sector) > 0.:           # (nor that of a single-ray run for a sector's)
+                model += f'a{float(self.orographic_sx_sector):g}s{float(self.orographic_sx_step):g}'
         out_str = (f'{case_id}_d{int(self.track_direction % 360)}'
                    f'_t{int(self.updraft_threshold * 100)}_{model}')
         if real_id is not None:
