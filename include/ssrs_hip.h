@@ -646,6 +646,42 @@ int ssrs_updraft_sheltered_sector(const void *dem, int dem_type, double res, con
                                   double min_updraft_val, double threshold, float *orograph, double *usable,
                                   double *sx_deg, int rows, int cols, int batch, void *stream);
 
+/* ----------------------------------------------------------------- smooth */
+
+/* K11 -- Gaussian smoothing of the improved orographic updraft: scipy.ndimage.gaussian_filter(x, sigma,
+ * mode='reflect') of an f32 raster x (batch, rows, cols), `sigma` in cells, with the clamp and the threshold function
+ * of ssrs_updraft_sheltered fused into the second pass.
+ *   R = int(4 sigma + 0.5) (truncate = 4).  On the host in f64: e[k] = exp(-0.5 / (sigma sigma) k k), k = -R .. R,
+ *       w[k] = e[k] / sum(e) (summed in ascending k): the radius and the weights of ssrs_gaussian_blur.  R = 0
+ *       (sigma < 0.125): w = {1}, the blur is the identity.  R > 512: SSRS_ERR_INVALID
+ *   load: a non-finite x (NaN, +-inf) enters as 0.0 -- the sheltered kernels give a nodata cell min_updraft_val, which
+ *       is -inf when the clamp is lifted, and 0.0 is what the unsmoothed model gives such a cell
+ *   boundary: 'reflect' (d c b a | a b c d | d c b a) to any depth.  An index i outside [0, n) reads m = i mod 2 n
+ *       taken non-negative, then m < n ? m : 2 n - 1 - m.  R may exceed 2 n; n = 1 is legal
+ *   axis 0 (rows) first, then axis 1 (columns), the intermediate in f64.  Per axis and position p:
+ *       acc = x[p] * w[0]; for k = R, R - 1, .., 1: acc = acc + (x[p - k] + x[p + k]) * w[k]; every product and sum
+ *       rounded (no contraction): the order of scipy's symmetric correlate1d.  The order does not depend on the tile a
+ *       cell falls in, on the path or on the case's place in the batch
+ *   smooth f64 = the second pass's sum; orograph f32 = (float)(smooth > min_updraft_val ? smooth : min_updraft_val);
+ *       usable f64 = the threshold function of that f32 widened again, in the arithmetic ssrs_updraft_sheltered uses
+ *       without slope / aspect rasters (that of ssrs_updraft_from_dem).  Any of the three may be NULL, not all;
+ *       orograph may be `in` itself (a case's first pass has read it before its second pass writes)
+ * path: SSRS_SMOOTH_AUTO stages a tile and its reflected halo of R cells along the pass's axis in LDS when R <= 128
+ * (sigma 30, the model's cap of 300 m at 10 m, is R = 120) and reads global memory through the index rule otherwise;
+ * _LDS / _GLOBAL force one (A/B; _LDS with R > 128 is SSRS_ERR_INVALID).  All paths give the same bits.
+ * workspace: ssrs_smooth_workspace_bytes() DEVICE bytes, 256-byte aligned -- the R + 1 weights and ONE f64 plane, which
+ * the cases of a batch use one after the other (the size does not grow with `batch`; 0 for arguments that would be
+ * refused).  Checked before any GPU work: `in` and workspace not NULL, rows, cols, batch >= 1, sigma finite and > 0,
+ * R <= 512, min_updraft_val not NaN, a threshold > 0 when usable is asked for, path, the workspace size.
+ * Asynchronous on `stream`; no host-device copy and no synchronisation (the weights travel as kernel arguments). */
+#define SSRS_SMOOTH_AUTO 0
+#define SSRS_SMOOTH_LDS 1
+#define SSRS_SMOOTH_GLOBAL 2
+size_t ssrs_smooth_workspace_bytes(int rows, int cols, int batch, double sigma);
+int ssrs_smooth_reflect(const float *in, double sigma, int path, double min_updraft_val, double threshold,
+                        double *smooth, float *orograph, double *usable, int rows, int cols, int batch,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------- georef */
 
 /* K10 -- Albers Equal Area Conic on an ellipsoid (Snyder, USGS PP 1395, eqs. 14-12 ... 14-21, 3-12, 3-16) and the

@@ -24,6 +24,7 @@ SSRS_SOLVE_NO_AMG = 1
 SSRS_TURBINE_BIN, SSRS_TURBINE_MAX = 32, 8192
 SSRS_RAY_AXES = {'row_north': 0, 'row_east': 1}                  # SSRS_RAY_ROW_NORTH / _ROW_EAST
 SSRS_SHELTER_PATH = {'auto': 0, 'lds': 1, 'global': 2}           # SSRS_SHELTER_AUTO / _LDS / _GLOBAL
+SSRS_SMOOTH_PATH = {'auto': 0, 'lds': 1, 'global': 2}            # SSRS_SMOOTH_AUTO / _LDS / _GLOBAL
 SSRS_INTERP = {'nearest': 0, 'linear': 1, 'cubic': 2}          # SSRS_INTERP_NEAREST / _LINEAR / _CUBIC
 
 EXPORTS = (
@@ -47,6 +48,7 @@ EXPORTS = (
     'ssrs_potential_workspace_bytes', 'ssrs_potential_solve',
     'ssrs_turbine_encounters', 'ssrs_turbine_encounter_counts',
     'ssrs_shelter_sx', 'ssrs_updraft_sheltered', 'ssrs_shelter_sx_sector', 'ssrs_updraft_sheltered_sector',
+    'ssrs_smooth_workspace_bytes', 'ssrs_smooth_reflect',
     'ssrs_projection_init_albers', 'ssrs_warp_lonlat_raster',
 )
 
@@ -176,6 +178,10 @@ def lib():
         L.ssrs_updraft_sheltered_sector.argtypes = [C.c_void_p, C.c_int, C.c_double] + [C.c_void_p] * 8 + \
             [C.c_int, C.POINTER(SsrsShelterParams), C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
              C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.ssrs_smooth_workspace_bytes.restype = C.c_size_t
+        L.ssrs_smooth_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double]
+        L.ssrs_smooth_reflect.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ssrs_projection_init_albers.argtypes = [C.POINTER(SsrsProjection)]
         L.ssrs_warp_lonlat_raster.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_double] * 5 + \
             [C.POINTER(SsrsProjection)] + [C.c_double] * 3 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -23,6 +23,7 @@ _SECTIONS = (
     ('WindToolKit settings', ('wtk_source', 'wtk_orographic_height', 'wtk_thermal_height',
                               'wtk_interp_type')),
     ('Updraft computation', ('thermals_realization_count', 'updraft_threshold',
+                             'orographic_smoothing', 'orographic_smooth_sigma',
                              'movement_model', 'orographic_sx_sector', 'orographic_sx_step',
                              'orographic_model', 'orographic_sx_dmax',
                              'orographic_height', 'orographic_coeffs')),
@@ -119,6 +120,12 @@ class Config:
     #                                     of Sx over the azimuths wdirn + j orographic_sx_step within the sector, at most 61 of
     #                                     them, in one device call; <case>_sx.npy holds the mean and the ids carry a<sector>s<step>
     orographic_sx_step: float = 5.      # degrees between the rays of that sector (> 0)
+    orographic_smoothing: str = 'none'  # none | gaussian.  'improved' only.  'gaussian': the adjusted updraft is blurred by a
+    #                                     Gaussian (scipy's gaussian_filter, mode='reflect', nodata entering as 0) before its clamp
+    #                                     and threshold, in two device passes; <case>_orograph.npy holds the
+    #                                     smoothed field and the ids carry g<sigma in metres>
+    orographic_smooth_sigma: float = 0.  # metres; 0 = the model's own width min(0.8 orographic_height + 16, 300) (recalled,
+    #                                     NOT verified).  Its radius int(4 sigma / resolution + 0.5) may be at most 512 cells
     hist_safe_tracks: int = 250_000     # tracks per sub-batch of a case: (i) histograms of several sub-batches are added up in 64
     #                                     bits; a sub-batch of more than 100 000 tracks is counted in 64 bits inside the library (a trap
     #                                     cell of the solved 10 m field takes 1.7e4 visits per track: 2^32 from ~245 000 tracks on;

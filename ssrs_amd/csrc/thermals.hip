@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "common.h"
+#include "gauss.h"          // blur_radius, blur_weights
 
 namespace ssrs {
 
@@ -198,18 +199,6 @@ __global__ __launch_bounds__(kBlock) void k_round_to_f32(const double *__restric
 }  // namespace ssrs
 
 using namespace ssrs;
-
-// scipy.ndimage._gaussian_kernel1d: radius = int(truncate * sigma + 0.5), truncate = 4
-static int blur_radius(double sigma) { return static_cast<int>(4.0 * sigma + 0.5); }
-
-static std::vector<double> blur_weights(double sigma, int radius)
-{
-    std::vector<double> w(2 * radius + 1);
-    double sum = 0.0;
-    for (int k = -radius; k <= radius; ++k) { w[k + radius] = std::exp(-0.5 / (sigma * sigma) * k * k); sum += w[k + radius]; }
-    for (double &v : w) v /= sum;
-    return w;
-}
 
 static int blocks_for(size_t n)
 {

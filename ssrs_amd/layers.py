@@ -363,14 +363,17 @@ def compute_sx(z_mat, res, wdirn, dmax=500., ray_axes='row_east', want='deg', pa
 
 def orographic_updraft_improved(z_mat, res, wspeed, wdirn, slope=None, aspect=None, dmax=500., height=80.,
                                 coeffs=IMPROVED_COEFFS, ray_axes=None, min_updraft_val=0., threshold=None,
-                                want_orograph=True, want_sx=False, path='auto', sector=0., sector_step=5.):
+                                want_orograph=True, want_sx=False, path='auto', sector=0., sector_step=5., smooth_sigma=0.):
     """The orographic updraft sheltered by upwind terrain and scaled to a flight height:
     w = max(min_updraft_val, w0 F_sx / F_h), w0 the value of updraft_from_dem (slope / aspect None: Horn stencil of
     the DEM) or of orographic_updraft (slope / aspect rasters) before its clamp, F_sx = max(0, 1 + g tan Sx),
     F_h = (a h^2 + b h + c) d^(e - cos(slope)) + f.  wspeed / wdirn: scalars or B scalars, or rasters (rows, cols) /
     (B, rows, cols).  ray_axes: the frame of the shelter ray, by default that of the aspect it multiplies --
     'row_east' for the DEM's own Horn aspect, 'row_north' for given layers.  sector / sector_step: as compute_sx
-    (tan Sx becomes the tangent of the sector's mean angle, Sx that mean).  Returns (orograph f32 | None,
+    (tan Sx becomes the tangent of the sector's mean angle, Sx that mean).  smooth_sigma > 0 (metres; 0 = off): the
+    field is computed without its clamp, rounded to f32 and blurred by a Gaussian of that width (smooth_orograph with
+    sigma_cells = smooth_sigma / res: scipy's gaussian_filter, mode='reflect', a nodata cell entering as 0), and the
+    clamp and the threshold act on the smoothed field; Sx is unaffected.  Returns (orograph f32 | None,
     usable f64 | None[, Sx degrees f64]) shaped (rows, cols) for a single case, else (B, rows, cols); numpy when
     z_mat is numpy."""
     if (slope is None) != (aspect is None):
@@ -382,6 +385,9 @@ def orographic_updraft_improved(z_mat, res, wspeed, wdirn, slope=None, aspect=No
                          f'{tuple(nat.SSRS_SHELTER_PATH)}')
     cf = check_improved_parameters(dmax, res, height, coeffs)
     sector_rays(sector, sector_step)
+    smooth = float(smooth_sigma) != 0.
+    if smooth:
+        smoothing_radius(float(smooth_sigma) / float(res), 'smooth_sigma / res')
     dem = float_dev(z_mat)
     rows, cols = _shape2(dem)
     s = a = None
@@ -407,16 +413,93 @@ def orographic_updraft_improved(z_mat, res, wspeed, wdirn, slope=None, aspect=No
             raise ValueError('wspeed and wdirn shapes differ')
     params = nat.SsrsShelterParams(float(dmax), nat.SSRS_RAY_AXES[ray_axes], nat.SSRS_SHELTER_PATH[path], float(height),
                                    (C.c_double * 7)(*cf))
-    oro = torch.empty((batch, rows, cols), dtype=torch.float32, device=dem.device) if want_orograph else None
+    oro = torch.empty((batch, rows, cols), dtype=torch.float32, device=dem.device) if want_orograph or smooth else None
     use = torch.empty((batch, rows, cols), dtype=torch.float64, device=dem.device) if threshold is not None else None
     sx = torch.empty((batch, rows, cols), dtype=torch.float64, device=dem.device) if want_sx else None
     head = (nat.ptr(dem), ftype(dem), C.c_double(res), _dptr(ur), _dptr(uc), _dptr(ws0), _dptr(wd0), nat.ptr(ws),
             nat.ptr(wd), nat.ptr(s), nat.ptr(a), nat.SSRS_F64 if s is None else ftype(s), C.byref(params))
     tail = (C.c_double(min_updraft_val), C.c_double(-1. if threshold is None else threshold), nat.ptr(oro), nat.ptr(use),
             nat.ptr(sx), rows, cols, batch, stream_ptr())
+    if smooth:                                  # the unclamped field, no threshold: both act on the smoothed field below
+        tail = (C.c_double(-np.inf), C.c_double(-1.), nat.ptr(oro), None) + tail[4:]
     if sector > 0.:
         nat.check(nat.lib().ssrs_updraft_sheltered_sector(*head, C.c_double(sector), C.c_double(sector_step), *tail))
     else:
         nat.check(nat.lib().ssrs_updraft_sheltered(*head, *tail))
+    if smooth:
+        _smooth_reflect(oro, float(smooth_sigma) / float(res), min_updraft_val, threshold, None,
+                        oro if want_orograph else None, use, 'auto')
+        oro = oro if want_orograph else None
     out = tuple(None if t is None else like_input(t[0] if single else t, z_mat) for t in (oro, use, sx))
     return out if want_sx else out[:2]
+
+
+# ---------------------------------------------------------------------------- K11: Gaussian smoothing of the updraft
+SMOOTH_MAX_RADIUS = 512
+
+
+def smoothing_sigma_m(height, sigma=0.):
+    """Width in metres of the Gaussian that smooths the improved orographic updraft: `sigma` when > 0, else the model's
+    own min(0.8 height + 16, 300) (recalled from the published model, UNVERIFIED: DESIGN.md limit 10).  ValueError for a
+    negative or non-finite sigma.  Host only."""
+    try:
+        s = float(sigma)
+    except (TypeError, ValueError):
+        s = np.nan
+    if not (np.isfinite(s) and s >= 0.):
+        raise ValueError(f'orographic_smooth_sigma = {sigma!r}: expected metres >= 0 (0 = the model\'s own width)')
+    return s if s > 0. else min(0.8 * float(height) + 16., 300.)
+
+
+def smoothing_radius(sigma_cells, name='sigma_cells'):
+    """R = int(4 sigma + 0.5) of a Gaussian of `sigma_cells` cells (scipy's truncate = 4).  ValueError unless sigma is
+    finite and > 0 and R <= 512.  Host only."""
+    try:
+        s = float(sigma_cells)
+    except (TypeError, ValueError):
+        s = np.nan
+    if not (np.isfinite(s) and s > 0.):
+        raise ValueError(f'{name} = {sigma_cells!r}: expected a width in cells > 0')
+    if not 4. * s + 0.5 < SMOOTH_MAX_RADIUS + 1.:
+        raise ValueError(f'{name} = {s:g} cells takes a radius R = int(4 sigma + 0.5) of more than {SMOOTH_MAX_RADIUS} cells')
+    return int(4. * s + 0.5)
+
+
+def _smooth_reflect(x, sigma_cells, min_updraft_val, threshold, smooth, oro, use, path):
+    """ssrs_smooth_reflect on the device tensor x f32 (B, rows, cols) into the given outputs (None = not asked for; oro
+    may be x itself: the first pass has read a case before the second writes it)."""
+    batch, rows, cols = x.shape
+    lib = nat.lib()
+    nbytes = lib.ssrs_smooth_workspace_bytes(rows, cols, batch, C.c_double(sigma_cells))
+    work = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=x.device)
+    nat.check(lib.ssrs_smooth_reflect(nat.ptr(x), C.c_double(sigma_cells), nat.SSRS_SMOOTH_PATH[path],
+                                      C.c_double(min_updraft_val), C.c_double(-1. if threshold is None else threshold),
+                                      nat.ptr(smooth), nat.ptr(oro), nat.ptr(use), rows, cols, batch, nat.ptr(work),
+                                      C.c_size_t(int(nbytes)), stream_ptr()))
+
+
+def smooth_orograph(orograph, sigma_cells, min_updraft_val=0., threshold=None, want_smooth=False, path='auto'):
+    """Gaussian smoothing of an orographic updraft raster: scipy.ndimage.gaussian_filter(x, sigma_cells,
+    mode='reflect') of the f32 raster `orograph`, (rows, cols) or (B, rows, cols), a non-finite value entering as 0; f64
+    inside, axis 0 first.  Returns (orograph f32 = the smoothed field clamped at min_updraft_val, usable f64 | None = its
+    threshold function when `threshold` is given[, smooth f64 = the unclamped sum]); numpy in, numpy out.
+    path: 'auto' | 'lds' | 'global' (A/B, the same bits)."""
+    smoothing_radius(sigma_cells)
+    if path not in nat.SSRS_SMOOTH_PATH:
+        raise ValueError(f'path = {path!r}: expected one of {tuple(nat.SSRS_SMOOTH_PATH)}')
+    if threshold is not None and not float(threshold) > 0.:
+        raise ValueError(f'threshold = {threshold!r}: expected > 0')
+    if np.isnan(float(min_updraft_val)):
+        raise ValueError('min_updraft_val is NaN')
+    if (orograph.dim() if is_tensor(orograph) else np.ndim(orograph)) not in (2, 3):
+        raise ValueError('orograph: expected a raster (rows, cols) or (B, rows, cols)')
+    x = to_dev(orograph, torch.float32)
+    single = x.dim() == 2
+    if single:
+        x = x[None]
+    oro = torch.empty_like(x)
+    use = torch.empty(x.shape, dtype=torch.float64, device=x.device) if threshold is not None else None
+    smooth = torch.empty(x.shape, dtype=torch.float64, device=x.device) if want_smooth else None
+    _smooth_reflect(x, float(sigma_cells), float(min_updraft_val), threshold, smooth, oro, use, path)
+    out = tuple(None if t is None else like_input(t[0] if single else t, orograph) for t in (oro, use, smooth))
+    return out if want_smooth else out[:2]

@@ -264,6 +264,18 @@ class Simulator(Config):
             layers.check_improved_parameters(self.orographic_sx_dmax, self.resolution, self.orographic_height,
                                              self.orographic_coeffs)
             layers.sector_rays(self.orographic_sx_sector, self.orographic_sx_step)
+            if str(self.orographic_smoothing).lower() not in ('none', 'gaussian'):
+                raise ValueError(f"orographic_smoothing = {self.orographic_smoothing!r}: expected 'none' or 'gaussian'")
+            sigma_m = layers.smoothing_sigma_m(self.orographic_height, self.orographic_smooth_sigma)
+            if str(self.orographic_smoothing).lower() == 'gaussian':
+                layers.smoothing_radius(sigma_m / float(self.resolution),
+                                        f'orographic_smooth_sigma = {sigma_m:g} m at resolution {self.resolution!r} m')
+
+    def _smooth_sigma_m(self):
+        """Width in metres of the Gaussian that smooths the improved orograph; 0 = no smoothing."""
+        if not self._improved() or str(self.orographic_smoothing).lower() != 'gaussian':
+            return 0.
+        return layers.smoothing_sigma_m(self.orographic_height, self.orographic_smooth_sigma)
 
     def _improved_args(self):
         """Keyword arguments of layers.orographic_updraft_improved for this run.  The shelter ray lives in the frame of
@@ -273,7 +285,8 @@ class Simulator(Config):
         given = 'Aspect' in self._terrain
         args = dict(dmax=float(self.orographic_sx_dmax), height=float(self.orographic_height),
                     coeffs=tuple(self.orographic_coeffs), ray_axes='row_north' if given else 'row_east', want_sx=True,
-                    sector=float(self.orographic_sx_sector), sector_step=float(self.orographic_sx_step))
+                    sector=float(self.orographic_sx_sector), sector_step=float(self.orographic_sx_step),
+                    smooth_sigma=self._smooth_sigma_m())
         if 'Slope' in self._terrain or 'Aspect' in self._terrain:
             args.update(slope=to_dev(self.get_terrain_slope(), torch.float64),
                         aspect=to_dev(self.get_terrain_aspect(), torch.float64))
@@ -528,6 +541,8 @@ class Simulator(Config):
             model = f'{self.movement_model}-sx{int(self.orographic_sx_dmax)}h{int(self.orographic_height)}'
             if float(self.orographic_sx_sector) > 0.:           # (nor that of a single-ray run for a sector's)
                 model += f'a{float(self.orographic_sx_sector):g}s{float(self.orographic_sx_step):g}'
+            if self._smooth_sigma_m() > 0.:                     # (nor that of an unsmoothed run for a smoothed one's)
+                model += f'g{self._smooth_sigma_m():g}'
         out_str = (f'{case_id}_d{int(self.track_direction % 360)}'
                    f'_t{int(self.updraft_threshold * 100)}_{model}')
         if real_id is not None:
