@@ -682,6 +682,60 @@ int ssrs_smooth_reflect(const float *in, double sigma, int path, double min_updr
                         double *smooth, float *orograph, double *usable, int rows, int cols, int batch,
                         void *workspace, size_t workspace_bytes, void *stream);
 
+/* -------------------------------------------------------- allen thermals */
+
+/* K12 -- Allen's (2006) field of discrete thermal updrafts, the model the reference carries commented out at
+ * ssrs/layers.py:304-493: one field (rows, cols) per call.  The caller computes, in f64 on the host, from the height z,
+ * the boundary-layer height zi and the convective velocity scale wstar:
+ *   zzi = z / zi, rbar = 0.102 zzi^(1/3) (1 - 0.25 zzi) zi, wtbar = zzi^(1/3) (1 - 1.1 zzi) wstar, z_below_zi = z < zi,
+ *   we = the environment sink (<= 0; 0 = none)
+ * Updraft k sits at (xt[k], yt[k]) metres from the centre of cell (0, 0) and has the gains wgain[k], rgain[k].
+ * PRECONDITION, checked by the Python wrapper and not here: every coordinate is finite and inside
+ * [0, cols res] x [0, rows res], every gain is finite.
+ *   table (n_updrafts, SSRS_ALLEN_TABLE_COLS) f64, one thread per updraft, every operation rounded, no contraction:
+ *       r2 = max(10, rbar rgain); r1r2 = r2 < 600 ? 0.0011 r2 + 0.14 : 0.8; r1 = r1r2 r2; wbar = wtbar wgain;
+ *       wpeak = 3 wbar (r2 r2 r2 - r2 r2 r1) / (r2 r2 r2 - r1 r1 r1), products from the left;
+ *       row = the first j in 0..5 with r1r2 < 0.5 (S[j] + S[j+1]), else 6, S = (0.14, 0.25, 0.36, 0.47, 0.58, 0.69, 0.80)
+ *       columns: r2, r1r2, r1, wbar, wpeak, row.  Kept in the workspace; also written to `table` when that is not NULL
+ *   cell (r, c) at (xc, yc) = (c res, r res) takes the updraft u with the smallest
+ *       d2 = (xc - xt)(xc - xt) + (yc - yt)(yc - yt)   (unfused), the lowest index among equal d2
+ *       nearest (rows, cols) int32 = u when not NULL
+ *   dist = sqrt(d2); rr2 = dist / r2[u]; (k1..k4) = row `row[u]` of Allen's shape table
+ *       ws = z_below_zi ? max(1 / (1 + pow(k1 fabs(rr2 + k3), k2)) + k4 rr2, 0) : 0
+ *       wl = (dist > r1[u] && rr2 < 2) ? (pi / 6) sin(pi rr2) : 0
+ *       wd = (0.5 < zzi && zzi <= 0.9) ? min(2.5 wl (zzi - 0.5), 0) : 0
+ *       w  = wpeak[u] ws + wd wbar[u]
+ *       if (we != 0 && dist > r1[u])  w = wpeak[u] != 0 ? w (1 - we / wpeak[u]) + we : we
+ *       out (rows, cols): SSRS_F64 = w, SSRS_F32 = w rounded once
+ * bins: a CSR over nbx x nby square bins of bin_size_m metres (>= res), bin_start int32 (nbx nby + 1), row-major
+ * (bin = by nbx + bx), bin_items int32.  An updraft is listed in the bin (min(floor(xt / bin_size_m), nbx - 1),
+ * min(floor(yt / bin_size_m), nby - 1)) and in no other; items ascend inside a bin.  Trusted, like the coordinates.
+ * path: SSRS_ALLEN_GLOBAL -- every cell scans its own bin, then ring after ring of bins, and stops once its best d2 is
+ * strictly below the square of (m - bin_size_m / 2^20), m = its distance to the nearest side of the scanned square that
+ * is not the domain's edge, or once no bin is left.  SSRS_ALLEN_AUTO -- a block of 256 cells (16 x 16) first stages the
+ * updrafts of the bins that meet its tile, plus one bin around them, in LDS and scans that list; a cell that cannot accept
+ * under the same criterion, and every cell of a tile whose list exceeds 512 updrafts, goes on with the ring scan.
+ * SSRS_ALLEN_LDS -- as _AUTO, but SSRS_ERR_INVALID ("does not fit") when some tile's list exceeds 512 updrafts; this
+ * path alone synchronises `stream` (the longest list comes to the host).  All paths give the same bits.
+ * workspace: ssrs_allen_workspace_bytes(n_updrafts) DEVICE bytes, 256-byte aligned (0 for a count that would be
+ * refused): 256 bytes of counters, then the table.  After the call its first uint64 holds the number of cells that
+ * finished on the ring scan under _AUTO / _LDS (a diagnostic; 0 under _GLOBAL).
+ * Checked before any GPU work, each refusal SSRS_ERR_INVALID naming the argument: xt, yt, wgain, rgain, bin_start,
+ * bin_items, out, workspace not NULL; 1 <= n_updrafts <= SSRS_ALLEN_MAX_UPDRAFTS; rows, cols >= 1; res finite and > 0;
+ * bin_size_m finite and >= res; nbx, nby in [1, 32768]; rbar, wtbar, zzi, we finite, zzi > 0, we <= 0; path; out_type;
+ * the workspace size.  Asynchronous on `stream` except as said for _LDS. */
+#define SSRS_ALLEN_MAX_UPDRAFTS (1 << 22)
+#define SSRS_ALLEN_TABLE_COLS 6
+#define SSRS_ALLEN_AUTO 0
+#define SSRS_ALLEN_LDS 1
+#define SSRS_ALLEN_GLOBAL 2
+size_t ssrs_allen_workspace_bytes(int n_updrafts);
+int ssrs_allen_thermal_field(const double *xt, const double *yt, const double *wgain, const double *rgain,
+                             int n_updrafts, const int32_t *bin_start, const int32_t *bin_items, double bin_size_m,
+                             int nbx, int nby, double rbar, double wtbar, double zzi, int z_below_zi, double we,
+                             double res, int rows, int cols, int path, void *out, int out_type, int32_t *nearest,
+                             double *table, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------- georef */
 
 /* K10 -- Albers Equal Area Conic on an ellipsoid (Snyder, USGS PP 1395, eqs. 14-12 ... 14-21, 3-12, 3-16) and the

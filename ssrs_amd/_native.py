@@ -25,6 +25,8 @@ SSRS_TURBINE_BIN, SSRS_TURBINE_MAX = 32, 8192
 SSRS_RAY_AXES = {'row_north': 0, 'row_east': 1}                  # SSRS_RAY_ROW_NORTH / _ROW_EAST
 SSRS_SHELTER_PATH = {'auto': 0, 'lds': 1, 'global': 2}           # SSRS_SHELTER_AUTO / _LDS / _GLOBAL
 SSRS_SMOOTH_PATH = {'auto': 0, 'lds': 1, 'global': 2}            # SSRS_SMOOTH_AUTO / _LDS / _GLOBAL
+SSRS_ALLEN_PATH = {'auto': 0, 'lds': 1, 'global': 2}             # SSRS_ALLEN_AUTO / _LDS / _GLOBAL
+SSRS_ALLEN_MAX_UPDRAFTS, SSRS_ALLEN_TABLE_COLS = 1 << 22, 6
 SSRS_INTERP = {'nearest': 0, 'linear': 1, 'cubic': 2}          # SSRS_INTERP_NEAREST / _LINEAR / _CUBIC
 
 EXPORTS = (
@@ -50,6 +52,7 @@ EXPORTS = (
     'ssrs_shelter_sx', 'ssrs_updraft_sheltered', 'ssrs_shelter_sx_sector', 'ssrs_updraft_sheltered_sector',
     'ssrs_smooth_workspace_bytes', 'ssrs_smooth_reflect',
     'ssrs_projection_init_albers', 'ssrs_warp_lonlat_raster',
+    'ssrs_allen_workspace_bytes', 'ssrs_allen_thermal_field',
 )
 
 
@@ -87,6 +90,13 @@ class SsrsShelterParams(C.Structure):
 class SsrsProjection(C.Structure):
     _fields_ = [(name, C.c_double) for name in ('a', 'e2', 'lat_1', 'lat_2', 'lat_0', 'lon_0', 'x_0', 'y_0',
                                                 'n', 'C', 'rho0', 'e')]
+
+
+# ssrs_allen_thermal_field: xt, yt, wgain, rgain, n, bin_start, bin_items, bin_size_m, nbx, nby, rbar, wtbar, zzi, z_below_zi,
+# we, res, rows, cols, path, out, out_type, nearest, table, workspace, workspace_bytes, stream
+ALLEN_FIELD_ARGTYPES = [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int] + \
+    [C.c_double] * 3 + [C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
 
 
 class SsrsError(RuntimeError):
@@ -186,6 +196,9 @@ def lib():
         L.ssrs_warp_lonlat_raster.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_double] * 5 + \
             [C.POINTER(SsrsProjection)] + [C.c_double] * 3 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                              C.c_int, C.c_int, C.c_void_p]
+        L.ssrs_allen_workspace_bytes.restype = C.c_size_t
+        L.ssrs_allen_workspace_bytes.argtypes = [C.c_int]
+        L.ssrs_allen_thermal_field.argtypes = ALLEN_FIELD_ARGTYPES
         _lib = L
     return _lib
 

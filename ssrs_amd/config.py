@@ -33,7 +33,8 @@ _SECTIONS = (
     ('Plotting and wind turbines', ('turbine_minimum_hubheight', 'turbine_mrkr_size',
                                     'fig_height', 'fig_dpi')),
     ('MI355X build', ('save_tracks', 'stepper_path', 'steps_per_launch', 'max_tracks_file_gb', 'hist_safe_tracks',
-                      'thermal_model', 'turbine_encounter_radius')),
+                      'thermal_model', 'thermal_allen_zi', 'thermal_allen_wstar', 'thermal_allen_sink',
+                      'turbine_encounter_radius')),
 )
 
 
@@ -100,6 +101,12 @@ class Config:
     steps_per_launch: int = 0           # 0 = library default
     max_tracks_file_gb: float = 64.     # refuse a <id>_tracks.pkl larger than this (tracks that wander to
     #                                     max_moves: 1 TB per 100k tracks on a solved 10 m field)
+    thermal_allen_zi: float = 0.        # thermal_model = 'allen': boundary-layer height zi in metres.  0 (snapshot / seasonal
+    #                                     only) = the mean of the case's own blheight layer, clipped below at 100 m
+    thermal_allen_wstar: float = 0.     # thermal_model = 'allen': convective velocity scale w* in m/s.  0 (snapshot / seasonal
+    #                                     only) = the mean Deardorff velocity of the case's own WTK layers
+    thermal_allen_sink: bool = False    # thermal_model = 'allen': the environment sink between the updrafts (Allen's sflag; off
+    #                                     in the reference's own call)
     turbine_encounter_radius: float = 0.  # metres; 0 = off.  > 0 (needs Simulator(turbines=...)): simulate_tracks also finds, per
     #                                     turbine, the tracks that came within this distance of it and after how many moves, from
     #                                     the trajectories on the device (produced even with save_tracks=False):
@@ -135,10 +142,13 @@ class Config:
     #                                     CU: 250 000 tracks = ~105 000 roaming at first, one round of 512-lane blocks, later
     #                                     ~78 000 in 256-lane blocks: 2.0 s per pass = 1.27e5 tracks/s against 1.0e5 for 140 000
     #                                     (rounds 3-4) and 1.15e5 for 300 000 (a second round of blocks; profiles/r04_roam_fill.txt)
-    thermal_model: str = 'random'       # random | wtk.  'random': the reference's compute_thermals, one field of smoothed random
+    thermal_model: str = 'random'       # random | wtk | allen.  'random': the reference's compute_thermals, one field of smoothed random
     #                                     blobs per realisation.  'wtk' (snapshot / seasonal, thermals_realization_count = 1): the
     #                                     Deardorff-velocity updraft at wtk_thermal_height from the case's own WTK layers
-    #                                     (pressure, temperature, blheight, surfheatflux in every wind entry)
+    #                                     (pressure, temperature, blheight, surfheatflux in every wind entry).  'allen': Allen's
+    #                                     (2006) field of discrete updrafts at wtk_thermal_height, one stochastic field per
+    #                                     realisation, their number and strength from zi and w* (thermal_allen_*);
+    #                                     the ids carry -allen
 
     def __str__(self):
         known = {f.name for f in fields(self)}

@@ -77,7 +77,8 @@ def classify(fields, x_km, y_km, gridsize, case, group='the four thermal layers'
     return Samples(form0, x, y, np.stack(arrays))
 
 
-def resolve_wind(wind, sim_mode, time_format, gridsize, wtk_interp_type, want_thermal, wtk_layers, project=None):
+def resolve_wind(wind, sim_mode, time_format, gridsize, wtk_interp_type, want_thermal, wtk_layers, project=None,
+                 thermal_model='wtk'):
     """The `wind=` argument of Simulator as one `WindCase` per entry.  project(lon, lat) -> x_km, y_km serves entries
     whose samples sit at 'lon', 'lat' (degrees)."""
     if isinstance(wind, dict):
@@ -117,8 +118,8 @@ def resolve_wind(wind, sim_mode, time_format, gridsize, wtk_interp_type, want_th
         if want_thermal:
             for name in THERMAL_LAYERS:
                 if item.get(name) is None:
-                    raise ValueError(f"{case}: thermal_model = 'wtk' needs the layer {name!r} ({wtk_layers[name]}) in "
-                                     'every wind entry')
+                    raise ValueError(f"{case}: thermal_model = {thermal_model!r} needs the layer {name!r} "
+                                     f'({wtk_layers[name]}) in every wind entry')
             group = classify([(name, item[name]) for name in THERMAL_LAYERS], x, y, gridsize, case)
             entry.thermal = to_km(group) if to_km else group
             _need_three(case, 'pressure', entry.thermal, method)

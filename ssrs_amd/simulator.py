@@ -55,7 +55,8 @@ class Simulator(Config):
         scattered points: x_km[npts], y_km[npts], arrays (npts,)).  Samples are
         interpolated as `wtk_interp_type` says ('nearest' | 'linear' | 'cubic', scipy
         griddata's methods as in the reference); rasters are taken as they are.
-        With thermal_model='wtk' every entry also carries 'pressure', 'temperature',
+        With thermal_model='wtk' (and with 'allen' while thermal_allen_zi or
+        thermal_allen_wstar is 0) every entry also carries 'pressure', 'temperature',
         'blheight' and 'surfheatflux' (the keys of `wtk_layers`), all four as (rows, cols)
         rasters, as samples (npts,) at x_km / y_km, or on the lattice (ny, nx).
         origin: projected (west, south) of cell (0, 0), or 'southwest_lonlat': the image of
@@ -138,7 +139,8 @@ class Simulator(Config):
                 raise ValueError(f'{self.sim_mode} mode needs injected wind data (wind=[...]); '
                                  'the WIND Toolkit download is out of scope')
             self._wind = inputs.resolve_wind(wind, self.sim_mode, self.time_format, self.gridsize, self.wtk_interp_type,
-                                             self._wtk_thermals(), self.wtk_layers, self._wind_km)
+                                             self._wtk_thermals() or self._allen_from_layers(), self.wtk_layers,
+                                             self._wind_km, str(self.thermal_model).lower())
             self.dtimes = [w.datetime for w in self._wind]
             self.case_ids = [w.case_id for w in self._wind]
             self.compute_orographic_updrafts_using_wtk()
@@ -242,9 +244,33 @@ class Simulator(Config):
     def _wtk_thermals(self):
         return str(self.thermal_model).lower() == 'wtk'
 
+    def _allen_thermals(self):
+        return str(self.thermal_model).lower() == 'allen'
+
+    def _allen_from_layers(self):
+        """thermal_model = 'allen' with zi or w* left at 0: they come from the case's own WTK layers."""
+        return self._allen_thermals() and not (float(self.thermal_allen_zi) > 0. and float(self.thermal_allen_wstar) > 0.)
+
     def _check_thermal_model(self):
-        if str(self.thermal_model).lower() not in ('random', 'wtk'):
-            raise ValueError(f"thermal_model = {self.thermal_model!r}: expected 'random' or 'wtk'")
+        if str(self.thermal_model).lower() not in ('random', 'wtk', 'allen'):
+            raise ValueError(f"thermal_model = {self.thermal_model!r}: expected 'random', 'wtk' or 'allen'")
+        if self._allen_thermals():
+            for name in ('thermal_allen_zi', 'thermal_allen_wstar'):
+                v = float(getattr(self, name))
+                if not (np.isfinite(v) and v >= 0.):
+                    raise ValueError(f'{name} = {getattr(self, name)!r}: expected a finite number >= 0 (0 = from the WTK layers)')
+            if not (np.isfinite(float(self.wtk_thermal_height)) and float(self.wtk_thermal_height) > 0.):
+                raise ValueError(f"thermal_model = 'allen' evaluates the updrafts at wtk_thermal_height = "
+                                 f'{self.wtk_thermal_height!r}: expected metres > 0')
+            if int(self.thermals_realization_count) < 1:
+                raise ValueError("thermal_model = 'allen' draws one field per realisation: thermals_realization_count must "
+                                 f'be at least 1, not {self.thermals_realization_count!r}')
+            if str(self.sim_mode).lower() == 'uniform':
+                if self._allen_from_layers():
+                    raise ValueError("thermal_model = 'allen' in uniform mode has no WTK layers to take them from: "
+                                     'thermal_allen_zi and thermal_allen_wstar must both be > 0 '
+                                     f'(got {self.thermal_allen_zi!r}, {self.thermal_allen_wstar!r})')
+                self._allen_count(float(self.thermal_allen_zi), float(self.thermal_allen_wstar))
         if self._wtk_thermals():
             if str(self.sim_mode).lower() not in ('snapshot', 'seasonal'):
                 raise ValueError("thermal_model = 'wtk' needs the WTK layers of a wind case: sim_mode must be 'snapshot' or "
@@ -456,23 +482,76 @@ class Simulator(Config):
                       'hull of the samples); their updraft is 0')
             self._save_f32(self._get_thermal_fname(case_id, 0, self.mode_data_dir), field)
 
+    def _thermal_seeds(self, case_id):
+        """One key per realisation of a case.  The reference draws every case / realisation from one advancing numpy
+        stream (layers.py:188-214), so all fields differ; here each gets its own key from (sim_seed, position of the
+        case, realisation)."""
+        base = (self.sim_seed if self.sim_seed >= 0 else
+                int.from_bytes(os.urandom(4), 'little'))
+        case_no = self.case_ids.index(case_id) if case_id in self.case_ids else 0
+        return [base + 7919 * (real_id + 1) + 104729 * case_no
+                for real_id in range(self.thermals_realization_count)]
+
+    def _allen_count(self, zi, wstar):
+        """The host scalars of an Allen field of this run; ValueError when its updrafts are too many."""
+        from .thermals import allen_scalars, ALLEN_MAX_UPDRAFTS
+        xsize = int(round((self.region_width_km[0] * 1000. / self.resolution)))
+        ysize = int(round((self.region_width_km[1] * 1000. / self.resolution)))
+        sc = allen_scalars(float(self.wtk_thermal_height), zi, wstar, (ysize, xsize), self.resolution,
+                           sink=bool(self.thermal_allen_sink))
+        if sc['N'] > ALLEN_MAX_UPDRAFTS:
+            raise ValueError(f"thermal_model = 'allen': N = {sc['N']} updrafts for zi = {zi:g} m at wtk_thermal_height = "
+                             f'{self.wtk_thermal_height!r} m on this region; at most {ALLEN_MAX_UPDRAFTS} are supported')
+        return sc
+
+    def allen_case_scalars(self, case_id: str):
+        """(zi, wstar) of a case under thermal_model = 'allen': the positive thermal_allen_* fields, else the means over
+        the case's WTK samples (or the finite cells of its rasters) of blheight.clip(min=100) and of
+        deardoff_velocity_function(compute_potential_temperature(p, T), blheight, surfheatflux)."""
+        zi, wstar = float(self.thermal_allen_zi), float(self.thermal_allen_wstar)
+        if zi > 0. and wstar > 0.:
+            return zi, wstar
+        entry = next(c for c in self._wind if c.case_id == case_id)
+        p, t, bl, q = (inputs.host_f64(a).ravel() for a in entry.thermal.values)
+        if not zi > 0.:
+            clipped = bl.clip(min=100.)
+            zi = float(clipped[np.isfinite(clipped)].mean())
+        if not wstar > 0.:
+            w = np.asarray(layers.deardoff_velocity_function(layers.compute_potential_temperature(p, t), bl, q))
+            wstar = float(w[np.isfinite(w)].mean())
+        return zi, wstar
+
+    def _write_allen_thermals(self, case_id):
+        """thermal_model = 'allen': `<case>_r<k>_thermals.npy` (f32) of every realisation of a case, one device call
+        each; the updrafts of realisation k come from its seed, their gains from the case's datetime."""
+        from .thermals import allen_datetime_gains, allen_updrafts, compute_allen_thermals
+        print('Computing thermal updrafts (Allen)...', flush=True)
+        zi, wstar = self.allen_case_scalars(case_id)
+        sc = self._allen_count(zi, wstar)
+        dtime = None
+        if str(self.sim_mode).lower() != 'uniform':
+            dtime = next(c for c in self._wind if c.case_id == case_id).datetime
+        gains = allen_datetime_gains(dtime)
+        for real_id, seed in enumerate(self._thermal_seeds(case_id)):
+            ups = allen_updrafts(sc['N'], self.gridsize, self.resolution, seed, gains)
+            field = compute_allen_thermals(*ups, self.gridsize, self.resolution, float(self.wtk_thermal_height), zi, wstar,
+                                           sink=bool(self.thermal_allen_sink), dtype=torch.float32)
+            self._save_f32(self._get_thermal_fname(case_id, real_id, self.mode_data_dir), field)
+
     def compute_thermal_updrafts(self, case_id: str):
-        """simulator.py:217-228; with thermal_model = 'wtk' the one field of the physical model instead."""
+        """simulator.py:217-228; with thermal_model = 'wtk' the one field of the physical model instead, with 'allen'
+        Allen's discrete updrafts."""
         if self._wtk_thermals():
             self._write_wtk_thermals([(c.case_id, c.thermal.as_points()) for c in self._wind if c.case_id == case_id])
+            return
+        if self._allen_thermals():
+            self._write_allen_thermals(case_id)
             return
         if self.thermals_realization_count > 0:
             from .thermals import compute_thermals_batch
             print('Computing thermal updrafts...', flush=True)
             aspect = self.get_terrain_aspect()
-            # the reference draws every case / realisation from one advancing numpy stream
-            # (layers.py:188-214), so all fields differ; here each gets its own counter-based
-            # key from (sim_seed, position of the case, realisation)
-            base = (self.sim_seed if self.sim_seed >= 0 else
-                    int.from_bytes(os.urandom(4), 'little'))
-            case_no = self.case_ids.index(case_id) if case_id in self.case_ids else 0
-            seeds = [base + 7919 * (real_id + 1) + 104729 * case_no
-                     for real_id in range(self.thermals_realization_count)]
+            seeds = self._thermal_seeds(case_id)
             # one fused call per case, in the f32 the files hold; at most 1 GiB of fields at a time
             chunk = max(1, (1 << 30) // (4 * aspect.shape[0] * aspect.shape[1]))
             aspect = to_dev(aspect, torch.float64)
@@ -543,6 +622,8 @@ class Simulator(Config):
                 model += f'a{float(self.orographic_sx_sector):g}s{float(self.orographic_sx_step):g}'
             if self._smooth_sigma_m() > 0.:                     # (nor that of an unsmoothed run for a smoothed one's)
                 model += f'g{self._smooth_sigma_m():g}'
+        if self._allen_thermals():                              # (nor a potential of another thermal model)
+            model += '-allen'
         out_str = (f'{case_id}_d{int(self.track_direction % 360)}'
                    f'_t{int(self.updraft_threshold * 100)}_{model}')
         if real_id is not None:
