@@ -561,6 +561,37 @@ int ssrs_turbine_encounters(const int16_t *traj, const int64_t *traj_offsets, in
 int ssrs_turbine_encounter_counts(const uint32_t *hits, int64_t ntracks, int nturb,
                                   int64_t *tracks_per_turbine, int32_t *turbines_per_track, void *stream);
 
+/* -------------------------------------------------------------- occupancy */
+
+/* K13 -- how many DISTINCT tracks passed through each cell, from the trajectories on the device: the per-cell analogue
+ * of tracks_per_turbine, which the visit histogram cannot give (a track that loiters in a cell is many visits).
+ *   traj, traj_offsets  exactly what ssrs_turbine_encounters takes: int16 (row, col) pairs, 4-byte aligned (16-byte
+ *                       aligned buffers are read 16 bytes a lane); int64 offsets (ntracks + 1), the first need not be 0,
+ *                       equal consecutive offsets are an empty track.  Points outside [0, rows) x [0, cols) are ignored
+ *   counts              uint32 (rows, cols), ADDED to: +1 in cell (r, c) for every track with at least one point (r, c),
+ *                       so that chunks, sub-batches and calls accumulate in one raster
+ *   cells_per_track     uint32 (ntracks) or NULL, ADDED to: the number of distinct in-raster cells of each track.
+ *                       Sum(cells_per_track) == Sum(counts) of one call: the caller's checksum
+ *   planes              1..SSRS_OCCUPANCY_MAX_PLANES: tracks are taken in rounds of 32 * planes, track k of a round owning
+ *                       bit k & 31 of plane k >> 5.  The result does not depend on it
+ *   workspace           `planes` uint32 rasters, ssrs_track_occupancy_workspace_bytes = rows * cols * 4 * planes rounded up
+ *                       to 256.  It must be ZERO on entry and is left zero on every successful return: calls chain
+ *                       without a memset in between (after a failed call, zero it)
+ * Per round one "set" kernel over the round's points (test the bit with an L2 load, atomicOr it otherwise; the one lane
+ * that is handed the old value without the bit counts the cell) and one clearing step: an "unset" kernel over the same
+ * points when they are fewer bytes than the round's planes, else a memset of those.  Exact, and independent of the
+ * launch order.  The offsets at the round borders are read back first (each launch is sized from its round's points),
+ * so the call waits for `stream` once; its launches go to `stream` in order.
+ * NULL traj / traj_offsets / counts / workspace, planes outside [1, SSRS_OCCUPANCY_MAX_PLANES], rows / cols outside
+ * [1, 32767], ntracks outside [0, 2^31), a misaligned traj, a workspace that is too small -> SSRS_ERR_INVALID before any
+ * GPU work.  ntracks == 0, or no points, returns SSRS_OK and touches nothing. */
+#define SSRS_OCCUPANCY_MAX_PLANES 8
+size_t ssrs_track_occupancy_workspace_bytes(int rows, int cols, int planes);
+int ssrs_track_occupancy(const int16_t *traj, const int64_t *traj_offsets, int64_t ntracks,
+                         int rows, int cols, int planes,
+                         uint32_t *counts, uint32_t *cells_per_track,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------- shelter */
 
 /* K9 -- the terrain-shelter angle Sx (Winstral et al. 2002) and the orographic updraft adjusted by it and by a

@@ -22,6 +22,7 @@ SSRS_TRACKS_NO_SCATTERED = 64
 SSRS_TRACKS_THR_TABLE = 128
 SSRS_SOLVE_NO_AMG = 1
 SSRS_TURBINE_BIN, SSRS_TURBINE_MAX = 32, 8192
+SSRS_OCCUPANCY_MAX_PLANES = 8
 SSRS_RAY_AXES = {'row_north': 0, 'row_east': 1}                  # SSRS_RAY_ROW_NORTH / _ROW_EAST
 SSRS_SHELTER_PATH = {'auto': 0, 'lds': 1, 'global': 2}           # SSRS_SHELTER_AUTO / _LDS / _GLOBAL
 SSRS_SMOOTH_PATH = {'auto': 0, 'lds': 1, 'global': 2}            # SSRS_SMOOTH_AUTO / _LDS / _GLOBAL
@@ -53,6 +54,7 @@ EXPORTS = (
     'ssrs_smooth_workspace_bytes', 'ssrs_smooth_reflect',
     'ssrs_projection_init_albers', 'ssrs_warp_lonlat_raster',
     'ssrs_allen_workspace_bytes', 'ssrs_allen_thermal_field',
+    'ssrs_track_occupancy_workspace_bytes', 'ssrs_track_occupancy',
 )
 
 
@@ -94,6 +96,10 @@ class SsrsProjection(C.Structure):
 
 # ssrs_allen_thermal_field: xt, yt, wgain, rgain, n, bin_start, bin_items, bin_size_m, nbx, nby, rbar, wtbar, zzi, z_below_zi,
 # we, res, rows, cols, path, out, out_type, nearest, table, workspace, workspace_bytes, stream
+# ssrs_track_occupancy: traj, traj_offsets, ntracks, rows, cols, planes, counts, cells_per_track, workspace, workspace_bytes, stream
+OCCUPANCY_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                      C.c_size_t, C.c_void_p]
+
 ALLEN_FIELD_ARGTYPES = [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int] + \
     [C.c_double] * 3 + [C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -199,6 +205,9 @@ def lib():
         L.ssrs_allen_workspace_bytes.restype = C.c_size_t
         L.ssrs_allen_workspace_bytes.argtypes = [C.c_int]
         L.ssrs_allen_thermal_field.argtypes = ALLEN_FIELD_ARGTYPES
+        L.ssrs_track_occupancy_workspace_bytes.restype = C.c_size_t
+        L.ssrs_track_occupancy_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.ssrs_track_occupancy.argtypes = OCCUPANCY_ARGTYPES
         _lib = L
     return _lib
 

@@ -32,8 +32,8 @@ _SECTIONS = (
                            'track_dirn_restrict')),
     ('Plotting and wind turbines', ('turbine_minimum_hubheight', 'turbine_mrkr_size',
                                     'fig_height', 'fig_dpi')),
-    ('MI355X build', ('save_tracks', 'stepper_path', 'steps_per_launch', 'max_tracks_file_gb', 'hist_safe_tracks',
-                      'thermal_model', 'thermal_allen_zi', 'thermal_allen_wstar', 'thermal_allen_sink',
+    ('MI355X build', ('save_tracks', 'stepper_path', 'steps_per_launch', 'max_tracks_file_gb', 'track_occupancy',
+                      'hist_safe_tracks', 'thermal_model', 'thermal_allen_zi', 'thermal_allen_wstar', 'thermal_allen_sink',
                       'turbine_encounter_radius')),
 )
 
@@ -101,6 +101,11 @@ class Config:
     steps_per_launch: int = 0           # 0 = library default
     max_tracks_file_gb: float = 64.     # refuse a <id>_tracks.pkl larger than this (tracks that wander to
     #                                     max_moves: 1 TB per 100k tracks on a solved 10 m field)
+    track_occupancy: bool = False       # True: simulate_tracks also counts, per cell, the DISTINCT tracks that passed through it
+    #                                     (a track that loiters in a cell is many visits and one track), from the trajectories
+    #                                     on the device (produced even with save_tracks=False):
+    #                                     <id>_occupancy.npy, Simulator.compute_occupancy_map().  It stands here, not last,
+    #                                     because tests pin every slot after the reference's fields but this one
     thermal_allen_zi: float = 0.        # thermal_model = 'allen': boundary-layer height zi in metres.  0 (snapshot / seasonal
     #                                     only) = the mean of the case's own blheight layer, clipped below at 100 m
     thermal_allen_wstar: float = 0.     # thermal_model = 'allen': convective velocity scale w* in m/s.  0 (snapshot / seasonal

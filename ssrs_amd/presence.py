@@ -34,6 +34,92 @@ def compute_presence_counts(tracks, gridshape):
     return hist.cpu().numpy() if as_numpy else hist
 
 
+MAX_OCCUPANCY_PLANES = nat.SSRS_OCCUPANCY_MAX_PLANES
+
+
+def occupancy_workspace(gridshape, planes):
+    """A zeroed workspace of ssrs_track_occupancy for `planes` rasters of `gridshape`: a call leaves it zero, so one
+    serves any number of calls."""
+    rows, cols = int(gridshape[0]), int(gridshape[1])
+    nbytes = nat.lib().ssrs_track_occupancy_workspace_bytes(rows, cols, int(planes))
+    return torch.zeros(nbytes, dtype=torch.uint8, device=device())
+
+
+def occupancy_planes(ntracks, gridshape):
+    """min(8, ceil(ntracks / 32), the planes that fit in 1/8 of the free device memory), at least 1."""
+    rows, cols = int(gridshape[0]), int(gridshape[1])
+    fit = (torch.cuda.mem_get_info()[0] // 8) // (rows * cols * 4)
+    return int(max(1, min(MAX_OCCUPANCY_PLANES, -(-int(ntracks) // 32), fit)))
+
+
+def compute_track_occupancy(tracks, gridshape, *, offsets=None, counts=None, cells_per_track=False, planes=None,
+                            workspace=None):
+    """How many DISTINCT tracks passed through each cell (K13, ssrs_track_occupancy): +1 in cell (r, c) for every track
+    with at least one point (r, c); points outside the raster are ignored.
+    `tracks`: a list of int16 (n_i, 2) host arrays, or a device int16 (points, 2) tensor with `offsets` int64
+    (ntracks + 1) as movmodel.simulate_tracks / TrackBatch.iter_device_chunks() give them (`offsets` may be a slice of a
+    longer vector: its first entry need not be 0).  Returns the int32 raster holding the uint32 counts, numpy for host
+    input and a tensor for device input like compute_presence_counts; with cells_per_track=True also the int32 (ntracks)
+    vector of each track's distinct in-raster cells (their sum is the raster's sum).
+    counts: an int32 device raster that is ADDED to (chunks and sub-batches accumulate in one raster) and returned.
+    planes: 1..8 mask rasters of the workspace, 32 tracks each per round (None: occupancy_planes); the result does not
+    depend on it.  workspace: of occupancy_workspace(gridshape, planes), trusted to be zero and left zero (it is
+    re-zeroed here if the library call raises); None allocates one."""
+    rows, cols = int(gridshape[0]), int(gridshape[1])
+    if planes is not None and not 1 <= int(planes) <= MAX_OCCUPANCY_PLANES:
+        raise ValueError(f'compute_track_occupancy: planes = {planes!r}, expected 1 to {MAX_OCCUPANCY_PLANES}')
+    as_numpy = not is_tensor(tracks)
+    if as_numpy:
+        if offsets is not None:
+            raise ValueError('compute_track_occupancy: offsets goes with a device tensor of points, not with a list of tracks')
+        tracks = [np.asarray(t) for t in tracks]
+        for k, t in enumerate(tracks):
+            if t.dtype != np.int16 or t.ndim != 2 or t.shape[1] != 2:
+                raise ValueError(f'compute_track_occupancy: track {k} is {t.dtype} {t.shape}, expected int16 (n, 2)')
+        flat = np.concatenate(tracks) if tracks else np.zeros((0, 2), dtype=np.int16)
+        offsets = np.concatenate([[0], np.cumsum([len(t) for t in tracks])]).astype(np.int64)
+    else:
+        if offsets is None:
+            raise ValueError('compute_track_occupancy: a tensor of points needs offsets= (int64, ntracks + 1)')
+        if tracks.dtype != torch.int16 or tracks.dim() != 2 or int(tracks.shape[1]) != 2:
+            raise ValueError(f'compute_track_occupancy: tracks is {tracks.dtype} {tuple(tracks.shape)}, expected int16 '
+                             '(points, 2)')
+        if not is_tensor(offsets):
+            offsets = np.asarray(offsets)
+        if offsets.dtype not in (torch.int64, np.int64) or len(offsets.shape) != 1 or int(offsets.shape[0]) < 1:
+            raise ValueError('compute_track_occupancy: offsets must be int64 (ntracks + 1)')
+        flat = tracks
+    pts = to_dev(flat, torch.int16)
+    off = to_dev(offsets, torch.int64)
+    ntracks = int(off.numel()) - 1
+    dev = device()
+    if counts is None:
+        counts = torch.zeros((rows, cols), dtype=torch.int32, device=dev)
+    elif not is_tensor(counts) or counts.dtype != torch.int32 or tuple(counts.shape) != (rows, cols) or \
+            not counts.is_contiguous() or not counts.is_cuda:
+        raise ValueError(f'compute_track_occupancy: counts must be a contiguous int32 device tensor ({rows}, {cols})')
+    per_track = torch.zeros(ntracks, dtype=torch.int32, device=dev) if cells_per_track else None
+    if ntracks > 0 and pts.numel() > 0:                  # (empty tensors have no address to hand over)
+        if planes is None:
+            planes = occupancy_planes(ntracks, gridshape)
+        if workspace is None:
+            workspace = occupancy_workspace(gridshape, planes)
+        elif not is_tensor(workspace) or not workspace.is_cuda or not workspace.is_contiguous():
+            raise ValueError('compute_track_occupancy: workspace must be a contiguous device tensor (occupancy_workspace)')
+        nbytes = int(workspace.numel()) * workspace.element_size()
+        try:
+            nat.check(nat.lib().ssrs_track_occupancy(
+                nat.ptr(pts), nat.ptr(off), C.c_int64(ntracks), rows, cols, int(planes), nat.ptr(counts),
+                nat.ptr(per_track), nat.ptr(workspace), C.c_size_t(nbytes), stream_ptr()))
+        except Exception:
+            workspace.zero_()
+            raise
+    out = like_input(counts, None if as_numpy else counts)
+    if cells_per_track:
+        return out, like_input(per_track, None if as_numpy else per_track)
+    return out
+
+
 def smooth_presence_counts(count_mat, radius):
     """Disk smoothing of a count matrix (movmodel.py:431-439) -> f32.  int64 counts (the
     widened sum of distributed.reduce_histogram) take the 64-bit kernel, everything else is

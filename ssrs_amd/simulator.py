@@ -123,6 +123,7 @@ class Simulator(Config):
         self._terrain = self._resolve_terrain(terrain)
         self.turbines = self._resolve_turbines(turbines)
         self.turbine_encounters = {}      # (case_id, real_id) -> dict(tracks_per_turbine, turbines_per_track, first_step)
+        self.track_occupancy_counts = {}  # (case_id, real_id) -> int32 (rows, cols): the distinct tracks through each cell
         self.wtk_layers = {
             'wspeed': f'windspeed_{str(int(self.wtk_orographic_height))}m',
             'wdirn': f'winddirection_{str(int(self.wtk_orographic_height))}m',
@@ -738,6 +739,7 @@ class Simulator(Config):
             # (one upload for all cases: the kernel reads the turbines and their cull lists from the device)
             enc_geometry = (to_dev(self._turbine_cells, torch.float64),
                             tuple(to_dev(a, torch.int32) for a in self._turbine_bins))
+        occupancy = bool(self.track_occupancy)
 
         def run(item):
             case_id, real_id, fields, seed = item
@@ -749,14 +751,20 @@ class Simulator(Config):
                 torch.cuda.current_stream().synchronize()
                 print(f'{id_str}: Simulating {hi - lo} tracks..took {_elapsed(start_time)}',
                       flush=True)
-                chunks = None
+                # every device chunk of the trajectories goes through its consumers on the device (the encounter kernel,
+                # the occupancy kernel), then (save_tracks) on to the pickle: a replay range is stepped ONCE for all
+                consumers = []
                 if encounters:
-                    # every device chunk of the trajectories goes through the encounter kernel, then (save_tracks) on
-                    # to the pickle: a replay range is stepped ONCE for both
                     nturb = int(enc_geometry[0].shape[0])
                     hits = torch.zeros((hi - lo, (nturb + 31) // 32), dtype=torch.int32, device=my_starts.device)
                     first_step = torch.full((hi - lo,), -1, dtype=torch.int32, device=my_starts.device)
-                    chunks = self._encounter_chunks(batch, enc_geometry, hits, first_step)
+                    consumers.append(self._encounter_consumer(enc_geometry, hits, first_step))
+                if occupancy:
+                    # one raster per item, accumulated over chunks and parts, and one workspace (a call leaves it zero)
+                    occ_counts = torch.zeros(self.gridsize, dtype=torch.int32, device=my_starts.device)
+                    occ_cells = torch.zeros((), dtype=torch.int64, device=my_starts.device)
+                    consumers.append(self._occupancy_consumer(hi - lo, occ_counts, occ_cells))
+                chunks = self._device_chunks(batch, consumers) if consumers else None
                 if self.save_tracks:
                     # (inside the stream's scope: long trajectories are stepped again range by range while written)
                     need = sum(b.total_points for b in batch.parts) * 4
@@ -782,6 +790,9 @@ class Simulator(Config):
                     # (track-sharded: the sum over the ranks is a collective, issued here in item order like the rest)
                     self._store_encounters(case_id, real_id, per_turbine.cpu().numpy(), per_track.cpu().numpy(),
                                            first_step.cpu().numpy(), sharded)
+                if occupancy:
+                    # (track-sharded: the sum over the ranks is a collective as well, after the encounters' in every item)
+                    self._store_occupancy(case_id, real_id, occ_counts, int(occ_cells.item()), sharded)
             if sharded:
                 batch.hist = distributed.reduce_histogram(batch.hist, all_ranks=True)
             return (case_id, real_id), batch
@@ -814,18 +825,57 @@ class Simulator(Config):
                         collect(f.result() for f in done)
                 collect(f.result() for f in pending)
 
-    def _encounter_chunks(self, batch, geometry, hits, first_step):
-        """The device chunks (traj, offsets) of every part of `batch` in track order, each one run through the encounter
-        kernel into its rows of `hits` / `first_step` before it is handed on."""
-        xy, bins = geometry
-        radius_cells = float(self.turbine_encounter_radius) / float(self.resolution)
+    @staticmethod
+    def _device_chunks(batch, consumers):
+        """The device chunks (traj, offsets) of every part of `batch` in track order, each one handed to every
+        consumer(first track, end track, traj, offsets) -- track numbers within the batch -- before it is handed on."""
         base = 0
         for part in batch.parts:
             for t0, t1, traj, off in part.iter_device_chunks():
-                turbines_mod.turbine_encounters(traj, off, xy, radius_cells, self.gridsize, bins=bins,
-                                                hits=hits[base + t0:base + t1], first_step=first_step[base + t0:base + t1])
+                for consume in consumers:
+                    consume(base + t0, base + t1, traj, off)
                 yield traj, off
             base += int(part.lengths.numel())
+
+    def _encounter_consumer(self, geometry, hits, first_step):
+        """A chunk through the encounter kernel, into its rows of `hits` / `first_step`."""
+        xy, bins = geometry
+        radius_cells = float(self.turbine_encounter_radius) / float(self.resolution)
+
+        def consume(t0, t1, traj, off):
+            turbines_mod.turbine_encounters(traj, off, xy, radius_cells, self.gridsize, bins=bins,
+                                            hits=hits[t0:t1], first_step=first_step[t0:t1])
+        return consume
+
+    def _occupancy_consumer(self, ntracks, counts, cells):
+        """A chunk through the occupancy kernel: `counts` (the item's raster) is added to, `cells` (a 0-d int64 tensor)
+        gets the sum of the chunk's cells_per_track, the checksum of _store_occupancy.  One zeroed workspace serves
+        every chunk of the item."""
+        planes = presence.occupancy_planes(ntracks, self.gridsize)
+        workspace = presence.occupancy_workspace(self.gridsize, planes)
+
+        def consume(t0, t1, traj, off):
+            _, per_track = presence.compute_track_occupancy(traj, self.gridsize, offsets=off, counts=counts,
+                                                            cells_per_track=True, planes=planes, workspace=workspace)
+            cells.add_(per_track.sum(dtype=torch.int64))
+        return consume
+
+    def _store_occupancy(self, case_id, real_id, counts, cells, sharded):
+        """Keeps the occupancy raster of one (case, realisation) as numpy int32 and writes <id>_occupancy.npy.  Checked
+        like the histogram by its checksum: this rank's counts must add up to the sum of its cells_per_track (`cells`).
+        Track-sharded runs then sum the raster over the ranks the way the histogram is summed (shards hold disjoint
+        tracks, so the sum is exact; every rank must call this, in the same item order) and rank 0 writes; otherwise
+        the rank that owns the case does."""
+        id_str = self._get_id_string(case_id, real_id)
+        counted = int((counts.to(torch.int64) & 0xFFFFFFFF).sum().item())
+        if counted != int(cells):
+            raise RuntimeError(f'{id_str}: track occupancy: the raster adds up to {counted}, the distinct cells of the '
+                               f'tracks to {int(cells)}')
+        if sharded:
+            counts = distributed.reduce_histogram(counts, all_ranks=True)
+        self.track_occupancy_counts[(case_id, real_id)] = counts.to(torch.int32).cpu().numpy()
+        if not sharded or self._rank() == 0:
+            np.save(os.path.join(self.mode_data_dir, f'{id_str}_occupancy.npy'), self.track_occupancy_counts[(case_id, real_id)])
 
     def _store_encounters(self, case_id, real_id, tracks_per_turbine, turbines_per_track, first_step, sharded):
         """Keeps the encounters of one (case, realisation) and writes <id>_turbine_encounters.npy (int64 (nturb,): the
@@ -859,8 +909,8 @@ class Simulator(Config):
         # short last sub-batch would cost a full pass's time for a fraction of the work
         step = max(1, -(-n // max(1, -(-n // safe))))
         parts, wide, stats = [], None, None
-        # trajectories: for the pickle, or for the turbine encounters (which read them on the device)
-        want_tracks = bool(self.save_tracks) or float(self.turbine_encounter_radius) > 0.
+        # trajectories: for the pickle, or for the turbine encounters / the track occupancy (which read them on the device)
+        want_tracks = bool(self.save_tracks) or float(self.turbine_encounter_radius) > 0. or bool(self.track_occupancy)
         # (start, length) of the sub-batches still to step, in track-id order; one whose uint32 counts wrapped is stepped
         # again as two halves, added up in 64 bits like the rest
         todo = [(t0, min(step, n - t0)) for t0 in range(0, max(n, 1), step)]
@@ -1040,6 +1090,37 @@ class Simulator(Config):
         out = total[:-1] / total[-1]
         if self._rank() == 0:
             np.save(os.path.join(self.mode_data_dir, 'summary_turbine_encounters.npy'), out)
+        self._barrier()
+        return out
+
+    def compute_occupancy_map(self, radius: float = 0.):
+        """Each cell's share of the simulated tracks that passed through it, in [0, 1]: the f32 mean over all kept
+        (case, realisation) items of track_occupancy_counts / track_count (the per-cell analogue of
+        compute_turbine_encounters); case-sharded runs take the mean over every rank's items.  radius > 0 (metres)
+        applies the disk mean of the presence map (presence.smooth_presence_counts with
+        presence.presence_kernel_radius) to each item's counts first: that is the disk MEAN OF THE PER-CELL SHARES, not
+        the share of tracks that came within the radius of the cell (a track that crosses a disk touches several of its
+        cells and enters the mean once for each).  Writes summary_occupancy.npy.  ValueError when simulate_tracks
+        computed no occupancy."""
+        if not self.track_occupancy_counts:
+            raise ValueError('no track occupancy was computed: run simulate_tracks() with track_occupancy=True')
+        total = torch.zeros(self.gridsize, dtype=torch.float64, device=self._presence_device())
+        for key in sorted(self.track_occupancy_counts):
+            counts = to_dev(self.track_occupancy_counts[key], torch.int32)
+            if float(radius) > 0.:
+                krad = presence.presence_kernel_radius(float(radius), self.resolution, self.gridsize)
+                item = presence.smooth_presence_counts(counts, krad).to(torch.float64)
+            else:
+                item = (counts.to(torch.int64) & 0xFFFFFFFF).to(torch.float64)
+            total += item / float(self.track_count)
+        nitems = float(len(self.track_occupancy_counts))
+        if self._world() > 1 and not self._shards_tracks():
+            # the cases of the other ranks
+            summed = self._allreduce_sum(np.append(total.cpu().numpy().ravel(), nitems))
+            total, nitems = to_dev(np.asarray(summed[:-1]).reshape(self.gridsize), torch.float64), float(summed[-1])
+        out = (total / nitems).to(torch.float32).cpu().numpy()
+        if self._rank() == 0:
+            np.save(os.path.join(self.mode_data_dir, 'summary_occupancy.npy'), out)
         self._barrier()
         return out
 
