@@ -328,7 +328,8 @@ typedef struct SsrsTrackStats {
     int64_t roam_slow_wave_pairs; /* ... and how many of them sent some lane through the single-move sequence
                                      (near-ties, flag entries, moves out of the window, burn-in) */
     int32_t roam_shuffles;        /* times a SETTLED roaming batch had the tracks of its windows dealt afresh
-                                     (every SSRS_TRACKS_ROAM_SHUFFLE batches, default 16; part of wander_sorts) */
+                                     (every SSRS_TRACKS_ROAM_SHUFFLE batches: default 16, and 4 while 256-lane blocks step
+                                     with feeder waves; part of wander_sorts) */
     int32_t roam_wide_launches;   /* of roam_launches: those run with 512-lane blocks (two list blocks of one window per CU: batches
                                      whose survivors outnumber one round of 256-lane blocks; SSRS_TRACKS_ROAM_WIDE) */
 } SsrsTrackStats;
@@ -881,6 +882,22 @@ int ssrs_potential_solve(const double *conductivity, const uint8_t *fixed_mask,
 int ssrs_uniform_selftest(uint64_t seed, const uint64_t *track,
                           const uint64_t *step, double *out, size_t n,
                           void *stream);
+
+/* The roaming stepper's hand-over word of n (track, block) pairs next to the
+ * four words of rocRAND's engine for the same block:
+ *   packed[i] = (x & 0xFFFF0000) | (z >> 16) of words[4 i .. 4 i + 3] = x, y, z, w.
+ * Device self-check of what a feeder wave writes for its stepping wave. */
+int ssrs_roam_pair_word_selftest(uint64_t seed, const uint64_t *track,
+                                 const uint64_t *block, uint32_t *packed,
+                                 uint32_t *words, size_t n, void *stream);
+
+/* Wave-pairs of the roaming stepper in the calling thread's last
+ * ssrs_tracks_simulate* call (host values, thread-local; either may be NULL):
+ *   fed  pairs whose uniforms a feeder wave handed over
+ *   own  pairs whose Philox block the stepping wave computed itself
+ * fed + own == SsrsTrackStats.roam_wave_pairs of that call.
+ * SSRS_TRACKS_ROAM_FEED=0 runs without feeder waves (fed == 0). */
+void ssrs_tracks_roam_feed_counts(int64_t *fed, int64_t *own);
 
 #ifdef __cplusplus
 }

@@ -274,6 +274,25 @@ __global__ void k_uniform_selftest(uint64_t seed, const uint64_t *track, const u
     out[i] = same ? u : __longlong_as_double(0x7FF8000000000000ll);
 }
 
+// What k_step_roam compares of a block: the top 16 bits of words x and z, one per move of the pair.  A feeder wave
+// hands them to its stepping wave as ONE dword per pair (k_step_roam<REV, 256, true>).
+__device__ __forceinline__ uint32_t roam_pair_word(uint64_t seed, uint64_t track, uint64_t blk)
+{
+    const uint4 w = philox_block_b3(seed, track, blk);
+    return (w.x & 0xFFFF0000u) | (w.z >> 16);
+}
+
+// (block indices directly: the packed dword next to the four words of rocRAND's engine)
+__global__ void k_roam_pair_word_selftest(uint64_t seed, const uint64_t *track, const uint64_t *blk,
+                                          uint32_t *packed, uint32_t *words, size_t n)
+{
+    const size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
+    if (i >= n) return;
+    const uint4 w = philox_block(seed, track[i], blk[i]);
+    packed[i] = roam_pair_word(seed, track[i], blk[i]);
+    words[4 * i] = w.x; words[4 * i + 1] = w.y; words[4 * i + 2] = w.z; words[4 * i + 3] = w.w;
+}
+
 // ------------------------------------------------------------ move decision
 __host__ __device__ __forceinline__ double sum9(const double *x)
 {   // numpy pairwise summation for n = 9
@@ -676,6 +695,7 @@ struct alignas(16) TrackCtl {
     unsigned long long dbg_tsum, dbg_tmax, dbg_waves, dbg_slowmax;   // SSRS_TRACKS_DEBUG_ROAM: wave lifetimes of one launch
     uint32_t roam_stop;                                              // k_step_roam: launch + 1 of the launch whose first wave is through its steps
     uint32_t deal_live;                                              // k_wander_windows: live tracks it found (the host picks the deal's block width from it)
+    unsigned long long roam_fed, roam_own;   // k_step_roam: wave-pairs whose uniforms came from the feeder wave / from the wave's own Philox (sum: roam_pairs)
 };
 
 static_assert(sizeof(TrackCtl) <= 128 * sizeof(uint32_t), "final read-back slot of pinned_counts()");
@@ -802,6 +822,7 @@ struct StepArgs {
     int cheap_exact;             // k_step_thr: near-ties through exact_three first (A/B: SSRS_TRACKS_NO_CHEAP_EXACT)
     unsigned long long *dbg_buf; // diagnostic builds (SSRS_DEBUG_WAVE_DUMP): one record per wave
     int debug_roam;              // k_step_roam: wave lifetimes into the control block (SSRS_TRACKS_DEBUG_ROAM)
+    int roam_feed;               // k_step_roam<.., 256, true>: 1: the feeder waves produce every trip, 2: the even trips only (SSRS_TRACKS_ROAM_FEED)
     uint32_t vis_r, vis_c;       // visit key = row * vis_r + col * vis_c: (cols, 1), or (1, rows) when
                                  // the front is a column (east / west headings: transposed binning)
 };
@@ -1103,6 +1124,7 @@ __global__ void k_ctl_init(TrackCtl *ctl, const PriorArg pr, double *__restrict_
         ctl->error = bad; ctl->par_min = 0xFFFFFFFFu; ctl->steps = 0; ctl->strays = 0; ctl->bin_done = 0; ctl->pad = 0; ctl->roam_slow = 0; ctl->roam_pairs = 0;
         ctl->dbg_tsum = ctl->dbg_tmax = ctl->dbg_waves = ctl->dbg_slowmax = 0;
         ctl->roam_stop = ctl->deal_live = 0;
+        ctl->roam_fed = ctl->roam_own = 0;
     }
     if (d < 9) ctl->prior[d] = pr.v[d];
     if (d >= 9) return;
@@ -2323,20 +2345,46 @@ __global__ __launch_bounds__(kBlock) void k_fine_build(const double *__restrict_
 // BT = 256: one block of list slots (rounds 3-4).  BT = 512 / 1024 ("wide", round 4): TWO / FOUR consecutive blocks of the list --
 // which the wide deal fills from one window -- share the CU's one 144-KB window with 8 / 16 waves, 2 / 4 per SIMD: a batch whose
 // survivors outnumber 256 CUs x 256 lanes then still steps in ONE round of blocks (k_deal_sorted, profiles/r04_roam_fill.txt)
-template <bool REV, int BT = kBlock>
-__global__ __launch_bounds__(BT) void k_step_roam(const StepArgs a, const ThrPrior pr)
+//
+// FEED (BT = 256 only, launched with 512 threads): thread BT + j is the FEEDER of thread j; wave 4 + g shares its SIMD with
+// stepping wave g, which alone leaves half of the SIMD's issue slots unused (one wave issues a vector instruction every
+// ~4 clocks and up, the SIMD one every 2).  The feeder computes the Philox blocks of its lanes -- the block index of a pair is
+// blk0 + it / 2, fixed per lane for the whole launch, whatever the track does -- and hands them over through a ring in LDS:
+// one 16-byte record per lane and TRIP (four pairs, one dword each: roam_pair_word), kFeedDepth trips deep, a tag per slot.
+//   feeder:   waits (bounded: s_sleep and look again) until trip n < read + kFeedDepth, writes the records of trip n, then
+//             the slot's tag = n.  Leaves at DONE, after a.steps / 8 trips, or when its idle polls run out.
+//   stepper:  reads slot and tag of trip n + 1 at the top of trip n (the LDS latency is off its chain), publishes
+//             read = n + 1, and takes trip n's uniforms from the record if its tag was n.  Any other tag: it computes the
+//             four blocks itself, as the kernel without feeders does.  It NEVER waits.  On every way out it publishes DONE.
+// The LDS executes one wave's operations in order, so tag-after-data on the feeder and tag-before-data on the stepper make
+// a record whose tag matches complete, and the stepper's `read` store follows its read of the slot it frees.
+constexpr int kFeedDepth = 3;                        // (the window leaves 16 KB: 4 waves x 3 slots x 1 KB + tags)
+constexpr uint32_t kFeedDone = 0xFFFFFFFFu, kFeedNoTag = 0xFFFFFFFFu;
+template <bool REV, int BT = kBlock, bool FEED = false>
+__global__ __launch_bounds__(FEED ? 2 * BT : BT) void k_step_roam(const StepArgs a, const ThrPrior pr)
 {
+    static_assert(!FEED || BT == kBlock, "feeder waves: narrow blocks only");
+    constexpr int NT = FEED ? 2 * BT : BT;           // threads of the block; BT: its list slots
     __shared__ uint32_t s_win[kWinRows * kWinCols];
     __shared__ int s_box[4];
     __shared__ int s_wid[BT / 64];
-    for (int q = threadIdx.x; q < kWinRows * kWinCols; q += BT) s_win[q] = 0u;
+    __shared__ uint4 s_ring[FEED ? (BT / 64) * kFeedDepth * 64 : 1];
+    __shared__ uint32_t s_tag[FEED ? (BT / 64) * kFeedDepth : 1];
+    __shared__ uint32_t s_read[BT / 64];             // per stepping wave: trips whose slot it has read, or kFeedDone
+    // (wave-uniform, and known to the compiler as such)
+    const bool feeder = FEED && __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x)) >= BT;
+    const uint32_t tid = feeder ? threadIdx.x - BT : threadIdx.x;    // the list slot of the thread, or of the thread it feeds
+    const int lane = threadIdx.x & 63, wv = static_cast<int>(tid >> 6);
+    for (int q = threadIdx.x; q < kWinRows * kWinCols; q += NT) s_win[q] = 0u;
     if (threadIdx.x == 0) { s_box[0] = s_box[1] = 0x7fffffff; s_box[2] = s_box[3] = -1; }
+    if (FEED && threadIdx.x < (BT / 64) * kFeedDepth) s_tag[threadIdx.x] = kFeedNoTag;
+    if (FEED && threadIdx.x < BT / 64) s_read[threadIdx.x] = 0u;
     __syncthreads();
     TrackCtl *ctl = a.ctl;
     const int in_slot = a.launch & 3, out_slot = (a.launch + 1) & 3;
     const uint32_t xcd = blockIdx.x % kXcd;
     const uint32_t nlive = ctl->count[in_slot][xcd];
-    const uint32_t il = (blockIdx.x / kXcd) * BT + threadIdx.x;
+    const uint32_t il = (blockIdx.x / kXcd) * BT + tid;
     const uint32_t i = xcd * a.cap + il;
     if (blockIdx.x == 0 && threadIdx.x < kXcd) ctl->count[(a.launch + 2) & 3][threadIdx.x] = 0;
 
@@ -2349,6 +2397,29 @@ __global__ __launch_bounds__(BT) void k_step_roam(const StepArgs a, const ThrPri
     live0 = live0 && s.k >= 0 && rc < 8u;                 // (every track has made its first move)
     rc &= 7u;
     int row = s.pos & 0xFFFF, col = (s.pos >> 16) & 0xFFFF;
+    int k = s.k;
+    // iterations [it_base, it_base + steps) of the batch; a lane steps while rel <= it < rel + span
+    // (see k_step_thr: rel is odd or 0, k - rel is even, one Philox block per even / odd pair)
+    const long long rel64 = (a.coherent ? static_cast<long long>(s.aux >> 9) : 0) + 1 - a.it_base;
+    const int rel = rel64 > 0x3fffffffLL ? 0x3fffffff : (rel64 < 0 ? 0 : static_cast<int>(rel64));
+    const long long left = a.max_k - k;
+    uint32_t span = !live0 ? 0u : (left > 0x3fffffffLL ? 0x3fffffffu : (left < 0 ? 0u : static_cast<uint32_t>(left)));
+    const int blk0 = (k - rel) >> 1;
+    const unsigned long long track = a.track_base + static_cast<unsigned long long>(t);
+    // the block index of pair `p` of the launch (it = 2 p), as every path forms it
+    auto blk_of = [&](const int p) __attribute__((always_inline)) {
+        return static_cast<unsigned long long>(static_cast<uint32_t>(blk0 + p));
+    };
+    // ---- the feeder's side of the ring: the four pairs of trip n (it = 8 n ... 8 n + 7) of its lanes, then the tag
+    const uint32_t ntrips = static_cast<uint32_t>(a.steps) >> 3;
+    auto feed_trip = [&](const uint32_t n) __attribute__((always_inline)) {
+        const int p = 4 * static_cast<int>(n);
+        const uint4 r = make_uint4(roam_pair_word(a.seed, track, blk_of(p)), roam_pair_word(a.seed, track, blk_of(p + 1)),
+                                   roam_pair_word(a.seed, track, blk_of(p + 2)), roam_pair_word(a.seed, track, blk_of(p + 3)));
+        const uint32_t slot = static_cast<uint32_t>(wv * kFeedDepth) + n % static_cast<uint32_t>(kFeedDepth);
+        s_ring[slot * 64u + static_cast<uint32_t>(lane)] = r;
+        if (lane == 0) __hip_atomic_store(&s_tag[slot], n, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
     // the block's histogram window: as in k_step_thr<6> (the window the sort filled this block from; the
     // bounding box of its tracks otherwise)
     int win_r0 = 0, win_c0 = 0;
@@ -2374,7 +2445,7 @@ __global__ __launch_bounds__(BT) void k_step_roam(const StepArgs a, const ThrPri
             const unsigned long long lm = __ballot(wid != 0x7fffffff);
             wid = lm ? __shfl(wid, __ffsll(static_cast<long long>(lm)) - 1) : 0x7fffffff;
         }
-        if ((threadIdx.x & 63) == 0) s_wid[threadIdx.x >> 6] = wid;
+        if (lane == 0) s_wid[wv] = wid;                   // (a feeder wave: what its stepping wave writes)
         __syncthreads();
         wid = 0x7fffffff;
         for (int q = BT / 64 - 1; q >= 0; --q) wid = s_wid[q] != 0x7fffffff ? s_wid[q] : wid;
@@ -2385,6 +2456,12 @@ __global__ __launch_bounds__(BT) void k_step_roam(const StepArgs a, const ThrPri
         const bool placed = wid != 0x7fffffff;
         __syncthreads();
         if (!placed && !fits && threadIdx.x == 0) { s_box[0] = r_lo; s_box[1] = c_lo; s_box[2] = r_hi; s_box[3] = c_hi; }
+        // priming: the first kFeedDepth trips are in the ring before any stepping wave looks (launches of two trips exist)
+        if (feeder && __any(live0 && span != 0u)) {
+#pragma unroll 1
+            for (uint32_t n = 0; n < static_cast<uint32_t>(kFeedDepth) && n < ntrips; ++n)
+                if (a.roam_feed != 2 || !(n & 1u)) feed_trip(n);
+        }
         __syncthreads();
         if (s_box[2] >= 0) {
             win_r0 = (s_box[0] + s_box[2] + 1 - kWinRows) / 2;
@@ -2394,15 +2471,32 @@ __global__ __launch_bounds__(BT) void k_step_roam(const StepArgs a, const ThrPri
     const char *pair = reinterpret_cast<const char *>(a.roam);
     const uint32_t ucols = static_cast<uint32_t>(a.cols);
     const uint32_t last_cell = static_cast<uint32_t>(a.rows) * ucols - 1u;
-    int k = s.k;
-    // iterations [it_base, it_base + steps) of the batch; a lane steps while rel <= it < rel + span
-    // (see k_step_thr: rel is odd or 0, k - rel is even, one Philox block per even / odd pair)
-    const long long rel64 = (a.coherent ? static_cast<long long>(s.aux >> 9) : 0) + 1 - a.it_base;
-    const int rel = rel64 > 0x3fffffffLL ? 0x3fffffff : (rel64 < 0 ? 0 : static_cast<int>(rel64));
-    const long long left = a.max_k - k;
-    uint32_t span = !live0 ? 0u : (left > 0x3fffffffLL ? 0x3fffffffu : (left < 0 ? 0u : static_cast<uint32_t>(left)));
-    const int blk0 = (k - rel) >> 1;
-    const unsigned long long track = a.track_base + static_cast<unsigned long long>(t);
+    // ---- the feeder's main loop (its first kFeedDepth trips are in the ring already).  Behind it the feeder holds no
+    // track: it runs through the stepper's code as a wave without live lanes, to the barriers of the epilogue
+    if (feeder) {
+        if (__any(live0 && span != 0u)) {
+            uint32_t n = ntrips < static_cast<uint32_t>(kFeedDepth) ? ntrips : static_cast<uint32_t>(kFeedDepth);
+            // The only wait of the hand-over, and it is bounded: a trip of the stepping wave lasts about three naps
+            // of 1024 clocks; at eight times that many idle looks the feeder gives up (the stepping wave goes on with
+            // its own Philox)
+            uint32_t naps = 1024u + 3u * static_cast<uint32_t>(a.steps);
+            while (n < ntrips) {
+                const uint32_t rd = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(
+                    __hip_atomic_load(&s_read[wv], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP))));
+                if (rd == kFeedDone) break;
+                if (n >= rd + static_cast<uint32_t>(kFeedDepth)) {          // (rd <= ntrips: no wrap)
+                    if (naps-- == 0u) break;
+                    __builtin_amdgcn_s_sleep(16);
+                    continue;
+                }
+                if (n <= rd) { n = rd + 1u; continue; }                     // overtaken: the slots up to trip rd have been read
+                if (a.roam_feed != 2 || !(n & 1u)) feed_trip(n);
+                ++n;
+            }
+        }
+        live0 = false;
+        span = 0u;
+    }
     const char *tab = reinterpret_cast<const char *>(a.table);
     const uint32_t psh = static_cast<uint32_t>(a.plane_shift);
     const uint32_t rev_e = pr.rev_e;
@@ -2511,9 +2605,12 @@ __global__ __launch_bounds__(BT) void k_step_roam(const StepArgs a, const ThrPri
     int it = 0;
     uint32_t n_pairs = 0, n_slow = 0;                         // wave-uniform
     const unsigned long long t_begin = a.debug_roam ? __builtin_amdgcn_s_memtime() : 0ull;
-    auto one_pair = [&]() __attribute__((always_inline)) {
-        const uint4 w4 = philox_block_b3(a.seed, track, static_cast<unsigned long long>(static_cast<uint32_t>(blk0 + (it >> 1))));
-        const uint32_t ufa = w4.x >> 16, ufb = w4.z >> 16;
+    // (given: the pair's two uniforms come in `uf`, packed as roam_pair_word packs them; the slow path, which wants all
+    // four words, then computes the block after all)
+    auto one_pair = [&](const uint32_t uf, const bool given) __attribute__((always_inline)) {
+        uint4 w4 = make_uint4(0u, 0u, 0u, 0u);
+        if (!given) w4 = philox_block_b3(a.seed, track, blk_of(it >> 1));
+        const uint32_t ufa = given ? uf >> 16 : w4.x >> 16, ufb = given ? uf & 0xFFFFu : w4.z >> 16;
         const bool st_a = static_cast<uint32_t>(it - rel) < span, st_b = static_cast<uint32_t>(it + 1 - rel) < span;
         // (copies into locals before any select: see k_step_thr on selects of captured variables)
         const uint32_t q0 = E.x, qa = E.y, qb = E.z, qc = E.w;
@@ -2594,6 +2691,7 @@ __global__ __launch_bounds__(BT) void k_step_roam(const StepArgs a, const ThrPri
                 ++n_slow;
                 if (slow) {
                     if (fast) { row = win_r0 + wr; col = win_c0 + wc; }       // the state the lane stands on, as a cell again
+                    if (given) w4 = philox_block_b3(a.seed, track, blk_of(it >> 1));
 #pragma unroll 1
                     for (int h = 0; h < 2; ++h)
                         if (static_cast<uint32_t>(it + h - rel) < span) slow_step(h ? w4.z : w4.x, h ? w4.w : w4.y);
@@ -2612,6 +2710,22 @@ __global__ __launch_bounds__(BT) void k_step_roam(const StepArgs a, const ThrPri
     const uint32_t stop_stamp = static_cast<uint32_t>(a.launch) + 1u;
     uint32_t stop_seen = 0u;
     bool stopped = false;
+    // ---- the stepping wave's side of the ring: slot and tag of the coming trip, asked for a trip ahead.  The tag first:
+    // the LDS takes a wave's reads in order (the asm statements keep the compiler from caching or reordering them)
+    uint32_t fd_tag = kFeedNoTag, trip = 0u, fd_slot = 0u, n_fed = 0u;              // trip, fd_slot, n_fed: wave-uniform
+    uint4 fd_rec = make_uint4(0u, 0u, 0u, 0u);
+    auto feed_read = [&]() __attribute__((always_inline)) {
+        const uint32_t slot = static_cast<uint32_t>(wv * kFeedDepth) + fd_slot;
+        asm volatile("" ::: "memory");
+        fd_tag = __hip_atomic_load(&s_tag[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        asm volatile("" ::: "memory");
+        fd_rec = s_ring[slot * 64u + static_cast<uint32_t>(lane)];
+        asm volatile("" ::: "memory");
+    };
+    if (FEED && !feeder) {
+        feed_read();
+        __builtin_amdgcn_s_setprio(1);               // the SIMD's issue slots to the stepping wave first
+    }
     for (; it + 8 <= a.steps; ) {
         // (one scalar test per trip; the flag as it was one trip ago: its load is never waited for on its own)
         // (a wave with a lane that still waits for its release runs the launch out: the host counts a.steps
@@ -2621,12 +2735,38 @@ __global__ __launch_bounds__(BT) void k_step_roam(const StepArgs a, const ThrPri
                               static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(stop_seen))) == stop_stamp;
         if (((stepping | waiting) == 0ull) | stop_now) { stopped = stop_now; break; }
         if (a.roam_stop) stop_seen = __hip_atomic_load(&ctl->roam_stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (FEED) {
+            // (a feeder never comes here: none of its lanes steps or waits)
+            const bool fed = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(fd_tag))) == trip;
+            uint4 rec = fd_rec;
+            // this trip's slot is read -- the feeder may fill it again -- and the next trip's is asked for
+            ++trip;
+            if (lane == 0) __hip_atomic_store(&s_read[wv], trip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            fd_slot = fd_slot + 1u == static_cast<uint32_t>(kFeedDepth) ? 0u : fd_slot + 1u;
+            feed_read();
+            if (!fed) {
+                const int p = it >> 1;
+                rec = make_uint4(roam_pair_word(a.seed, track, blk_of(p)), roam_pair_word(a.seed, track, blk_of(p + 1)),
+                                 roam_pair_word(a.seed, track, blk_of(p + 2)), roam_pair_word(a.seed, track, blk_of(p + 3)));
+            }
+            n_fed += fed ? 4u : 0u;
+            one_pair(rec.x, true);
+            one_pair(rec.y, true);
+            one_pair(rec.z, true);
+            one_pair(rec.w, true);
+        } else {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) one_pair();
+            for (int u = 0; u < 4; ++u) one_pair(0u, false);
+        }
     }
     for (; it < a.steps && !stopped; ) {                     // a.steps is even (host)
         if (!__any(static_cast<uint32_t>(it - rel) < span || (it < rel && span != 0u))) break;
-        one_pair();
+        one_pair(0u, false);
+    }
+    if (FEED && !feeder) {
+        // every way out of the two loops comes by here: the stop flag, nothing left to step, the steps run out
+        __builtin_amdgcn_s_setprio(0);
+        if (lane == 0) __hip_atomic_store(&s_read[wv], kFeedDone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     if (a.roam_stop && !stopped && it >= a.steps && (threadIdx.x & 63) == 0) atomicMax(&ctl->roam_stop, stop_stamp);
     if (fast) { row = win_r0 + wr; col = win_c0 + wc; }
@@ -2638,6 +2778,8 @@ __global__ __launch_bounds__(BT) void k_step_roam(const StepArgs a, const ThrPri
     }
     if ((threadIdx.x & 63) == 0 && n_pairs) {
         atomicAdd(&ctl->roam_pairs, static_cast<unsigned long long>(n_pairs));
+        atomicAdd(&ctl->roam_own, static_cast<unsigned long long>(n_pairs - n_fed));
+        if (n_fed) atomicAdd(&ctl->roam_fed, static_cast<unsigned long long>(n_fed));
         if (n_slow) atomicAdd(&ctl->roam_slow, static_cast<unsigned long long>(n_slow));
         if (a.debug_roam) {
             const unsigned long long dt = __builtin_amdgcn_s_memtime() - t_begin;
@@ -2649,7 +2791,7 @@ __global__ __launch_bounds__(BT) void k_step_roam(const StepArgs a, const ThrPri
     }
 #ifdef SSRS_DEBUG_WAVE_DUMP
     // (diagnostic build only, tools/dev/r03_wave_dump.sh: one record per wave of ONE launch)
-    if (a.debug_roam && a.launch == SSRS_DEBUG_WAVE_DUMP && a.dbg_buf) {
+    if (a.debug_roam && a.launch == SSRS_DEBUG_WAVE_DUMP && a.dbg_buf && !feeder) {
         const unsigned long long dt = __builtin_amdgcn_s_memtime() - t_begin;
         const int lanes = __popcll(__ballot(live0));
         uint32_t wst = win_stray;
@@ -2663,7 +2805,7 @@ __global__ __launch_bounds__(BT) void k_step_roam(const StepArgs a, const ThrPri
     }
 #endif
     __syncthreads();
-    for (int q = threadIdx.x; q < kWinRows * kWinCols; q += BT) {
+    for (int q = threadIdx.x; q < kWinRows * kWinCols; q += NT) {
         const uint32_t n = s_win[q];
         if (n) atomicAdd(&a.hist[static_cast<uint32_t>(win_r0 + q / kWinCols) * ucols + static_cast<uint32_t>(win_c0 + q % kWinCols)], n);
     }
@@ -2680,9 +2822,8 @@ __global__ __launch_bounds__(BT) void k_step_roam(const StepArgs a, const ThrPri
     }
     // one reservation per block, every lane keeps its slot, the dead leave tombstones (k_step_thr<6>)
     __shared__ uint32_t s_surv[BT / 64 + 1];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int nsurv = __popcll(__ballot(active));
-    if (lane == 0) s_surv[wv] = static_cast<uint32_t>(nsurv);
+    if (lane == 0 && !feeder) s_surv[wv] = static_cast<uint32_t>(nsurv);
     __syncthreads();
     if (threadIdx.x == 0) {
         uint32_t tot = 0;
@@ -2691,8 +2832,8 @@ __global__ __launch_bounds__(BT) void k_step_roam(const StepArgs a, const ThrPri
     }
     __syncthreads();
     const uint32_t basei = s_surv[BT / 64];
-    if (basei != 0xFFFFFFFFu) {
-        a.list_out[xcd * a.cap + basei + threadIdx.x] = active ? t : -1;
+    if (basei != 0xFFFFFFFFu && !feeder) {
+        a.list_out[xcd * a.cap + basei + tid] = active ? t : -1;
         if (active) {
             TrackState o;
             o.pos = static_cast<int32_t>((static_cast<uint32_t>(row) & 0xFFFFu) | (static_cast<uint32_t>(col) << 16));
@@ -3782,6 +3923,26 @@ extern "C" int ssrs_transition_thr_build(const double *updraft, const float *pot
     return SSRS_OK;
 }
 
+extern "C" int ssrs_roam_pair_word_selftest(uint64_t seed, const uint64_t *track, const uint64_t *block,
+                                            uint32_t *packed, uint32_t *words, size_t n, void *stream)
+{
+    SSRS_REQUIRE(track && block && packed && words, "ssrs_roam_pair_word_selftest: NULL pointer");
+    if (n == 0) return SSRS_OK;
+    hipLaunchKernelGGL(k_roam_pair_word_selftest, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256),
+                       0, as_stream(stream), seed, track, block, packed, words, n);
+    SSRS_HIP_CHECK(hipGetLastError());
+    return SSRS_OK;
+}
+
+// fed / own wave-pairs of the calling thread's last ssrs_tracks_simulate* call (SsrsTrackStats keeps its layout)
+static thread_local int64_t g_roam_fed = 0, g_roam_own = 0;
+
+extern "C" void ssrs_tracks_roam_feed_counts(int64_t *fed, int64_t *own)
+{
+    if (fed) *fed = g_roam_fed;
+    if (own) *own = g_roam_own;
+}
+
 extern "C" int ssrs_uniform_selftest(uint64_t seed, const uint64_t *track, const uint64_t *step,
                                      double *out, size_t n, void *stream)
 {
@@ -3820,6 +3981,9 @@ struct TrackSwitches {
     long long roam_wide_from;
     int roam_width;              // SSRS_TRACKS_ROAM_WIDTH=1|2|4: that width at every deal (A/B); 0: chosen
     int roam_shuffle;            // batches between two shuffles of a settled roaming batch (SSRS_TRACKS_ROAM_SHUFFLE, 0: never)
+    int roam_shuffle_fed;        // ... while its blocks are narrow and step with feeder waves
+    int roam_feed;               // SSRS_TRACKS_ROAM_FEED: narrow roaming launches with feeder waves (unset, 1: on; 0: off; 2: the feeders
+                                 // skip every odd trip -- tests: fed trips and the stepping wave's own Philox alternate)
 };
 
 static TrackSwitches read_track_switches()
@@ -3841,8 +4005,18 @@ static TrackSwitches read_track_switches()
     if (const char *e = std::getenv("SSRS_TRACKS_ROAM_WIDE")) sw.roam_wide_from = std::atoll(e);
     sw.roam_width = 0;
     if (const char *e = std::getenv("SSRS_TRACKS_ROAM_WIDTH")) { const int w = std::atoi(e); if (w == 1 || w == 2 || w == 4) sw.roam_width = w; }
+    sw.roam_feed = 1;
+    if (const char *e = std::getenv("SSRS_TRACKS_ROAM_FEED")) { const int f = std::atoi(e); if (f == 0 || f == 2) sw.roam_feed = f; }
+    // (a forced wide width is the A/B of the kernels without feeders: the narrow launches such a call still makes, those
+    // before its first deal, run without them too)
+    if (sw.roam_width > 1) sw.roam_feed = 0;
+    // Every 16 batches (round 3) -- but every 4 while the deal is narrow and its launches have feeder waves: a block's pair
+    // time then follows its CU's live lanes (620 to 720 clocks where every wave took ~757) and a launch ends with its
+    // fastest wave, so the tracks of the slower blocks fell behind between two shuffles and the pass grew a tail of 20
+    // nearly empty launches (profiles/roam_feed.md)
     sw.roam_shuffle = 16;
-    if (const char *e = std::getenv("SSRS_TRACKS_ROAM_SHUFFLE")) sw.roam_shuffle = std::atoi(e);
+    sw.roam_shuffle_fed = sw.roam_feed ? 4 : 16;
+    if (const char *e = std::getenv("SSRS_TRACKS_ROAM_SHUFFLE")) sw.roam_shuffle = sw.roam_shuffle_fed = std::atoi(e);
     return sw;
 }
 
@@ -4051,6 +4225,7 @@ int TrackRun::plan_and_init()
     a.thr = ws.thr;
     a.wander = ws.wander;
     a.debug_roam = sw.debug_roam ? 1 : 0;
+    a.roam_feed = sw.roam_feed;
     a.roam_stop = sw.roam_stop ? 1 : 0;
     a.dbg_buf = nullptr;
 #ifdef SSRS_DEBUG_WAVE_DUMP
@@ -4163,7 +4338,7 @@ int TrackRun::choose_front_path()
     a.v16_offset = geom.offset;
 
     pol.thr = thr; pol.tiles_ok = tiles_ok; pol.cache_ok = cache_ok; pol.never_scattered = never_scattered;
-    pol.front = a.pf_dir != 0; pol.may_rebalance = sw.rebalance; pol.debug = sw.debug; pol.roam_shuffle = sw.roam_shuffle;
+    pol.front = a.pf_dir != 0; pol.may_rebalance = sw.rebalance; pol.debug = sw.debug; pol.roam_shuffle = sw.roam_shuffle_fed;   // (narrow until a deal says otherwise)
     pol.ntracks = ntracks; pol.crossing = p->rows + p->cols;
     pol.binning_on = binning_on; pol.tiles_on = tiles_on; pol.scattered = scattered;
     pol.cached = cache_ok && scattered;
@@ -4281,6 +4456,10 @@ void TrackRun::launch_stepper(bool first_move, bool v16, unsigned blocks, int Sl
                             if (rev) hipLaunchKernelGGL((k_step_roam<true, 4 * kBlock>), dim3(wblocks), dim3(bt), 0, st, a, thr_prior);
                             else hipLaunchKernelGGL((k_step_roam<false, 4 * kBlock>), dim3(wblocks), dim3(bt), 0, st, a, thr_prior);
                         }
+                    } else if (a.roam_feed) {
+                        // a feeder wave beside every stepping wave: 512 threads on the block's 256 list slots
+                        if (rev) hipLaunchKernelGGL((k_step_roam<true, kBlock, true>), dim3(blocks), dim3(2 * kBlock), 0, st, a, thr_prior);
+                        else hipLaunchKernelGGL((k_step_roam<false, kBlock, true>), dim3(blocks), dim3(2 * kBlock), 0, st, a, thr_prior);
                     } else if (rev) hipLaunchKernelGGL(k_step_roam<true>, dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
                     else hipLaunchKernelGGL(k_step_roam<false>, dim3(blocks), dim3(kBlock), 0, st, a, thr_prior);
 #ifdef SSRS_DEBUG_WAVE_DUMP
@@ -4303,9 +4482,11 @@ void TrackRun::launch_stepper(bool first_move, bool v16, unsigned blocks, int Sl
                         (void)hipStreamSynchronize(st);
                         memcpy(&cb, &host_counts[kFinalSlot], sizeof(TrackCtl));
                         if (cb.dbg_waves)
-                            fprintf(stderr, "[roam] launch %d blocks %u Sl %d: %llu waves, mean %.0f clk, max %.0f clk (x%.2f); slowest-by-slow-pairs wave: %llu of %llu pairs slow\n",
+                            fprintf(stderr, "[roam] launch %d blocks %u Sl %d: %llu waves, mean %.0f clk, max %.0f clk (x%.2f); slowest-by-slow-pairs wave: %llu of %llu pairs slow; "
+                                    "wave-pairs so far %llu, fed %llu\n",
                                     launch, blocks, Sl, cb.dbg_waves, static_cast<double>(cb.dbg_tsum) / cb.dbg_waves, static_cast<double>(cb.dbg_tmax),
-                                    static_cast<double>(cb.dbg_tmax) * cb.dbg_waves / static_cast<double>(cb.dbg_tsum), cb.dbg_slowmax >> 32, cb.dbg_slowmax & 0xFFFFFFFFull);
+                                    static_cast<double>(cb.dbg_tmax) * cb.dbg_waves / static_cast<double>(cb.dbg_tsum), cb.dbg_slowmax >> 32, cb.dbg_slowmax & 0xFFFFFFFFull,
+                                    cb.roam_pairs, cb.roam_fed);
                         (void)hipMemsetAsync(&ws.ctl->dbg_tsum, 0, 4 * sizeof(unsigned long long), st);
                     }
                     return;
@@ -4425,6 +4606,7 @@ int TrackRun::wander_sort()
         }
         if (sw.roam_width) roam_width = sw.roam_width;
     }
+    pol.roam_shuffle = roam_width > 1 ? sw.roam_shuffle : sw.roam_shuffle_fed;
     hipLaunchKernelGGL(k_deal_sorted, dim3(64), dim3(1024), 0, st, k1, sorted, ws.list[(launch + 1) & 1], ws.ctl,
                        (launch + 1) & 3, (launch + 2) & 3, ws.cap, sw.deal_contiguous ? 1 : 0, roam_width);
     ++launch;
@@ -4617,6 +4799,8 @@ int TrackRun::finish(int rc, SsrsTrackStats *stats)
         hipStreamSynchronize(st) != hipSuccess)
         return set_error(SSRS_ERR_HIP, "final read-back failed");
     memcpy(&host_ctl, &host_counts[kFinalSlot], sizeof(TrackCtl));
+    g_roam_fed = static_cast<int64_t>(host_ctl.roam_fed);
+    g_roam_own = static_cast<int64_t>(host_ctl.roam_own);
     if (stats) {
         stats->total_steps = static_cast<int64_t>(host_ctl.steps);
         stats->launches = launch;
@@ -4668,6 +4852,7 @@ static int tracks_simulate_impl(const TrackCall &c, SsrsTrackStats *stats)
     int rc = check_track_args(c);
     if (rc != SSRS_OK) return rc;
     if (stats) *stats = SsrsTrackStats{};
+    g_roam_fed = g_roam_own = 0;
     if (SsrsTrajRecorder *rec = c.rec) {
         rec->used = 0;
         rec->chunks.clear();

@@ -461,6 +461,8 @@ def simulate_tracks(move_dirn, starts, grid_shape, memory_parameter=1,
             nat.ptr(lengths), nat.ptr(ws), C.c_size_t(ws_bytes), C.byref(stats), stream_ptr()))
     elif not want_tracks:
         run(hist, None, None)
+    roam_fed, roam_own = C.c_int64(0), C.c_int64(0)      # of this thread's last stepper call, the one `stats` describes
+    nat.lib().ssrs_tracks_roam_feed_counts(C.byref(roam_fed), C.byref(roam_own))
     return TrackBatch(lengths, ends, hist, traj, offsets, replay=replay, stats=
                       dict(total_steps=int(stats.total_steps), launches=int(stats.launches),
                            kernel_ms=float(stats.kernel_ms), wall_ms=float(stats.wall_ms),
@@ -477,6 +479,7 @@ def simulate_tracks(move_dirn, starts, grid_shape, memory_parameter=1,
                            roam_fine_settled=int(stats.reserved0),
                            roam_wave_pairs=int(stats.roam_wave_pairs),
                            roam_slow_wave_pairs=int(stats.roam_slow_wave_pairs),
+                           roam_fed_wave_pairs=int(roam_fed.value), roam_own_wave_pairs=int(roam_own.value),
                            roam_shuffles=int(stats.roam_shuffles),
                            roam_wide_launches=int(stats.roam_wide_launches)))
 
@@ -504,6 +507,21 @@ def uniforms(seed, track, step):
         C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), nat.ptr(tr), nat.ptr(sp), nat.ptr(out),
         C.c_size_t(tr.numel()), stream_ptr()))
     return out.cpu().numpy()
+
+
+def roam_pair_words(seed, track, block):
+    """The roaming stepper's hand-over word of each (track, Philox block) and the block's four words as rocRAND's engine
+    gives them: (packed uint32 (n,), words uint32 (n, 4)), evaluated on the device."""
+    tr = to_dev(np.asarray(track, dtype=np.uint64).view(np.int64), torch.int64).reshape(-1)
+    bk = to_dev(np.asarray(block, dtype=np.uint64).view(np.int64), torch.int64).reshape(-1)
+    if tr.numel() != bk.numel():
+        raise ValueError('track and block lengths differ')
+    packed = torch.empty(tr.numel(), dtype=torch.int32, device=tr.device)
+    words = torch.empty((tr.numel(), 4), dtype=torch.int32, device=tr.device)
+    nat.check(nat.lib().ssrs_roam_pair_word_selftest(
+        C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), nat.ptr(tr), nat.ptr(bk), nat.ptr(packed), nat.ptr(words),
+        C.c_size_t(tr.numel()), stream_ptr()))
+    return packed.cpu().numpy().view(np.uint32), words.cpu().numpy().view(np.uint32)
 
 
 # ---------------------------------------------------------------- re-exports
