@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define SSRS_VERSION 108 /* 0.1.8 */
+#define SSRS_VERSION 109 /* 0.1.9 */
 
 #define SSRS_OK 0
 #define SSRS_ERR_INVALID (-1) /* bad argument (message says which) */
@@ -890,6 +890,16 @@ int ssrs_uniform_selftest(uint64_t seed, const uint64_t *track,
 int ssrs_roam_pair_word_selftest(uint64_t seed, const uint64_t *track,
                                  const uint64_t *block, uint32_t *packed,
                                  uint32_t *words, size_t n, void *stream);
+
+/* The roaming regime's tables for a raster, built by the very launches ssrs_tracks_simulate uses when a batch
+ * starts to roam.  thr: the table of ssrs_transition_thr_build for the same updraft / potential / prior.
+ * pair_out: rows*cols*8 entries of 16 bytes (e0, ea, eb, ec), state = cell*8 + last move;
+ * fine_out: rows*cols*8 entries of 8 bytes (t1, t2).
+ * prior_words [host], 38 uint32 or NULL: ThrPrior zero_e[8], reversal, thr9[9], rev_ok, rev_rc, rev_e, then
+ * FinePrior zero_t1[8], zero_t2[8], reversal.
+ * rows, cols >= 3, rows*cols <= 2^25.  Asynchronous on `stream`. */
+int ssrs_roam_tables_selftest(const double *updraft, const float *potential, const double *prior, const float *thr,
+                              int rows, int cols, void *pair_out, void *fine_out, uint32_t *prior_words, void *stream);
 
 /* Wave-pairs of the roaming stepper in the calling thread's last
  * ssrs_tracks_simulate* call (host values, thread-local; either may be NULL):

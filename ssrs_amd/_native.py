@@ -55,7 +55,7 @@ EXPORTS = (
     'ssrs_projection_init_albers', 'ssrs_warp_lonlat_raster',
     'ssrs_allen_workspace_bytes', 'ssrs_allen_thermal_field',
     'ssrs_track_occupancy_workspace_bytes', 'ssrs_track_occupancy',
-    'ssrs_roam_pair_word_selftest', 'ssrs_tracks_roam_feed_counts',
+    'ssrs_roam_pair_word_selftest', 'ssrs_tracks_roam_feed_counts', 'ssrs_roam_tables_selftest',
 )
 
 
@@ -210,6 +210,7 @@ def lib():
         L.ssrs_track_occupancy_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
         L.ssrs_track_occupancy.argtypes = OCCUPANCY_ARGTYPES
         L.ssrs_roam_pair_word_selftest.argtypes = [C.c_uint64] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
+        L.ssrs_roam_tables_selftest.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 4
         L.ssrs_tracks_roam_feed_counts.restype = None
         L.ssrs_tracks_roam_feed_counts.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         _lib = L

@@ -1467,7 +1467,7 @@ __device__ __forceinline__ void split_cell(uint32_t c, uint32_t cols, double inv
 // and a step is: one 4-byte gather, two integer subtractions from the top 16 bits of the uniform,
 // two sign bits -> the chosen cell.  |T - 2^16 cdf_k/cdf_8| <= 0.55 (rounding 0.5; the builder's
 // f32 arithmetic 6e-7 relative = 0.04 units; the reference's normalise-twice sequence
-// 1e-15; the clamp only matters where
+// 1e-15; measured state by state against the oracle: 0.508, profiles/table_margins.md; the clamp only matters where
 // the uniform's top bits are 65534 / 65535, which the band covers) and the uniform's top 16 bits
 // ufi satisfy ufi <= 2^16 u < ufi + 1, so ufi - T >= 1 means cdf_k/cdf_8 <= u and ufi - T <= -2
 // means it is not (0.45 units of margin either way): the decision is the reference's unless ufi - T is -1 or 0 (3e-5 per boundary),
@@ -1486,6 +1486,8 @@ __device__ __forceinline__ void split_cell(uint32_t c, uint32_t cols, double inv
 // Eight planes (one per last move) of 4-byte entries: neighbouring tracks gather from the same
 // few cache lines (32 cells per 128-byte line), which is what the CU's address unit charges for.
 constexpr uint32_t kThrPoison = 0x0000FFFFu, kThrBoundary = 0x0001FFFFu, kThrReversal = 0x0002FFFFu;
+// staged "reciprocals" of updrafts beyond the f32 builder's reach (k_transition_thr): negative, told apart by size
+constexpr float kThrBigUpdraft = -5.9604645e-28f, kThrInfUpdraft = -2.9802322e-28f;
 
 // The table is eight planes (one per last move rc) of 4-byte entries, plane p at byte offset
 // p << thr_plane_shift: a power-of-two stride makes a step's address one shift-or
@@ -1519,8 +1521,12 @@ struct ThrPrior {
 // of the reference's boundary (the band above), i.e. 7e-6 in probability, and an f32 weight is
 // good to 3e-7 relative (v_rcp_f32 is 1 ulp).  What f32 cannot represent goes to the exact
 // sequence instead (a poisoned entry):
-//   * an updraft above 1e20 (v_rcp_f32 flushes denormal results): its reciprocal is staged as NaN,
-//     which poisons the nine cells around it;
+//   * an updraft above 1e20 (v_rcp_f32 flushes denormal results): it is staged as a NEGATIVE placeholder of the size of
+//     1e20's reciprocal (kThrBigUpdraft; kThrInfUpdraft for +inf, whose own cell has an infinite centre weight and is
+//     poisoned whole).  The weights of the nine cells around it then have the right signs and the right zeros but not
+//     the right sizes: their rows are poisoned unless all three weights are zero -- a zero row and a reversal are what
+//     they are in f64 whatever the sizes (tests/test_gpu_tables.py, the poison field: such rows used to be poisoned too,
+//     safe but not what the table's classes say);
 //   * a NaN / infinite weight anywhere in the window (the reference's own rule for NaN,
 //     movmodel.py:228-230; f32 overflow joins it): the sum of the eight raw weights is not finite;
 //   * a row whose total leaves [1e-30, 1e30] (denormal weights have large RELATIVE errors; the
@@ -1555,13 +1561,16 @@ __global__ __launch_bounds__(kBlock) void k_transition_thr(
         float2 c;
 #ifdef SSRS_PROBE_K2A_NOLOAD
         const float v = 1.0f + (g & 255);
+        const double vd = v;
         c.y = HASPOT ? 1000.f - (g & 1023) : 0.f;
 #else
-        const float v = static_cast<float>(updraft[g]);
+        const double vd = updraft[g];
+        const float v = static_cast<float>(vd);
         c.y = HASPOT ? potential[g] : 0.f;
 #endif
         const float w = fmaxf(v, 1e-06f);                    // clip(min=1e-6); NaN is restored below
-        c.x = (v <= 1e20f) ? __builtin_amdgcn_rcpf(w) * 5.9604645e-08f : __builtin_nanf("");
+        const float out_of_reach = vd != vd ? __builtin_nanf("") : (vd > 1.7e308 ? kThrInfUpdraft : kThrBigUpdraft);
+        c.x = (v <= 1e20f) ? __builtin_amdgcn_rcpf(w) * 5.9604645e-08f : out_of_reach;
         s_cell[i] = c;
     }
     __syncthreads();
@@ -1579,11 +1588,13 @@ __global__ __launch_bounds__(kBlock) void k_transition_thr(
         float w[9];
         const float2 cc = s_cell[lr * LW + lc];
         float sum = 0.f;                                     // not finite <=> some raw weight (or the centre) is not
+        bool big = cc.x < 0.f;                               // an updraft above 1e20 in the window: signs only
 #pragma unroll
         for (int j = 0; j < 9; ++j) {
             if (j == 4) continue;
             const float2 cq = s_cell[(lr + dr_of(j)) * LW + lc + dc_of(j)];
-            float v = __builtin_amdgcn_rcpf(cc.x + cq.x);    // 2^23 x harmonic mean
+            big |= cq.x < 0.f;
+            float v = __builtin_amdgcn_rcpf(fabsf(cc.x) + fabsf(cq.x));    // 2^23 x harmonic mean
             if (HASPOT) {
                 const float d = cc.y - cq.y;
                 v *= (j & 1) ? d : d * SSRS_NINV_DIAG;       // d x ninv stays f32 in the reference as well
@@ -1591,7 +1602,7 @@ __global__ __launch_bounds__(kBlock) void k_transition_thr(
             sum += v;
             w[j] = fmaxf(v, 0.f);                            // clip(min=0)
         }
-        const bool bad = !(fabsf(sum) <= 3e38f);
+        const bool bad = !(fabsf(sum) <= 3e38f) | (cc.x == kThrInfUpdraft);   // (an infinite centre: its own weight is not finite)
         const bool ovr = bad | !interior;
         const uint32_t ovr_e = interior ? kThrPoison : kThrBoundary;
 #pragma unroll
@@ -1604,7 +1615,7 @@ __global__ __launch_bounds__(kBlock) void k_transition_thr(
             const auto pk = __builtin_amdgcn_cvt_pknorm_u16(w[ka] * r, ab * r); // T1 | T2 << 16, T1 <= T2
             uint32_t e = __builtin_bit_cast(uint32_t, pk);
             // as integers: 1e-30 <= tot <= 1e30 (tot >= 0 or NaN)
-            const bool fine = (__float_as_uint(tot) - 0x0DA24260u) <= (0x7149F2CAu - 0x0DA24260u);
+            const bool fine = !big & ((__float_as_uint(tot) - 0x0DA24260u) <= (0x7149F2CAu - 0x0DA24260u));
             e = fine ? e : kThrPoison;
             asm volatile("" : "+v"(e));                      // or the compiler branches around the six lines above
             e = (tot == 0.f) ? zero_row[rc] : e;
@@ -3923,6 +3934,26 @@ extern "C" int ssrs_transition_thr_build(const double *updraft, const float *pot
     return SSRS_OK;
 }
 
+// The roaming regime's tables: the pair table of the whole raster from the threshold table `tab` (planes behind `guard`
+// bytes, plane_shift apart), and, where fine_out is given, the fine table of the near-ties from the raw fields.  The one
+// launch site of both builders: the run (TrackRun::build_roam_tables) and ssrs_roam_tables_selftest come through here.
+static void launch_roam_tables(const void *tab, uint32_t guard, int plane_shift, const ThrPrior &pr, bool rev, const FinePrior &fp,
+                               const double *updraft, const float *potential, int rows, int cols, RoamEntry *pair_out,
+                               FineEntry *fine_out, hipStream_t st)
+{
+    const char *tabc = reinterpret_cast<const char *>(tab);
+    const unsigned grid = 256 * 16;
+    if (rev) hipLaunchKernelGGL(k_roam_build<true>, dim3(grid), dim3(kBlock), 0, st, tabc, guard, plane_shift, rows, cols, pair_out, pr);
+    else hipLaunchKernelGGL(k_roam_build<false>, dim3(grid), dim3(kBlock), 0, st, tabc, guard, plane_shift, rows, cols, pair_out, pr);
+    if (fine_out) {
+        const int tx = (cols + kTabW - 1) / kTabW, ty = (rows + kTabH - 1) / kTabH, nt = tx * ty;
+        if (potential) hipLaunchKernelGGL(k_fine_build<true>, dim3(static_cast<unsigned>(nt)), dim3(kBlock), 0, st, updraft, potential,
+                                          fine_out, rows, cols, tx, nt, fp);
+        else hipLaunchKernelGGL(k_fine_build<false>, dim3(static_cast<unsigned>(nt)), dim3(kBlock), 0, st, updraft, potential,
+                                fine_out, rows, cols, tx, nt, fp);
+    }
+}
+
 extern "C" int ssrs_roam_pair_word_selftest(uint64_t seed, const uint64_t *track, const uint64_t *block,
                                             uint32_t *packed, uint32_t *words, size_t n, void *stream)
 {
@@ -4018,6 +4049,35 @@ static TrackSwitches read_track_switches()
     sw.roam_shuffle_fed = sw.roam_feed ? 4 : 16;
     if (const char *e = std::getenv("SSRS_TRACKS_ROAM_SHUFFLE")) sw.roam_shuffle = sw.roam_shuffle_fed = std::atoi(e);
     return sw;
+}
+
+// A reversal row steps as an ordinary row of last move rev_rc (k_step_thr's REV, k_roam_build<true>, k_step_roam<true>)
+static bool reversal_as_row(const ThrPrior &pr, const TrackSwitches &sw) { return pr.rev_ok != 0 && sw.rev; }
+
+extern "C" int ssrs_roam_tables_selftest(const double *updraft, const float *potential, const double *prior, const float *thr,
+                                         int rows, int cols, void *pair_out, void *fine_out, uint32_t *prior_words, void *stream)
+{
+    SSRS_REQUIRE(updraft && prior && thr && pair_out && fine_out, "ssrs_roam_tables_selftest: updraft/prior/thr/pair_out/fine_out is NULL");
+    SSRS_REQUIRE(rows >= 3 && cols >= 3, "ssrs_roam_tables_selftest: need rows, cols >= 3");
+    SSRS_REQUIRE(static_cast<size_t>(rows) * static_cast<size_t>(cols) <= kPairMaxCells,
+                 "ssrs_roam_tables_selftest: the pair table is addressed with 32-bit offsets (rows * cols <= 2^25)");
+    SSRS_REQUIRE((reinterpret_cast<uintptr_t>(thr) & 63u) == 0, "ssrs_roam_tables_selftest: thr must be 64-byte aligned");
+    SSRS_REQUIRE(((reinterpret_cast<uintptr_t>(pair_out) | reinterpret_cast<uintptr_t>(fine_out)) & 15u) == 0,
+                 "ssrs_roam_tables_selftest: pair_out and fine_out must be 16-byte aligned");
+    ThrPrior pr;
+    FinePrior fp;
+    prior_tables(prior, &pr);
+    fine_prior_tables(prior, &fp);
+    static_assert(sizeof(ThrPrior) == 21 * 4 && sizeof(FinePrior) == 17 * 4, "prior_words: 38 dwords");
+    if (prior_words) {
+        std::memcpy(prior_words, &pr, sizeof(pr));
+        std::memcpy(prior_words + 21, &fp, sizeof(fp));
+    }
+    launch_roam_tables(thr, static_cast<uint32_t>(thr_guard_bytes(cols)), thr_plane_shift(rows, cols), pr,
+                       reversal_as_row(pr, read_track_switches()), fp, updraft, potential, rows, cols,
+                       static_cast<RoamEntry *>(pair_out), static_cast<FineEntry *>(fine_out), as_stream(stream));
+    SSRS_HIP_CHECK(hipGetLastError());
+    return SSRS_OK;
 }
 
 static_assert(offsetof(TrackCtl, steps) == kSlotSteps * sizeof(uint32_t) &&
@@ -4315,7 +4375,7 @@ int TrackRun::choose_front_path()
     }
     // pair table (k_step_roam): built when the batch starts to roam; A/B switches SSRS_TRACKS_NO_ROAM_TABLE, SSRS_TRACKS_DEAL_ROUND_ROBIN
     roam_ok = cache_ok && ws.roam != nullptr && sw.roam_table;
-    rev = thr_prior.rev_ok != 0 && sw.rev;
+    rev = reversal_as_row(thr_prior, sw);
     // (the key arrays hold 2 n words >= the list slots; the coarse grid of k_wander_windows fits its LDS)
     wander_sort_ok = ntracks >= kWanderMinTracks &&
                      static_cast<long long>((p->rows + kBinRows - 1) / kBinRows) * ((p->cols + kBinCols - 1) / kBinCols) <= kWanderBins;
@@ -4618,22 +4678,10 @@ int TrackRun::wander_sort()
 // The batch starts to roam: the pair table, for the whole raster (~2 ms at 5000 x 6000), and the fine table
 void TrackRun::build_roam_tables()
 {
-    const char *tabc = reinterpret_cast<const char *>(c.table);
-    const unsigned grid = 256 * 16;
-    if (rev) hipLaunchKernelGGL(k_roam_build<true>, dim3(grid), dim3(kBlock), 0, st, tabc, a.guard, a.plane_shift, p->rows, p->cols,
-                                ws.roam, thr_prior);
-    else hipLaunchKernelGGL(k_roam_build<false>, dim3(grid), dim3(kBlock), 0, st, tabc, a.guard, a.plane_shift, p->rows, p->cols,
-                            ws.roam, thr_prior);
-    if (a.fine) {
-        FinePrior fp;
-        fine_prior_tables(p->prior, &fp);
-        const int tx = (p->cols + kTabW - 1) / kTabW, ty = (p->rows + kTabH - 1) / kTabH, nt = tx * ty;
-        FineEntry *fine_out = reinterpret_cast<FineEntry *>(const_cast<void *>(a.fine));
-        if (c.potential) hipLaunchKernelGGL(k_fine_build<true>, dim3(static_cast<unsigned>(nt)), dim3(kBlock), 0, st, c.updraft, c.potential,
-                                            fine_out, p->rows, p->cols, tx, nt, fp);
-        else hipLaunchKernelGGL(k_fine_build<false>, dim3(static_cast<unsigned>(nt)), dim3(kBlock), 0, st, c.updraft, c.potential,
-                                fine_out, p->rows, p->cols, tx, nt, fp);
-    }
+    FinePrior fp;
+    fine_prior_tables(p->prior, &fp);
+    launch_roam_tables(c.table, a.guard, a.plane_shift, thr_prior, rev, fp, c.updraft, c.potential, p->rows, p->cols, ws.roam,
+                       reinterpret_cast<FineEntry *>(const_cast<void *>(a.fine)), st);
     roam_ready = true;
     marks_adjacent = false;
 }

@@ -524,6 +524,27 @@ def roam_pair_words(seed, track, block):
     return packed.cpu().numpy().view(np.uint32), words.cpu().numpy().view(np.uint32)
 
 
+def roam_tables_selftest(updraft, potential, move_dirn, thr=None):
+    """The roaming regime's pair and fine tables of a raster and heading (degrees), built by the stepper's own launches
+    from the threshold table `thr` of the same fields and heading (default: a fresh one): numpy uint32 arrays
+    (pair[rows, cols, 8, 4], fine[rows, cols, 8, 2], prior_words[38])."""
+    upd = to_dev(updraft, torch.float64)
+    pot = to_dev(potential, torch.float32)
+    rows, cols = int(upd.shape[0]), int(upd.shape[1])
+    if thr is None:
+        thr = build_transition_table(upd, pot, thr=True, move_dirn=move_dirn)
+    elif table_kind(thr, rows, cols) != 'thr':
+        raise ValueError('thr is not a threshold table')
+    prior = np.ascontiguousarray(get_directional_probs(float(move_dirn) * np.pi / 180.), dtype=np.float64)
+    pair = torch.empty((rows, cols, 8, 4), dtype=torch.int32, device=upd.device)
+    fine = torch.empty((rows, cols, 8, 2), dtype=torch.int32, device=upd.device)
+    words = np.zeros(38, dtype=np.uint32)
+    nat.check(nat.lib().ssrs_roam_tables_selftest(
+        nat.ptr(upd), nat.ptr(pot), prior.ctypes.data_as(C.c_void_p), nat.ptr(thr), rows, cols, nat.ptr(pair), nat.ptr(fine),
+        words.ctypes.data_as(C.c_void_p), stream_ptr()))
+    return pair.cpu().numpy().view(np.uint32), fine.cpu().numpy().view(np.uint32), words
+
+
 # ---------------------------------------------------------------- re-exports
 from .presence import (compute_presence_counts, compute_smooth_presence_counts)  # noqa: E402
 from . import potential as _potential  # noqa: E402

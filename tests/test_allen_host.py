@@ -178,7 +178,7 @@ def test_c_abi_argument_errors():
     INV = _native.SSRS_ERR_INVALID
     for name in ('ssrs_allen_workspace_bytes', 'ssrs_allen_thermal_field'):
         assert hasattr(lib, name) and name in _native.EXPORTS
-    assert lib.ssrs_version() == 108
+    assert lib.ssrs_version() == 109
     size = lib.ssrs_allen_workspace_bytes
     assert size(1) == 512 and size(149) == 256 + (149 * 48 + 255) // 256 * 256 and size(1 << 22) == 256 + (48 << 22)
     assert size(0) == 0 and size(-3) == 0 and size((1 << 22) + 1) == 0

@@ -28,7 +28,7 @@ def test_header_symbols_are_exported():
 def test_version_and_error_text():
     from ssrs_amd import _native
     lib = _native.lib()
-    assert lib.ssrs_version() == 108
+    assert lib.ssrs_version() == 109
     assert isinstance(lib.ssrs_last_error(), bytes)
 
 
@@ -74,6 +74,29 @@ def test_argument_validation_needs_no_gpu():
     assert rc == _native.SSRS_ERR_INVALID
     with pytest.raises(ValueError):
         _native.check(rc)
+
+
+def test_roam_tables_selftest_refuses_before_any_gpu_work():
+    from ssrs_amd import _native
+    lib = _native.lib()
+    prior = (C.c_double * 9)()
+    words = (C.c_uint32 * 38)()
+    raw = (C.c_char * 256)()
+    base = C.addressof(raw)
+    a64 = (base + 63) // 64 * 64                       # a 64-byte aligned address inside `raw` (never dereferenced)
+
+    def call(updraft=a64, potential=None, prior=C.addressof(prior), thr=a64, rows=8, cols=8, pair=a64, fine=a64):
+        return lib.ssrs_roam_tables_selftest(updraft, potential, prior, thr, rows, cols, pair, fine, C.addressof(words), None)
+
+    for kw in ({'updraft': None}, {'prior': None}, {'thr': None}, {'pair': None}, {'fine': None}):
+        assert call(**kw) == _native.SSRS_ERR_INVALID and b'is NULL' in lib.ssrs_last_error(), kw
+    for kw in ({'rows': 2}, {'cols': 2}):
+        assert call(**kw) == _native.SSRS_ERR_INVALID and b'rows, cols >= 3' in lib.ssrs_last_error(), kw
+    assert call(rows=8192, cols=4097) == _native.SSRS_ERR_INVALID and b'2^25' in lib.ssrs_last_error()
+    assert call(thr=a64 + 32) == _native.SSRS_ERR_INVALID and b'64-byte aligned' in lib.ssrs_last_error()
+    assert call(pair=a64 + 8) == _native.SSRS_ERR_INVALID and b'16-byte aligned' in lib.ssrs_last_error()
+    assert call(fine=a64 + 8) == _native.SSRS_ERR_INVALID and b'16-byte aligned' in lib.ssrs_last_error()
+    assert list(words) == [0] * 38                     # nothing was written either
 
 
 def test_product_fails_loudly_without_gpu():

@@ -147,7 +147,7 @@ def test_new_entry_points_validate_without_a_gpu():
                 dict(nb=C.c_size_t(cb - 1)), dict(nb=C.c_size_t(0))]:
         assert cubic(**bad) == INV, bad
         assert b'ssrs_wind_from_triangles_cubic' in lib.ssrs_last_error()
-    assert lib.ssrs_version() == 108
+    assert lib.ssrs_version() == 109
 
 
 def test_unknown_method_is_a_value_error(tmp_path):

@@ -71,7 +71,7 @@ def test_new_entry_points_validate_without_a_gpu():
     for name in ('ssrs_potential_temperature', 'ssrs_deardorff_velocity', 'ssrs_thermal_updraft',
                  'ssrs_scalar_interp_workspace_bytes', 'ssrs_scalar_from_samples', 'ssrs_wtk_thermal_fields'):
         assert hasattr(lib, name) and name in _native.EXPORTS
-    assert lib.ssrs_version() == 108
+    assert lib.ssrs_version() == 109
     buf = (C.c_char * (1 << 16))()
     p = C.cast(buf, C.c_void_p)
     d = lambda v: C.c_double(v)
