@@ -593,6 +593,61 @@ int ssrs_track_occupancy(const int16_t *traj, const int64_t *traj_offsets, int64
                          uint32_t *counts, uint32_t *cells_per_track,
                          void *workspace, size_t workspace_bytes, void *stream);
 
+/* --------------------------------------------------------------- altitude */
+
+/* K14 -- flight height above ground along every track, and rotor-zone presence.  THIS BUILD'S OWN MODEL (the reference has
+ * no altitude model), defined in integers so that the scan gives the same bits however it is grouped.  All heights are
+ * int32 millimetres above ground.
+ *   cellinfo  one {int32 climb, int32 elev} pair per cell (8 bytes, 8-byte aligned), built by ssrs_altitude_cellinfo:
+ *       climb = (int32) clip(rint((w - sink) * scale), -2^26, 2^26): the millimetres gained on one orthogonal move out of the
+ *               cell.  w is the un-thresholded updraft (f32 or f64, widened to f64, NaN read as 0), sink in m/s, scale =
+ *               1000 * resolution / airspeed; the subtraction and the product round on their own, as
+ *               np.rint((w.astype(f64) - sink) * scale) does
+ *       elev  = (int32) clip(rint(1000 * z), -2^30, 2^30) of the DEM z; a NaN (nodata) z gives the sentinel INT32_MIN
+ *   a move from point k = (r, c) to point k + 1 = (r', c') of a track is diagonal iff r' != r and c' != c (a burn-in jump
+ *       is one move, whatever its length);  step = diagonal ? (int32)(((int64)climb[r, c] * 92682 + 32768) >> 16) : climb[r, c]
+ *       (arithmetic shift; 92682 = round(sqrt(2) * 2^16));  a_k = step - (elev[r', c'] - elev[r, c]), the terrain difference
+ *       being 0 when either elev is the sentinel;  a_k = 0 when either point lies outside [0, rows) x [0, cols)
+ *   h_0 = clamp(start, floor, ceil);  h_{k+1} = clamp(h_k + a_k, floor, ceil), the sum in int64
+ *   a point is "in the rotor zone" iff it lies inside the raster and band_lo <= h <= band_hi
+ * ssrs_track_altitude:
+ *   traj, traj_offsets, ntracks   exactly what ssrs_track_occupancy takes (the first offset need not be 0, equal consecutive
+ *                       offsets are an empty track, traj 4-byte aligned)
+ *   params              {start, floor, ceil, band_lo, band_hi} in mm
+ *   outputs, each may be NULL; the per-point ones are indexed like traj and written for the points
+ *   [traj_offsets[0], traj_offsets[ntracks]) only:
+ *     alt               int32 per point, OVERWRITTEN: the height
+ *     band_hist         uint32 (rows, cols), ADDED to: +1 in the cell of every point in the rotor zone
+ *     traj_band         int16 pairs, OVERWRITTEN: traj with every point that is not in the rotor zone replaced by (-1, -1);
+ *                       ssrs_turbine_encounters and ssrs_track_occupancy ignore such points, so it feeds them as it stands
+ *     in_band, h_min, h_max   int32 (ntracks), OVERWRITTEN: the track's points in the rotor zone, and the least and the
+ *                       greatest height over ALL its points; an empty track gets 0, INT32_MAX, INT32_MIN.
+ *                       Sum(in_band) == Sum(added to band_hist): the caller's checksum
+ *   workspace           24 bytes per tile of SSRS_ALTITUDE_TILE points (its operator and its first and last track), ssrs_track_altitude_workspace_bytes(points of the
+ *                       chunk), 16-byte aligned; its contents before and after a call mean nothing
+ * Three launches in `stream`'s order: the composed operator x -> min(max(x + A, L), H) of every tile of consecutive points
+ * of the chunk; one block that scans those; every tile again behind its carry, writing the outputs.  No block waits for
+ * another.  Exact, and independent of the launch order.  traj_offsets[0] and traj_offsets[ntracks] are read back first
+ * (the launches are sized from them), so the call waits for `stream` once.  16-byte aligned traj / alt / traj_band are read
+ * and written 16 bytes a lane.
+ * NULL traj / traj_offsets / cellinfo / params / workspace, rows / cols outside [1, 32767], ntracks outside [0, 2^31), a
+ * misaligned traj, traj_band, cellinfo or workspace, floor > ceil, band_lo > band_hi, a workspace smaller than
+ * ssrs_track_altitude_workspace_bytes(0) -> SSRS_ERR_INVALID before any GPU work; a workspace too small for the chunk's
+ * points -> SSRS_ERR_INVALID once the two offsets are known, before any launch.  ntracks == 0, or no points, returns
+ * SSRS_OK and touches nothing. */
+#define SSRS_ALTITUDE_TILE 4096
+typedef struct SsrsAltitudeParams {
+    int32_t start, floor, ceil, band_lo, band_hi;
+} SsrsAltitudeParams;
+int ssrs_altitude_cellinfo(const void *updraft, int updraft_type, const void *dem, int dem_type, int rows, int cols,
+                           double sink, double scale, int32_t *cellinfo, void *stream);
+size_t ssrs_track_altitude_workspace_bytes(int64_t npoints);
+int ssrs_track_altitude(const int16_t *traj, const int64_t *traj_offsets, int64_t ntracks,
+                        const int32_t *cellinfo, int rows, int cols, const SsrsAltitudeParams *params,
+                        int32_t *alt, uint32_t *band_hist, int16_t *traj_band,
+                        int32_t *in_band, int32_t *h_min, int32_t *h_max,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------- shelter */
 
 /* K9 -- the terrain-shelter angle Sx (Winstral et al. 2002) and the orographic updraft adjusted by it and by a

@@ -23,6 +23,7 @@ SSRS_TRACKS_THR_TABLE = 128
 SSRS_SOLVE_NO_AMG = 1
 SSRS_TURBINE_BIN, SSRS_TURBINE_MAX = 32, 8192
 SSRS_OCCUPANCY_MAX_PLANES = 8
+SSRS_ALTITUDE_TILE = 4096
 SSRS_RAY_AXES = {'row_north': 0, 'row_east': 1}                  # SSRS_RAY_ROW_NORTH / _ROW_EAST
 SSRS_SHELTER_PATH = {'auto': 0, 'lds': 1, 'global': 2}           # SSRS_SHELTER_AUTO / _LDS / _GLOBAL
 SSRS_SMOOTH_PATH = {'auto': 0, 'lds': 1, 'global': 2}            # SSRS_SMOOTH_AUTO / _LDS / _GLOBAL
@@ -55,6 +56,7 @@ EXPORTS = (
     'ssrs_projection_init_albers', 'ssrs_warp_lonlat_raster',
     'ssrs_allen_workspace_bytes', 'ssrs_allen_thermal_field',
     'ssrs_track_occupancy_workspace_bytes', 'ssrs_track_occupancy',
+    'ssrs_altitude_cellinfo', 'ssrs_track_altitude_workspace_bytes', 'ssrs_track_altitude',
     'ssrs_roam_pair_word_selftest', 'ssrs_tracks_roam_feed_counts', 'ssrs_roam_tables_selftest',
 )
 
@@ -104,6 +106,19 @@ OCCUPANCY_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_i
 ALLEN_FIELD_ARGTYPES = [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int] + \
     [C.c_double] * 3 + [C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+
+
+class SsrsAltitudeParams(C.Structure):
+    _fields_ = [(name, C.c_int32) for name in ('start', 'floor', 'ceil', 'band_lo', 'band_hi')]
+
+
+# ssrs_altitude_cellinfo: updraft, updraft_type, dem, dem_type, rows, cols, sink, scale, cellinfo, stream
+ALTITUDE_CELLINFO_ARGTYPES = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p,
+                              C.c_void_p]
+# ssrs_track_altitude: traj, traj_offsets, ntracks, cellinfo, rows, cols, params, alt, band_hist, traj_band, in_band, h_min,
+# h_max, workspace, workspace_bytes, stream
+ALTITUDE_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.POINTER(SsrsAltitudeParams)] + \
+    [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]
 
 
 class SsrsError(RuntimeError):
@@ -209,6 +224,10 @@ def lib():
         L.ssrs_track_occupancy_workspace_bytes.restype = C.c_size_t
         L.ssrs_track_occupancy_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
         L.ssrs_track_occupancy.argtypes = OCCUPANCY_ARGTYPES
+        L.ssrs_altitude_cellinfo.argtypes = ALTITUDE_CELLINFO_ARGTYPES
+        L.ssrs_track_altitude_workspace_bytes.restype = C.c_size_t
+        L.ssrs_track_altitude_workspace_bytes.argtypes = [C.c_int64]
+        L.ssrs_track_altitude.argtypes = ALTITUDE_ARGTYPES
         L.ssrs_roam_pair_word_selftest.argtypes = [C.c_uint64] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
         L.ssrs_roam_tables_selftest.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 4
         L.ssrs_tracks_roam_feed_counts.restype = None

@@ -33,6 +33,8 @@ _SECTIONS = (
     ('Plotting and wind turbines', ('turbine_minimum_hubheight', 'turbine_mrkr_size',
                                     'fig_height', 'fig_dpi')),
     ('MI355X build', ('save_tracks', 'stepper_path', 'steps_per_launch', 'max_tracks_file_gb', 'track_occupancy',
+                      'flight_height', 'flight_height_start', 'flight_height_floor', 'flight_height_ceiling',
+                      'flight_airspeed', 'flight_sink_rate', 'rotor_zone',
                       'hist_safe_tracks', 'thermal_model', 'thermal_allen_zi', 'thermal_allen_wstar', 'thermal_allen_sink',
                       'turbine_encounter_radius')),
 )
@@ -106,6 +108,20 @@ class Config:
     #                                     on the device (produced even with save_tracks=False):
     #                                     <id>_occupancy.npy, Simulator.compute_occupancy_map().  It stands here, not last,
     #                                     because tests pin every slot after the reference's fields but this one
+    flight_height: bool = False         # True: simulate_tracks also integrates a height above ground along every track -- THIS
+    #                                     BUILD'S OWN model, the reference has none (limit 13): each move adds
+    #                                     (updraft - sink) * resolution / airspeed (times sqrt(2) on a diagonal) less the terrain's
+    #                                     rise, clamped to [floor, ceiling] -- and counts the points inside rotor_zone, from the
+    #                                     trajectories on the device (produced even with save_tracks=False):
+    #                                     <id>_rotor_presence.npy, <id>_flight_heights.npy, with turbine_encounter_radius > 0 also
+    #                                     <id>_rotor_turbine_encounters.npy; Simulator.compute_rotor_presence_map()
+    flight_height_start: float = 100.   # metres above ground at a track's first point.  The heights and the band below are
+    #                                     PLACEHOLDERS: set them for the species and the turbines at hand
+    flight_height_floor: float = 10.    # metres: the height never falls below it
+    flight_height_ceiling: float = 1000.  # metres: nor rises above it
+    flight_airspeed: float = 15.        # m/s, still air: a move of one cell takes resolution / airspeed seconds
+    flight_sink_rate: float = -1.       # m/s lost in still air; < 0 = updraft_threshold
+    rotor_zone: Tuple[float, float] = (30., 150.)   # metres above ground, both ends inclusive
     thermal_allen_zi: float = 0.        # thermal_model = 'allen': boundary-layer height zi in metres.  0 (snapshot / seasonal
     #                                     only) = the mean of the case's own blheight layer, clipped below at 100 m
     thermal_allen_wstar: float = 0.     # thermal_model = 'allen': convective velocity scale w* in m/s.  0 (snapshot / seasonal

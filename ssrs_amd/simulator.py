@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from .config import Config
-from . import distributed, inputs, layers, movmodel, presence
+from . import distributed, flight, inputs, layers, movmodel, presence
 from . import turbines as turbines_mod
 from . import potential as potential_mod
 from ._device import to_dev
@@ -76,6 +76,8 @@ class Simulator(Config):
         self._check_orographic_model()
         if not float(self.turbine_encounter_radius) >= 0.:
             raise ValueError(f'turbine_encounter_radius = {self.turbine_encounter_radius!r}: expected metres >= 0 (0 = off)')
+        if self.flight_height:
+            self._flight_params()
         print(f'\n---- SSRS in {self.sim_mode} mode')
         print(f'Run name: {self.run_name}')
         if self.sim_seed >= 0:                                    # simulator.py:50-52
@@ -124,6 +126,9 @@ class Simulator(Config):
         self.turbines = self._resolve_turbines(turbines)
         self.turbine_encounters = {}      # (case_id, real_id) -> dict(tracks_per_turbine, turbines_per_track, first_step)
         self.track_occupancy_counts = {}  # (case_id, real_id) -> int32 (rows, cols): the distinct tracks through each cell
+        self.rotor_presence_counts = {}   # (case_id, real_id) -> int32 (rows, cols) holding uint32: points in the rotor zone
+        self.flight_heights = {}          # (case_id, real_id) -> int32 (this rank's tracks, 3): [in zone, h_min, h_max] in mm
+        self.rotor_turbine_encounters = {}  # as turbine_encounters, of the points in the rotor zone only
         self.wtk_layers = {
             'wspeed': f'windspeed_{str(int(self.wtk_orographic_height))}m',
             'wdirn': f'winddirection_{str(int(self.wtk_orographic_height))}m',
@@ -727,12 +732,15 @@ class Simulator(Config):
                     raise ValueError(f'unknown movement_model {self.movement_model!r}')
                 updrafts = self._load_updrafts_dev(case_id) if fluid else \
                     [None] * (1 + int(self.thermals_realization_count))
-                for real_id, updraft in enumerate(updrafts):
+                # (flight_height reads the UN-thresholded field of every item, whatever the movement model)
+                raw = self._updraft_fields(case_id, lambda fname: to_dev(np.load(fname), torch.float32)) \
+                    if self.flight_height else [None] * len(updrafts)
+                for (real_id, updraft), lift in zip(enumerate(updrafts), raw):
                     if self.sim_seed > 0:
                         np.random.seed(self.sim_seed + real_id)
                     fields = (updraft, self._potential_dev(updraft, case_id, real_id)) if fluid \
                         else (None, None)
-                    yield (case_id, real_id, fields, self._stream_seed(real_id))
+                    yield (case_id, real_id, fields, self._stream_seed(real_id), lift)
 
         encounters = float(self.turbine_encounter_radius) > 0.
         if encounters:
@@ -740,9 +748,12 @@ class Simulator(Config):
             enc_geometry = (to_dev(self._turbine_cells, torch.float64),
                             tuple(to_dev(a, torch.int32) for a in self._turbine_bins))
         occupancy = bool(self.track_occupancy)
+        heights = bool(self.flight_height)
+        if heights:
+            dem = to_dev(self._terrain['Elevation'], torch.float64)
 
         def run(item):
-            case_id, real_id, fields, seed = item
+            case_id, real_id, fields, seed, lift = item
             self.last_seeds[(case_id, real_id)] = seed
             id_str = self._get_id_string(case_id, real_id)
             start_time = time.time()
@@ -764,6 +775,15 @@ class Simulator(Config):
                     occ_counts = torch.zeros(self.gridsize, dtype=torch.int32, device=my_starts.device)
                     occ_cells = torch.zeros((), dtype=torch.int64, device=my_starts.device)
                     consumers.append(self._occupancy_consumer(hi - lo, occ_counts, occ_cells))
+                if heights:
+                    # one rotor-zone raster per item, this rank's per-track rows, and (with encounters) a second bitmap
+                    # from the points in the rotor zone alone
+                    fly = dict(band_hist=torch.zeros(self.gridsize, dtype=torch.int32, device=my_starts.device),
+                               rows=torch.zeros((hi - lo, 3), dtype=torch.int32, device=my_starts.device))
+                    if encounters:
+                        fly['hits'] = torch.zeros_like(hits)
+                        fly['first_step'] = torch.full_like(first_step, -1)
+                    consumers.append(self._flight_consumer(lift, dem, fly, enc_geometry if encounters else None))
                 chunks = self._device_chunks(batch, consumers) if consumers else None
                 if self.save_tracks:
                     # (inside the stream's scope: long trajectories are stepped again range by range while written)
@@ -793,6 +813,9 @@ class Simulator(Config):
                 if occupancy:
                     # (track-sharded: the sum over the ranks is a collective as well, after the encounters' in every item)
                     self._store_occupancy(case_id, real_id, occ_counts, int(occ_cells.item()), sharded)
+                if heights:
+                    # (track-sharded: its collectives come last in every item)
+                    self._store_flight(case_id, real_id, fly, nturb if encounters else 0, sharded)
             if sharded:
                 batch.hist = distributed.reduce_histogram(batch.hist, all_ranks=True)
             return (case_id, real_id), batch
@@ -860,6 +883,73 @@ class Simulator(Config):
             cells.add_(per_track.sum(dtype=torch.int64))
         return consume
 
+    def _flight_params(self):
+        """(heights in metres for flight.compute_track_altitudes, airspeed, sink rate) of the flight_* fields, checked."""
+        airspeed = float(self.flight_airspeed)
+        if not airspeed > 0.:
+            raise ValueError(f'flight_airspeed = {self.flight_airspeed!r}: expected m/s > 0')
+        sink = float(self.flight_sink_rate)
+        if sink != sink:
+            raise ValueError(f'flight_sink_rate = {self.flight_sink_rate!r}: expected m/s (< 0 = updraft_threshold)')
+        if sink < 0.:
+            sink = float(self.updraft_threshold)
+        kw = dict(start=self.flight_height_start, floor=self.flight_height_floor, ceil=self.flight_height_ceiling,
+                  band=self.rotor_zone)
+        flight.height_params(who='Config.flight_height_* / rotor_zone', **kw)
+        return kw, airspeed, sink
+
+    def _flight_consumer(self, lift, dem, fly, geometry):
+        """A chunk through the flight-height scan (K14): `fly['band_hist']` is added to, the chunk's tracks get their rows of
+        `fly['rows']`; with `geometry` the points in the rotor zone go through the encounter kernel into `fly['hits']` /
+        `fly['first_step']`.  The item's cellinfo is built here, from its un-thresholded updraft `lift` and the DEM."""
+        kw, airspeed, sink = self._flight_params()
+        cellinfo = flight.altitude_cellinfo(lift, dem, self.resolution, airspeed, sink)
+        radius_cells = float(self.turbine_encounter_radius) / float(self.resolution)
+
+        def consume(t0, t1, traj, off):
+            out = flight.compute_track_altitudes(traj, cellinfo, self.gridsize, offsets=off, band_hist=fly['band_hist'],
+                                                 want_masked=geometry is not None, **kw)
+            fly['rows'][t0:t1] = out['heights']
+            if geometry is not None:
+                xy, bins = geometry
+                turbines_mod.turbine_encounters(out['masked'], off, xy, radius_cells, self.gridsize, bins=bins,
+                                                hits=fly['hits'][t0:t1], first_step=fly['first_step'][t0:t1])
+        return consume
+
+    def _store_flight(self, case_id, real_id, fly, nturb, sharded):
+        """Keeps the rotor-zone raster and the per-track heights of one (case, realisation) and writes
+        <id>_rotor_presence.npy (int32 holding uint32) and <id>_flight_heights.npy (int32 (tracks, 3): [points in the zone,
+        least, greatest height in mm]); with encounters also <id>_rotor_turbine_encounters.npy.  Checked by its checksum:
+        this rank's raster must add up to the in-zone points of its tracks.  Track-sharded runs sum the raster (and the
+        per-turbine counts) over the ranks as _store_occupancy does and rank 0 writes the raster; the per-track rows stay
+        this rank's tracks, like first_step, and <id>_flight_heights.npy is then rank 0's share."""
+        id_str = self._get_id_string(case_id, real_id)
+        counts, rows = fly['band_hist'], fly['rows']
+        counted = int((counts.to(torch.int64) & 0xFFFFFFFF).sum().item())
+        in_zone = int(rows[:, 0].sum(dtype=torch.int64).item())
+        if counted != in_zone:
+            raise RuntimeError(f'{id_str}: rotor presence: the raster adds up to {counted}, the in-zone points of the '
+                               f'tracks to {in_zone}')
+        if sharded:
+            counts = distributed.reduce_histogram(counts, all_ranks=True)
+        key = (case_id, real_id)
+        self.rotor_presence_counts[key] = counts.to(torch.int32).cpu().numpy()
+        self.flight_heights[key] = rows.cpu().numpy()
+        writes = not sharded or self._rank() == 0
+        if writes:
+            np.save(os.path.join(self.mode_data_dir, f'{id_str}_rotor_presence.npy'), self.rotor_presence_counts[key])
+            np.save(os.path.join(self.mode_data_dir, f'{id_str}_flight_heights.npy'), self.flight_heights[key])
+        if 'hits' in fly:
+            per_turbine, per_track = turbines_mod.encounter_counts(fly['hits'], nturb)
+            per_turbine = per_turbine.cpu().numpy().astype(np.int64)
+            if sharded:
+                per_turbine = np.asarray(self._allreduce_sum(per_turbine), dtype=np.int64)
+            self.rotor_turbine_encounters[key] = dict(
+                tracks_per_turbine=per_turbine, turbines_per_track=per_track.cpu().numpy().astype(np.int32),
+                first_step=fly['first_step'].cpu().numpy().astype(np.int32))
+            if writes:
+                np.save(os.path.join(self.mode_data_dir, f'{id_str}_rotor_turbine_encounters.npy'), per_turbine)
+
     def _store_occupancy(self, case_id, real_id, counts, cells, sharded):
         """Keeps the occupancy raster of one (case, realisation) as numpy int32 and writes <id>_occupancy.npy.  Checked
         like the histogram by its checksum: this rank's counts must add up to the sum of its cells_per_track (`cells`).
@@ -910,7 +1000,8 @@ class Simulator(Config):
         step = max(1, -(-n // max(1, -(-n // safe))))
         parts, wide, stats = [], None, None
         # trajectories: for the pickle, or for the turbine encounters / the track occupancy (which read them on the device)
-        want_tracks = bool(self.save_tracks) or float(self.turbine_encounter_radius) > 0. or bool(self.track_occupancy)
+        want_tracks = bool(self.save_tracks) or float(self.turbine_encounter_radius) > 0. or bool(self.track_occupancy) or \
+            bool(self.flight_height)
         # (start, length) of the sub-batches still to step, in track-id order; one whose uint32 counts wrapped is stepped
         # again as two halves, added up in 64 bits like the rest
         todo = [(t0, min(step, n - t0)) for t0 in range(0, max(n, 1), step)]
@@ -1022,9 +1113,14 @@ class Simulator(Config):
         flat = np.concatenate(tracks) if len(tracks) else np.zeros((0, 2), dtype=np.int16)
         return presence.compute_presence_counts(torch.from_numpy(flat).cuda(), self.gridsize)
 
-    def _presence_summary(self, krad):
+    def _presence_summary(self, krad, counts_for=None, may_be_empty=False):
         """The normalisation ladder of plot_presence_map / plot_windplant_presence_map (simulator.py:521-546, :572-586)
-        with a disk of `krad` cells: (the f32 summary map, the same on every rank; this rank's per-case maps)."""
+        with a disk of `krad` cells: (the f32 summary map, the same on every rank; this rank's per-case maps).
+        counts_for(case_id, real_id): the source of the counts, _counts_for (the visit histograms) by default.
+        may_be_empty: a raster may be all zero (a visit histogram never is: every track has its first point); its
+        division by the maximum is then left out, so it contributes zeros, and so on up the ladder."""
+        counts_for = counts_for or self._counts_for
+        some = (lambda t: bool((t != 0).any())) if may_be_empty else (lambda t: True)
         dev = self._presence_device()
         summary = torch.zeros(self.gridsize, dtype=torch.float64, device=dev)
         case_presence = {}
@@ -1032,13 +1128,17 @@ class Simulator(Config):
             nreal = 1 + int(self.thermals_realization_count)
             case_prob = torch.zeros(self.gridsize, dtype=torch.float64, device=dev)
             for real_id in range(nreal):
-                counts = self._counts_for(case_id, real_id)
-                prprob = presence.smooth_presence_counts(counts, krad)
-                presence.normalise_add(prprob, case_prob)       # prprob /= amax; case += prprob
-            presence.normalise_add(case_prob, summary)          # case /= amax; summary += case
+                counts = counts_for(case_id, real_id)
+                if some(counts):
+                    prprob = presence.smooth_presence_counts(counts, krad)
+                    presence.normalise_add(prprob, case_prob)   # prprob /= amax; case += prprob
+            if some(case_prob):
+                presence.normalise_add(case_prob, summary)      # case /= amax; summary += case
             case_presence[case_id] = case_prob
         if not self._shards_tracks():
             distributed.reduce_presence_sum(summary)                        # cases of the other ranks
+        if not some(summary):
+            return np.zeros(self.gridsize, dtype=np.float32), case_presence
         return presence.normalise_to_f32(summary).cpu().numpy(), case_presence  # summary /= amax -> f32
 
     def compute_presence_map(self, radius: float = 1000.):
@@ -1048,6 +1148,21 @@ class Simulator(Config):
             presence.presence_kernel_radius(radius, self.resolution, self.gridsize))
         if self._rank() == 0:
             np.save(os.path.join(self.mode_data_dir, 'summary_presence.npy'), out)
+        self._barrier()
+        return out
+
+    def compute_rotor_presence_map(self, radius: float = 1000.):
+        """compute_presence_map of the points in the rotor zone alone (flight_height=True): the same ladder
+        over rotor_presence_counts.  A (case, realisation) without a point in the zone contributes zeros.  Returns the
+        f32 summary map and writes summary_rotor_presence.npy.  ValueError when simulate_tracks computed no heights."""
+        if not self.rotor_presence_counts:
+            raise ValueError('no rotor-zone presence was computed: run simulate_tracks() with flight_height=True')
+        out, self.case_rotor_presence = self._presence_summary(
+            presence.presence_kernel_radius(radius, self.resolution, self.gridsize),
+            counts_for=lambda case_id, real_id: to_dev(self.rotor_presence_counts[(case_id, real_id)], torch.int32),
+            may_be_empty=True)
+        if self._rank() == 0:
+            np.save(os.path.join(self.mode_data_dir, 'summary_rotor_presence.npy'), out)
         self._barrier()
         return out
 
