@@ -562,6 +562,48 @@ int ssrs_turbine_encounters(const int16_t *traj, const int64_t *traj_offsets, in
 int ssrs_turbine_encounter_counts(const uint32_t *hits, int64_t ntracks, int nturb,
                                   int64_t *tracks_per_turbine, int32_t *turbines_per_track, void *stream);
 
+/* K15 -- which tracks passed through which turbine's OWN rotor envelope, and for how many points (the exposure): the
+ * encounter test above in three dimensions with per-turbine geometry, from the trajectories and the heights of
+ * ssrs_track_altitude on the device.  A turbine t is a vertical cylinder in absolute heights: (xt, yt) f64 in cell units
+ * as above, reach_t f64 in cells, and [z_lo_t, z_hi_t] int32 millimetres above the DEM's datum.  Point k = (r, c) of a
+ * track is inside turbine t iff
+ *     it lies inside the raster,
+ *     e = elev[r, c] (cellinfo[(r * cols + c) * 2 + 1]) is not the nodata sentinel INT32_MIN,
+ *     dx * dx + dy * dy <= reach_t * reach_t   with dx = (double)c - xt, dy = (double)r - yt, every product and the sum
+ *                                               rounded on their own, `<=` (the expression of ssrs_turbine_encounters), and
+ *     z_lo_t <= (int64)e + alt[k] <= z_hi_t    both ends included.
+ * A turbine whose reach_t is NaN or negative, whose xt or yt is NaN, or whose z_lo_t > z_hi_t is hit by nothing.
+ *   traj, traj_offsets, ntracks   exactly what ssrs_turbine_encounters takes (the first offset need not be 0, equal
+ *                       consecutive offsets are an empty track, traj 4-byte aligned)
+ *   alt                 int32 per point, indexed like traj, 4-byte aligned: the height above the ground of the point's cell
+ *                       in mm (ssrs_track_altitude's `alt`).  When traj AND alt are 16-byte aligned both are read 16 bytes a
+ *                       lane
+ *   cellinfo            the {climb, elev} raster of ssrs_altitude_cellinfo (rows, cols), 8-byte aligned; only elev is read,
+ *                       and only for points whose bin holds a turbine
+ *   turbines            (nturb, 2) f64 [xt, yt];  reach (nturb) f64;  zband (nturb, 2) int32 [z_lo, z_hi], 8-byte aligned;
+ *                       1 <= nturb <= SSRS_TURBINE_MAX
+ *   bin_start, bin_items  the caller's cull in the CSR form of ssrs_turbine_encounters, built from the per-turbine reach.
+ *                       The lists only cull: the test above decides, a list that omits a turbine loses its hits in that
+ *                       bin, and one that names a turbine twice in a bin counts its points there twice
+ *   hits                uint32 (ntracks, ceil(nturb / 32)), ORed into: the layout of ssrs_turbine_encounters, so
+ *                       ssrs_turbine_encounter_counts serves it unchanged
+ *   first_step          int32 (ntracks) or NULL, UNSIGNED minimum with what is there (-1 = none): the index within the
+ *                       track of its first point inside any turbine's cylinder
+ *   points_per_turbine  uint64 (nturb) or NULL, ADDED to: the track points inside each turbine's cylinder.  64 bits end
+ *                       to end towards the caller; inside, a lane keeps one (turbine, count) pair in registers over its
+ *                       points, hands it to a uint32 counter per turbine in the block's LDS (4 bytes a turbine) when the
+ *                       turbine changes, and the block adds its non-zero counters once, at its end
+ * One streaming pass of 8 bytes per point, asynchronous on `stream`; everything is OR, min and sums of integers: the same
+ * result from run to run, independent of the launch order.  The occupied-bin mask lives in LDS while it and the exposure
+ * counters fit 60 KB together (and the raster has at most 262 144 bins); beyond, bin_start is read per point.
+ * NULL pointers (first_step and points_per_turbine excepted), ntracks outside [0, 2^31), nturb outside
+ * [1, SSRS_TURBINE_MAX], rows / cols outside [1, 32767], a misaligned traj, alt, cellinfo, zband or points_per_turbine ->
+ * SSRS_ERR_INVALID before any GPU work.  ntracks == 0, or no points, returns SSRS_OK and touches nothing. */
+int ssrs_rotor_encounters(const int16_t *traj, const int64_t *traj_offsets, int64_t ntracks, const int32_t *alt,
+                          const int32_t *cellinfo, int rows, int cols, const double *turbines, const double *reach,
+                          const int32_t *zband, int nturb, const int32_t *bin_start, const int32_t *bin_items,
+                          uint32_t *hits, int32_t *first_step, uint64_t *points_per_turbine, void *stream);
+
 /* -------------------------------------------------------------- occupancy */
 
 /* K13 -- how many DISTINCT tracks passed through each cell, from the trajectories on the device: the per-cell analogue

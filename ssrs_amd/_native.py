@@ -50,7 +50,7 @@ EXPORTS = (
     'ssrs_presence_smooth_u64',
     'ssrs_presence_normalise_add', 'ssrs_presence_normalise_f32',
     'ssrs_potential_workspace_bytes', 'ssrs_potential_solve',
-    'ssrs_turbine_encounters', 'ssrs_turbine_encounter_counts',
+    'ssrs_turbine_encounters', 'ssrs_turbine_encounter_counts', 'ssrs_rotor_encounters',
     'ssrs_shelter_sx', 'ssrs_updraft_sheltered', 'ssrs_shelter_sx_sector', 'ssrs_updraft_sheltered_sector',
     'ssrs_smooth_workspace_bytes', 'ssrs_smooth_reflect',
     'ssrs_projection_init_albers', 'ssrs_warp_lonlat_raster',
@@ -119,6 +119,12 @@ ALTITUDE_CELLINFO_ARGTYPES = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
 # h_max, workspace, workspace_bytes, stream
 ALTITUDE_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.POINTER(SsrsAltitudeParams)] + \
     [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]
+
+
+# ssrs_rotor_encounters: traj, traj_offsets, ntracks, alt, cellinfo, rows, cols, turbines, reach, zband, nturb, bin_start,
+# bin_items, hits, first_step, points_per_turbine, stream
+ROTOR_ENCOUNTERS_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + \
+    [C.c_int] + [C.c_void_p] * 6
 
 
 class SsrsError(RuntimeError):
@@ -228,6 +234,8 @@ def lib():
         L.ssrs_track_altitude_workspace_bytes.restype = C.c_size_t
         L.ssrs_track_altitude_workspace_bytes.argtypes = [C.c_int64]
         L.ssrs_track_altitude.argtypes = ALTITUDE_ARGTYPES
+        if hasattr(L, 'ssrs_rotor_encounters'):
+            L.ssrs_rotor_encounters.argtypes = ROTOR_ENCOUNTERS_ARGTYPES
         L.ssrs_roam_pair_word_selftest.argtypes = [C.c_uint64] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
         L.ssrs_roam_tables_selftest.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 4
         L.ssrs_tracks_roam_feed_counts.restype = None

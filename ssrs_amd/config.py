@@ -34,7 +34,7 @@ _SECTIONS = (
                                     'fig_height', 'fig_dpi')),
     ('MI355X build', ('save_tracks', 'stepper_path', 'steps_per_launch', 'max_tracks_file_gb', 'track_occupancy',
                       'flight_height', 'flight_height_start', 'flight_height_floor', 'flight_height_ceiling',
-                      'flight_airspeed', 'flight_sink_rate', 'rotor_zone',
+                      'flight_airspeed', 'flight_sink_rate', 'rotor_zone', 'rotor_geometry', 'rotor_clearance',
                       'hist_safe_tracks', 'thermal_model', 'thermal_allen_zi', 'thermal_allen_wstar', 'thermal_allen_sink',
                       'turbine_encounter_radius')),
 )
@@ -122,6 +122,15 @@ class Config:
     flight_airspeed: float = 15.        # m/s, still air: a move of one cell takes resolution / airspeed seconds
     flight_sink_rate: float = -1.       # m/s lost in still air; < 0 = updraft_threshold
     rotor_zone: Tuple[float, float] = (30., 150.)   # metres above ground, both ends inclusive
+    rotor_geometry: str = 'band'        # band | turbine.  'band': rotor_zone, one height band above ground for all turbines.
+    #                                     'turbine' (needs flight_height=True and Simulator(turbines=...) with t_hh and t_rd):
+    #                                     simulate_tracks also tests every track point against each turbine's OWN cylinder --
+    #                                     within t_rd / 2 of it in the plane, and between t_hh -+ t_rd / 2 above the ground the
+    #                                     TURBINE stands on, in absolute heights -- and counts per turbine the tracks through it
+    #                                     and the points inside it (the exposure), on the device (limit 14):
+    #                                     <id>_turbine_rotor_encounters.npy, Simulator.compute_turbine_rotor_encounters().  The
+    #                                     two fields stand here, after rotor_zone, because tests pin the slots further down
+    rotor_clearance: float = 0.         # metres added to the rotor radius of 'turbine', in the plane and in height
     thermal_allen_zi: float = 0.        # thermal_model = 'allen': boundary-layer height zi in metres.  0 (snapshot / seasonal
     #                                     only) = the mean of the case's own blheight layer, clipped below at 100 m
     thermal_allen_wstar: float = 0.     # thermal_model = 'allen': convective velocity scale w* in m/s.  0 (snapshot / seasonal

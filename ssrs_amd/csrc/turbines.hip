@@ -15,6 +15,13 @@
 //     settled, an unknown one is tested with a load (bits are only ever set and steps only ever fall, so a stale
 //     read costs a redundant atomic, never a wrong result), and the lanes of a wave that still have news for
 //     the same word combine it before ONE atomic.
+//
+// K15 -- rotor encounters: the same walk (kRotor) with a cylinder per turbine instead of one disk for all.  The height
+// above ground of every point streams in next to it (4 B more), the elevation of its cell is gathered only in occupied
+// bins, and the test is reach_t in the plane and z_lo_t <= elev + alt <= z_hi_t in 64-bit millimetres.  The exposure
+// (points inside each cylinder) is counted without an atomic per point: a lane keeps ONE (turbine, count) pair in
+// registers across its points and spans and adds it to the block's uint32 counter in LDS only when the turbine changes
+// or the wave ends; the block adds its non-zero counters to the uint64 totals once, at its end.
 #include <climits>
 
 #include "common.h"
@@ -29,6 +36,7 @@ constexpr long long kTurbMinSpans = 4;        // spans per wave at least: small 
 // Nothing but speed depends on it: the blocks do not talk to each other.
 constexpr int kTurbBlocks = 256 * 6;
 constexpr int kTurbMaskWords = 8192;          // 32 KB of LDS: rasters of up to 262 144 bins keep the mask there
+constexpr int kRotorLdsWords = 15 * 1024;     // K15: mask and exposure counters (4 B a turbine) together, 60 KB
 
 __device__ __forceinline__ int wave_or(int v)
 {
@@ -63,40 +71,23 @@ struct TurbArgs {
     const int *bin_start, *bin_items;
     int rows, cols, nbc, nbins, words;
     uint32_t *hits, *first_step;
+    // kRotor only
+    const int32_t *alt;            // mm above ground, indexed like traj
+    const int32_t *cellinfo;       // {climb, elev} per cell
+    const double *reach;           // cells, per turbine
+    const int2 *zband;             // {z_lo, z_hi} mm above the datum, per turbine
+    unsigned long long *points;    // per turbine, or NULL
+    int cnt_off;                   // the block's counters: s_mask[cnt_off + turbine]
 };
 
-// kVec: 16-byte loads (traj is 16-byte aligned).  kMask: the occupied-bin mask fits LDS.
-template <bool kVec, bool kMask>
-__global__ __launch_bounds__(kBlock) void k_turbine_encounters(const TurbArgs a)
+// The walk of one wave over its spans (no barrier inside: a wave without spans returns at once).
+// kVec: 16-byte loads (traj, and alt with it, are 16-byte aligned).  kMask: the occupied-bin mask fits LDS.
+// kRotor: K15's cylinders; s_cnt = the block's exposure counters, or NULL when they are not asked for.
+template <bool kVec, bool kMask, bool kRotor>
+__device__ __forceinline__ void turbine_walk(const TurbArgs &a, const uint32_t *s_mask, uint32_t *s_cnt,
+                                             int (*s_mark)[kTurbSpan], const long long p0, const long long p1,
+                                             const long long a0, const long long nspans, const long long per_wave)
 {
-    extern __shared__ uint32_t s_mask[];
-    __shared__ alignas(16) int s_mark[kTurbWaves][kTurbSpan];       // (read and zeroed 16 bytes a lane)
-
-    const long long p0 = a.off[0], p1 = a.off[a.ntracks];
-    if (p0 < 0 || p1 <= p0) return;
-    // spans are cut at multiples of four points of the BUFFER, so that a lane's four points are one aligned load
-    const long long a0 = p0 & ~3LL;
-    const long long nspans = (p1 - a0 + kTurbSpan - 1) / kTurbSpan;
-    const long long nwaves = static_cast<long long>(gridDim.x) * kTurbWaves;
-    long long per_wave = (nspans + nwaves - 1) / nwaves;
-    per_wave = per_wave < kTurbMinSpans ? kTurbMinSpans : per_wave;
-    if (static_cast<long long>(blockIdx.x) * kTurbWaves * per_wave >= nspans) return;      // (the whole block)
-
-    if (kMask) {
-        for (int w = threadIdx.x; w < (a.nbins + 31) / 32; w += kBlock) {
-            uint32_t bits = 0;
-            const int b0 = w * 32, b1 = b0 + 32 < a.nbins ? b0 + 32 : a.nbins;
-            int lo = a.bin_start[b0];
-            for (int b = b0; b < b1; ++b) {
-                const int hi = a.bin_start[b + 1];
-                bits |= hi > lo ? 1u << (b - b0) : 0u;
-                lo = hi;
-            }
-            s_mask[w] = bits;
-        }
-        __syncthreads();
-    }
-
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
     int *mark = s_mark[wave];
@@ -131,16 +122,36 @@ __global__ __launch_bounds__(kBlock) void k_turbine_encounters(const TurbArgs a)
         if (i0 + 3 >= p0 && i0 + 3 < p1) v.w = a.traj[i0 + 3];
         return v;
     };
+    // (kRotor) the heights of the same four points, fetched the same way; without kRotor nothing is read
+    auto fetch_alt = [&](long long u) {
+        if constexpr (!kRotor) return make_int4(0, 0, 0, 0);
+        else return *reinterpret_cast<const int4 *>(a.alt + (a0 + u * kTurbSpan + 4 * lane));
+    };
+    auto fetch_alt_edge = [&](long long u) {
+        int4 v = make_int4(0, 0, 0, 0);
+        if constexpr (kRotor) {
+            const long long i0 = a0 + u * kTurbSpan + 4 * lane;
+            if (i0 + 0 >= p0 && i0 + 0 < p1) v.x = a.alt[i0 + 0];
+            if (i0 + 1 >= p0 && i0 + 1 < p1) v.y = a.alt[i0 + 1];
+            if (i0 + 2 >= p0 && i0 + 2 < p1) v.z = a.alt[i0 + 2];
+            if (i0 + 3 >= p0 && i0 + 3 < p1) v.w = a.alt[i0 + 3];
+        }
+        return v;
+    };
 
     // what this lane knows to be settled: the bits of one bitmap word, the first step of one track
     long long known_word = -1, known_track = -1, known_start = 0;
     uint32_t known_bits = 0, known_step = 0xFFFFFFFFu;
+    // (kRotor) the exposure this lane has not handed to the block yet: pend_cnt points inside turbine pend_tb
+    int pend_tb = 0;
+    uint32_t pend_cnt = 0;
 
-    // one span: `cur` its points, `t_end` = off[t + 1]
-    auto span = [&](const long long u, const uint4 cur, const long long t_end) {
+    // one span: `cur` its points (`cur_alt` their heights), `t_end` = off[t + 1]
+    auto span = [&](const long long u, const uint4 cur, const int4 cur_alt, const long long t_end) {
         const long long s = a0 + u * kTurbSpan, s_end = s + kTurbSpan;
         const long long i0 = s + 4 * lane;
         const uint32_t pts[4] = {cur.x, cur.y, cur.z, cur.w};
+        const int alts[4] = {cur_alt.x, cur_alt.y, cur_alt.z, cur_alt.w};
 
         // ---- the track of every point: off[t] <= max(s, p0), and every later track starts at or after s
         int rel[4] = {0, 0, 0, 0};
@@ -196,6 +207,14 @@ __global__ __launch_bounds__(kBlock) void k_turbine_encounters(const TurbArgs a)
                 k0 = a.bin_start[bin];
                 k1 = a.bin_start[bin + 1];
             }
+            long long z = 0;                      // (kRotor) the point's height above the datum, mm
+            if constexpr (kRotor) {
+                if (k0 < k1) {
+                    const int elev = a.cellinfo[2 * (static_cast<long long>(r) * a.cols + c) + 1];
+                    z = static_cast<long long>(elev) + alts[j];
+                    if (elev == INT_MIN) k1 = k0;  // nodata under the point: inside no cylinder
+                }
+            }
             const long long track = t + rel[j];
             bool in_any = false;
             while (__ballot(k0 < k1) != 0) {
@@ -206,10 +225,31 @@ __global__ __launch_bounds__(kBlock) void k_turbine_encounters(const TurbArgs a)
                     if (static_cast<unsigned>(tb) < static_cast<unsigned>(a.nturb)) {
                         const double dx = static_cast<double>(c) - a.turb[2 * tb];
                         const double dy = static_cast<double>(r) - a.turb[2 * tb + 1];
-                        hit = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)) <= a.r2;
+                        const double d2 = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
+                        if constexpr (kRotor) {
+                            const double reach = a.reach[tb];
+                            hit = reach >= 0.0 && d2 <= __dmul_rn(reach, reach);
+                            if (hit) {
+                                const int2 zb = a.zband[tb];
+                                hit = z >= zb.x && z <= zb.y;
+                            }
+                        } else {
+                            hit = d2 <= a.r2;
+                        }
                     }
                 }
                 in_any |= hit;
+                if constexpr (kRotor) {
+                    // ---- exposure: one more point inside tb; the block hears of it when the lane moves to another turbine
+                    if (hit && s_cnt != nullptr) {
+                        if (tb != pend_tb && pend_cnt != 0) {
+                            atomicAdd(&s_cnt[pend_tb], pend_cnt);
+                            pend_cnt = 0;
+                        }
+                        pend_tb = tb;
+                        ++pend_cnt;
+                    }
+                }
                 // ---- hits: bit tb of the track's row
                 const long long word = track * a.words + (tb >> 5);
                 const uint32_t bit = 1u << (tb & 31);
@@ -276,15 +316,68 @@ __global__ __launch_bounds__(kBlock) void k_turbine_encounters(const TurbArgs a)
         const long long u_vec = u1 < whole ? u1 : whole;
         if (u < u_vec) {
             uint4 next = fetch(u);
+            int4 next_alt = fetch_alt(u);
             for (; u < u_vec; ++u) {
                 const uint4 cur = next;
+                const int4 cur_alt = next_alt;
                 const long long t_end = a.off[t + 1];
                 next = fetch(u + 1 < u_vec ? u + 1 : u);
-                span(u, cur, t_end);
+                next_alt = fetch_alt(u + 1 < u_vec ? u + 1 : u);
+                span(u, cur, cur_alt, t_end);
             }
         }
     }
-    for (; u < u1; ++u) span(u, fetch_edge(u), a.off[t + 1]);
+    for (; u < u1; ++u) span(u, fetch_edge(u), fetch_alt_edge(u), a.off[t + 1]);
+    if constexpr (kRotor) {
+        if (pend_cnt != 0) atomicAdd(&s_cnt[pend_tb], pend_cnt);
+    }
+}
+
+template <bool kVec, bool kMask, bool kRotor>
+__global__ __launch_bounds__(kBlock) void k_turbine_encounters(const TurbArgs a)
+{
+    extern __shared__ uint32_t s_mask[];
+    __shared__ alignas(16) int s_mark[kTurbWaves][kTurbSpan];       // (read and zeroed 16 bytes a lane)
+
+    const long long p0 = a.off[0], p1 = a.off[a.ntracks];
+    if (p0 < 0 || p1 <= p0) return;
+    // spans are cut at multiples of four points of the BUFFER, so that a lane's four points are one aligned load
+    const long long a0 = p0 & ~3LL;
+    const long long nspans = (p1 - a0 + kTurbSpan - 1) / kTurbSpan;
+    const long long nwaves = static_cast<long long>(gridDim.x) * kTurbWaves;
+    long long per_wave = (nspans + nwaves - 1) / nwaves;
+    per_wave = per_wave < kTurbMinSpans ? kTurbMinSpans : per_wave;
+    if (static_cast<long long>(blockIdx.x) * kTurbWaves * per_wave >= nspans) return;      // (the whole block)
+
+    if (kMask) {
+        for (int w = threadIdx.x; w < (a.nbins + 31) / 32; w += kBlock) {
+            uint32_t bits = 0;
+            const int b0 = w * 32, b1 = b0 + 32 < a.nbins ? b0 + 32 : a.nbins;
+            int lo = a.bin_start[b0];
+            for (int b = b0; b < b1; ++b) {
+                const int hi = a.bin_start[b + 1];
+                bits |= hi > lo ? 1u << (b - b0) : 0u;
+                lo = hi;
+            }
+            s_mask[w] = bits;
+        }
+    }
+    // (kRotor) the block's exposure counters, uint32: a block walks far fewer than 2^32 points
+    uint32_t *s_cnt = kRotor && a.points != nullptr ? s_mask + a.cnt_off : nullptr;
+    if (s_cnt != nullptr)
+        for (int tb = threadIdx.x; tb < a.nturb; tb += kBlock) s_cnt[tb] = 0;
+    if (kMask || kRotor) __syncthreads();
+
+    turbine_walk<kVec, kMask, kRotor>(a, s_mask, s_cnt, s_mark, p0, p1, a0, nspans, per_wave);
+
+    if constexpr (kRotor) {
+        // every wave of the block arrives here: one 64-bit add per turbine the block met
+        if (s_cnt != nullptr) {
+            __syncthreads();
+            for (int tb = threadIdx.x; tb < a.nturb; tb += kBlock)
+                if (s_cnt[tb] != 0) atomicAdd(a.points + tb, static_cast<unsigned long long>(s_cnt[tb]));
+        }
+    }
 }
 
 // turbines_per_track[k] = popcount of row k (bits at and above nturb are not counted)
@@ -324,6 +417,39 @@ __global__ __launch_bounds__(kBlock) void k_tracks_per_turbine(const uint32_t *_
         if (s_count[t]) atomicAdd(&out[t], static_cast<unsigned long long>(s_count[t]));
 }
 
+// what both walks take: the trajectories, the turbines, the cull lists and the per-track outputs
+static TurbArgs walk_args(const int16_t *traj, const int64_t *traj_offsets, int64_t ntracks, const double *turbines,
+                          int nturb, const int32_t *bin_start, const int32_t *bin_items, int rows, int cols,
+                          uint32_t *hits, int32_t *first_step)
+{
+    TurbArgs a = {};
+    a.traj = reinterpret_cast<const uint32_t *>(traj);
+    a.off = reinterpret_cast<const long long *>(traj_offsets);
+    a.ntracks = ntracks;
+    a.turb = turbines;
+    a.nturb = nturb;
+    a.bin_start = bin_start;
+    a.bin_items = bin_items;
+    a.rows = rows;
+    a.cols = cols;
+    a.nbc = (cols + SSRS_TURBINE_BIN - 1) / SSRS_TURBINE_BIN;
+    a.nbins = (rows + SSRS_TURBINE_BIN - 1) / SSRS_TURBINE_BIN * a.nbc;
+    a.words = (nturb + 31) / 32;
+    a.hits = hits;
+    a.first_step = reinterpret_cast<uint32_t *>(first_step);
+    return a;
+}
+
+template <bool kRotor>
+static void launch_encounters(const TurbArgs &a, bool vec, bool mask, size_t lds, hipStream_t st)
+{
+    const dim3 grid(kTurbBlocks), block(kBlock);
+    if (vec && mask) hipLaunchKernelGGL((k_turbine_encounters<true, true, kRotor>), grid, block, lds, st, a);
+    else if (vec) hipLaunchKernelGGL((k_turbine_encounters<true, false, kRotor>), grid, block, lds, st, a);
+    else if (mask) hipLaunchKernelGGL((k_turbine_encounters<false, true, kRotor>), grid, block, lds, st, a);
+    else hipLaunchKernelGGL((k_turbine_encounters<false, false, kRotor>), grid, block, lds, st, a);
+}
+
 }  // namespace ssrs
 
 using namespace ssrs;
@@ -346,32 +472,49 @@ extern "C" int ssrs_turbine_encounters(const int16_t *traj, const int64_t *traj_
     SSRS_REQUIRE(radius_cells >= 0.0, "ssrs_turbine_encounters: radius_cells is negative or NaN");
     SSRS_REQUIRE((reinterpret_cast<uintptr_t>(traj) & 3u) == 0, "ssrs_turbine_encounters: traj must be 4-byte aligned");
     if (ntracks == 0) return SSRS_OK;
-    TurbArgs a;
-    a.traj = reinterpret_cast<const uint32_t *>(traj);
-    a.off = reinterpret_cast<const long long *>(traj_offsets);
-    a.ntracks = ntracks;
-    a.turb = turbines;
-    a.nturb = nturb;
+    TurbArgs a = walk_args(traj, traj_offsets, ntracks, turbines, nturb, bin_start, bin_items, rows, cols, hits, first_step);
     a.r2 = radius_cells * radius_cells;
-    a.bin_start = bin_start;
-    a.bin_items = bin_items;
-    a.rows = rows;
-    a.cols = cols;
-    a.nbc = (cols + SSRS_TURBINE_BIN - 1) / SSRS_TURBINE_BIN;
-    a.nbins = (rows + SSRS_TURBINE_BIN - 1) / SSRS_TURBINE_BIN * a.nbc;
-    a.words = (nturb + 31) / 32;
-    a.hits = hits;
-    a.first_step = reinterpret_cast<uint32_t *>(first_step);
     const bool vec = (reinterpret_cast<uintptr_t>(traj) & 15u) == 0;
     const int mask_words = (a.nbins + 31) / 32;
     const bool mask = mask_words <= kTurbMaskWords;
-    const size_t lds = mask ? static_cast<size_t>(mask_words) * 4 : 0;
-    hipStream_t st = as_stream(stream);
-    const dim3 grid(kTurbBlocks), block(kBlock);
-    if (vec && mask) hipLaunchKernelGGL((k_turbine_encounters<true, true>), grid, block, lds, st, a);
-    else if (vec) hipLaunchKernelGGL((k_turbine_encounters<true, false>), grid, block, lds, st, a);
-    else if (mask) hipLaunchKernelGGL((k_turbine_encounters<false, true>), grid, block, lds, st, a);
-    else hipLaunchKernelGGL((k_turbine_encounters<false, false>), grid, block, lds, st, a);
+    launch_encounters<false>(a, vec, mask, mask ? static_cast<size_t>(mask_words) * 4 : 0, as_stream(stream));
+    SSRS_HIP_CHECK(hipGetLastError());
+    return SSRS_OK;
+}
+
+extern "C" int ssrs_rotor_encounters(const int16_t *traj, const int64_t *traj_offsets, int64_t ntracks, const int32_t *alt,
+                                     const int32_t *cellinfo, int rows, int cols, const double *turbines,
+                                     const double *reach, const int32_t *zband, int nturb, const int32_t *bin_start,
+                                     const int32_t *bin_items, uint32_t *hits, int32_t *first_step,
+                                     uint64_t *points_per_turbine, void *stream)
+{
+    SSRS_REQUIRE(traj && traj_offsets && alt && cellinfo && turbines && reach && zband && bin_start && bin_items && hits,
+                 "ssrs_rotor_encounters: NULL pointer");
+    SSRS_REQUIRE(ntracks >= 0 && ntracks <= INT32_MAX, "ssrs_rotor_encounters: ntracks = %lld outside [0, 2^31)",
+                 static_cast<long long>(ntracks));
+    SSRS_REQUIRE(nturb >= 1 && nturb <= SSRS_TURBINE_MAX, "ssrs_rotor_encounters: nturb = %d outside [1, %d]", nturb,
+                 SSRS_TURBINE_MAX);
+    SSRS_REQUIRE(rows >= 1 && rows <= 32767 && cols >= 1 && cols <= 32767,
+                 "ssrs_rotor_encounters: a %d x %d raster (int16 points: 1..32767 either way)", rows, cols);
+    SSRS_REQUIRE((reinterpret_cast<uintptr_t>(traj) & 3u) == 0 && (reinterpret_cast<uintptr_t>(alt) & 3u) == 0,
+                 "ssrs_rotor_encounters: traj and alt must be 4-byte aligned");
+    SSRS_REQUIRE((reinterpret_cast<uintptr_t>(cellinfo) & 7u) == 0 && (reinterpret_cast<uintptr_t>(zband) & 7u) == 0 &&
+                     (reinterpret_cast<uintptr_t>(points_per_turbine) & 7u) == 0,
+                 "ssrs_rotor_encounters: cellinfo, zband and points_per_turbine must be 8-byte aligned");
+    if (ntracks == 0) return SSRS_OK;
+    TurbArgs a = walk_args(traj, traj_offsets, ntracks, turbines, nturb, bin_start, bin_items, rows, cols, hits, first_step);
+    a.alt = alt;
+    a.cellinfo = cellinfo;
+    a.reach = reach;
+    a.zband = reinterpret_cast<const int2 *>(zband);
+    a.points = reinterpret_cast<unsigned long long *>(points_per_turbine);
+    const bool vec = ((reinterpret_cast<uintptr_t>(traj) | reinterpret_cast<uintptr_t>(alt)) & 15u) == 0;
+    // mask and counters share the dynamic LDS; together with the 4 KB of marks a block stays within 64 KB
+    const int mask_words = (a.nbins + 31) / 32;
+    const int cnt_words = a.points ? nturb : 0;
+    const bool mask = mask_words <= kTurbMaskWords && mask_words + cnt_words <= kRotorLdsWords;
+    a.cnt_off = mask ? mask_words : 0;
+    launch_encounters<true>(a, vec, mask, static_cast<size_t>(a.cnt_off + cnt_words) * 4, as_stream(stream));
     SSRS_HIP_CHECK(hipGetLastError());
     return SSRS_OK;
 }

@@ -18,6 +18,7 @@ import json
 import os
 import pickle
 import time
+import warnings
 from dataclasses import asdict
 
 import numpy as np
@@ -78,6 +79,7 @@ class Simulator(Config):
             raise ValueError(f'turbine_encounter_radius = {self.turbine_encounter_radius!r}: expected metres >= 0 (0 = off)')
         if self.flight_height:
             self._flight_params()
+        self._check_rotor_geometry(turbines)
         print(f'\n---- SSRS in {self.sim_mode} mode')
         print(f'Run name: {self.run_name}')
         if self.sim_seed >= 0:                                    # simulator.py:50-52
@@ -129,6 +131,8 @@ class Simulator(Config):
         self.rotor_presence_counts = {}   # (case_id, real_id) -> int32 (rows, cols) holding uint32: points in the rotor zone
         self.flight_heights = {}          # (case_id, real_id) -> int32 (this rank's tracks, 3): [in zone, h_min, h_max] in mm
         self.rotor_turbine_encounters = {}  # as turbine_encounters, of the points in the rotor zone only
+        self.turbine_rotor_encounters = {}  # rotor_geometry='turbine': (case_id, real_id) -> dict(tracks_per_turbine,
+        #                                     points_per_turbine int64, turbines_per_track, first_step int32)
         self.wtk_layers = {
             'wspeed': f'windspeed_{str(int(self.wtk_orographic_height))}m',
             'wdirn': f'winddirection_{str(int(self.wtk_orographic_height))}m',
@@ -217,9 +221,28 @@ class Simulator(Config):
                              'nothing about where the grid lies on the ellipsoid')
         return self.projection
 
+    def _rotor_per_turbine(self):
+        return str(self.rotor_geometry).lower() == 'turbine'
+
+    def _check_rotor_geometry(self, turbines):
+        """rotor_geometry / rotor_clearance, and what 'turbine' needs that can be told before anything is computed."""
+        if str(self.rotor_geometry).lower() not in ('band', 'turbine'):
+            raise ValueError(f"rotor_geometry = {self.rotor_geometry!r}: expected 'band' or 'turbine'")
+        if not self._rotor_per_turbine():
+            return
+        clearance = float(self.rotor_clearance)
+        if clearance != clearance or clearance in (float('inf'), float('-inf')):
+            raise ValueError(f'rotor_clearance = {self.rotor_clearance!r}: expected metres')
+        if not self.flight_height:
+            raise ValueError("rotor_geometry = 'turbine' needs flight_height=True: the cylinders are tested against the "
+                             'heights along the tracks')
+        if turbines is None:
+            raise ValueError("rotor_geometry = 'turbine' needs turbines: none were given (Simulator(..., turbines=...))")
+
     def _resolve_turbines(self, turbines):
         """The injected turbines inside `bounds` at or above `turbine_minimum_hubheight` (None stays None); with
-        turbine_encounter_radius > 0 also their cell coordinates and the cull lists of the encounter kernel."""
+        turbine_encounter_radius > 0 also their cell coordinates and the cull lists of the encounter kernel; with
+        rotor_geometry = 'turbine' their cylinders (turbines.rotor_geometry) and the cull lists from the per-turbine reach."""
         radius = float(self.turbine_encounter_radius)
         if turbines is not None and turbines_mod.has_lonlat_only(turbines):
             # the USWTDB columns, projected as turbines.py:52-62 of the reference does
@@ -238,6 +261,23 @@ class Simulator(Config):
             self._turbine_cells = turbines.cell_coordinates(self.bounds, self.resolution)
             self._turbine_bins = turbines_mod.build_bins(self._turbine_cells, radius / float(self.resolution),
                                                          self.gridsize)
+        if self._rotor_per_turbine():
+            if len(turbines) == 0:
+                raise ValueError("rotor_geometry = 'turbine' needs turbines: none of those given lies inside the bounds at "
+                                 'or above turbine_minimum_hubheight')
+            if len(turbines) > turbines_mod.MAX_TURBINES:
+                raise ValueError(f'{len(turbines)} turbines inside the bounds: rotor encounters are counted for at most '
+                                 f'{turbines_mod.MAX_TURBINES}')
+            dem = self._terrain['Elevation']
+            reach, zband = turbines_mod.rotor_geometry(turbines, dem, self.bounds, self.resolution,
+                                                       float(self.rotor_clearance))
+            cells = turbines.cell_coordinates(self.bounds, self.resolution)
+            rb, cb, known = turbines_mod.base_cells(cells, self.gridsize)
+            nodata = int((np.isnan(dem[rb, cb]) | ~known).sum())
+            if nodata:
+                warnings.warn(f"rotor_geometry = 'turbine': {nodata} of the {len(turbines)} turbines stand on a nodata cell "
+                              'of the DEM; their cylinders are empty and nothing encounters them')
+            self._rotor_cylinders = (cells, reach, zband, turbines_mod.build_bins(cells, reach, self.gridsize))
         return turbines
 
     THERMAL_LAYERS = inputs.THERMAL_LAYERS      # keys of wtk_layers
@@ -747,6 +787,11 @@ class Simulator(Config):
             # (one upload for all cases: the kernel reads the turbines and their cull lists from the device)
             enc_geometry = (to_dev(self._turbine_cells, torch.float64),
                             tuple(to_dev(a, torch.int32) for a in self._turbine_bins))
+        rotor = None
+        if self._rotor_per_turbine():
+            cells, reach, zband, bins = self._rotor_cylinders
+            rotor = (to_dev(cells, torch.float64), to_dev(reach, torch.float64), to_dev(zband, torch.int32),
+                     tuple(to_dev(a, torch.int32) for a in bins))
         occupancy = bool(self.track_occupancy)
         heights = bool(self.flight_height)
         if heights:
@@ -783,7 +828,14 @@ class Simulator(Config):
                     if encounters:
                         fly['hits'] = torch.zeros_like(hits)
                         fly['first_step'] = torch.full_like(first_step, -1)
-                    consumers.append(self._flight_consumer(lift, dem, fly, enc_geometry if encounters else None))
+                    if rotor is not None:
+                        # every turbine's own cylinder: a third bitmap, and the points inside each (the exposure)
+                        n_rotor = int(rotor[0].shape[0])
+                        fly['rotor_hits'] = torch.zeros((hi - lo, (n_rotor + 31) // 32), dtype=torch.int32,
+                                                        device=my_starts.device)
+                        fly['rotor_first_step'] = torch.full((hi - lo,), -1, dtype=torch.int32, device=my_starts.device)
+                        fly['rotor_points'] = torch.zeros(n_rotor, dtype=torch.int64, device=my_starts.device)
+                    consumers.append(self._flight_consumer(lift, dem, fly, enc_geometry if encounters else None, rotor))
                 chunks = self._device_chunks(batch, consumers) if consumers else None
                 if self.save_tracks:
                     # (inside the stream's scope: long trajectories are stepped again range by range while written)
@@ -898,18 +950,25 @@ class Simulator(Config):
         flight.height_params(who='Config.flight_height_* / rotor_zone', **kw)
         return kw, airspeed, sink
 
-    def _flight_consumer(self, lift, dem, fly, geometry):
+    def _flight_consumer(self, lift, dem, fly, geometry, rotor=None):
         """A chunk through the flight-height scan (K14): `fly['band_hist']` is added to, the chunk's tracks get their rows of
         `fly['rows']`; with `geometry` the points in the rotor zone go through the encounter kernel into `fly['hits']` /
-        `fly['first_step']`.  The item's cellinfo is built here, from its un-thresholded updraft `lift` and the DEM."""
+        `fly['first_step']`; with `rotor` (the cylinders on the device) the points and their heights go through the rotor
+        kernel (K15) into `fly['rotor_hits']` / `fly['rotor_first_step']` / `fly['rotor_points']`.  The item's cellinfo is
+        built here, from its un-thresholded updraft `lift` and the DEM."""
         kw, airspeed, sink = self._flight_params()
         cellinfo = flight.altitude_cellinfo(lift, dem, self.resolution, airspeed, sink)
         radius_cells = float(self.turbine_encounter_radius) / float(self.resolution)
 
         def consume(t0, t1, traj, off):
             out = flight.compute_track_altitudes(traj, cellinfo, self.gridsize, offsets=off, band_hist=fly['band_hist'],
-                                                 want_masked=geometry is not None, **kw)
+                                                 want_masked=geometry is not None, want_alt=rotor is not None, **kw)
             fly['rows'][t0:t1] = out['heights']
+            if rotor is not None:
+                cells, reach, zband, rotor_bins = rotor
+                turbines_mod.rotor_encounters(traj, out['alt'], off, cellinfo, cells, reach, zband, self.gridsize,
+                                              bins=rotor_bins, hits=fly['rotor_hits'][t0:t1],
+                                              first_step=fly['rotor_first_step'][t0:t1], points=fly['rotor_points'])
             if geometry is not None:
                 xy, bins = geometry
                 turbines_mod.turbine_encounters(out['masked'], off, xy, radius_cells, self.gridsize, bins=bins,
@@ -949,6 +1008,19 @@ class Simulator(Config):
                 first_step=fly['first_step'].cpu().numpy().astype(np.int32))
             if writes:
                 np.save(os.path.join(self.mode_data_dir, f'{id_str}_rotor_turbine_encounters.npy'), per_turbine)
+        if 'rotor_hits' in fly:
+            # rotor_geometry = 'turbine': <id>_turbine_rotor_encounters.npy, int64 (nturb, 2) [tracks, points]; track-sharded
+            # runs sum both columns over the ranks, the per-track rows stay this rank's
+            per_turbine, per_track = turbines_mod.encounter_counts(fly['rotor_hits'], int(fly['rotor_points'].numel()))
+            both = torch.stack([per_turbine, fly['rotor_points']], 1).cpu().numpy().astype(np.int64)
+            if sharded:
+                both = np.asarray(self._allreduce_sum(both.reshape(-1)), dtype=np.int64).reshape(-1, 2)
+            self.turbine_rotor_encounters[key] = dict(
+                tracks_per_turbine=both[:, 0].copy(), points_per_turbine=both[:, 1].copy(),
+                turbines_per_track=per_track.cpu().numpy().astype(np.int32),
+                first_step=fly['rotor_first_step'].cpu().numpy().astype(np.int32))
+            if writes:
+                np.save(os.path.join(self.mode_data_dir, f'{id_str}_turbine_rotor_encounters.npy'), both)
 
     def _store_occupancy(self, case_id, real_id, counts, cells, sharded):
         """Keeps the occupancy raster of one (case, realisation) as numpy int32 and writes <id>_occupancy.npy.  Checked
@@ -1205,6 +1277,30 @@ class Simulator(Config):
         out = total[:-1] / total[-1]
         if self._rank() == 0:
             np.save(os.path.join(self.mode_data_dir, 'summary_turbine_encounters.npy'), out)
+        self._barrier()
+        return out
+
+    def compute_turbine_rotor_encounters(self):
+        """Per turbine, the share of the simulated tracks that passed through its own rotor cylinder and the points they
+        spent inside it per simulated track (rotor_geometry = 'turbine'): f64 (nturb, 2), the mean over all
+        (case, realisation) items of [tracks_per_turbine, points_per_turbine] / track_count, in the order of
+        `turbines.get_locations()`; case-sharded runs take the mean over every rank's items.  Writes
+        summary_turbine_rotor_encounters.npy.  ValueError when simulate_tracks computed none."""
+        if not self.turbine_rotor_encounters:
+            raise ValueError("no rotor encounters were computed: run simulate_tracks() with flight_height=True, "
+                             "rotor_geometry='turbine' and turbines")
+        items = [self.turbine_rotor_encounters[key] for key in sorted(self.turbine_rotor_encounters)]
+        nturb = items[0]['tracks_per_turbine'].size
+        total = np.zeros(2 * nturb + 1, dtype=np.float64)                  # [tracks ..., points ..., number of items]
+        for enc in items:
+            total[:nturb] += enc['tracks_per_turbine'] / float(self.track_count)
+            total[nturb:-1] += enc['points_per_turbine'] / float(self.track_count)
+            total[-1] += 1.
+        if self._world() > 1 and not self._shards_tracks():
+            total = self._allreduce_sum(total)                      # the cases of the other ranks
+        out = np.ascontiguousarray((total[:-1] / total[-1]).reshape(2, nturb).T)
+        if self._rank() == 0:
+            np.save(os.path.join(self.mode_data_dir, 'summary_turbine_rotor_encounters.npy'), out)
         self._barrier()
         return out
 

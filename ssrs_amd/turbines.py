@@ -149,15 +149,23 @@ def windplant_window(xloc, yloc, pad, bounds, resolution, gridsize):
 
 
 def build_bins(xy_cells, radius_cells, gridshape):
-    """The cull lists of ssrs_turbine_encounters: (bin_start int32 (nbr * nbc + 1), bin_items int32), a CSR over bins
-    of 32 x 32 cells listing, in ascending order, the turbines whose disk can reach a cell of the bin.
+    """The cull lists of ssrs_turbine_encounters / ssrs_rotor_encounters: (bin_start int32 (nbr * nbc + 1), bin_items
+    int32), a CSR over bins of 32 x 32 cells listing, in ascending order, the turbines whose disk can reach a cell of the
+    bin.  radius_cells: one radius for all (a negative or NaN one raises), or one per turbine (nturb,) -- there a NaN or
+    negative entry puts its turbine in no list.
     Conservative: the disk's bounding box, one cell wider on every side than the real numbers ask for (the exact
     test rounds c - xt before it squares), against the bin's cells.  A turbine with a NaN coordinate is in no list."""
     rows, cols = int(gridshape[0]), int(gridshape[1])
     xy = np.asarray(xy_cells, dtype=np.float64).reshape(-1, 2)
-    radius = float(radius_cells)
-    if not radius >= 0.:
-        raise ValueError(f'radius_cells = {radius_cells!r}: expected a number >= 0')
+    if np.ndim(radius_cells) == 0:
+        if not float(radius_cells) >= 0.:
+            raise ValueError(f'radius_cells = {radius_cells!r}: expected a number >= 0')
+        radius = np.full(xy.shape[0], float(radius_cells))
+    else:
+        radius = np.asarray(radius_cells, dtype=np.float64).reshape(-1)
+        if radius.shape != (xy.shape[0],):
+            raise ValueError(f'radius_cells has {radius.size} entries for {xy.shape[0]} turbines')
+        radius = np.where(radius >= 0., radius, np.nan)          # (NaN travels through the box below into `ok`)
     nbr, nbc = -(-rows // BIN), -(-cols // BIN)
     bins, items = [], []
     # first / last cell of the widened box, clipped to the raster (in floats first: coordinates may be huge)
@@ -178,7 +186,7 @@ def build_bins(xy_cells, radius_cells, gridshape):
     bins = np.concatenate(bins) if bins else np.zeros(0, dtype=np.int64)
     items = np.concatenate(items) if items else np.zeros(0, dtype=np.int32)
     if bins.size >= 2 ** 31:
-        raise ValueError(f'build_bins: {bins.size} list entries do not fit int32 (radius_cells = {radius})')
+        raise ValueError(f'build_bins: {bins.size} list entries do not fit int32 (radius_cells up to {np.nanmax(radius)})')
     order = np.argsort(bins, kind='stable')                # turbines were appended in ascending order
     bin_start = np.zeros(nbr * nbc + 1, dtype=np.int64)
     np.cumsum(np.bincount(bins, minlength=nbr * nbc), out=bin_start[1:])
@@ -258,3 +266,121 @@ def encounter_counts(hits, nturb):
         nat.check(nat.lib().ssrs_turbine_encounter_counts(
             nat.ptr(h), C.c_int64(ntracks), nturb, nat.ptr(per_turbine), nat.ptr(per_track), stream_ptr()))
     return per_turbine, per_track
+
+
+def base_cells(xy_cells, gridshape):
+    """(rb, cb, known): the cell a turbine stands on -- the nearest one, clamped into the raster -- and whether both of its
+    coordinates are numbers (rb = cb = 0 where not)."""
+    rows, cols = int(gridshape[0]), int(gridshape[1])
+    xy = np.asarray(xy_cells, dtype=np.float64).reshape(-1, 2)
+    known = ~np.isnan(xy).any(1)
+    rb = np.clip(np.rint(np.where(known, xy[:, 1], 0.)), 0, rows - 1).astype(np.int64)
+    cb = np.clip(np.rint(np.where(known, xy[:, 0], 0.)), 0, cols - 1).astype(np.int64)
+    return rb, cb, known
+
+
+def _mm(metres):
+    """rint(1000 x) as int64, NaN -> 0 (the caller masks it), clipped far inside int64."""
+    with np.errstate(invalid='ignore'):
+        v = np.clip(np.rint(1000. * np.asarray(metres, dtype=np.float64)), -2. ** 62, 2. ** 62)
+    return np.where(np.isnan(v), 0., v).astype(np.int64)
+
+
+def rotor_geometry(turbines, dem, bounds, resolution, clearance=0.):
+    """The cylinders of ssrs_rotor_encounters from a `Turbines` with `t_hh` and `t_rd`: (reach f64 (nturb,) in cells, zband
+    int32 (nturb, 2) in mm above the DEM's datum).  rad = t_rd / 2 + clearance metres; reach = rad / resolution; the band
+    is [base + mm(t_hh - rad), base + mm(t_hh + rad)] with mm(x) = rint(1000 x), summed in int64 and clipped to int32,
+    where base is the elevation of the cell the turbine stands on (base_cells) by cellinfo's own formula,
+    clip(rint(1000 z), +-2^30).  A NaN base (nodata), t_hh or t_rd gives the empty band (1, 0) and reach = NaN: such a
+    turbine is hit by nothing.  dem: numpy or a device tensor (rows, cols); only nturb of its values are gathered."""
+    missing = [name for name in ('t_hh', 't_rd') if name not in turbines.columns]
+    if missing:
+        raise ValueError(f'rotor_geometry: the turbines have no column {" / ".join(missing)} '
+                         '(t_hh = hub height, t_rd = rotor diameter, metres)')
+    resolution, clearance = float(resolution), float(clearance)
+    if not resolution > 0. or clearance != clearance:
+        raise ValueError(f'rotor_geometry: resolution = {resolution!r}, clearance = {clearance!r} (resolution > 0)')
+    if len(np.shape(dem)) != 2:
+        raise ValueError(f'rotor_geometry: dem has shape {tuple(np.shape(dem))}, expected (rows, cols)')
+    rb, cb, known = base_cells(turbines.cell_coordinates(bounds, resolution), np.shape(dem))
+    if is_tensor(dem):
+        z = dem[torch.from_numpy(rb).to(dem.device), torch.from_numpy(cb).to(dem.device)].cpu().numpy()
+    else:
+        z = np.asarray(dem)[rb, cb]
+    z = np.where(known, z.astype(np.float64), np.nan)
+    hh = np.asarray(turbines.columns['t_hh'], dtype=np.float64)
+    rad = np.asarray(turbines.columns['t_rd'], dtype=np.float64) / 2. + clearance
+    empty = np.isnan(z) | np.isnan(hh) | np.isnan(rad)
+    base = np.clip(_mm(z), -2 ** 30, 2 ** 30)
+    i32 = np.iinfo(np.int32)
+    z_lo = np.clip(base + _mm(hh - rad), i32.min, i32.max)
+    z_hi = np.clip(base + _mm(hh + rad), i32.min, i32.max)
+    zband = np.stack([np.where(empty, 1, z_lo), np.where(empty, 0, z_hi)], 1).astype(np.int32)
+    return np.where(empty, np.nan, rad / resolution), zband
+
+
+def rotor_encounters(traj, alt, offsets, cellinfo, xy_cells, reach, zband, gridshape, bins=None, hits=None, first_step=None,
+                     points=None):
+    """ssrs_rotor_encounters on device tensors (K15): the tracks through every turbine's own cylinder, and the points inside
+    it.  traj, offsets, xy_cells, bins, hits and first_step as turbine_encounters takes them; alt int32 (points) as
+    flight.compute_track_altitudes(want_alt=True) gives it, indexed like traj; cellinfo of flight.altitude_cellinfo; reach
+    (nturb,) f64 and zband (nturb, 2) int32 of rotor_geometry.  bins are built here from `reach` when None.  points: int64
+    device tensor (nturb,), ADDED to when given (the exposure).  first_step=False / points=False leave that output out
+    (None is returned in its place).  Returns (hits, first_step, points)."""
+    who = 'rotor_encounters'
+    rows, cols = int(gridshape[0]), int(gridshape[1])
+    xy = xy_cells if is_tensor(xy_cells) else np.asarray(xy_cells, dtype=np.float64).reshape(-1, 2)
+    xy = to_dev(xy, torch.float64).reshape(-1, 2)
+    nturb = int(xy.shape[0])
+    if not 1 <= nturb <= MAX_TURBINES:
+        raise ValueError(f'{who}: {nturb} turbines, expected 1 to {MAX_TURBINES}')
+    reach_dev = to_dev(reach if is_tensor(reach) else np.asarray(reach, dtype=np.float64), torch.float64).reshape(-1)
+    zband_dev = to_dev(zband if is_tensor(zband) else np.asarray(zband, dtype=np.int32), torch.int32)
+    if int(reach_dev.numel()) != nturb or tuple(zband_dev.shape) != (nturb, 2):
+        raise ValueError(f'{who}: reach has {reach_dev.numel()} entries and zband shape {tuple(zband_dev.shape)} for '
+                         f'{nturb} turbines, expected ({nturb},) and ({nturb}, 2)')
+    off = to_dev(offsets, torch.int64).reshape(-1)
+    ntracks = int(off.numel()) - 1
+    if ntracks < 0:
+        raise ValueError(f'{who}: offsets needs at least one entry')
+    pts = to_dev(traj, torch.int16).reshape(-1, 2)
+    heights = to_dev(alt, torch.int32).reshape(-1)
+    if int(heights.numel()) != int(pts.shape[0]):
+        raise ValueError(f'{who}: alt has {heights.numel()} entries for {pts.shape[0]} points (it is indexed like traj)')
+    if not is_tensor(cellinfo) or cellinfo.dtype != torch.int32 or tuple(cellinfo.shape) != (rows, cols, 2) or \
+            not cellinfo.is_contiguous() or not cellinfo.is_cuda:
+        raise ValueError(f'{who}: cellinfo must be a contiguous int32 device tensor ({rows}, {cols}, 2) (altitude_cellinfo)')
+    words = (nturb + 31) // 32
+    dev = device()
+    if hits is None:
+        hits = torch.zeros((ntracks, words), dtype=torch.int32, device=dev)
+    if first_step is None:
+        first_step = torch.full((ntracks,), -1, dtype=torch.int32, device=dev)
+    if points is None:
+        points = torch.zeros(nturb, dtype=torch.int64, device=dev)
+    first_step = None if first_step is False else first_step
+    points = None if points is False else points
+    if hits.dtype != torch.int32 or tuple(hits.shape) != (ntracks, words) or not hits.is_contiguous() or not hits.is_cuda:
+        raise ValueError(f'{who}: hits must be a contiguous int32 device tensor ({ntracks}, {words})')
+    if first_step is not None and (first_step.dtype != torch.int32 or tuple(first_step.shape) != (ntracks,) or
+                                   not first_step.is_contiguous() or not first_step.is_cuda):
+        raise ValueError(f'{who}: first_step must be a contiguous int32 device tensor ({ntracks},)')
+    if points is not None and (points.dtype != torch.int64 or tuple(points.shape) != (nturb,) or
+                               not points.is_contiguous() or not points.is_cuda):
+        raise ValueError(f'{who}: points must be a contiguous int64 device tensor ({nturb},)')
+    nbins = -(-rows // BIN) * -(-cols // BIN)
+    if bins is None:
+        bins = build_bins(xy.cpu().numpy(), reach_dev.cpu().numpy(), gridshape)
+    if not is_tensor(bins[0]):
+        _check_bins(bins[0], bins[1], nbins, nturb)
+    bin_start, bin_items = to_dev(bins[0], torch.int32), to_dev(bins[1], torch.int32)
+    if int(bin_start.numel()) != nbins + 1:
+        raise ValueError(f'bins: bin_start has {bin_start.numel()} entries, expected {nbins + 1} for this raster')
+    if ntracks == 0 or pts.numel() == 0 or bin_items.numel() == 0:
+        # nothing to read, or no cylinder reaches the raster (empty tensors have no address to hand over)
+        return hits, first_step, points
+    nat.check(nat.lib().ssrs_rotor_encounters(
+        nat.ptr(pts), nat.ptr(off), C.c_int64(ntracks), nat.ptr(heights), nat.ptr(cellinfo), rows, cols, nat.ptr(xy),
+        nat.ptr(reach_dev), nat.ptr(zband_dev), nturb, nat.ptr(bin_start), nat.ptr(bin_items), nat.ptr(hits),
+        nat.ptr(first_step), nat.ptr(points), stream_ptr()))
+    return hits, first_step, points
