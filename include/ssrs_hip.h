@@ -690,6 +690,57 @@ int ssrs_track_altitude(const int16_t *traj, const int64_t *traj_offsets, int64_
                         int32_t *in_band, int32_t *h_min, int32_t *h_max,
                         void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------ flight time */
+
+/* K16 -- flight time along every track: wind-drift microseconds per cell, per track and over the rotor zone.  THIS BUILD'S
+ * OWN MODEL (the reference has none), defined in integers so that any grouping of the work gives the same bits.
+ *   scalars   va (airspeed), gmin (least ground speed) in mm/s and res_mm (cell size in mm) of SsrsFlightTimeParams:
+ *       1 <= va <= 2^20, 1 <= gmin <= va, 1 <= res_mm <= 10^6.  diag_mm = (res_mm * 92682 + 32768) >> 16;
+ *       num_orth = res_mm * 10^6, num_diag = diag_mm * 10^6 (int64);  CAP = 2^31 - 1 microseconds
+ *   windinfo  one {int32 wr, int32 wc} pair per cell (8 bytes, 8-byte aligned), built by ssrs_flight_windinfo: the
+ *       velocity of the AIR along +row and +col in mm/s.  With (ur, uc) the upwind unit step of the shelter ray below
+ *       (SSRS_RAY_ROW_NORTH (cos A, sin A), SSRS_RAY_ROW_EAST (sin A, cos A), A = wdirn * pi / 180 in f64):
+ *       wr = (int32) clip(rint((-1000 * wspeed) * ur), -2^20, 2^20), wc likewise with uc; the two products round on their
+ *       own; a component that is not a number (NaN speed or direction) is 0, still air.  f32 inputs are widened to f64
+ *   a move from point k = (r, c) to point k + 1 = (r', c') of the same track: sr = sign(r' - r), sc = sign(c' - c) (a
+ *       burn-in jump is ONE move in the direction of its signs); (wr, wc) is the wind of the cell the move LEAVES.
+ *       either point outside [0, rows) x [0, cols): dt = 0
+ *       sr == sc == 0:   dt = min((num_orth + va / 2) / va, CAP)
+ *       orthogonal:      a = sr * wr or sc * wc (along the move), b = the other component, cross2 = b * b, num = num_orth
+ *       diagonal:        a = ((sr * wr + sc * wc) * 46341 + 32768) >> 16 (arithmetic shift), b = sr * wc - sc * wr,
+ *                        cross2 = (b * b) >> 1, num = num_diag
+ *       s = va * va - cross2 (int64);  g = gmin if s <= 0, else max(a + isqrt(s), gmin), isqrt the exact floor square root
+ *       dt = min((num + (g >> 1)) / g, CAP) microseconds, by floor division
+ * ssrs_track_time:
+ *   traj, traj_offsets, ntracks   exactly what ssrs_track_altitude takes
+ *   masked              NULL, or ssrs_track_altitude's traj_band of the same points: point k is "in the zone" iff
+ *                       masked[k] has row >= 0
+ *   windinfo            the raster above, or NULL: (uniform_wr, uniform_wc), each within +-2^20, in every cell
+ *   outputs, each may be NULL; dt is indexed like traj and written for [traj_offsets[0], traj_offsets[ntracks]) only:
+ *     time_hist         uint64 (rows, cols) microseconds, ADDED to: the dt of every move, in the cell it leaves
+ *     band_time_hist    uint64 (rows, cols), ADDED to: the same for the moves that leave a point in the zone (needs masked)
+ *     per_track         int64 (ntracks, 2), OVERWRITTEN (whenever ntracks > 0): [total, in zone] of the track's moves.
+ *                       The last point of a track, single-point and empty tracks contribute 0.  Sum(total) == Sum(added
+ *                       to time_hist) and Sum(in zone) == Sum(added to band_time_hist) modulo 2^64: the caller's checksums
+ *     dt                int32 per point, OVERWRITTEN: the dt of the move that leaves the point, 0 at a track's last point
+ * One memset of per_track and one launch in `stream`'s order; a block takes SSRS_FLIGHT_TIME_TILE consecutive points.
+ * Exact, and independent of the launch order.  traj_offsets[0] and traj_offsets[ntracks] are read back first (the launch
+ * is sized from them), so the call waits for `stream` once.  16-byte aligned traj / masked / dt are read and written 16
+ * bytes a lane.
+ * NULL traj / traj_offsets / params, rows / cols outside [1, 32767], ntracks outside [0, 2^31), a misaligned buffer, a
+ * scalar out of range, band_time_hist without masked -> SSRS_ERR_INVALID before any GPU work.  ntracks == 0 returns SSRS_OK
+ * and touches nothing; no points writes per_track only. */
+#define SSRS_FLIGHT_TIME_TILE 4096
+typedef struct SsrsFlightTimeParams {
+    int32_t va, gmin, res_mm;
+} SsrsFlightTimeParams;
+int ssrs_flight_windinfo(const void *wspeed, const void *wdirn, int type, int rows, int cols, int ray_axes,
+                         int32_t *windinfo, void *stream);
+int ssrs_track_time(const int16_t *traj, const int64_t *traj_offsets, int64_t ntracks, const int16_t *masked,
+                    const int32_t *windinfo, int uniform_wr, int uniform_wc, int rows, int cols,
+                    const SsrsFlightTimeParams *params, uint64_t *time_hist, uint64_t *band_time_hist,
+                    int64_t *per_track, int32_t *dt, void *stream);
+
 /* ---------------------------------------------------------------- shelter */
 
 /* K9 -- the terrain-shelter angle Sx (Winstral et al. 2002) and the orographic updraft adjusted by it and by a

@@ -57,6 +57,7 @@ EXPORTS = (
     'ssrs_allen_workspace_bytes', 'ssrs_allen_thermal_field',
     'ssrs_track_occupancy_workspace_bytes', 'ssrs_track_occupancy',
     'ssrs_altitude_cellinfo', 'ssrs_track_altitude_workspace_bytes', 'ssrs_track_altitude',
+    'ssrs_flight_windinfo', 'ssrs_track_time',
     'ssrs_roam_pair_word_selftest', 'ssrs_tracks_roam_feed_counts', 'ssrs_roam_tables_selftest',
 )
 
@@ -119,6 +120,18 @@ ALTITUDE_CELLINFO_ARGTYPES = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
 # h_max, workspace, workspace_bytes, stream
 ALTITUDE_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.POINTER(SsrsAltitudeParams)] + \
     [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]
+
+
+class SsrsFlightTimeParams(C.Structure):
+    _fields_ = [(name, C.c_int32) for name in ('va', 'gmin', 'res_mm')]
+
+
+# ssrs_flight_windinfo: wspeed, wdirn, type, rows, cols, ray_axes, windinfo, stream
+FLIGHT_WINDINFO_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+# ssrs_track_time: traj, traj_offsets, ntracks, masked, windinfo, uniform_wr, uniform_wc, rows, cols, params, time_hist,
+# band_time_hist, per_track, dt, stream
+TRACK_TIME_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                       C.POINTER(SsrsFlightTimeParams)] + [C.c_void_p] * 5
 
 
 # ssrs_rotor_encounters: traj, traj_offsets, ntracks, alt, cellinfo, rows, cols, turbines, reach, zband, nturb, bin_start,
@@ -234,6 +247,8 @@ def lib():
         L.ssrs_track_altitude_workspace_bytes.restype = C.c_size_t
         L.ssrs_track_altitude_workspace_bytes.argtypes = [C.c_int64]
         L.ssrs_track_altitude.argtypes = ALTITUDE_ARGTYPES
+        L.ssrs_flight_windinfo.argtypes = FLIGHT_WINDINFO_ARGTYPES
+        L.ssrs_track_time.argtypes = TRACK_TIME_ARGTYPES
         if hasattr(L, 'ssrs_rotor_encounters'):
             L.ssrs_rotor_encounters.argtypes = ROTOR_ENCOUNTERS_ARGTYPES
         L.ssrs_roam_pair_word_selftest.argtypes = [C.c_uint64] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]

@@ -35,7 +35,7 @@ _SECTIONS = (
     ('MI355X build', ('save_tracks', 'stepper_path', 'steps_per_launch', 'max_tracks_file_gb', 'track_occupancy',
                       'flight_height', 'flight_height_start', 'flight_height_floor', 'flight_height_ceiling',
                       'flight_airspeed', 'flight_sink_rate', 'rotor_zone', 'rotor_geometry', 'rotor_clearance',
-                      'hist_safe_tracks', 'thermal_model', 'thermal_allen_zi', 'thermal_allen_wstar', 'thermal_allen_sink',
+                      'flight_time', 'flight_min_groundspeed', 'hist_safe_tracks', 'thermal_model', 'thermal_allen_zi', 'thermal_allen_wstar', 'thermal_allen_sink',
                       'turbine_encounter_radius')),
 )
 
@@ -131,6 +131,17 @@ class Config:
     #                                     <id>_turbine_rotor_encounters.npy, Simulator.compute_turbine_rotor_encounters().  The
     #                                     two fields stand here, after rotor_zone, because tests pin the slots further down
     rotor_clearance: float = 0.         # metres added to the rotor radius of 'turbine', in the plane and in height
+    flight_time: bool = False           # True: simulate_tracks also gives every move a duration -- THIS BUILD'S OWN model, the
+    #                                     reference has none (limit 15): the move's length over the ground speed
+    #                                     the bird keeps along it at flight_airspeed in the wind of the cell it leaves (the case's
+    #                                     wind at wtk_orographic_height), in integer microseconds -- and sums them per cell and per
+    #                                     track, from the trajectories on the device (produced even with save_tracks=False):
+    #                                     <id>_residence_time.npy, <id>_flight_times.npy, with flight_height=True also
+    #                                     <id>_rotor_residence_time.npy (the time in rotor_zone);
+    #                                     Simulator.compute_residence_time_map().  The two fields stand here, after
+    #                                     rotor_clearance, because tests pin the slots on either side
+    flight_min_groundspeed: float = 1.  # m/s: the ground speed along a move never falls below it (a headwind, or a cross wind
+    #                                     the bird cannot hold its heading against); 0.001 .. flight_airspeed
     thermal_allen_zi: float = 0.        # thermal_model = 'allen': boundary-layer height zi in metres.  0 (snapshot / seasonal
     #                                     only) = the mean of the case's own blheight layer, clipped below at 100 m
     thermal_allen_wstar: float = 0.     # thermal_model = 'allen': convective velocity scale w* in m/s.  0 (snapshot / seasonal

@@ -79,6 +79,8 @@ class Simulator(Config):
             raise ValueError(f'turbine_encounter_radius = {self.turbine_encounter_radius!r}: expected metres >= 0 (0 = off)')
         if self.flight_height:
             self._flight_params()
+        if self.flight_time:
+            self._time_params()
         self._check_rotor_geometry(turbines)
         print(f'\n---- SSRS in {self.sim_mode} mode')
         print(f'Run name: {self.run_name}')
@@ -131,6 +133,9 @@ class Simulator(Config):
         self.rotor_presence_counts = {}   # (case_id, real_id) -> int32 (rows, cols) holding uint32: points in the rotor zone
         self.flight_heights = {}          # (case_id, real_id) -> int32 (this rank's tracks, 3): [in zone, h_min, h_max] in mm
         self.rotor_turbine_encounters = {}  # as turbine_encounters, of the points in the rotor zone only
+        self.residence_time_counts = {}   # flight_time: (case_id, real_id) -> int64 (rows, cols) holding uint64 microseconds
+        self.rotor_residence_time_counts = {}  # the same of the moves that leave a point in the rotor zone (flight_height too)
+        self.flight_times = {}            # (case_id, real_id) -> int64 (this rank's tracks, 2): [total, in zone] microseconds
         self.turbine_rotor_encounters = {}  # rotor_geometry='turbine': (case_id, real_id) -> dict(tracks_per_turbine,
         #                                     points_per_turbine int64, turbines_per_track, first_step int32)
         self.wtk_layers = {
@@ -775,12 +780,17 @@ class Simulator(Config):
                 # (flight_height reads the UN-thresholded field of every item, whatever the movement model)
                 raw = self._updraft_fields(case_id, lambda fname: to_dev(np.load(fname), torch.float32)) \
                     if self.flight_height else [None] * len(updrafts)
+                # (flight_time: one windinfo per wind case, the scalar pair in uniform mode; finished before a worker's
+                # stream reads it)
+                wind = self._time_wind(case_id) if self.flight_time else None
+                if torch.is_tensor(wind):
+                    torch.cuda.current_stream().synchronize()
                 for (real_id, updraft), lift in zip(enumerate(updrafts), raw):
                     if self.sim_seed > 0:
                         np.random.seed(self.sim_seed + real_id)
                     fields = (updraft, self._potential_dev(updraft, case_id, real_id)) if fluid \
                         else (None, None)
-                    yield (case_id, real_id, fields, self._stream_seed(real_id), lift)
+                    yield (case_id, real_id, fields, self._stream_seed(real_id), lift, wind)
 
         encounters = float(self.turbine_encounter_radius) > 0.
         if encounters:
@@ -796,9 +806,10 @@ class Simulator(Config):
         heights = bool(self.flight_height)
         if heights:
             dem = to_dev(self._terrain['Elevation'], torch.float64)
+        timed = bool(self.flight_time)
 
         def run(item):
-            case_id, real_id, fields, seed, lift = item
+            case_id, real_id, fields, seed, lift, wind = item
             self.last_seeds[(case_id, real_id)] = seed
             id_str = self._get_id_string(case_id, real_id)
             start_time = time.time()
@@ -835,7 +846,16 @@ class Simulator(Config):
                                                         device=my_starts.device)
                         fly['rotor_first_step'] = torch.full((hi - lo,), -1, dtype=torch.int32, device=my_starts.device)
                         fly['rotor_points'] = torch.zeros(n_rotor, dtype=torch.int64, device=my_starts.device)
-                    consumers.append(self._flight_consumer(lift, dem, fly, enc_geometry if encounters else None, rotor))
+                    consumers.append(self._flight_consumer(lift, dem, fly, enc_geometry if encounters else None, rotor,
+                                                           keep_masked=timed))
+                if timed:
+                    # after the flight consumer, whose traj_band of the chunk it reads: one raster of microseconds per
+                    # item (two with flight_height), accumulated over chunks and parts, and this rank's per-track rows
+                    spent = dict(time_hist=torch.zeros(self.gridsize, dtype=torch.int64, device=my_starts.device),
+                                 rows=torch.zeros((hi - lo, 2), dtype=torch.int64, device=my_starts.device))
+                    if heights:
+                        spent['band_time_hist'] = torch.zeros_like(spent['time_hist'])
+                    consumers.append(self._time_consumer(wind, spent, fly if heights else None))
                 chunks = self._device_chunks(batch, consumers) if consumers else None
                 if self.save_tracks:
                     # (inside the stream's scope: long trajectories are stepped again range by range while written)
@@ -868,6 +888,9 @@ class Simulator(Config):
                 if heights:
                     # (track-sharded: its collectives come last in every item)
                     self._store_flight(case_id, real_id, fly, nturb if encounters else 0, sharded)
+                if timed:
+                    # (track-sharded: after the heights' collectives in every item)
+                    self._store_flight_time(case_id, real_id, spent, sharded)
             if sharded:
                 batch.hist = distributed.reduce_histogram(batch.hist, all_ranks=True)
             return (case_id, real_id), batch
@@ -950,20 +973,24 @@ class Simulator(Config):
         flight.height_params(who='Config.flight_height_* / rotor_zone', **kw)
         return kw, airspeed, sink
 
-    def _flight_consumer(self, lift, dem, fly, geometry, rotor=None):
+    def _flight_consumer(self, lift, dem, fly, geometry, rotor=None, keep_masked=False):
         """A chunk through the flight-height scan (K14): `fly['band_hist']` is added to, the chunk's tracks get their rows of
         `fly['rows']`; with `geometry` the points in the rotor zone go through the encounter kernel into `fly['hits']` /
         `fly['first_step']`; with `rotor` (the cylinders on the device) the points and their heights go through the rotor
         kernel (K15) into `fly['rotor_hits']` / `fly['rotor_first_step']` / `fly['rotor_points']`.  The item's cellinfo is
-        built here, from its un-thresholded updraft `lift` and the DEM."""
+        built here, from its un-thresholded updraft `lift` and the DEM.  keep_masked: the chunk's traj_band stays in
+        `fly['masked']` for the consumer behind this one (_time_consumer)."""
         kw, airspeed, sink = self._flight_params()
         cellinfo = flight.altitude_cellinfo(lift, dem, self.resolution, airspeed, sink)
         radius_cells = float(self.turbine_encounter_radius) / float(self.resolution)
 
         def consume(t0, t1, traj, off):
             out = flight.compute_track_altitudes(traj, cellinfo, self.gridsize, offsets=off, band_hist=fly['band_hist'],
-                                                 want_masked=geometry is not None, want_alt=rotor is not None, **kw)
+                                                 want_masked=geometry is not None or keep_masked,
+                                                 want_alt=rotor is not None, **kw)
             fly['rows'][t0:t1] = out['heights']
+            if keep_masked:
+                fly['masked'] = out['masked']
             if rotor is not None:
                 cells, reach, zband, rotor_bins = rotor
                 turbines_mod.rotor_encounters(traj, out['alt'], off, cellinfo, cells, reach, zband, self.gridsize,
@@ -974,6 +1001,69 @@ class Simulator(Config):
                 turbines_mod.turbine_encounters(out['masked'], off, xy, radius_cells, self.gridsize, bins=bins,
                                                 hits=fly['hits'][t0:t1], first_step=fly['first_step'][t0:t1])
         return consume
+
+    def _time_params(self):
+        """Keyword arguments of flight.compute_track_times from the resolution and the flight_* fields, checked."""
+        kw = dict(resolution=self.resolution, airspeed=self.flight_airspeed, min_groundspeed=self.flight_min_groundspeed)
+        flight.time_params(who='Config.resolution / flight_airspeed / flight_min_groundspeed', **kw)
+        return kw
+
+    def _time_ray_axes(self):
+        """The frame of the wind's components: that of the aspect, as _improved_args chooses the shelter ray's."""
+        return 'row_north' if 'Slope' in self._terrain or 'Aspect' in self._terrain else 'row_east'
+
+    def _time_wind(self, case_id):
+        """The wind compute_track_times reads for one case: the scalar pair in uniform mode, otherwise the windinfo raster
+        of the case's per-cell wind (_wind_rasters, at wtk_orographic_height)."""
+        if self.sim_mode.lower() == 'uniform':
+            return float(self.uniform_windspeed), float(self.uniform_winddirn)
+        entry = next(w for w in self._wind if w.case_id == case_id)
+        return flight.wind_cellinfo(*self._wind_rasters(entry), self._time_ray_axes())
+
+    def _time_consumer(self, wind, spent, fly):
+        """A chunk through the flight-time kernel (K16): `spent['time_hist']` (and, with `fly`, the flight consumer's dict
+        whose 'masked' is the chunk's traj_band, `spent['band_time_hist']`) is added to, the chunk's tracks get their rows
+        of `spent['rows']`."""
+        kw = self._time_params()
+        ray_axes = self._time_ray_axes()
+
+        def consume(t0, t1, traj, off):
+            out = flight.compute_track_times(traj, self.gridsize, offsets=off, wind=wind, ray_axes=ray_axes,
+                                             masked=None if fly is None else fly.pop('masked'),
+                                             time_hist=spent['time_hist'], band_time_hist=spent.get('band_time_hist'), **kw)
+            spent['rows'][t0:t1] = out['times']
+        return consume
+
+    def _store_flight_time(self, case_id, real_id, spent, sharded):
+        """Keeps the flight-time rasters and the per-track rows of one (case, realisation) and writes
+        <id>_residence_time.npy (int64 holding uint64 microseconds), <id>_flight_times.npy (int64 (tracks, 2): [total, in
+        the rotor zone]) and, with flight_height, <id>_rotor_residence_time.npy.  Checked by its checksums: each raster of
+        this rank must add up, modulo 2^64, to its column of the rows.  Track-sharded runs sum the rasters over the ranks
+        as _store_flight does and rank 0 writes; the per-track rows stay this rank's tracks, and <id>_flight_times.npy
+        is then rank 0's share."""
+        id_str = self._get_id_string(case_id, real_id)
+        rows = spent['rows']
+        names = (('time_hist', 0, 'residence_time', self.residence_time_counts),
+                 ('band_time_hist', 1, 'rotor_residence_time', self.rotor_residence_time_counts))
+        key = (case_id, real_id)
+        writes = not sharded or self._rank() == 0
+        for name, column, stem, keep in names:
+            if name not in spent:
+                continue
+            raster = spent[name]
+            # (int64 sums wrap like the uint64 ones they hold: equal modulo 2^64 is equal here)
+            counted, summed = int(raster.sum().item()), int(rows[:, column].sum().item())
+            if counted != summed:
+                raise RuntimeError(f'{id_str}: flight time: the {stem} raster adds up to {counted % 2 ** 64} us, the tracks '
+                                   f'to {summed % 2 ** 64} us')
+            if sharded:
+                raster = distributed.reduce_histogram(raster, all_ranks=True)
+            keep[key] = raster.cpu().numpy()
+            if writes:
+                np.save(os.path.join(self.mode_data_dir, f'{id_str}_{stem}.npy'), keep[key])
+        self.flight_times[key] = rows.cpu().numpy()
+        if writes:
+            np.save(os.path.join(self.mode_data_dir, f'{id_str}_flight_times.npy'), self.flight_times[key])
 
     def _store_flight(self, case_id, real_id, fly, nturb, sharded):
         """Keeps the rotor-zone raster and the per-track heights of one (case, realisation) and writes
@@ -1073,7 +1163,7 @@ class Simulator(Config):
         parts, wide, stats = [], None, None
         # trajectories: for the pickle, or for the turbine encounters / the track occupancy (which read them on the device)
         want_tracks = bool(self.save_tracks) or float(self.turbine_encounter_radius) > 0. or bool(self.track_occupancy) or \
-            bool(self.flight_height)
+            bool(self.flight_height) or bool(self.flight_time)
         # (start, length) of the sub-batches still to step, in track-id order; one whose uint32 counts wrapped is stepped
         # again as two halves, added up in 64 bits like the rest
         todo = [(t0, min(step, n - t0)) for t0 in range(0, max(n, 1), step)]
@@ -1236,6 +1326,38 @@ class Simulator(Config):
         if self._rank() == 0:
             np.save(os.path.join(self.mode_data_dir, 'summary_rotor_presence.npy'), out)
         self._barrier()
+        return out
+
+    def _time_share_map(self, counts, radius, fname, what):
+        if not counts:
+            raise ValueError(f'no {what} was computed: run simulate_tracks() with flight_time=True'
+                             + (' and flight_height=True' if 'rotor' in fname else ''))
+        out, per_case = self._presence_summary(
+            presence.presence_kernel_radius(radius, self.resolution, self.gridsize) if radius > 0. else 0,
+            counts_for=lambda case_id, real_id: to_dev(counts[(case_id, real_id)], torch.int64), may_be_empty=True)
+        total = float(out.sum(dtype=np.float64))
+        if total > 0.:
+            out = (out.astype(np.float64) / total).astype(np.float32)
+        if self._rank() == 0:
+            np.save(os.path.join(self.mode_data_dir, fname), out)
+        self._barrier()
+        return out, per_case
+
+    def compute_residence_time_map(self, radius: float = 1000.):
+        """Each cell's share of all flight time (flight_time=True): the ladder of compute_presence_map over
+        residence_time_counts -- the 64-bit disk smoothing (ssrs_presence_smooth_u64) of every item's microseconds, the
+        same normalisations over realisations and cases -- and the summary divided by its sum, so that the map adds up to
+        1 (a run without a timed move gives zeros).  radius = 0: no smoothing; one item is then its raster over its
+        total.  Returns the f32 map and writes summary_residence_time.npy.  ValueError when simulate_tracks timed nothing."""
+        out, self.case_residence_time = self._time_share_map(self.residence_time_counts, float(radius),
+                                                             'summary_residence_time.npy', 'flight time')
+        return out
+
+    def compute_rotor_residence_time_map(self, radius: float = 1000.):
+        """compute_residence_time_map of the time spent in the rotor zone alone (flight_time=True and flight_height=True):
+        each cell's share of it.  Writes summary_rotor_residence_time.npy."""
+        out, self.case_rotor_residence_time = self._time_share_map(self.rotor_residence_time_counts, float(radius),
+                                                                   'summary_rotor_residence_time.npy', 'rotor-zone flight time')
         return out
 
     def compute_windplant_presence_map(self, pname, radius: float = 100., pad: float = 2000.):
