@@ -1016,7 +1016,14 @@ size_t ssrs_potential_workspace_bytes(int rows, int cols);
  *                 movmodel.py:21-57, evaluated by the host)
  *   fixed_values  f64 (rows, cols): boundary energy on those cells
  *   initial_guess f64 (rows, cols) or NULL
- *   potential     f32 (rows, cols) out, as `pot_energy.astype(np.float32)` */
+ *   potential     f32 (rows, cols) out, as `pot_energy.astype(np.float32)`
+ *   max_iterations caps the PCG and BiCGStab iterations together (honoured to the next
+ *                 multiple of 5, the interval of PCG's checks); a solve that stops there
+ *                 returns SSRS_OK with converged == 0 and its best iterate, projected onto
+ *                 the range of the Dirichlet values (the solution obeys the maximum
+ *                 principle, an unfinished iterate need not; a converged field is written
+ *                 as it is).  Only the fall-back after a BiCGStab breakdown has a budget
+ *                 of its own. */
 int ssrs_potential_solve(const double *conductivity, const uint8_t *fixed_mask,
                          const double *fixed_values, const double *initial_guess,
                          float *potential, int rows, int cols, double rel_tol,

@@ -436,9 +436,18 @@ def neighbour_lists(grid_shape):
     return rows.astype(np.uint32), cols.astype(np.uint32), facs
 
 
-def solve_potential(conductivity, move_dirn):
+def solve_potential(conductivity, move_dirn, numpy2=False):
     """movmodel.py:87-128 (+ simulator.py:259-288): row-normalised conductance
-    matrix, Dirichlet nodes, scipy SuperLU direct solve.  Returns f32 (R, C)."""
+    matrix, Dirichlet nodes, scipy SuperLU direct solve.  Returns f32 (R, C).
+
+    `numpy2`: the entry of a zero-conductivity pair, `1e-08 / np.float32(fac)`, is an
+    f64 value under the NumPy < 1.24 the reference was written for (the default here
+    and what ssrs_potential_solve implements) and an f32 value under NumPy >= 2, the
+    NumPy the goldens were made with: a 6e-8 relative wobble on a 1e-8 entry, far
+    below the f32 output tolerance -- unless no pair at all is live.  Then the
+    reference's `np.array(vals)` is an f32 array, the row normalisation runs in f32,
+    the rows no longer sum to one and an all-dead 9 x 61 raster moves by 5e-3 of 1000
+    (fixture G16)."""
     import scipy.sparse as ss
     import scipy.sparse.linalg as ssl
     conductivity = np.asarray(conductivity, dtype=np.float64)
@@ -450,13 +459,16 @@ def solve_potential(conductivity, move_dirn):
     c = c.astype(np.int64)
     ca = conductivity[r % nrow, r // nrow]
     cb = conductivity[c % nrow, c // nrow]
+    live = (ca != 0) & (cb != 0)
     with np.errstate(divide='ignore'):
-        hm = np.where((ca != 0) & (cb != 0), 2. / (1. / ca + 1 / cb), 1e-08)
+        hm = np.where(live, 2. / (1. / ca + 1 / cb), 1e-08)
     vals = hm / facs          # f64 / f4 -> f64, as `harmonic_mean(...) / fac`
+    if numpy2:
+        dead = np.float32(1e-08) / facs
+        # np.array(vals) of the reference: f64 as soon as one pair is live, f32 if none is
+        vals = np.where(live, vals, dead.astype(np.float64)) if live.any() else dead
     g = ss.coo_matrix((vals, (r, c)), shape=(n, n)).tocsr()
-    # row-normalise (movmodel.py:110-112); NB on NumPy>=2 the reference's
-    # `1e-08 / np.float32(fac)` is f32-rounded for zero-conductivity pairs -- a
-    # 6e-8 relative wobble on a 1e-8 entry, far below the f32 output tolerance.
+    # row-normalise (movmodel.py:110-112)
     row_sums = np.add.reduceat(g.data, g.indptr[:-1])
     g.data = g.data / row_sums[np.repeat(np.arange(n), np.diff(g.indptr))]
     inodes = np.setdiff1d(np.arange(n), bnodes, assume_unique=True)

@@ -75,6 +75,10 @@ def solve_potential(updraft, move_dirn, rel_tol=1e-15, max_iterations=2000,
     up to 6e-3 when the solver stops just under it, 1e-15 leaves < 1e-3
     (tests/dev/soak_potential.py; the direct solve itself is only good to ~1e-3 at
     condition numbers of 1e10), at ~25 % more iterations than 1e-12.
+
+    max_iterations caps the iterations (to the next multiple of 5).  A solve that stops
+    there warns and returns its best iterate, kept inside the range of the boundary
+    energies; stats['converged'] tells.
     """
     cond = to_dev(updraft, torch.float64)
     rows, cols = int(cond.shape[0]), int(cond.shape[1])

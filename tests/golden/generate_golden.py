@@ -17,6 +17,9 @@ algorithm with the uniform made explicit (cumsum -> /last -> searchsorted
 legacy-MT trajectories bit for bit before any Philox-driven golden is made.
 
 Usage:  python tests/golden/generate_golden.py [--skip-c1] [--skip-10m]
+Fixtures with a generator of their own (each imports what it shares from here or from its neighbours):
+G13 generate_g13_thermals.py, G14 generate_g14_raster_edges.py, G15 generate_g15_wtk_thermals.py,
+G16 generate_g16_potential_shapes.py (reuses reference_system and exact_potential below).
 While generating, every vector is also compared with oracle/ssrs_oracle.py and
 the script aborts on any mismatch.
 """
