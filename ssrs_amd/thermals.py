@@ -1,6 +1,7 @@
 """Thermal updraft realisations (a5) on the device, behind the reference's
 `compute_thermals(aspect, thermal_intensity_scale)` (/root/reference/ssrs/
-layers.py:188-214).  Statistical parity only: see csrc/thermals.hip.
+layers.py:188-214).  Statistical parity with the reference's RNG stream only: see csrc/thermals.hip; the device's own
+rule is restated cell by cell in tests/thermals_ref.py.
 `compute_wtk_thermals` is the other thermal model (Config.thermal_model = 'wtk'): the Deardorff-velocity updraft of
 ssrs/layers.py:25-60 from a snapshot's own WTK layers, deterministic; see csrc/wtk_thermals.hip.
 `compute_allen_thermals` is the third (Config.thermal_model = 'allen'): Allen's (2006) field of discrete updrafts, the

@@ -3,7 +3,8 @@ on the MI355X: bit identity with the two-stage chain thermal_seeds -> gaussian_b
 the reference's own output (fixture G13), the seeding held to the reference ensemble of G13 by the
 two-sample z statistics of g13_stats.py (|z| <= 5, derivation there), the Simulator's files, and
 stream behaviour.  The reference replays a serial global RNG, so parity of the seeding is statistical;
-everything else here is exact."""
+everything else here is exact.  Rasters below one tile, thinner than the radius, other radii and the device's own
+seeding rule cell by cell: thermals_ref.CASES, test_gpu_thermal_parity.py."""
 import os
 from dataclasses import replace
 
