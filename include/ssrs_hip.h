@@ -604,6 +604,36 @@ int ssrs_rotor_encounters(const int16_t *traj, const int64_t *traj_offsets, int6
                           const int32_t *zband, int nturb, const int32_t *bin_start, const int32_t *bin_items,
                           uint32_t *hits, int32_t *first_step, uint64_t *points_per_turbine, void *stream);
 
+/* K15, timed -- the same walk with the exposure in TIME: ssrs_rotor_encounters' arguments plus
+ *   dt                  int32 per point, indexed like traj and alt, 4-byte aligned, required: the microseconds of the move
+ *                       that LEAVES the point (ssrs_track_time's `dt`; a track's last point carries 0, so a track that ends
+ *                       inside a cylinder adds no time for that point).  Read only for points inside at least one cylinder,
+ *                       never outside [traj_offsets[0], traj_offsets[ntracks])
+ *   time_per_turbine    uint64 (nturb), 8-byte aligned, required, ADDED to:
+ *                           time_per_turbine[t] += (int64)dt[k]   for every point k inside turbine t
+ *                       by the four conditions above, unchanged.  The sums are those of the sign-extended dt modulo 2^64:
+ *                       ssrs_track_time never writes a negative dt, a caller's negative value is added as it stands.  A cull
+ *                       list that names a turbine twice in a bin adds the point's time twice, as it does for the points
+ * hits, first_step and points_per_turbine are what ssrs_rotor_encounters gives on the same input, bit for bit; first_step
+ * and points_per_turbine stay optional and independent of the time.
+ * No atomic per point: a lane's pending pair becomes (turbine, count, time), the time in 64 bits (one dt may be 2^31 - 1),
+ * handed over when the turbine changes and at the end of its walk; the block keeps a uint64 time counter per turbine in LDS
+ * beside the uint32 point counter (12 bytes a turbine together) and adds the non-zero ones to time_per_turbine once, at its
+ * end.  THE LDS RULE: mask, point counters and time counters share the 60 KB.  The mask goes first: it stays in LDS only
+ * while all three fit (beyond, bin_start is read per point).  Without the mask the point counters come next and the time
+ * counters take what is left, 8 bytes a turbine from turbine 0 upwards: up to SSRS_ROTOR_TIMED_LDS_TURBINES turbines (7680
+ * when points_per_turbine is NULL) every counter is in LDS; beyond, the hand-overs of the turbines past the last LDS counter
+ * go to time_per_turbine as 64-bit global adds (still one per change of turbine, not one per point).  The result is the
+ * same integers on either side.
+ * Errors as ssrs_rotor_encounters; a NULL or misaligned dt or time_per_turbine -> SSRS_ERR_INVALID before any GPU work.
+ * ntracks == 0, or no points, returns SSRS_OK and touches nothing. */
+#define SSRS_ROTOR_TIMED_LDS_TURBINES 5120
+int ssrs_rotor_encounters_timed(const int16_t *traj, const int64_t *traj_offsets, int64_t ntracks, const int32_t *alt,
+                                const int32_t *dt, const int32_t *cellinfo, int rows, int cols, const double *turbines,
+                                const double *reach, const int32_t *zband, int nturb, const int32_t *bin_start,
+                                const int32_t *bin_items, uint32_t *hits, int32_t *first_step,
+                                uint64_t *points_per_turbine, uint64_t *time_per_turbine, void *stream);
+
 /* -------------------------------------------------------------- occupancy */
 
 /* K13 -- how many DISTINCT tracks passed through each cell, from the trajectories on the device: the per-cell analogue

@@ -22,6 +22,7 @@ SSRS_TRACKS_NO_SCATTERED = 64
 SSRS_TRACKS_THR_TABLE = 128
 SSRS_SOLVE_NO_AMG = 1
 SSRS_TURBINE_BIN, SSRS_TURBINE_MAX = 32, 8192
+SSRS_ROTOR_TIMED_LDS_TURBINES = 5120
 SSRS_OCCUPANCY_MAX_PLANES = 8
 SSRS_ALTITUDE_TILE = 4096
 SSRS_RAY_AXES = {'row_north': 0, 'row_east': 1}                  # SSRS_RAY_ROW_NORTH / _ROW_EAST
@@ -50,7 +51,7 @@ EXPORTS = (
     'ssrs_presence_smooth_u64',
     'ssrs_presence_normalise_add', 'ssrs_presence_normalise_f32',
     'ssrs_potential_workspace_bytes', 'ssrs_potential_solve',
-    'ssrs_turbine_encounters', 'ssrs_turbine_encounter_counts', 'ssrs_rotor_encounters',
+    'ssrs_turbine_encounters', 'ssrs_turbine_encounter_counts', 'ssrs_rotor_encounters', 'ssrs_rotor_encounters_timed',
     'ssrs_shelter_sx', 'ssrs_updraft_sheltered', 'ssrs_shelter_sx_sector', 'ssrs_updraft_sheltered_sector',
     'ssrs_smooth_workspace_bytes', 'ssrs_smooth_reflect',
     'ssrs_projection_init_albers', 'ssrs_warp_lonlat_raster',
@@ -138,6 +139,10 @@ TRACK_TIME_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p
 # bin_items, hits, first_step, points_per_turbine, stream
 ROTOR_ENCOUNTERS_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + \
     [C.c_int] + [C.c_void_p] * 6
+# ssrs_rotor_encounters_timed: traj, traj_offsets, ntracks, alt, dt, cellinfo, rows, cols, turbines, reach, zband, nturb,
+# bin_start, bin_items, hits, first_step, points_per_turbine, time_per_turbine, stream
+ROTOR_ENCOUNTERS_TIMED_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + \
+    [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 7
 
 
 class SsrsError(RuntimeError):
@@ -251,6 +256,8 @@ def lib():
         L.ssrs_track_time.argtypes = TRACK_TIME_ARGTYPES
         if hasattr(L, 'ssrs_rotor_encounters'):
             L.ssrs_rotor_encounters.argtypes = ROTOR_ENCOUNTERS_ARGTYPES
+        if hasattr(L, 'ssrs_rotor_encounters_timed'):
+            L.ssrs_rotor_encounters_timed.argtypes = ROTOR_ENCOUNTERS_TIMED_ARGTYPES
         L.ssrs_roam_pair_word_selftest.argtypes = [C.c_uint64] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
         L.ssrs_roam_tables_selftest.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 4
         L.ssrs_tracks_roam_feed_counts.restype = None

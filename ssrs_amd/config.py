@@ -35,7 +35,7 @@ _SECTIONS = (
     ('MI355X build', ('save_tracks', 'stepper_path', 'steps_per_launch', 'max_tracks_file_gb', 'track_occupancy',
                       'flight_height', 'flight_height_start', 'flight_height_floor', 'flight_height_ceiling',
                       'flight_airspeed', 'flight_sink_rate', 'rotor_zone', 'rotor_geometry', 'rotor_clearance',
-                      'flight_time', 'flight_min_groundspeed', 'hist_safe_tracks', 'thermal_model', 'thermal_allen_zi', 'thermal_allen_wstar', 'thermal_allen_sink',
+                      'flight_time', 'flight_min_groundspeed', 'rotor_exposure_time', 'hist_safe_tracks', 'thermal_model', 'thermal_allen_zi', 'thermal_allen_wstar', 'thermal_allen_sink',
                       'turbine_encounter_radius')),
 )
 
@@ -142,6 +142,13 @@ class Config:
     #                                     rotor_clearance, because tests pin the slots on either side
     flight_min_groundspeed: float = 1.  # m/s: the ground speed along a move never falls below it (a headwind, or a cross wind
     #                                     the bird cannot hold its heading against); 0.001 .. flight_airspeed
+    rotor_exposure_time: bool = False   # True (needs flight_height=True, rotor_geometry='turbine', flight_time=True and turbines
+    #                                     with t_hh and t_rd): simulate_tracks also sums, per turbine, the durations of the moves
+    #                                     that leave a point inside its cylinder -- the exposure in microseconds instead of
+    #                                     points, on the device (DESIGN.md K15 timed, limits 14 and 15; the heights and the
+    #                                     durations underneath are this build's placeholder models):
+    #                                     <id>_turbine_rotor_time.npy, Simulator.compute_turbine_rotor_time().  It stands here,
+    #                                     after flight_min_groundspeed, because tests pin every other slot
     thermal_allen_zi: float = 0.        # thermal_model = 'allen': boundary-layer height zi in metres.  0 (snapshot / seasonal
     #                                     only) = the mean of the case's own blheight layer, clipped below at 100 m
     thermal_allen_wstar: float = 0.     # thermal_model = 'allen': convective velocity scale w* in m/s.  0 (snapshot / seasonal

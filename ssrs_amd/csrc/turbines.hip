@@ -22,6 +22,13 @@
 // (points inside each cylinder) is counted without an atomic per point: a lane keeps ONE (turbine, count) pair in
 // registers across its points and spans and adds it to the block's uint32 counter in LDS only when the turbine changes
 // or the wave ends; the block adds its non-zero counters to the uint64 totals once, at its end.
+//
+// K15, timed (kTimed) -- the exposure in microseconds: dt[i] of every point inside a cylinder is added to that turbine's
+// total.  dt is loaded only for a point that hit (the common point still costs one mask lookup; 4 B more per point INSIDE a
+// cylinder, and a parked track's hits are consecutive points, so those loads coalesce).  The lane's pair becomes (turbine,
+// count, time) with the time in 64 bits, the block keeps a uint64 counter per turbine in LDS behind the uint32 ones, and
+// adds the non-zero ones once.  The LDS rule is in the header: the mask goes first, then the time counters of the highest
+// turbines, whose hand-overs become global 64-bit adds.
 #include <climits>
 
 #include "common.h"
@@ -37,6 +44,8 @@ constexpr long long kTurbMinSpans = 4;        // spans per wave at least: small 
 constexpr int kTurbBlocks = 256 * 6;
 constexpr int kTurbMaskWords = 8192;          // 32 KB of LDS: rasters of up to 262 144 bins keep the mask there
 constexpr int kRotorLdsWords = 15 * 1024;     // K15: mask and exposure counters (4 B a turbine) together, 60 KB
+// (timed: 4 + 8 B a turbine; without the mask that many turbines keep every counter in LDS)
+static_assert(kRotorLdsWords / 3 == SSRS_ROTOR_TIMED_LDS_TURBINES, "the header's LDS rule");
 
 __device__ __forceinline__ int wave_or(int v)
 {
@@ -78,15 +87,22 @@ struct TurbArgs {
     const int2 *zband;             // {z_lo, z_hi} mm above the datum, per turbine
     unsigned long long *points;    // per turbine, or NULL
     int cnt_off;                   // the block's counters: s_mask[cnt_off + turbine]
+    // kTimed only
+    const int32_t *dt;             // microseconds of the move that leaves the point, indexed like traj
+    unsigned long long *time;      // per turbine
+    int time_off;                  // the block's time counters: 8-byte words from s_mask + time_off (even)
+    int time_lds;                  // turbines [0, time_lds) have one; the others' hand-overs go to `time`
 };
 
 // The walk of one wave over its spans (no barrier inside: a wave without spans returns at once).
 // kVec: 16-byte loads (traj, and alt with it, are 16-byte aligned).  kMask: the occupied-bin mask fits LDS.
 // kRotor: K15's cylinders; s_cnt = the block's exposure counters, or NULL when they are not asked for.
-template <bool kVec, bool kMask, bool kRotor>
+// kTimed (with kRotor): the time inside the cylinders too; s_time = the block's time counters.
+template <bool kVec, bool kMask, bool kRotor, bool kTimed>
 __device__ __forceinline__ void turbine_walk(const TurbArgs &a, const uint32_t *s_mask, uint32_t *s_cnt,
-                                             int (*s_mark)[kTurbSpan], const long long p0, const long long p1,
-                                             const long long a0, const long long nspans, const long long per_wave)
+                                             unsigned long long *s_time, int (*s_mark)[kTurbSpan], const long long p0,
+                                             const long long p1, const long long a0, const long long nspans,
+                                             const long long per_wave)
 {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
@@ -145,6 +161,17 @@ __device__ __forceinline__ void turbine_walk(const TurbArgs &a, const uint32_t *
     // (kRotor) the exposure this lane has not handed to the block yet: pend_cnt points inside turbine pend_tb
     int pend_tb = 0;
     uint32_t pend_cnt = 0;
+    // (kTimed) and their time, modulo 2^64: the pair is kept whether or not the points are asked for
+    unsigned long long pend_time = 0;
+    auto hand_over = [&]() {
+        if (s_cnt != nullptr) atomicAdd(&s_cnt[pend_tb], pend_cnt);
+        if (pend_time != 0) {
+            if (pend_tb < a.time_lds) atomicAdd(&s_time[pend_tb], pend_time);
+            else atomicAdd(a.time + pend_tb, pend_time);
+        }
+        pend_cnt = 0;
+        pend_time = 0;
+    };
 
     // one span: `cur` its points (`cur_alt` their heights), `t_end` = off[t + 1]
     auto span = [&](const long long u, const uint4 cur, const int4 cur_alt, const long long t_end) {
@@ -217,6 +244,8 @@ __device__ __forceinline__ void turbine_walk(const TurbArgs &a, const uint32_t *
             }
             const long long track = t + rel[j];
             bool in_any = false;
+            unsigned long long dt_us = 0;         // (kTimed) dt[i], sign-extended, loaded at the point's first hit
+            bool have_dt = false;
             while (__ballot(k0 < k1) != 0) {
                 bool hit = false;
                 int tb = 0;
@@ -239,7 +268,19 @@ __device__ __forceinline__ void turbine_walk(const TurbArgs &a, const uint32_t *
                     }
                 }
                 in_any |= hit;
-                if constexpr (kRotor) {
+                if constexpr (kTimed) {
+                    // ---- exposure in points and time (a hit lies inside [p0, p1): so does the load)
+                    if (hit) {
+                        if (!have_dt) {
+                            dt_us = static_cast<unsigned long long>(static_cast<long long>(a.dt[i]));
+                            have_dt = true;
+                        }
+                        if (tb != pend_tb && pend_cnt != 0) hand_over();
+                        pend_tb = tb;
+                        ++pend_cnt;
+                        pend_time += dt_us;
+                    }
+                } else if constexpr (kRotor) {
                     // ---- exposure: one more point inside tb; the block hears of it when the lane moves to another turbine
                     if (hit && s_cnt != nullptr) {
                         if (tb != pend_tb && pend_cnt != 0) {
@@ -328,14 +369,17 @@ __device__ __forceinline__ void turbine_walk(const TurbArgs &a, const uint32_t *
         }
     }
     for (; u < u1; ++u) span(u, fetch_edge(u), fetch_alt_edge(u), a.off[t + 1]);
-    if constexpr (kRotor) {
+    if constexpr (kTimed) {
+        if (pend_cnt != 0) hand_over();
+    } else if constexpr (kRotor) {
         if (pend_cnt != 0) atomicAdd(&s_cnt[pend_tb], pend_cnt);
     }
 }
 
-template <bool kVec, bool kMask, bool kRotor>
+template <bool kVec, bool kMask, bool kRotor, bool kTimed>
 __global__ __launch_bounds__(kBlock) void k_turbine_encounters(const TurbArgs a)
 {
+    static_assert(kRotor || !kTimed, "the timed walk is the rotor walk");
     extern __shared__ uint32_t s_mask[];
     __shared__ alignas(16) int s_mark[kTurbWaves][kTurbSpan];       // (read and zeroed 16 bytes a lane)
 
@@ -366,11 +410,26 @@ __global__ __launch_bounds__(kBlock) void k_turbine_encounters(const TurbArgs a)
     uint32_t *s_cnt = kRotor && a.points != nullptr ? s_mask + a.cnt_off : nullptr;
     if (s_cnt != nullptr)
         for (int tb = threadIdx.x; tb < a.nturb; tb += kBlock) s_cnt[tb] = 0;
+    // (kTimed) the block's time counters, uint64: the same dynamic LDS under an 8-byte aligned name
+    unsigned long long *s_time = nullptr;
+    if constexpr (kTimed) {
+        extern __shared__ unsigned long long s_dyn64[];
+        s_time = s_dyn64 + (a.time_off >> 1);
+        for (int tb = threadIdx.x; tb < a.time_lds; tb += kBlock) s_time[tb] = 0;
+    }
     if (kMask || kRotor) __syncthreads();
 
-    turbine_walk<kVec, kMask, kRotor>(a, s_mask, s_cnt, s_mark, p0, p1, a0, nspans, per_wave);
+    turbine_walk<kVec, kMask, kRotor, kTimed>(a, s_mask, s_cnt, s_time, s_mark, p0, p1, a0, nspans, per_wave);
 
-    if constexpr (kRotor) {
+    if constexpr (kTimed) {
+        // every wave of the block arrives here: one 64-bit add per turbine the block met, for the points and for the time
+        __syncthreads();
+        if (s_cnt != nullptr)
+            for (int tb = threadIdx.x; tb < a.nturb; tb += kBlock)
+                if (s_cnt[tb] != 0) atomicAdd(a.points + tb, static_cast<unsigned long long>(s_cnt[tb]));
+        for (int tb = threadIdx.x; tb < a.time_lds; tb += kBlock)
+            if (s_time[tb] != 0) atomicAdd(a.time + tb, s_time[tb]);
+    } else if constexpr (kRotor) {
         // every wave of the block arrives here: one 64-bit add per turbine the block met
         if (s_cnt != nullptr) {
             __syncthreads();
@@ -440,14 +499,14 @@ static TurbArgs walk_args(const int16_t *traj, const int64_t *traj_offsets, int6
     return a;
 }
 
-template <bool kRotor>
+template <bool kRotor, bool kTimed = false>
 static void launch_encounters(const TurbArgs &a, bool vec, bool mask, size_t lds, hipStream_t st)
 {
     const dim3 grid(kTurbBlocks), block(kBlock);
-    if (vec && mask) hipLaunchKernelGGL((k_turbine_encounters<true, true, kRotor>), grid, block, lds, st, a);
-    else if (vec) hipLaunchKernelGGL((k_turbine_encounters<true, false, kRotor>), grid, block, lds, st, a);
-    else if (mask) hipLaunchKernelGGL((k_turbine_encounters<false, true, kRotor>), grid, block, lds, st, a);
-    else hipLaunchKernelGGL((k_turbine_encounters<false, false, kRotor>), grid, block, lds, st, a);
+    if (vec && mask) hipLaunchKernelGGL((k_turbine_encounters<true, true, kRotor, kTimed>), grid, block, lds, st, a);
+    else if (vec) hipLaunchKernelGGL((k_turbine_encounters<true, false, kRotor, kTimed>), grid, block, lds, st, a);
+    else if (mask) hipLaunchKernelGGL((k_turbine_encounters<false, true, kRotor, kTimed>), grid, block, lds, st, a);
+    else hipLaunchKernelGGL((k_turbine_encounters<false, false, kRotor, kTimed>), grid, block, lds, st, a);
 }
 
 }  // namespace ssrs
@@ -482,25 +541,28 @@ extern "C" int ssrs_turbine_encounters(const int16_t *traj, const int64_t *traj_
     return SSRS_OK;
 }
 
-extern "C" int ssrs_rotor_encounters(const int16_t *traj, const int64_t *traj_offsets, int64_t ntracks, const int32_t *alt,
-                                     const int32_t *cellinfo, int rows, int cols, const double *turbines,
-                                     const double *reach, const int32_t *zband, int nturb, const int32_t *bin_start,
-                                     const int32_t *bin_items, uint32_t *hits, int32_t *first_step,
-                                     uint64_t *points_per_turbine, void *stream)
+// ssrs_rotor_encounters and its timed form (`timed`: dt and time_per_turbine are required): one set of checks, one launch
+static int rotor_call(const char *who, bool timed, const int16_t *traj, const int64_t *traj_offsets, int64_t ntracks,
+                      const int32_t *alt, const int32_t *dt, const int32_t *cellinfo, int rows, int cols,
+                      const double *turbines, const double *reach, const int32_t *zband, int nturb, const int32_t *bin_start,
+                      const int32_t *bin_items, uint32_t *hits, int32_t *first_step, uint64_t *points_per_turbine,
+                      uint64_t *time_per_turbine, void *stream)
 {
     SSRS_REQUIRE(traj && traj_offsets && alt && cellinfo && turbines && reach && zband && bin_start && bin_items && hits,
-                 "ssrs_rotor_encounters: NULL pointer");
-    SSRS_REQUIRE(ntracks >= 0 && ntracks <= INT32_MAX, "ssrs_rotor_encounters: ntracks = %lld outside [0, 2^31)",
+                 "%s: NULL pointer", who);
+    SSRS_REQUIRE(!timed || (dt && time_per_turbine), "%s: NULL pointer (dt and time_per_turbine are required)", who);
+    SSRS_REQUIRE(ntracks >= 0 && ntracks <= INT32_MAX, "%s: ntracks = %lld outside [0, 2^31)", who,
                  static_cast<long long>(ntracks));
-    SSRS_REQUIRE(nturb >= 1 && nturb <= SSRS_TURBINE_MAX, "ssrs_rotor_encounters: nturb = %d outside [1, %d]", nturb,
-                 SSRS_TURBINE_MAX);
+    SSRS_REQUIRE(nturb >= 1 && nturb <= SSRS_TURBINE_MAX, "%s: nturb = %d outside [1, %d]", who, nturb, SSRS_TURBINE_MAX);
     SSRS_REQUIRE(rows >= 1 && rows <= 32767 && cols >= 1 && cols <= 32767,
-                 "ssrs_rotor_encounters: a %d x %d raster (int16 points: 1..32767 either way)", rows, cols);
+                 "%s: a %d x %d raster (int16 points: 1..32767 either way)", who, rows, cols);
     SSRS_REQUIRE((reinterpret_cast<uintptr_t>(traj) & 3u) == 0 && (reinterpret_cast<uintptr_t>(alt) & 3u) == 0,
-                 "ssrs_rotor_encounters: traj and alt must be 4-byte aligned");
+                 "%s: traj and alt must be 4-byte aligned", who);
     SSRS_REQUIRE((reinterpret_cast<uintptr_t>(cellinfo) & 7u) == 0 && (reinterpret_cast<uintptr_t>(zband) & 7u) == 0 &&
                      (reinterpret_cast<uintptr_t>(points_per_turbine) & 7u) == 0,
-                 "ssrs_rotor_encounters: cellinfo, zband and points_per_turbine must be 8-byte aligned");
+                 "%s: cellinfo, zband and points_per_turbine must be 8-byte aligned", who);
+    SSRS_REQUIRE((reinterpret_cast<uintptr_t>(dt) & 3u) == 0, "%s: dt must be 4-byte aligned", who);
+    SSRS_REQUIRE((reinterpret_cast<uintptr_t>(time_per_turbine) & 7u) == 0, "%s: time_per_turbine must be 8-byte aligned", who);
     if (ntracks == 0) return SSRS_OK;
     TurbArgs a = walk_args(traj, traj_offsets, ntracks, turbines, nturb, bin_start, bin_items, rows, cols, hits, first_step);
     a.alt = alt;
@@ -512,11 +574,45 @@ extern "C" int ssrs_rotor_encounters(const int16_t *traj, const int64_t *traj_of
     // mask and counters share the dynamic LDS; together with the 4 KB of marks a block stays within 64 KB
     const int mask_words = (a.nbins + 31) / 32;
     const int cnt_words = a.points ? nturb : 0;
-    const bool mask = mask_words <= kTurbMaskWords && mask_words + cnt_words <= kRotorLdsWords;
-    a.cnt_off = mask ? mask_words : 0;
-    launch_encounters<true>(a, vec, mask, static_cast<size_t>(a.cnt_off + cnt_words) * 4, as_stream(stream));
+    if (!timed) {
+        const bool mask = mask_words <= kTurbMaskWords && mask_words + cnt_words <= kRotorLdsWords;
+        a.cnt_off = mask ? mask_words : 0;
+        launch_encounters<true>(a, vec, mask, static_cast<size_t>(a.cnt_off + cnt_words) * 4, as_stream(stream));
+    } else {
+        // the header's LDS rule: the mask stays only while the time counters of every turbine fit behind it and the point
+        // counters (at an even word: they are 8 bytes each); without it the time counters take what the point counters leave
+        a.dt = dt;
+        a.time = reinterpret_cast<unsigned long long *>(time_per_turbine);
+        const bool mask = mask_words <= kTurbMaskWords && ((mask_words + cnt_words + 1) & ~1) + 2 * nturb <= kRotorLdsWords;
+        a.cnt_off = mask ? mask_words : 0;
+        a.time_off = (a.cnt_off + cnt_words + 1) & ~1;
+        const int room = (kRotorLdsWords - a.time_off) / 2;
+        a.time_lds = nturb < room ? nturb : room;
+        launch_encounters<true, true>(a, vec, mask, static_cast<size_t>(a.time_off + 2 * a.time_lds) * 4, as_stream(stream));
+    }
     SSRS_HIP_CHECK(hipGetLastError());
     return SSRS_OK;
+}
+
+extern "C" int ssrs_rotor_encounters(const int16_t *traj, const int64_t *traj_offsets, int64_t ntracks, const int32_t *alt,
+                                     const int32_t *cellinfo, int rows, int cols, const double *turbines,
+                                     const double *reach, const int32_t *zband, int nturb, const int32_t *bin_start,
+                                     const int32_t *bin_items, uint32_t *hits, int32_t *first_step,
+                                     uint64_t *points_per_turbine, void *stream)
+{
+    return rotor_call("ssrs_rotor_encounters", false, traj, traj_offsets, ntracks, alt, nullptr, cellinfo, rows, cols, turbines,
+                      reach, zband, nturb, bin_start, bin_items, hits, first_step, points_per_turbine, nullptr, stream);
+}
+
+extern "C" int ssrs_rotor_encounters_timed(const int16_t *traj, const int64_t *traj_offsets, int64_t ntracks,
+                                           const int32_t *alt, const int32_t *dt, const int32_t *cellinfo, int rows, int cols,
+                                           const double *turbines, const double *reach, const int32_t *zband, int nturb,
+                                           const int32_t *bin_start, const int32_t *bin_items, uint32_t *hits,
+                                           int32_t *first_step, uint64_t *points_per_turbine, uint64_t *time_per_turbine,
+                                           void *stream)
+{
+    return rotor_call("ssrs_rotor_encounters_timed", true, traj, traj_offsets, ntracks, alt, dt, cellinfo, rows, cols, turbines,
+                      reach, zband, nturb, bin_start, bin_items, hits, first_step, points_per_turbine, time_per_turbine, stream);
 }
 
 extern "C" int ssrs_turbine_encounter_counts(const uint32_t *hits, int64_t ntracks, int nturb,

@@ -81,6 +81,7 @@ class Simulator(Config):
             self._flight_params()
         if self.flight_time:
             self._time_params()
+        self._check_rotor_exposure_time()
         self._check_rotor_geometry(turbines)
         print(f'\n---- SSRS in {self.sim_mode} mode')
         print(f'Run name: {self.run_name}')
@@ -137,7 +138,8 @@ class Simulator(Config):
         self.rotor_residence_time_counts = {}  # the same of the moves that leave a point in the rotor zone (flight_height too)
         self.flight_times = {}            # (case_id, real_id) -> int64 (this rank's tracks, 2): [total, in zone] microseconds
         self.turbine_rotor_encounters = {}  # rotor_geometry='turbine': (case_id, real_id) -> dict(tracks_per_turbine,
-        #                                     points_per_turbine int64, turbines_per_track, first_step int32)
+        #                                     points_per_turbine int64, turbines_per_track, first_step int32; with
+        #                                     rotor_exposure_time also time_per_turbine int64, microseconds)
         self.wtk_layers = {
             'wspeed': f'windspeed_{str(int(self.wtk_orographic_height))}m',
             'wdirn': f'winddirection_{str(int(self.wtk_orographic_height))}m',
@@ -228,6 +230,19 @@ class Simulator(Config):
 
     def _rotor_per_turbine(self):
         return str(self.rotor_geometry).lower() == 'turbine'
+
+    def _check_rotor_exposure_time(self):
+        """rotor_exposure_time sums K16's durations over K15's cylinders along K14's heights: it needs all three.  (The
+        turbines, and their t_hh / t_rd, are rotor_geometry = 'turbine''s to ask for.)"""
+        if not self.rotor_exposure_time:
+            return
+        for ok, field, why in ((self.flight_height, 'flight_height=True', 'the cylinders are tested against the heights '
+                                'along the tracks'),
+                               (self._rotor_per_turbine(), "rotor_geometry='turbine'", 'the time is summed inside every '
+                                "turbine's own cylinder (turbines with t_hh and t_rd)"),
+                               (self.flight_time, 'flight_time=True', 'the time of every move is what is summed')):
+            if not ok:
+                raise ValueError(f'rotor_exposure_time = True needs {field}: {why}')
 
     def _check_rotor_geometry(self, turbines):
         """rotor_geometry / rotor_clearance, and what 'turbine' needs that can be told before anything is computed."""
@@ -807,6 +822,7 @@ class Simulator(Config):
         if heights:
             dem = to_dev(self._terrain['Elevation'], torch.float64)
         timed = bool(self.flight_time)
+        exposure = bool(self.rotor_exposure_time)       # (the constructor saw to heights, timed and rotor)
 
         def run(item):
             case_id, real_id, fields, seed, lift, wind = item
@@ -846,8 +862,10 @@ class Simulator(Config):
                                                         device=my_starts.device)
                         fly['rotor_first_step'] = torch.full((hi - lo,), -1, dtype=torch.int32, device=my_starts.device)
                         fly['rotor_points'] = torch.zeros(n_rotor, dtype=torch.int64, device=my_starts.device)
+                        if exposure:
+                            fly['rotor_time'] = torch.zeros(n_rotor, dtype=torch.int64, device=my_starts.device)
                     consumers.append(self._flight_consumer(lift, dem, fly, enc_geometry if encounters else None, rotor,
-                                                           keep_masked=timed))
+                                                           keep_masked=timed, defer_rotor=exposure))
                 if timed:
                     # after the flight consumer, whose traj_band of the chunk it reads: one raster of microseconds per
                     # item (two with flight_height), accumulated over chunks and parts, and this rank's per-track rows
@@ -855,7 +873,7 @@ class Simulator(Config):
                                  rows=torch.zeros((hi - lo, 2), dtype=torch.int64, device=my_starts.device))
                     if heights:
                         spent['band_time_hist'] = torch.zeros_like(spent['time_hist'])
-                    consumers.append(self._time_consumer(wind, spent, fly if heights else None))
+                    consumers.append(self._time_consumer(wind, spent, fly if heights else None, rotor if exposure else None))
                 chunks = self._device_chunks(batch, consumers) if consumers else None
                 if self.save_tracks:
                     # (inside the stream's scope: long trajectories are stepped again range by range while written)
@@ -973,15 +991,19 @@ class Simulator(Config):
         flight.height_params(who='Config.flight_height_* / rotor_zone', **kw)
         return kw, airspeed, sink
 
-    def _flight_consumer(self, lift, dem, fly, geometry, rotor=None, keep_masked=False):
+    def _flight_consumer(self, lift, dem, fly, geometry, rotor=None, keep_masked=False, defer_rotor=False):
         """A chunk through the flight-height scan (K14): `fly['band_hist']` is added to, the chunk's tracks get their rows of
         `fly['rows']`; with `geometry` the points in the rotor zone go through the encounter kernel into `fly['hits']` /
         `fly['first_step']`; with `rotor` (the cylinders on the device) the points and their heights go through the rotor
         kernel (K15) into `fly['rotor_hits']` / `fly['rotor_first_step']` / `fly['rotor_points']`.  The item's cellinfo is
         built here, from its un-thresholded updraft `lift` and the DEM.  keep_masked: the chunk's traj_band stays in
-        `fly['masked']` for the consumer behind this one (_time_consumer)."""
+        `fly['masked']` for the consumer behind this one (_time_consumer).  defer_rotor (rotor_exposure_time): the rotor
+        kernel is not called here but behind K16, where the chunk's dt exists: the chunk's alt stays in `fly['alt']` and the
+        item's cellinfo in `fly['cellinfo']` for _time_consumer."""
         kw, airspeed, sink = self._flight_params()
         cellinfo = flight.altitude_cellinfo(lift, dem, self.resolution, airspeed, sink)
+        if defer_rotor:
+            fly['cellinfo'] = cellinfo
         radius_cells = float(self.turbine_encounter_radius) / float(self.resolution)
 
         def consume(t0, t1, traj, off):
@@ -991,7 +1013,9 @@ class Simulator(Config):
             fly['rows'][t0:t1] = out['heights']
             if keep_masked:
                 fly['masked'] = out['masked']
-            if rotor is not None:
+            if defer_rotor:
+                fly['alt'] = out['alt']
+            elif rotor is not None:
                 cells, reach, zband, rotor_bins = rotor
                 turbines_mod.rotor_encounters(traj, out['alt'], off, cellinfo, cells, reach, zband, self.gridsize,
                                               bins=rotor_bins, hits=fly['rotor_hits'][t0:t1],
@@ -1020,18 +1044,27 @@ class Simulator(Config):
         entry = next(w for w in self._wind if w.case_id == case_id)
         return flight.wind_cellinfo(*self._wind_rasters(entry), self._time_ray_axes())
 
-    def _time_consumer(self, wind, spent, fly):
+    def _time_consumer(self, wind, spent, fly, rotor=None):
         """A chunk through the flight-time kernel (K16): `spent['time_hist']` (and, with `fly`, the flight consumer's dict
         whose 'masked' is the chunk's traj_band, `spent['band_time_hist']`) is added to, the chunk's tracks get their rows
-        of `spent['rows']`."""
+        of `spent['rows']`.  With `rotor` (rotor_exposure_time: the cylinders on the device) the chunk's dt is kept and the
+        rotor kernel runs here in its timed form, on the chunk's alt that the flight consumer left in `fly['alt']`, into
+        `fly['rotor_hits']` / `fly['rotor_first_step']` / `fly['rotor_points']` / `fly['rotor_time']`."""
         kw = self._time_params()
         ray_axes = self._time_ray_axes()
 
         def consume(t0, t1, traj, off):
             out = flight.compute_track_times(traj, self.gridsize, offsets=off, wind=wind, ray_axes=ray_axes,
                                              masked=None if fly is None else fly.pop('masked'),
-                                             time_hist=spent['time_hist'], band_time_hist=spent.get('band_time_hist'), **kw)
+                                             time_hist=spent['time_hist'], band_time_hist=spent.get('band_time_hist'),
+                                             want_dt=rotor is not None, **kw)
             spent['rows'][t0:t1] = out['times']
+            if rotor is not None:
+                cells, reach, zband, rotor_bins = rotor
+                turbines_mod.rotor_encounters(traj, fly.pop('alt'), off, fly['cellinfo'], cells, reach, zband, self.gridsize,
+                                              bins=rotor_bins, hits=fly['rotor_hits'][t0:t1],
+                                              first_step=fly['rotor_first_step'][t0:t1], points=fly['rotor_points'],
+                                              dt=out['dt'], time=fly['rotor_time'])
         return consume
 
     def _store_flight_time(self, case_id, real_id, spent, sharded):
@@ -1068,7 +1101,9 @@ class Simulator(Config):
     def _store_flight(self, case_id, real_id, fly, nturb, sharded):
         """Keeps the rotor-zone raster and the per-track heights of one (case, realisation) and writes
         <id>_rotor_presence.npy (int32 holding uint32) and <id>_flight_heights.npy (int32 (tracks, 3): [points in the zone,
-        least, greatest height in mm]); with encounters also <id>_rotor_turbine_encounters.npy.  Checked by its checksum:
+        least, greatest height in mm]); with encounters also <id>_rotor_turbine_encounters.npy; with rotor_geometry = 'turbine'
+        <id>_turbine_rotor_encounters.npy and, with rotor_exposure_time, <id>_turbine_rotor_time.npy (int64 (nturb,)
+        microseconds, refused when a turbine has time without points or more than points x (2^31 - 1)).  Checked by its checksum:
         this rank's raster must add up to the in-zone points of its tracks.  Track-sharded runs sum the raster (and the
         per-turbine counts) over the ranks as _store_occupancy does and rank 0 writes the raster; the per-track rows stay
         this rank's tracks, like first_step, and <id>_flight_heights.npy is then rank 0's share."""
@@ -1103,14 +1138,32 @@ class Simulator(Config):
             # runs sum both columns over the ranks, the per-track rows stay this rank's
             per_turbine, per_track = turbines_mod.encounter_counts(fly['rotor_hits'], int(fly['rotor_points'].numel()))
             both = torch.stack([per_turbine, fly['rotor_points']], 1).cpu().numpy().astype(np.int64)
+            spent = fly['rotor_time'].cpu().numpy().astype(np.int64) if 'rotor_time' in fly else None
+            if spent is not None:
+                # rotor_exposure_time: the cheap invariant that stands in for a checksum -- K16 writes 0 <= dt <= 2^31 - 1, so
+                # a turbine's time is at most that much per point inside it, and none without a point
+                # (Python integers: points x (2^31 - 1) passes int64 from 2^32 points on)
+                most = both[:, 1].astype(object) * (2 ** 31 - 1)
+                wrong = np.nonzero((spent < 0) | (spent.astype(object) > most).astype(bool))[0]
+                if wrong.size:
+                    t = int(wrong[0])
+                    raise RuntimeError(f'{id_str}: rotor exposure time: turbine {t} has {int(spent[t]) % 2 ** 64} us for '
+                                       f'{int(both[t, 1])} points inside its cylinder ({wrong.size} turbines like it)')
             if sharded:
                 both = np.asarray(self._allreduce_sum(both.reshape(-1)), dtype=np.int64).reshape(-1, 2)
+                if spent is not None:
+                    spent = np.asarray(self._allreduce_sum(spent), dtype=np.int64)
             self.turbine_rotor_encounters[key] = dict(
                 tracks_per_turbine=both[:, 0].copy(), points_per_turbine=both[:, 1].copy(),
                 turbines_per_track=per_track.cpu().numpy().astype(np.int32),
                 first_step=fly['rotor_first_step'].cpu().numpy().astype(np.int32))
+            if spent is not None:
+                # <id>_turbine_rotor_time.npy, int64 (nturb,) microseconds
+                self.turbine_rotor_encounters[key]['time_per_turbine'] = spent
             if writes:
                 np.save(os.path.join(self.mode_data_dir, f'{id_str}_turbine_rotor_encounters.npy'), both)
+                if spent is not None:
+                    np.save(os.path.join(self.mode_data_dir, f'{id_str}_turbine_rotor_time.npy'), spent)
 
     def _store_occupancy(self, case_id, real_id, counts, cells, sharded):
         """Keeps the occupancy raster of one (case, realisation) as numpy int32 and writes <id>_occupancy.npy.  Checked
@@ -1423,6 +1476,28 @@ class Simulator(Config):
         out = np.ascontiguousarray((total[:-1] / total[-1]).reshape(2, nturb).T)
         if self._rank() == 0:
             np.save(os.path.join(self.mode_data_dir, 'summary_turbine_rotor_encounters.npy'), out)
+        self._barrier()
+        return out
+
+    def compute_turbine_rotor_time(self):
+        """Per turbine, the seconds spent inside its own rotor cylinder per simulated track (rotor_exposure_time = True;
+        DESIGN.md K15 timed): f64 (nturb,), the mean over all (case, realisation) items of time_per_turbine / 1e6 /
+        track_count, in the order of `turbines.get_locations()`; case-sharded runs take the mean over every rank's items.
+        Writes summary_turbine_rotor_time.npy.  ValueError when simulate_tracks computed none."""
+        items = [self.turbine_rotor_encounters[key] for key in sorted(self.turbine_rotor_encounters)]
+        items = [enc for enc in items if 'time_per_turbine' in enc]
+        if not items:
+            raise ValueError('no rotor exposure time was computed: run simulate_tracks() with rotor_exposure_time=True '
+                             "(flight_height=True, rotor_geometry='turbine', flight_time=True and turbines)")
+        total = np.zeros(items[0]['time_per_turbine'].size + 1, dtype=np.float64)          # [..., number of items]
+        for enc in items:
+            total[:-1] += enc['time_per_turbine'] / 1e6 / float(self.track_count)
+            total[-1] += 1.
+        if self._world() > 1 and not self._shards_tracks():
+            total = self._allreduce_sum(total)                      # the cases of the other ranks
+        out = total[:-1] / total[-1]
+        if self._rank() == 0:
+            np.save(os.path.join(self.mode_data_dir, 'summary_turbine_rotor_time.npy'), out)
         self._barrier()
         return out
 

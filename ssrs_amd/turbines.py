@@ -320,13 +320,16 @@ def rotor_geometry(turbines, dem, bounds, resolution, clearance=0.):
 
 
 def rotor_encounters(traj, alt, offsets, cellinfo, xy_cells, reach, zband, gridshape, bins=None, hits=None, first_step=None,
-                     points=None):
+                     points=None, dt=None, time=None):
     """ssrs_rotor_encounters on device tensors (K15): the tracks through every turbine's own cylinder, and the points inside
     it.  traj, offsets, xy_cells, bins, hits and first_step as turbine_encounters takes them; alt int32 (points) as
     flight.compute_track_altitudes(want_alt=True) gives it, indexed like traj; cellinfo of flight.altitude_cellinfo; reach
     (nturb,) f64 and zband (nturb, 2) int32 of rotor_geometry.  bins are built here from `reach` when None.  points: int64
     device tensor (nturb,), ADDED to when given (the exposure).  first_step=False / points=False leave that output out
-    (None is returned in its place).  Returns (hits, first_step, points)."""
+    (None is returned in its place).  Returns (hits, first_step, points).
+    dt: int32 (points) as flight.compute_track_times(want_dt=True) gives it, indexed like traj: the call is then
+    ssrs_rotor_encounters_timed and returns (hits, first_step, points, time); time: int64 device tensor (nturb,) holding
+    uint64 microseconds, ADDED to when given and created zero otherwise -- the dt of the points inside each cylinder."""
     who = 'rotor_encounters'
     rows, cols = int(gridshape[0]), int(gridshape[1])
     xy = xy_cells if is_tensor(xy_cells) else np.asarray(xy_cells, dtype=np.float64).reshape(-1, 2)
@@ -347,11 +350,24 @@ def rotor_encounters(traj, alt, offsets, cellinfo, xy_cells, reach, zband, grids
     heights = to_dev(alt, torch.int32).reshape(-1)
     if int(heights.numel()) != int(pts.shape[0]):
         raise ValueError(f'{who}: alt has {heights.numel()} entries for {pts.shape[0]} points (it is indexed like traj)')
+    if dt is None and time is not None:
+        raise ValueError(f'{who}: time is given without dt (the exposure time is summed from dt)')
+    if dt is not None:
+        if (dt.dtype != torch.int32) if is_tensor(dt) else (np.asarray(dt).dtype != np.int32):
+            raise ValueError(f'{who}: dt must be int32 microseconds indexed like traj (compute_track_times(want_dt=True))')
+        moves = to_dev(dt, torch.int32).reshape(-1)
+        if int(moves.numel()) != int(pts.shape[0]):
+            raise ValueError(f'{who}: dt has {moves.numel()} entries for {pts.shape[0]} points (it is indexed like traj)')
     if not is_tensor(cellinfo) or cellinfo.dtype != torch.int32 or tuple(cellinfo.shape) != (rows, cols, 2) or \
             not cellinfo.is_contiguous() or not cellinfo.is_cuda:
         raise ValueError(f'{who}: cellinfo must be a contiguous int32 device tensor ({rows}, {cols}, 2) (altitude_cellinfo)')
     words = (nturb + 31) // 32
     dev = device()
+    if dt is not None and time is None:
+        time = torch.zeros(nturb, dtype=torch.int64, device=dev)
+    if dt is not None and (not is_tensor(time) or time.dtype != torch.int64 or tuple(time.shape) != (nturb,) or
+                           not time.is_contiguous() or not time.is_cuda):
+        raise ValueError(f'{who}: time must be a contiguous int64 device tensor ({nturb},)')
     if hits is None:
         hits = torch.zeros((ntracks, words), dtype=torch.int32, device=dev)
     if first_step is None:
@@ -378,7 +394,13 @@ def rotor_encounters(traj, alt, offsets, cellinfo, xy_cells, reach, zband, grids
         raise ValueError(f'bins: bin_start has {bin_start.numel()} entries, expected {nbins + 1} for this raster')
     if ntracks == 0 or pts.numel() == 0 or bin_items.numel() == 0:
         # nothing to read, or no cylinder reaches the raster (empty tensors have no address to hand over)
-        return hits, first_step, points
+        return (hits, first_step, points) if dt is None else (hits, first_step, points, time)
+    if dt is not None:
+        nat.check(nat.lib().ssrs_rotor_encounters_timed(
+            nat.ptr(pts), nat.ptr(off), C.c_int64(ntracks), nat.ptr(heights), nat.ptr(moves), nat.ptr(cellinfo), rows, cols,
+            nat.ptr(xy), nat.ptr(reach_dev), nat.ptr(zband_dev), nturb, nat.ptr(bin_start), nat.ptr(bin_items),
+            nat.ptr(hits), nat.ptr(first_step), nat.ptr(points), nat.ptr(time), stream_ptr()))
+        return hits, first_step, points, time
     nat.check(nat.lib().ssrs_rotor_encounters(
         nat.ptr(pts), nat.ptr(off), C.c_int64(ntracks), nat.ptr(heights), nat.ptr(cellinfo), rows, cols, nat.ptr(xy),
         nat.ptr(reach_dev), nat.ptr(zband_dev), nturb, nat.ptr(bin_start), nat.ptr(bin_items), nat.ptr(hits),

@@ -13,7 +13,14 @@ in two steps:
 and `tools/microbench/stream 1` (--stream-bin, the built yardstick) in the same visit.  Without --step this is the driver: it
 runs each step as a child under its own `timeout -k 10`, stops at the first that fails, and writes the table to --out.
 Algorithmic bytes: 8 B per point for K15 (traj and alt), 4 B for K8; the elevation gathers, the turbine tables and the atomics
-are left out."""
+are left out.
+
+--timed adds the leg of the timed form (ssrs_rotor_encounters_timed): `K15 timed`, the same call with the dt K16 computes for
+these points in a uniform wind and time_per_turbine (8 B a point plus 4 B per point inside a cylinder).  --parent-lib <a
+libssrs_hip.so built from the parent commit> makes the driver run every step four times in one visit -- the parent's library,
+this tree's with the timed leg, the parent's again (SSRS_HIP_LIB selects the library of a child) -- and print, per step, the
+parent's two medians of the untimed K15, their difference (the run-to-run spread), this tree's median, and whether it lies
+within that spread of the parent's."""
 import argparse
 import json
 import os
@@ -27,23 +34,34 @@ ap.add_argument('--long-length', type=float, default=7.5e6)
 ap.add_argument('--step', choices=('spread', 'parked'), default=None)
 ap.add_argument('--stream-bin', default=None, help='built tools/microbench/stream.hip; run as `<bin> 1`')
 ap.add_argument('--out', default=None, help='write the markdown table here as well')
+ap.add_argument('--timed', action='store_true', help='also time ssrs_rotor_encounters_timed')
+ap.add_argument('--parent-lib', default=None, help="the parent commit's library: the untimed K15 of both, side by side")
 args = ap.parse_args()
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 STEP_SECONDS = 300
 
 
+def run_step(step, timed, lib=None):
+    cmd = ['timeout', '-k', '10', str(STEP_SECONDS), sys.executable, os.path.abspath(__file__), '--step', step,
+           '--points', repr(args.points), '--long-length', repr(args.long_length)] + (['--timed'] if timed else [])
+    env = dict(os.environ, SSRS_HIP_LIB=os.path.abspath(lib)) if lib else None
+    run = subprocess.run(cmd, capture_output=True, text=True, env=env)
+    sys.stdout.write(run.stdout)
+    if run.returncode != 0:
+        sys.stderr.write(run.stderr)
+        sys.exit(f'step {step} ended with status {run.returncode}: nothing more is started')
+    return json.loads(run.stdout.strip().splitlines()[-1])
+
+
 def driver():
-    lines, results = [], {}
+    lines, results, parent = [], {}, {}
     for step in ('spread', 'parked'):
-        cmd = ['timeout', '-k', '10', str(STEP_SECONDS), sys.executable, os.path.abspath(__file__), '--step', step,
-               '--points', repr(args.points), '--long-length', repr(args.long_length)]
-        run = subprocess.run(cmd, capture_output=True, text=True)
-        sys.stdout.write(run.stdout)
-        if run.returncode != 0:
-            sys.stderr.write(run.stderr)
-            sys.exit(f'step {step} ended with status {run.returncode}: nothing more is started')
-        results[step] = json.loads(run.stdout.strip().splitlines()[-1])
+        if args.parent_lib:
+            parent[step] = [run_step(step, False, args.parent_lib)]
+        results[step] = run_step(step, args.timed)
+        if args.parent_lib:
+            parent[step].append(run_step(step, False, args.parent_lib))
     head = results['spread']
     lines += [f'{head["rows"]} x {head["cols"]}, {head["points"]:.2e} points, {head["nshort"]} tracks of 5000 points and '
               f'{head["nlong"]} of {head["long_length"]}, {head["nturb"]} turbines, {head["device"]}', '',
@@ -51,7 +69,9 @@ def driver():
               '|---|---|---|---|---|---|---|---|']
     for step, res in results.items():
         k8 = res['calls']['K8']['median']
-        for call, nbytes in (('K15', 8), ('K15 bitmap', 8), ('K8', 4)):
+        for call, nbytes in (('K15 timed', 8), ('K15', 8), ('K15 bitmap', 8), ('K8', 4)):
+            if call not in res['calls']:
+                continue
             t = res['calls'][call]
             lines.append(f'| {step} | {call} | {nbytes} | {t["median"]:.3f} | {res["points"] / t["median"] / 1e6:.2f} | '
                          f'{res["points"] * nbytes / t["median"] / 1e6:.0f} | {t["median"] / k8:.2f} | '
@@ -60,6 +80,23 @@ def driver():
     for step, res in results.items():
         lines.append(f'{step}: {res["inside"]} (point, turbine) pairs inside a cylinder, {res["tracks_hit"]} tracks with one, '
                      f'{res["turbines_hit"]} turbines met; K8 at {res["radius"]:.2f} cells: {res["k8_tracks_hit"]} tracks')
+    for step, res in results.items():
+        if 'K15 timed' in res['calls']:
+            lines.append(f'{step}: K15 timed / K15 = {res["calls"]["K15 timed"]["median"] / res["calls"]["K15"]["median"]:.3f}; '
+                         f'{res["time_us"]} us inside the cylinders over {res["inside"]} (point, turbine) pairs')
+    if parent:
+        lines += ['', '| step | untimed K15 | median ms | runs (ms) |', '|---|---|---|---|']
+        for step, (first, second) in parent.items():
+            for label, res in (('parent, first', first), ('this tree', results[step]), ('parent, second', second)):
+                t = res['calls']['K15']
+                lines.append(f'| {step} | {label} | {t["median"]:.4f} | {", ".join(f"{m:.4f}" for m in t["runs"])} |')
+        lines.append('')
+        for step, (first, second) in parent.items():
+            a, b, new = (r['calls']['K15']['median'] for r in (first, second, results[step]))
+            spread, centre = abs(a - b), (a + b) / 2.
+            lines.append(f'{step}: the parent\'s medians {a:.4f} and {b:.4f} ms differ by {spread:.4f} ms (the run-to-run spread); '
+                         f'this tree\'s {new:.4f} ms lies {abs(new - centre):.4f} ms from their mean {centre:.4f}: '
+                         f'{"within" if abs(new - centre) <= spread else "OUTSIDE"} the spread')
     if args.stream_bin:
         run = subprocess.run(['timeout', '-k', '10', '120', args.stream_bin, '1'], capture_output=True, text=True)
         sys.stdout.write(run.stdout)
@@ -145,10 +182,20 @@ def step(which):
         state['hits'] = torch.zeros((ntracks, words), dtype=torch.int32, device=dev)
         state['first'] = torch.full((ntracks,), -1, dtype=torch.int32, device=dev)
         state['points'] = torch.zeros(nturb, dtype=torch.int64, device=dev)
+        state['time'] = torch.zeros(nturb, dtype=torch.int64, device=dev)
 
     def k15(points):
         tb.rotor_encounters(traj, alt, off, cellinfo, xy_dev, reach_dev, zband_dev, (rows, cols), bins=bins, hits=state['hits'],
                             first_step=state['first'], points=state['points'] if points else False)
+
+    if args.timed:
+        # the dt K16 gives these points in a uniform wind: every point inside a cylinder then costs one more 4-byte load
+        dt = flight.compute_track_times(traj, (rows, cols), offsets=off, resolution=res, airspeed=15., wind=(8., 240.),
+                                        want_dt=True)['dt']
+
+    def k15_timed():
+        tb.rotor_encounters(traj, alt, off, cellinfo, xy_dev, reach_dev, zband_dev, (rows, cols), bins=bins, hits=state['hits'],
+                            first_step=state['first'], points=state['points'], dt=dt, time=state['time'])
 
     def k8():
         tb.turbine_encounters(traj, off, xy_dev, radius, (rows, cols), bins=bins8, hits=state['hits'], first_step=state['first'])
@@ -170,7 +217,13 @@ def step(which):
     calls['K15 bitmap'] = median_ms(lambda: k15(False))
     calls['K15'] = median_ms(lambda: k15(True))
     per_turbine, _ = tb.encounter_counts(state['hits'], nturb)
-    print(json.dumps(dict(rows=rows, cols=cols, points=total, nshort=nshort, nlong=nlong, long_length=length, nturb=nturb,
+    extra = {}
+    if args.timed:
+        untimed = {k: state[k].clone() for k in ('hits', 'first', 'points')}
+        calls['K15 timed'] = median_ms(k15_timed)
+        assert all(torch.equal(state[k], v) for k, v in untimed.items()), 'the timed call changed hits, first_step or points'
+        extra = dict(time_us=int(state['time'].sum()))
+    print(json.dumps(dict(**extra, rows=rows, cols=cols, points=total, nshort=nshort, nlong=nlong, long_length=length, nturb=nturb,
                           device=torch.cuda.get_device_name(0), radius=radius, calls=calls,
                           inside=int(state['points'].sum()), tracks_hit=int((state['first'] >= 0).sum()),
                           turbines_hit=int((per_turbine > 0).sum()), k8_tracks_hit=k8_tracks_hit)), flush=True)
