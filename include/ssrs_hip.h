@@ -1094,6 +1094,12 @@ int ssrs_roam_tables_selftest(const double *updraft, const float *potential, con
  * SSRS_TRACKS_ROAM_FEED=0 runs without feeder waves (fed == 0). */
 void ssrs_tracks_roam_feed_counts(int64_t *fed, int64_t *own);
 
+/* Waves of the roaming stepper that left a launch because its stop flag was
+ * up (the launch's first wave was through its steps), summed over the calling
+ * thread's last ssrs_tracks_simulate* call (host value, thread-local).
+ * 0 with SSRS_TRACKS_NO_ROAM_STOP. */
+int64_t ssrs_tracks_roam_stopped_waves(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,7 @@ EXPORTS = (
     'ssrs_altitude_cellinfo', 'ssrs_track_altitude_workspace_bytes', 'ssrs_track_altitude',
     'ssrs_flight_windinfo', 'ssrs_track_time',
     'ssrs_roam_pair_word_selftest', 'ssrs_tracks_roam_feed_counts', 'ssrs_roam_tables_selftest',
+    'ssrs_tracks_roam_stopped_waves',
 )
 
 
@@ -262,6 +263,8 @@ def lib():
         L.ssrs_roam_tables_selftest.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 4
         L.ssrs_tracks_roam_feed_counts.restype = None
         L.ssrs_tracks_roam_feed_counts.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.ssrs_tracks_roam_stopped_waves.restype = C.c_int64
+        L.ssrs_tracks_roam_stopped_waves.argtypes = []
         _lib = L
     return _lib
 

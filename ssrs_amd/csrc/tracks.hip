@@ -696,6 +696,7 @@ struct alignas(16) TrackCtl {
     uint32_t roam_stop;                                              // k_step_roam: launch + 1 of the launch whose first wave is through its steps
     uint32_t deal_live;                                              // k_wander_windows: live tracks it found (the host picks the deal's block width from it)
     unsigned long long roam_fed, roam_own;   // k_step_roam: wave-pairs whose uniforms came from the feeder wave / from the wave's own Philox (sum: roam_pairs)
+    unsigned long long roam_stopped;         // k_step_roam: waves that left a launch because its stop flag was up
 };
 
 static_assert(sizeof(TrackCtl) <= 128 * sizeof(uint32_t), "final read-back slot of pinned_counts()");
@@ -1124,7 +1125,7 @@ __global__ void k_ctl_init(TrackCtl *ctl, const PriorArg pr, double *__restrict_
         ctl->error = bad; ctl->par_min = 0xFFFFFFFFu; ctl->steps = 0; ctl->strays = 0; ctl->bin_done = 0; ctl->pad = 0; ctl->roam_slow = 0; ctl->roam_pairs = 0;
         ctl->dbg_tsum = ctl->dbg_tmax = ctl->dbg_waves = ctl->dbg_slowmax = 0;
         ctl->roam_stop = ctl->deal_live = 0;
-        ctl->roam_fed = ctl->roam_own = 0;
+        ctl->roam_fed = ctl->roam_own = ctl->roam_stopped = 0;
     }
     if (d < 9) ctl->prior[d] = pr.v[d];
     if (d >= 9) return;
@@ -2364,9 +2365,10 @@ __global__ __launch_bounds__(kBlock) void k_fine_build(const double *__restrict_
 // one 16-byte record per lane and TRIP (four pairs, one dword each: roam_pair_word), kFeedDepth trips deep, a tag per slot.
 //   feeder:   waits (bounded: s_sleep and look again) until trip n < read + kFeedDepth, writes the records of trip n, then
 //             the slot's tag = n.  Leaves at DONE, after a.steps / 8 trips, or when its idle polls run out.
-//   stepper:  reads slot and tag of trip n + 1 at the top of trip n (the LDS latency is off its chain), publishes
-//             read = n + 1, and takes trip n's uniforms from the record if its tag was n.  Any other tag: it computes the
-//             four blocks itself, as the kernel without feeders does.  It NEVER waits.  On every way out it publishes DONE.
+//   stepper:  behind the third gather of trip n - 1 (before the loop for trip 0) it takes tag and record of trip n, which it
+//             asked for a trip earlier (the LDS latency is off its chain), publishes read = n + 1, asks for slot and tag of
+//             trip n + 1, and steps trip n on the record if its tag was n.  Any other tag: it computes the four blocks
+//             itself, as the kernel without feeders does.  It NEVER waits.  On every way out it publishes DONE.
 // The LDS executes one wave's operations in order, so tag-after-data on the feeder and tag-before-data on the stepper make
 // a record whose tag matches complete, and the stepper's `read` store follows its read of the slot it frees.
 constexpr int kFeedDepth = 3;                        // (the window leaves 16 KB: 4 waves x 3 slots x 1 KB + tags)
@@ -2495,7 +2497,7 @@ __global__ __launch_bounds__(FEED ? 2 * BT : BT) void k_step_roam(const StepArgs
                 const uint32_t rd = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(
                     __hip_atomic_load(&s_read[wv], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP))));
                 if (rd == kFeedDone) break;
-                if (n >= rd + static_cast<uint32_t>(kFeedDepth)) {          // (rd <= ntrips: no wrap)
+                if (n >= rd + static_cast<uint32_t>(kFeedDepth)) {          // (rd <= ntrips + 1: no wrap)
                     if (naps-- == 0u) break;
                     __builtin_amdgcn_s_sleep(16);
                     continue;
@@ -2616,9 +2618,36 @@ __global__ __launch_bounds__(FEED ? 2 * BT : BT) void k_step_roam(const StepArgs
     int it = 0;
     uint32_t n_pairs = 0, n_slow = 0;                         // wave-uniform
     const unsigned long long t_begin = a.debug_roam ? __builtin_amdgcn_s_memtime() : 0ull;
+    // A launch ends when its FIRST wave is through its steps: that wave raises the flag (launch + 1: the control
+    // block is zeroed per call and launches count up), every other wave whose tracks are all released leaves at
+    // its next trip.  A released track's Philox block index follows from its own k, so nothing ties the waves'
+    // iteration counts together -- and a wave that is slower (a track on its way
+    // out of its basin pays a global atomic per visit outside the block's window: +257 clocks per pair,
+    // profiles/r03_roam_waves.txt) no longer holds the other 900 back for the 12 % it is behind.
+    const uint32_t stop_stamp = static_cast<uint32_t>(a.launch) + 1u;
+    uint32_t stop_seen = 0u;
+    bool stopped = false;
+    // ---- whether the wave goes on to its next trip (of eight iterations, from the next multiple of 8 behind `it`),
+    // decided a pair and more ahead of it.  All of it is wave-uniform.
+    // (a wave with a lane that still waits for its release runs the launch out: the host counts a.steps
+    // iterations for it, and a track released one launch late would start on the odd half of a Philox block)
+    // (no launch's stamp is 0xFFFFFFFF: without the stop flag nothing ever matches, and no branch asks which it is)
+    const uint32_t stop_match = a.roam_stop ? stop_stamp : 0xFFFFFFFFu;
+    unsigned long long stepping = 0ull, waiting = 0ull;
+    bool stop_hit = false, stop_now = false, leave = false;
+    auto look_ahead = [&](const bool first = false) __attribute__((always_inline)) {
+        const int itn = first ? 0 : (it | 7) + 1;
+        stepping = __ballot(static_cast<uint32_t>(itn - rel) < span);
+        waiting = __ballot(itn < rel && span != 0u);
+    };
+    auto decide = [&]() __attribute__((always_inline)) {
+        stop_now = stop_hit & (waiting == 0ull);
+        leave = ((stepping | waiting) == 0ull) | stop_now;
+    };
     // (given: the pair's two uniforms come in `uf`, packed as roam_pair_word packs them; the slow path, which wants all
-    // four words, then computes the block after all)
-    auto one_pair = [&](const uint32_t uf, const bool given) __attribute__((always_inline)) {
+    // four words, then computes the block after all.  flag: the launch's stop flag is asked for behind this pair's gather.
+    // recheck: the look ahead has been taken already, and a lane that ends its track here takes it again)
+    auto one_pair = [&](const uint32_t uf, const bool given, const bool flag = false, const bool recheck = false) __attribute__((always_inline)) {
         uint4 w4 = make_uint4(0u, 0u, 0u, 0u);
         if (!given) w4 = philox_block_b3(a.seed, track, blk_of(it >> 1));
         const uint32_t ufa = given ? uf >> 16 : w4.x >> 16, ufb = given ? uf & 0xFFFFu : w4.z >> 16;
@@ -2659,6 +2688,13 @@ __global__ __launch_bounds__(FEED ? 2 * BT : BT) void k_step_roam(const StepArgs
         {
             const uint32_t cb = static_cast<uint32_t>(cell_b) < last_cell ? static_cast<uint32_t>(cell_b) : last_cell;
             E = *reinterpret_cast<const uint4 *>(pair + ((cb << 7) | (ncb4 << 2)));
+        }
+        // the launch's stop flag, asked for straight behind a gather (the compiler barrier keeps it there) and without a
+        // branch around it: it is the younger load, so the next pair's wait for its entry need not cover it, and a whole
+        // pair passes before its value is looked at (the trip loop below)
+        if (flag) {
+            asm volatile("" ::: "memory");
+            stop_seen = __hip_atomic_load(&ctl->roam_stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         // ---- behind the gather: window coordinates of the two visits, the tests
         const int wra = wr + dra, wca = wc + dca, wrb = wra + drb, wcb = wca + dcb;
@@ -2708,19 +2744,11 @@ __global__ __launch_bounds__(FEED ? 2 * BT : BT) void k_step_roam(const StepArgs
                         if (static_cast<uint32_t>(it + h - rel) < span) slow_step(h ? w4.z : w4.x, h ? w4.w : w4.y);
                     enter(true);
                 }
+                if (recheck) { look_ahead(); decide(); }                       // (a track may have ended: span = 0)
             }
         }
         it += 2;
     };
-    // A launch ends when its FIRST wave is through its steps: that wave raises the flag (launch + 1: the control
-    // block is zeroed per call and launches count up), every other wave whose tracks are all released leaves at
-    // its next trip.  A released track's Philox block index follows from its own k, so nothing ties the waves'
-    // iteration counts together -- and a wave that is slower (a track on its way
-    // out of its basin pays a global atomic per visit outside the block's window: +257 clocks per pair,
-    // profiles/r03_roam_waves.txt) no longer holds the other 900 back for the 12 % it is behind.
-    const uint32_t stop_stamp = static_cast<uint32_t>(a.launch) + 1u;
-    uint32_t stop_seen = 0u;
-    bool stopped = false;
     // ---- the stepping wave's side of the ring: slot and tag of the coming trip, asked for a trip ahead.  The tag first:
     // the LDS takes a wave's reads in order (the asm statements keep the compiler from caching or reordering them)
     uint32_t fd_tag = kFeedNoTag, trip = 0u, fd_slot = 0u, n_fed = 0u;              // trip, fd_slot, n_fed: wave-uniform
@@ -2733,41 +2761,59 @@ __global__ __launch_bounds__(FEED ? 2 * BT : BT) void k_step_roam(const StepArgs
         fd_rec = s_ring[slot * 64u + static_cast<uint32_t>(lane)];
         asm volatile("" ::: "memory");
     };
+    // this trip's slot is read -- the feeder may fill it again -- and the next trip's is asked for.  (a feeder never
+    // comes here: none of its lanes steps or waits)
+    bool fed = false;
+    uint4 rec = make_uint4(0u, 0u, 0u, 0u);
+    auto take_trip = [&]() __attribute__((always_inline)) {
+        fed = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(fd_tag))) == trip;
+        rec = fd_rec;
+        const int p = 4 * static_cast<int>(trip);                      // (trip n begins at it = 8 n)
+        ++trip;
+        if (lane == 0) __hip_atomic_store(&s_read[wv], trip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        fd_slot = fd_slot + 1u == static_cast<uint32_t>(kFeedDepth) ? 0u : fd_slot + 1u;
+        feed_read();
+        if (!fed && !leave && 2 * p + 8 <= a.steps) {                   // (leave never turns false again)
+            rec = make_uint4(roam_pair_word(a.seed, track, blk_of(p)), roam_pair_word(a.seed, track, blk_of(p + 1)),
+                             roam_pair_word(a.seed, track, blk_of(p + 2)), roam_pair_word(a.seed, track, blk_of(p + 3)));
+        }
+    };
+    look_ahead(true);                                // (the first trip; no flag has been looked at)
+    decide();
     if (FEED && !feeder) {
         feed_read();
+        take_trip();
         __builtin_amdgcn_s_setprio(1);               // the SIMD's issue slots to the stepping wave first
     }
+    // How a trip is laid out.  Its four pairs are a chain: wait for the entry, ~37 instructions, the next gather, and
+    // then that gather's shadow, the ~58 instructions of the pair that the chain does not wait for.  A trip's
+    // housekeeping is dealt over the shadows, so that the pair across the trip boundary is no longer than the others:
+    //   behind gather 1   the stop flag's load (the flag as it was about a trip ago when it decides), the fed count,
+    //                     the two ballots of the next trip's first iteration
+    //   behind gather 2   the flag's value against this launch's stamp, `leave` for the next trip
+    //   behind gather 3   the ring: tag and record of the next trip taken, `read` published, the slot behind it asked for
+    //   behind gather 4   the test of `leave` and the loop branch
     for (; it + 8 <= a.steps; ) {
-        // (one scalar test per trip; the flag as it was one trip ago: its load is never waited for on its own)
-        // (a wave with a lane that still waits for its release runs the launch out: the host counts a.steps
-        // iterations for it, and a track released one launch late would start on the odd half of a Philox block)
-        const unsigned long long stepping = __ballot(static_cast<uint32_t>(it - rel) < span), waiting = __ballot(it < rel && span != 0u);
-        const bool stop_now = a.roam_stop && waiting == 0ull &&
-                              static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(stop_seen))) == stop_stamp;
-        if (((stepping | waiting) == 0ull) | stop_now) { stopped = stop_now; break; }
-        if (a.roam_stop) stop_seen = __hip_atomic_load(&ctl->roam_stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (leave) { stopped = stop_now; break; }
         if (FEED) {
-            // (a feeder never comes here: none of its lanes steps or waits)
-            const bool fed = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(fd_tag))) == trip;
-            uint4 rec = fd_rec;
-            // this trip's slot is read -- the feeder may fill it again -- and the next trip's is asked for
-            ++trip;
-            if (lane == 0) __hip_atomic_store(&s_read[wv], trip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            fd_slot = fd_slot + 1u == static_cast<uint32_t>(kFeedDepth) ? 0u : fd_slot + 1u;
-            feed_read();
-            if (!fed) {
-                const int p = it >> 1;
-                rec = make_uint4(roam_pair_word(a.seed, track, blk_of(p)), roam_pair_word(a.seed, track, blk_of(p + 1)),
-                                 roam_pair_word(a.seed, track, blk_of(p + 2)), roam_pair_word(a.seed, track, blk_of(p + 3)));
-            }
+            one_pair(rec.x, true, true);
             n_fed += fed ? 4u : 0u;
-            one_pair(rec.x, true);
-            one_pair(rec.y, true);
-            one_pair(rec.z, true);
-            one_pair(rec.w, true);
+            look_ahead();
+            one_pair(rec.y, true, false, true);
+            stop_hit = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(stop_seen))) == stop_match;
+            decide();
+            const uint32_t uf3 = rec.z, uf4 = rec.w;
+            one_pair(uf3, true, false, true);
+            take_trip();
+            one_pair(uf4, true, false, true);
         } else {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) one_pair(0u, false);
+            one_pair(0u, false, true);
+            look_ahead();
+            one_pair(0u, false, false, true);
+            stop_hit = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(stop_seen))) == stop_match;
+            decide();
+            one_pair(0u, false, false, true);
+            one_pair(0u, false, false, true);
         }
     }
     for (; it < a.steps && !stopped; ) {                     // a.steps is even (host)
@@ -2780,6 +2826,7 @@ __global__ __launch_bounds__(FEED ? 2 * BT : BT) void k_step_roam(const StepArgs
         if (lane == 0) __hip_atomic_store(&s_read[wv], kFeedDone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     if (a.roam_stop && !stopped && it >= a.steps && (threadIdx.x & 63) == 0) atomicMax(&ctl->roam_stop, stop_stamp);
+    if (stopped && (threadIdx.x & 63) == 0) atomicAdd(&ctl->roam_stopped, 1ull);
     if (fast) { row = win_r0 + wr; col = win_c0 + wc; }
     {
         uint32_t nf = n_fine;
@@ -3974,6 +4021,11 @@ extern "C" void ssrs_tracks_roam_feed_counts(int64_t *fed, int64_t *own)
     if (own) *own = g_roam_own;
 }
 
+// waves of that call that left a roaming launch on its stop flag
+static thread_local int64_t g_roam_stopped = 0;
+
+extern "C" int64_t ssrs_tracks_roam_stopped_waves(void) { return g_roam_stopped; }
+
 extern "C" int ssrs_uniform_selftest(uint64_t seed, const uint64_t *track, const uint64_t *step,
                                      double *out, size_t n, void *stream)
 {
@@ -4849,6 +4901,7 @@ int TrackRun::finish(int rc, SsrsTrackStats *stats)
     memcpy(&host_ctl, &host_counts[kFinalSlot], sizeof(TrackCtl));
     g_roam_fed = static_cast<int64_t>(host_ctl.roam_fed);
     g_roam_own = static_cast<int64_t>(host_ctl.roam_own);
+    g_roam_stopped = static_cast<int64_t>(host_ctl.roam_stopped);
     if (stats) {
         stats->total_steps = static_cast<int64_t>(host_ctl.steps);
         stats->launches = launch;
@@ -4900,7 +4953,7 @@ static int tracks_simulate_impl(const TrackCall &c, SsrsTrackStats *stats)
     int rc = check_track_args(c);
     if (rc != SSRS_OK) return rc;
     if (stats) *stats = SsrsTrackStats{};
-    g_roam_fed = g_roam_own = 0;
+    g_roam_fed = g_roam_own = g_roam_stopped = 0;
     if (SsrsTrajRecorder *rec = c.rec) {
         rec->used = 0;
         rec->chunks.clear();

@@ -480,6 +480,7 @@ def simulate_tracks(move_dirn, starts, grid_shape, memory_parameter=1,
                            roam_wave_pairs=int(stats.roam_wave_pairs),
                            roam_slow_wave_pairs=int(stats.roam_slow_wave_pairs),
                            roam_fed_wave_pairs=int(roam_fed.value), roam_own_wave_pairs=int(roam_own.value),
+                           roam_stopped_waves=int(nat.lib().ssrs_tracks_roam_stopped_waves()),
                            roam_shuffles=int(stats.roam_shuffles),
                            roam_wide_launches=int(stats.roam_wide_launches)))
 
