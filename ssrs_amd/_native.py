@@ -32,36 +32,105 @@ SSRS_ALLEN_PATH = {'auto': 0, 'lds': 1, 'global': 2}             # SSRS_ALLEN_AU
 SSRS_ALLEN_MAX_UPDRAFTS, SSRS_ALLEN_TABLE_COLS = 1 << 22, 6
 SSRS_INTERP = {'nearest': 0, 'linear': 1, 'cubic': 2}          # SSRS_INTERP_NEAREST / _LINEAR / _CUBIC
 
-EXPORTS = (
-    'ssrs_version', 'ssrs_build_flags', 'ssrs_last_error', 'ssrs_device_info', 'ssrs_slope_aspect',
-    'ssrs_orographic_updraft', 'ssrs_threshold_updraft', 'ssrs_updraft_from_dem',
-    'ssrs_lattice_workspace_bytes', 'ssrs_updraft_from_dem_lattice',
-    'ssrs_wind_from_lattice', 'ssrs_wind_triangles_workspace_bytes', 'ssrs_wind_from_triangles',
-    'ssrs_wind_nearest_workspace_bytes', 'ssrs_wind_nearest_index', 'ssrs_wind_from_nearest',
-    'ssrs_wind_cubic_workspace_bytes', 'ssrs_wind_from_triangles_cubic', 'ssrs_thermal_seeds', 'ssrs_blur_workspace_bytes',
-    'ssrs_gaussian_blur', 'ssrs_thermal_fields', 'ssrs_potential_temperature', 'ssrs_deardorff_velocity',
-    'ssrs_thermal_updraft', 'ssrs_scalar_interp_workspace_bytes', 'ssrs_scalar_from_samples', 'ssrs_wtk_thermal_fields',
-    'ssrs_track_params_init', 'ssrs_transition_table_build',
-    'ssrs_transition_ring_bytes', 'ssrs_transition_ring_build',
-    'ssrs_transition_thr_bytes', 'ssrs_transition_thr_build',
-    'ssrs_tracks_workspace_bytes', 'ssrs_tracks_workspace_bytes_ex', 'ssrs_tracks_simulate', 'ssrs_uniform_selftest',
-    'ssrs_traj_recorder_create', 'ssrs_traj_recorder_destroy', 'ssrs_traj_recorder_complete',
-    'ssrs_traj_recorder_used', 'ssrs_tracks_simulate_rec', 'ssrs_tracks_gather', 'ssrs_tracks_simulate_h64',
-    'ssrs_hist_reduce', 'ssrs_presence_count', 'ssrs_presence_workspace_bytes', 'ssrs_presence_smooth',
-    'ssrs_presence_smooth_u64',
-    'ssrs_presence_normalise_add', 'ssrs_presence_normalise_f32',
-    'ssrs_potential_workspace_bytes', 'ssrs_potential_solve',
-    'ssrs_turbine_encounters', 'ssrs_turbine_encounter_counts', 'ssrs_rotor_encounters', 'ssrs_rotor_encounters_timed',
-    'ssrs_shelter_sx', 'ssrs_updraft_sheltered', 'ssrs_shelter_sx_sector', 'ssrs_updraft_sheltered_sector',
-    'ssrs_smooth_workspace_bytes', 'ssrs_smooth_reflect',
-    'ssrs_projection_init_albers', 'ssrs_warp_lonlat_raster',
-    'ssrs_allen_workspace_bytes', 'ssrs_allen_thermal_field',
-    'ssrs_track_occupancy_workspace_bytes', 'ssrs_track_occupancy',
-    'ssrs_altitude_cellinfo', 'ssrs_track_altitude_workspace_bytes', 'ssrs_track_altitude',
-    'ssrs_flight_windinfo', 'ssrs_track_time',
-    'ssrs_roam_pair_word_selftest', 'ssrs_tracks_roam_feed_counts', 'ssrs_roam_tables_selftest',
-    'ssrs_tracks_roam_stopped_waves',
-)
+# One line per export of include/ssrs_hip.h: 'return:parameters', one character each (tests/test_native_abi.py checks
+# every line against the header).  i int, d double, z size_t, q int64_t, Q uint64_t, p any pointer (NULL = None),
+# s const char * (returned), v void.
+_KINDS = {'i': C.c_int, 'd': C.c_double, 'z': C.c_size_t, 'q': C.c_int64, 'Q': C.c_uint64, 'p': C.c_void_p,
+          's': C.c_char_p, 'v': None}
+PROTOTYPES = {
+    'ssrs_version': 'i:',
+    'ssrs_build_flags': 'i:',
+    'ssrs_last_error': 's:',
+    'ssrs_device_info': 'i:ipzpp',
+    'ssrs_slope_aspect': 'i:pidppiiip',
+    'ssrs_orographic_updraft': 'i:ppippippdpdpiiip',
+    'ssrs_threshold_updraft': 'i:pdpzp',
+    'ssrs_updraft_from_dem': 'i:piddddpdpiip',
+    'ssrs_lattice_workspace_bytes': 'z:iii',
+    'ssrs_updraft_from_dem_lattice': 'i:pidppiidddddpdpiiipzp',
+    'ssrs_wind_from_lattice': 'i:ppiidddddppiiip',
+    'ssrs_wind_triangles_workspace_bytes': 'z:iiii',
+    'ssrs_wind_from_triangles': 'i:pppppiidppiiipzp',
+    'ssrs_wind_nearest_workspace_bytes': 'z:iii',
+    'ssrs_wind_nearest_index': 'i:pidpiipzp',
+    'ssrs_wind_from_nearest': 'i:pppippiiip',
+    'ssrs_wind_cubic_workspace_bytes': 'z:iiiii',
+    'ssrs_wind_from_triangles_cubic': 'i:ppppppppiidppiiipzp',
+    'ssrs_thermal_seeds': 'i:pdQpiip',
+    'ssrs_blur_workspace_bytes': 'z:iid',
+    'ssrs_gaussian_blur': 'i:ppdiipzp',
+    'ssrs_thermal_fields': 'i:pddpipiiip',
+    'ssrs_potential_temperature': 'i:pppzp',
+    'ssrs_deardorff_velocity': 'i:pppdpzp',
+    'ssrs_thermal_updraft': 'i:pdppdpzp',
+    'ssrs_scalar_interp_workspace_bytes': 'z:iiiii',
+    'ssrs_scalar_from_samples': 'i:ipppppppiidpiiipzp',
+    'ssrs_wtk_thermal_fields': 'i:ipppppppiidpddpiiiipzp',
+    'ssrs_track_params_init': 'i:piiid',
+    'ssrs_transition_table_build': 'i:pppiip',
+    'ssrs_transition_ring_bytes': 'z:ii',
+    'ssrs_transition_ring_build': 'i:pppiip',
+    'ssrs_transition_thr_bytes': 'z:ii',
+    'ssrs_transition_thr_build': 'i:ppppiip',
+    'ssrs_tracks_workspace_bytes': 'z:q',
+    'ssrs_tracks_workspace_bytes_ex': 'z:qiii',
+    'ssrs_tracks_simulate': 'i:pppppqQQppppppzpp',
+    'ssrs_tracks_simulate_h64': 'i:pppppqQQpppppzpp',
+    'ssrs_traj_recorder_create': 'p:pz',
+    'ssrs_traj_recorder_destroy': 'v:p',
+    'ssrs_traj_recorder_complete': 'i:p',
+    'ssrs_traj_recorder_used': 'z:p',
+    'ssrs_tracks_simulate_rec': 'i:pppppqQQpppppzpp',
+    'ssrs_tracks_gather': 'i:ppqpppzp',
+    'ssrs_hist_reduce': 'i:pzipp',
+    'ssrs_presence_count': 'i:pqpiipp',
+    'ssrs_presence_workspace_bytes': 'z:iii',
+    'ssrs_presence_smooth': 'i:pipiipzp',
+    'ssrs_presence_smooth_u64': 'i:pipiipzp',
+    'ssrs_presence_normalise_add': 'i:pipzpp',
+    'ssrs_presence_normalise_f32': 'i:ppzpp',
+    'ssrs_turbine_encounters': 'i:ppqpidppiippp',
+    'ssrs_turbine_encounter_counts': 'i:pqippp',
+    'ssrs_rotor_encounters': 'i:ppqppiipppipppppp',
+    'ssrs_rotor_encounters_timed': 'i:ppqpppiipppippppppp',
+    'ssrs_track_occupancy_workspace_bytes': 'z:iii',
+    'ssrs_track_occupancy': 'i:ppqiiipppzp',
+    'ssrs_altitude_cellinfo': 'i:pipiiiddpp',
+    'ssrs_track_altitude_workspace_bytes': 'z:q',
+    'ssrs_track_altitude': 'i:ppqpiippppppppzp',
+    'ssrs_flight_windinfo': 'i:ppiiiipp',
+    'ssrs_track_time': 'i:ppqppiiiipppppp',
+    'ssrs_shelter_sx': 'i:pidpppdiippiiip',
+    'ssrs_updraft_sheltered': 'i:pidppppppppipddpppiiip',
+    'ssrs_shelter_sx_sector': 'i:pidpppdiiddppiiip',
+    'ssrs_updraft_sheltered_sector': 'i:pidppppppppipddddpppiiip',
+    'ssrs_smooth_workspace_bytes': 'z:iiid',
+    'ssrs_smooth_reflect': 'i:pdiddpppiiipzp',
+    'ssrs_allen_workspace_bytes': 'z:i',
+    'ssrs_allen_thermal_field': 'i:ppppippdiidddiddiiipipppzp',
+    'ssrs_projection_init_albers': 'i:p',
+    'ssrs_warp_lonlat_raster': 'i:piiidddddpdddpipppiip',
+    'ssrs_potential_workspace_bytes': 'z:ii',
+    'ssrs_potential_solve': 'i:pppppiidiipzpp',
+    'ssrs_uniform_selftest': 'i:Qpppzp',
+    'ssrs_roam_pair_word_selftest': 'i:Qppppzp',
+    'ssrs_roam_tables_selftest': 'i:ppppiipppp',
+    'ssrs_tracks_roam_feed_counts': 'v:pp',
+    'ssrs_tracks_roam_stopped_waves': 'q:',
+}
+EXPORTS = tuple(PROTOTYPES)
+
+
+def argtypes(name):
+    """The ctypes argtypes of export `name`, from its line of PROTOTYPES."""
+    return [_KINDS[k] for k in PROTOTYPES[name].partition(':')[2]]
+
+
+# read by the host tests that bind a CPU build of one kernel file by the library's own prototypes
+OCCUPANCY_ARGTYPES, ALLEN_FIELD_ARGTYPES, ALTITUDE_CELLINFO_ARGTYPES, ALTITUDE_ARGTYPES, FLIGHT_WINDINFO_ARGTYPES, \
+    TRACK_TIME_ARGTYPES, ROTOR_ENCOUNTERS_ARGTYPES, ROTOR_ENCOUNTERS_TIMED_ARGTYPES = map(argtypes, (
+        'ssrs_track_occupancy', 'ssrs_allen_thermal_field', 'ssrs_altitude_cellinfo', 'ssrs_track_altitude',
+        'ssrs_flight_windinfo', 'ssrs_track_time', 'ssrs_rotor_encounters', 'ssrs_rotor_encounters_timed'))
 
 
 class SsrsTrackParams(C.Structure):
@@ -100,50 +169,12 @@ class SsrsProjection(C.Structure):
                                                 'n', 'C', 'rho0', 'e')]
 
 
-# ssrs_allen_thermal_field: xt, yt, wgain, rgain, n, bin_start, bin_items, bin_size_m, nbx, nby, rbar, wtbar, zzi, z_below_zi,
-# we, res, rows, cols, path, out, out_type, nearest, table, workspace, workspace_bytes, stream
-# ssrs_track_occupancy: traj, traj_offsets, ntracks, rows, cols, planes, counts, cells_per_track, workspace, workspace_bytes, stream
-OCCUPANCY_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                      C.c_size_t, C.c_void_p]
-
-ALLEN_FIELD_ARGTYPES = [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int] + \
-    [C.c_double] * 3 + [C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-
-
 class SsrsAltitudeParams(C.Structure):
     _fields_ = [(name, C.c_int32) for name in ('start', 'floor', 'ceil', 'band_lo', 'band_hi')]
 
 
-# ssrs_altitude_cellinfo: updraft, updraft_type, dem, dem_type, rows, cols, sink, scale, cellinfo, stream
-ALTITUDE_CELLINFO_ARGTYPES = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p,
-                              C.c_void_p]
-# ssrs_track_altitude: traj, traj_offsets, ntracks, cellinfo, rows, cols, params, alt, band_hist, traj_band, in_band, h_min,
-# h_max, workspace, workspace_bytes, stream
-ALTITUDE_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.POINTER(SsrsAltitudeParams)] + \
-    [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]
-
-
 class SsrsFlightTimeParams(C.Structure):
     _fields_ = [(name, C.c_int32) for name in ('va', 'gmin', 'res_mm')]
-
-
-# ssrs_flight_windinfo: wspeed, wdirn, type, rows, cols, ray_axes, windinfo, stream
-FLIGHT_WINDINFO_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-# ssrs_track_time: traj, traj_offsets, ntracks, masked, windinfo, uniform_wr, uniform_wc, rows, cols, params, time_hist,
-# band_time_hist, per_track, dt, stream
-TRACK_TIME_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                       C.POINTER(SsrsFlightTimeParams)] + [C.c_void_p] * 5
-
-
-# ssrs_rotor_encounters: traj, traj_offsets, ntracks, alt, cellinfo, rows, cols, turbines, reach, zband, nturb, bin_start,
-# bin_items, hits, first_step, points_per_turbine, stream
-ROTOR_ENCOUNTERS_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + \
-    [C.c_int] + [C.c_void_p] * 6
-# ssrs_rotor_encounters_timed: traj, traj_offsets, ntracks, alt, dt, cellinfo, rows, cols, turbines, reach, zband, nturb,
-# bin_start, bin_items, hits, first_step, points_per_turbine, time_per_turbine, stream
-ROTOR_ENCOUNTERS_TIMED_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + \
-    [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 7
 
 
 class SsrsError(RuntimeError):
@@ -164,107 +195,13 @@ def lib():
                 f'{LIB_PATH} is missing: build it with `python ssrs_amd/csrc/build.py` '
                 '(hipcc, gfx950). ssrs_amd has no CPU fallback.')
         L = C.CDLL(LIB_PATH)
-        L.ssrs_version.restype = C.c_int
+        for name, proto in PROTOTYPES.items():
+            fn = getattr(L, name)
+            fn.restype = _KINDS[proto[0]]
+            fn.argtypes = argtypes(name)
         if L.ssrs_build_flags() & 1 and not os.environ.get('SSRS_ALLOW_PROBE_LIB'):
             raise ImportError(f'{LIB_PATH} is a timing-probe build (results are wrong on purpose); '
                               'set SSRS_ALLOW_PROBE_LIB=1 for timing runs only')
-        L.ssrs_last_error.restype = C.c_char_p
-        L.ssrs_tracks_workspace_bytes.restype = C.c_size_t
-        L.ssrs_tracks_workspace_bytes.argtypes = [C.c_int64]
-        L.ssrs_lattice_workspace_bytes.restype = C.c_size_t
-        L.ssrs_wind_triangles_workspace_bytes.restype = C.c_size_t
-        L.ssrs_wind_triangles_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
-        L.ssrs_lattice_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-        L.ssrs_wind_nearest_workspace_bytes.restype = C.c_size_t
-        L.ssrs_wind_nearest_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-        L.ssrs_wind_nearest_index.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_int,
-                                              C.c_void_p, C.c_size_t, C.c_void_p]
-        L.ssrs_wind_cubic_workspace_bytes.restype = C.c_size_t
-        L.ssrs_wind_cubic_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
-        L.ssrs_wind_from_triangles_cubic.argtypes = [C.c_void_p] * 8 + [C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
-                                                                        C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
-                                                                        C.c_void_p]
-        L.ssrs_tracks_workspace_bytes_ex.restype = C.c_size_t
-        L.ssrs_tracks_workspace_bytes_ex.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int]
-        L.ssrs_traj_recorder_create.restype = C.c_void_p
-        L.ssrs_traj_recorder_create.argtypes = [C.c_void_p, C.c_size_t]
-        L.ssrs_traj_recorder_destroy.restype = None
-        L.ssrs_traj_recorder_destroy.argtypes = [C.c_void_p]
-        L.ssrs_traj_recorder_complete.argtypes = [C.c_void_p]
-        L.ssrs_traj_recorder_used.restype = C.c_size_t
-        L.ssrs_traj_recorder_used.argtypes = [C.c_void_p]
-        L.ssrs_transition_thr_bytes.restype = C.c_size_t
-        L.ssrs_transition_thr_bytes.argtypes = [C.c_int, C.c_int]
-        L.ssrs_transition_ring_bytes.restype = C.c_size_t
-        L.ssrs_transition_ring_bytes.argtypes = [C.c_int, C.c_int]
-        if hasattr(L, 'ssrs_presence_workspace_bytes'):
-            L.ssrs_presence_workspace_bytes.restype = C.c_size_t
-            L.ssrs_presence_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-        if hasattr(L, 'ssrs_blur_workspace_bytes'):
-            L.ssrs_blur_workspace_bytes.restype = C.c_size_t
-            L.ssrs_blur_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_double]
-        L.ssrs_thermal_fields.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_uint64), C.c_int,
-                                          C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        L.ssrs_potential_temperature.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.ssrs_deardorff_velocity.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.ssrs_thermal_updraft.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_size_t,
-                                           C.c_void_p]
-        L.ssrs_scalar_interp_workspace_bytes.restype = C.c_size_t
-        L.ssrs_scalar_interp_workspace_bytes.argtypes = [C.c_int] * 5
-        L.ssrs_scalar_from_samples.argtypes = [C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int,
-                                                                             C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.ssrs_wtk_thermal_fields.argtypes = [C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_double,
-                                                                            C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                                                            C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
-        if hasattr(L, 'ssrs_potential_workspace_bytes'):
-            L.ssrs_potential_workspace_bytes.restype = C.c_size_t
-            L.ssrs_potential_workspace_bytes.argtypes = [C.c_int, C.c_int]
-        if hasattr(L, 'ssrs_turbine_encounters'):
-            L.ssrs_turbine_encounters.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_double,
-                                                  C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                                  C.c_void_p]
-            L.ssrs_turbine_encounter_counts.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.ssrs_shelter_sx.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
-                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        L.ssrs_updraft_sheltered.argtypes = [C.c_void_p, C.c_int, C.c_double] + [C.c_void_p] * 8 + \
-            [C.c_int, C.POINTER(SsrsShelterParams), C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
-             C.c_int, C.c_int, C.c_int, C.c_void_p]
-        L.ssrs_shelter_sx_sector.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
-                                             C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int,
-                                             C.c_int, C.c_int, C.c_void_p]
-        L.ssrs_updraft_sheltered_sector.argtypes = [C.c_void_p, C.c_int, C.c_double] + [C.c_void_p] * 8 + \
-            [C.c_int, C.POINTER(SsrsShelterParams), C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
-             C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        L.ssrs_smooth_workspace_bytes.restype = C.c_size_t
-        L.ssrs_smooth_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double]
-        L.ssrs_smooth_reflect.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.ssrs_projection_init_albers.argtypes = [C.POINTER(SsrsProjection)]
-        L.ssrs_warp_lonlat_raster.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_double] * 5 + \
-            [C.POINTER(SsrsProjection)] + [C.c_double] * 3 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                             C.c_int, C.c_int, C.c_void_p]
-        L.ssrs_allen_workspace_bytes.restype = C.c_size_t
-        L.ssrs_allen_workspace_bytes.argtypes = [C.c_int]
-        L.ssrs_allen_thermal_field.argtypes = ALLEN_FIELD_ARGTYPES
-        L.ssrs_track_occupancy_workspace_bytes.restype = C.c_size_t
-        L.ssrs_track_occupancy_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-        L.ssrs_track_occupancy.argtypes = OCCUPANCY_ARGTYPES
-        L.ssrs_altitude_cellinfo.argtypes = ALTITUDE_CELLINFO_ARGTYPES
-        L.ssrs_track_altitude_workspace_bytes.restype = C.c_size_t
-        L.ssrs_track_altitude_workspace_bytes.argtypes = [C.c_int64]
-        L.ssrs_track_altitude.argtypes = ALTITUDE_ARGTYPES
-        L.ssrs_flight_windinfo.argtypes = FLIGHT_WINDINFO_ARGTYPES
-        L.ssrs_track_time.argtypes = TRACK_TIME_ARGTYPES
-        if hasattr(L, 'ssrs_rotor_encounters'):
-            L.ssrs_rotor_encounters.argtypes = ROTOR_ENCOUNTERS_ARGTYPES
-        if hasattr(L, 'ssrs_rotor_encounters_timed'):
-            L.ssrs_rotor_encounters_timed.argtypes = ROTOR_ENCOUNTERS_TIMED_ARGTYPES
-        L.ssrs_roam_pair_word_selftest.argtypes = [C.c_uint64] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
-        L.ssrs_roam_tables_selftest.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 4
-        L.ssrs_tracks_roam_feed_counts.restype = None
-        L.ssrs_tracks_roam_feed_counts.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        L.ssrs_tracks_roam_stopped_waves.restype = C.c_int64
-        L.ssrs_tracks_roam_stopped_waves.argtypes = []
         _lib = L
     return _lib
 

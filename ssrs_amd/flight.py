@@ -90,7 +90,7 @@ def altitude_cellinfo(updraft, dem, resolution, airspeed, sink):
 
 def altitude_workspace(npoints):
     """A workspace of ssrs_track_altitude for chunks of up to `npoints` points (24 bytes per TILE points)."""
-    nbytes = nat.lib().ssrs_track_altitude_workspace_bytes(C.c_int64(int(npoints)))
+    nbytes = nat.lib().ssrs_track_altitude_workspace_bytes(int(npoints))
     return torch.empty(nbytes, dtype=torch.uint8, device=device())
 
 
@@ -144,9 +144,9 @@ def compute_track_altitudes(tracks, cellinfo, gridshape, *, offsets=None, start,
             workspace = altitude_workspace(npoints)
         nbytes = int(workspace.numel()) * workspace.element_size()
         nat.check(nat.lib().ssrs_track_altitude(
-            nat.ptr(pts), nat.ptr(off), C.c_int64(ntracks), nat.ptr(info), rows, cols, C.byref(params), nat.ptr(alt),
+            nat.ptr(pts), nat.ptr(off), ntracks, nat.ptr(info), rows, cols, C.byref(params), nat.ptr(alt),
             nat.ptr(band_hist), nat.ptr(masked), nat.ptr(heights[0]), nat.ptr(heights[1]), nat.ptr(heights[2]),
-            nat.ptr(workspace), C.c_size_t(nbytes), stream_ptr()))
+            nat.ptr(workspace), nbytes, stream_ptr()))
     ref = None if as_numpy else band_hist
     out = dict(band_hist=like_input(band_hist, ref), heights=like_input(heights.t().contiguous(), ref))
     if want_alt:
@@ -279,7 +279,7 @@ def compute_track_times(tracks, gridshape, *, offsets=None, resolution, airspeed
     dt = torch.zeros(npoints, dtype=torch.int32, device=dev) if want_dt else None
     if ntracks > 0 and npoints > 0:                      # (empty tensors have no address to hand over)
         nat.check(nat.lib().ssrs_track_time(
-            nat.ptr(pts), nat.ptr(off), C.c_int64(ntracks), nat.ptr(zone), nat.ptr(info), pair[0], pair[1], rows, cols,
+            nat.ptr(pts), nat.ptr(off), ntracks, nat.ptr(zone), nat.ptr(info), pair[0], pair[1], rows, cols,
             C.byref(params), nat.ptr(time_hist), nat.ptr(band_time_hist), nat.ptr(times), nat.ptr(dt), stream_ptr()))
     ref = None if as_numpy else time_hist
     out = dict(time_hist=like_input(time_hist, ref), times=like_input(times, ref))

@@ -38,9 +38,8 @@ def slope_aspect(z_mat, res, want_slope=True, want_aspect=True, out_dtype=torch.
     slope = torch.empty((rows, cols), dtype=out_dtype, device=dem.device) if want_slope else None
     aspect = torch.empty((rows, cols), dtype=out_dtype, device=dem.device) if want_aspect else None
     nat.check(nat.lib().ssrs_slope_aspect(
-        nat.ptr(dem), ftype(dem), C.c_double(res), nat.ptr(slope), nat.ptr(aspect),
-        nat.SSRS_F64 if out_dtype == torch.float64 else nat.SSRS_F32,
-        rows, cols, stream_ptr()))
+        nat.ptr(dem), ftype(dem), res, nat.ptr(slope), nat.ptr(aspect),
+        nat.SSRS_F64 if out_dtype == torch.float64 else nat.SSRS_F32, rows, cols, stream_ptr()))
     return (None if slope is None else like_input(slope, z_mat),
             None if aspect is None else like_input(aspect, z_mat))
 
@@ -97,8 +96,7 @@ def orographic_updraft(wspeed, wdirn, slope, aspect, min_updraft_val=0.,
         if threshold is not None else None
     nat.check(nat.lib().ssrs_orographic_updraft(
         nat.ptr(s), nat.ptr(a), ftype(s), nat.ptr(ws), nat.ptr(wd), wtype, ws0p, wd0p,
-        C.c_double(min_updraft_val), nat.ptr(oro),
-        C.c_double(-1.0 if threshold is None else threshold), nat.ptr(use),
+        min_updraft_val, nat.ptr(oro), -1.0 if threshold is None else threshold, nat.ptr(use),
         rows, cols, batch, stream_ptr()))
     if single:
         oro = None if oro is None else oro[0]
@@ -121,8 +119,7 @@ def get_above_threshold_speed(in_array, threshold):
     x = to_dev(in_array, torch.float32)
     out = torch.empty(x.shape, dtype=torch.float64, device=x.device)
     nat.check(nat.lib().ssrs_threshold_updraft(
-        nat.ptr(x), C.c_double(threshold), nat.ptr(out), C.c_size_t(x.numel()),
-        stream_ptr()))
+        nat.ptr(x), threshold, nat.ptr(out), x.numel(), stream_ptr()))
     return like_input(out, in_array)
 
 
@@ -144,10 +141,8 @@ def updraft_from_dem(z_mat, res, wspeed, wdirn, threshold=None, min_updraft_val=
     if use is None and threshold is not None:
         use = torch.empty((rows, cols), dtype=torch.float64, device=dem.device)
     nat.check(nat.lib().ssrs_updraft_from_dem(
-        nat.ptr(dem), ftype(dem), C.c_double(res), C.c_double(wspeed), C.c_double(wdirn),
-        C.c_double(min_updraft_val), nat.ptr(oro),
-        C.c_double(-1.0 if threshold is None else threshold), nat.ptr(use),
-        rows, cols, stream_ptr()))
+        nat.ptr(dem), ftype(dem), res, wspeed, wdirn, min_updraft_val, nat.ptr(oro),
+        -1.0 if threshold is None else threshold, nat.ptr(use), rows, cols, stream_ptr()))
     return (None if oro is None else like_input(oro, z_mat),
             None if use is None else like_input(use, z_mat))
 
@@ -183,10 +178,9 @@ def updraft_from_dem_lattice(z_mat, res, x_km, y_km, wspeed, wdirn, threshold=No
     nbytes = nat.lib().ssrs_lattice_workspace_bytes(nx, ny, batch)
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dem.device)
     nat.check(nat.lib().ssrs_updraft_from_dem_lattice(
-        nat.ptr(dem), ftype(dem), C.c_double(res), nat.ptr(ws.contiguous()), nat.ptr(wd.contiguous()),
-        nx, ny, C.c_double(x[0]), C.c_double(y[0]), C.c_double(dx), C.c_double(dy),
-        C.c_double(min_updraft_val), nat.ptr(oro), C.c_double(-1. if threshold is None else threshold),
-        nat.ptr(use), rows, cols, batch, nat.ptr(scratch), C.c_size_t(nbytes), stream_ptr()))
+        nat.ptr(dem), ftype(dem), res, nat.ptr(ws.contiguous()), nat.ptr(wd.contiguous()),
+        nx, ny, x[0], y[0], dx, dy, min_updraft_val, nat.ptr(oro), -1. if threshold is None else threshold,
+        nat.ptr(use), rows, cols, batch, nat.ptr(scratch), nbytes, stream_ptr()))
     if single:
         oro = None if oro is None else oro[0]
         use = None if use is None else use[0]
@@ -209,8 +203,7 @@ def compute_potential_temperature(pressure, temperature):
     (p, t), tensor_in = _elementwise_f64((pressure, temperature))
     out = torch.empty_like(p)
     if out.numel():
-        nat.check(nat.lib().ssrs_potential_temperature(nat.ptr(p), nat.ptr(t), nat.ptr(out), C.c_size_t(out.numel()),
-                                                       stream_ptr()))
+        nat.check(nat.lib().ssrs_potential_temperature(nat.ptr(p), nat.ptr(t), nat.ptr(out), out.numel(), stream_ptr()))
     return _elementwise_out(out, tensor_in)
 
 
@@ -220,8 +213,8 @@ def deardoff_velocity_function(pot_temperature, blayer_height, surface_heat_flux
     (th, zi, q), tensor_in = _elementwise_f64((pot_temperature, blayer_height, surface_heat_flux))
     out = torch.empty_like(th)
     if out.numel():
-        nat.check(nat.lib().ssrs_deardorff_velocity(nat.ptr(th), nat.ptr(zi), nat.ptr(q), C.c_double(min_updraft_val),
-                                                    nat.ptr(out), C.c_size_t(out.numel()), stream_ptr()))
+        nat.check(nat.lib().ssrs_deardorff_velocity(nat.ptr(th), nat.ptr(zi), nat.ptr(q), min_updraft_val,
+                                                    nat.ptr(out), out.numel(), stream_ptr()))
     return _elementwise_out(out, tensor_in)
 
 
@@ -236,9 +229,8 @@ def compute_thermal_updraft(zmat, deardoff_vel, blayer_height, min_updraft_val=1
         z0 = 0.
     out = torch.empty_like(w)
     if out.numel():
-        nat.check(nat.lib().ssrs_thermal_updraft(nat.ptr(z), C.c_double(z0), nat.ptr(w), nat.ptr(zi),
-                                                 C.c_double(min_updraft_val), nat.ptr(out), C.c_size_t(out.numel()),
-                                                 stream_ptr()))
+        nat.check(nat.lib().ssrs_thermal_updraft(nat.ptr(z), z0, nat.ptr(w), nat.ptr(zi), min_updraft_val, nat.ptr(out),
+                                                 out.numel(), stream_ptr()))
     return _elementwise_out(out, tensor_in)
 
 
@@ -349,12 +341,12 @@ def compute_sx(z_mat, res, wdirn, dmax=500., ray_axes='row_east', want='deg', pa
     deg = torch.empty((batch, rows, cols), dtype=torch.float64, device=dem.device) if want != 'tan' else None
     if sector > 0.:
         nat.check(nat.lib().ssrs_shelter_sx_sector(
-            nat.ptr(dem), ftype(dem), C.c_double(res), _dptr(ur), _dptr(uc), nat.ptr(wd), C.c_double(dmax),
-            nat.SSRS_RAY_AXES[ray_axes], nat.SSRS_SHELTER_PATH[path], C.c_double(sector), C.c_double(sector_step),
+            nat.ptr(dem), ftype(dem), res, _dptr(ur), _dptr(uc), nat.ptr(wd), dmax,
+            nat.SSRS_RAY_AXES[ray_axes], nat.SSRS_SHELTER_PATH[path], sector, sector_step,
             nat.ptr(tan), nat.ptr(deg), rows, cols, batch, stream_ptr()))
     else:
         nat.check(nat.lib().ssrs_shelter_sx(
-            nat.ptr(dem), ftype(dem), C.c_double(res), _dptr(ur), _dptr(uc), nat.ptr(wd), C.c_double(dmax),
+            nat.ptr(dem), ftype(dem), res, _dptr(ur), _dptr(uc), nat.ptr(wd), dmax,
             nat.SSRS_RAY_AXES[ray_axes], nat.SSRS_SHELTER_PATH[path], nat.ptr(tan), nat.ptr(deg), rows, cols, batch,
             stream_ptr()))
     out = [None if t is None else like_input(t[0] if single else t, z_mat) for t in (tan, deg)]
@@ -416,14 +408,14 @@ def orographic_updraft_improved(z_mat, res, wspeed, wdirn, slope=None, aspect=No
     oro = torch.empty((batch, rows, cols), dtype=torch.float32, device=dem.device) if want_orograph or smooth else None
     use = torch.empty((batch, rows, cols), dtype=torch.float64, device=dem.device) if threshold is not None else None
     sx = torch.empty((batch, rows, cols), dtype=torch.float64, device=dem.device) if want_sx else None
-    head = (nat.ptr(dem), ftype(dem), C.c_double(res), _dptr(ur), _dptr(uc), _dptr(ws0), _dptr(wd0), nat.ptr(ws),
+    head = (nat.ptr(dem), ftype(dem), res, _dptr(ur), _dptr(uc), _dptr(ws0), _dptr(wd0), nat.ptr(ws),
             nat.ptr(wd), nat.ptr(s), nat.ptr(a), nat.SSRS_F64 if s is None else ftype(s), C.byref(params))
-    tail = (C.c_double(min_updraft_val), C.c_double(-1. if threshold is None else threshold), nat.ptr(oro), nat.ptr(use),
-            nat.ptr(sx), rows, cols, batch, stream_ptr())
+    tail = (min_updraft_val, -1. if threshold is None else threshold, nat.ptr(oro), nat.ptr(use), nat.ptr(sx), rows, cols,
+            batch, stream_ptr())
     if smooth:                                  # the unclamped field, no threshold: both act on the smoothed field below
-        tail = (C.c_double(-np.inf), C.c_double(-1.), nat.ptr(oro), None) + tail[4:]
+        tail = (-np.inf, -1., nat.ptr(oro), None) + tail[4:]
     if sector > 0.:
-        nat.check(nat.lib().ssrs_updraft_sheltered_sector(*head, C.c_double(sector), C.c_double(sector_step), *tail))
+        nat.check(nat.lib().ssrs_updraft_sheltered_sector(*head, sector, sector_step, *tail))
     else:
         nat.check(nat.lib().ssrs_updraft_sheltered(*head, *tail))
     if smooth:
@@ -470,12 +462,11 @@ def _smooth_reflect(x, sigma_cells, min_updraft_val, threshold, smooth, oro, use
     may be x itself: the first pass has read a case before the second writes it)."""
     batch, rows, cols = x.shape
     lib = nat.lib()
-    nbytes = lib.ssrs_smooth_workspace_bytes(rows, cols, batch, C.c_double(sigma_cells))
+    nbytes = lib.ssrs_smooth_workspace_bytes(rows, cols, batch, sigma_cells)
     work = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=x.device)
-    nat.check(lib.ssrs_smooth_reflect(nat.ptr(x), C.c_double(sigma_cells), nat.SSRS_SMOOTH_PATH[path],
-                                      C.c_double(min_updraft_val), C.c_double(-1. if threshold is None else threshold),
-                                      nat.ptr(smooth), nat.ptr(oro), nat.ptr(use), rows, cols, batch, nat.ptr(work),
-                                      C.c_size_t(int(nbytes)), stream_ptr()))
+    nat.check(lib.ssrs_smooth_reflect(nat.ptr(x), sigma_cells, nat.SSRS_SMOOTH_PATH[path], min_updraft_val,
+                                      -1. if threshold is None else threshold, nat.ptr(smooth), nat.ptr(oro), nat.ptr(use),
+                                      rows, cols, batch, nat.ptr(work), nbytes, stream_ptr()))
 
 
 def smooth_orograph(orograph, sigma_cells, min_updraft_val=0., threshold=None, want_smooth=False, path='auto'):

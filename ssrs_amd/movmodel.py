@@ -81,8 +81,7 @@ def make_track_params(grid_shape, move_dirn, memory_parameter=1, scaling_paramet
                       binning=True, ring=False, scattered=None, thr=False):
     rows, cols = int(grid_shape[0]), int(grid_shape[1])
     p = nat.SsrsTrackParams()
-    nat.check(nat.lib().ssrs_track_params_init(C.byref(p), rows, cols, int(memory_parameter),
-                                               C.c_double(scaling_parameter)))
+    nat.check(nat.lib().ssrs_track_params_init(C.byref(p), rows, cols, int(memory_parameter), scaling_parameter))
     prior = get_directional_probs(move_dirn * np.pi / 180.)
     for k in range(9):
         p.prior[k] = float(prior[k])
@@ -367,10 +366,8 @@ def simulate_tracks(move_dirn, starts, grid_shape, memory_parameter=1,
     def run(hist_t, traj_t, off_t):
         nat.check(nat.lib().ssrs_tracks_simulate(
             C.byref(p), nat.ptr(upd), nat.ptr(pot), nat.ptr(table), nat.ptr(st),
-            C.c_int64(n), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-            C.c_uint64(int(track_id_base)), nat.ptr(hist_t), nat.ptr(ends),
-            nat.ptr(lengths), nat.ptr(traj_t), nat.ptr(off_t), nat.ptr(ws),
-            C.c_size_t(ws_bytes), C.byref(stats), stream_ptr()))
+            n, int(seed) & 0xFFFFFFFFFFFFFFFF, int(track_id_base), nat.ptr(hist_t), nat.ptr(ends),
+            nat.ptr(lengths), nat.ptr(traj_t), nat.ptr(off_t), nat.ptr(ws), ws_bytes, C.byref(stats), stream_ptr()))
 
     traj = offsets = None
     recorded = simulated = False
@@ -381,17 +378,15 @@ def simulate_tracks(move_dirn, starts, grid_shape, memory_parameter=1,
         pool_bytes = int(record_pool_bytes) if record_pool_bytes is not None else \
             default_record_pool_bytes(n, rows, cols)
         pool = torch.empty(max(256, pool_bytes // 256 * 256), dtype=torch.uint8, device=dev)
-        rec = nat.lib().ssrs_traj_recorder_create(nat.ptr(pool), C.c_size_t(pool.numel()))
+        rec = nat.lib().ssrs_traj_recorder_create(nat.ptr(pool), pool.numel())
         if not rec:
             nat.check(nat.SSRS_ERR_INVALID)
         try:
             nat.check(nat.lib().ssrs_tracks_simulate_rec(
                 C.byref(p), nat.ptr(upd), nat.ptr(pot), nat.ptr(table), nat.ptr(st),
-                C.c_int64(n), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-                C.c_uint64(int(track_id_base)), nat.ptr(hist), nat.ptr(ends),
-                nat.ptr(lengths), C.c_void_p(rec), nat.ptr(ws), C.c_size_t(ws_bytes),
-                C.byref(stats), stream_ptr()))
-            if nat.lib().ssrs_traj_recorder_complete(C.c_void_p(rec)) and \
+                n, int(seed) & 0xFFFFFFFFFFFFFFFF, int(track_id_base), nat.ptr(hist), nat.ptr(ends),
+                nat.ptr(lengths), rec, nat.ptr(ws), ws_bytes, C.byref(stats), stream_ptr()))
+            if nat.lib().ssrs_traj_recorder_complete(rec) and \
                     int(lengths.sum(dtype=torch.int64).item()) * 4 <= int(traj_budget_bytes):
                 offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
                 torch.cumsum(lengths, 0, out=offsets[1:])
@@ -399,13 +394,12 @@ def simulate_tracks(move_dirn, starts, grid_shape, memory_parameter=1,
                 traj = torch.empty((total, 2), dtype=torch.int16, device=dev)
                 cursor = torch.empty(n, dtype=torch.int32, device=dev)
                 nat.check(nat.lib().ssrs_tracks_gather(
-                    C.c_void_p(rec), nat.ptr(st), C.c_int64(n), nat.ptr(offsets), nat.ptr(traj),
-                    nat.ptr(cursor), C.c_size_t(4 * n), stream_ptr()))
+                    rec, nat.ptr(st), n, nat.ptr(offsets), nat.ptr(traj), nat.ptr(cursor), 4 * n, stream_ptr()))
                 torch.cuda.current_stream().synchronize()      # the pool dies with this scope
                 recorded = True
             simulated = True                  # lengths, end cells and the histogram are final
         finally:
-            nat.lib().ssrs_traj_recorder_destroy(C.c_void_p(rec))
+            nat.lib().ssrs_traj_recorder_destroy(rec)
             del pool
         if not recorded and is_ring:
             # the two-pass form runs the generic kernel, which reads the f64 table
@@ -447,18 +441,16 @@ def simulate_tracks(move_dirn, starts, grid_shape, memory_parameter=1,
                 st2 = nat.SsrsTrackStats()
                 nat.check(nat.lib().ssrs_tracks_simulate(
                     C.byref(two_p), nat.ptr(upd), nat.ptr(pot), nat.ptr(two_table), nat.ptr(sub),
-                    C.c_int64(m), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-                    C.c_uint64(int(track_id_base) + t0), None, nat.ptr(sub_end), nat.ptr(sub_len),
-                    nat.ptr(out), nat.ptr(off), nat.ptr(wss), C.c_size_t(wsb), C.byref(st2), stream_ptr()))
+                    m, int(seed) & 0xFFFFFFFFFFFFFFFF, int(track_id_base) + t0, None, nat.ptr(sub_end), nat.ptr(sub_len),
+                    nat.ptr(out), nat.ptr(off), nat.ptr(wss), wsb, C.byref(st2), stream_ptr()))
                 if not torch.equal(sub_len, lengths[t0:t1]):
                     raise RuntimeError('trajectory replay: a track changed its length between the passes')
                 return out, off
     elif hist64:
         nat.check(nat.lib().ssrs_tracks_simulate_h64(
             C.byref(p), nat.ptr(upd), nat.ptr(pot), nat.ptr(table), nat.ptr(st),
-            C.c_int64(n), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-            C.c_uint64(int(track_id_base)), nat.ptr(hist_scratch), nat.ptr(hist), nat.ptr(ends),
-            nat.ptr(lengths), nat.ptr(ws), C.c_size_t(ws_bytes), C.byref(stats), stream_ptr()))
+            n, int(seed) & 0xFFFFFFFFFFFFFFFF, int(track_id_base), nat.ptr(hist_scratch), nat.ptr(hist),
+            nat.ptr(ends), nat.ptr(lengths), nat.ptr(ws), ws_bytes, C.byref(stats), stream_ptr()))
     elif not want_tracks:
         run(hist, None, None)
     roam_fed, roam_own = C.c_int64(0), C.c_int64(0)      # of this thread's last stepper call, the one `stats` describes
@@ -505,8 +497,7 @@ def uniforms(seed, track, step):
         raise ValueError('track and step lengths differ')
     out = torch.empty(tr.numel(), dtype=torch.float64, device=tr.device)
     nat.check(nat.lib().ssrs_uniform_selftest(
-        C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), nat.ptr(tr), nat.ptr(sp), nat.ptr(out),
-        C.c_size_t(tr.numel()), stream_ptr()))
+        int(seed) & 0xFFFFFFFFFFFFFFFF, nat.ptr(tr), nat.ptr(sp), nat.ptr(out), tr.numel(), stream_ptr()))
     return out.cpu().numpy()
 
 
@@ -520,8 +511,8 @@ def roam_pair_words(seed, track, block):
     packed = torch.empty(tr.numel(), dtype=torch.int32, device=tr.device)
     words = torch.empty((tr.numel(), 4), dtype=torch.int32, device=tr.device)
     nat.check(nat.lib().ssrs_roam_pair_word_selftest(
-        C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), nat.ptr(tr), nat.ptr(bk), nat.ptr(packed), nat.ptr(words),
-        C.c_size_t(tr.numel()), stream_ptr()))
+        int(seed) & 0xFFFFFFFFFFFFFFFF, nat.ptr(tr), nat.ptr(bk), nat.ptr(packed), nat.ptr(words),
+        tr.numel(), stream_ptr()))
     return packed.cpu().numpy().view(np.uint32), words.cpu().numpy().view(np.uint32)
 
 

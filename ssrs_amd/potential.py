@@ -100,8 +100,7 @@ def solve_potential(updraft, move_dirn, rel_tol=1e-15, max_iterations=2000,
         ws = torch.empty(nbytes, dtype=torch.uint8, device=cond.device)
         rc = nat.lib().ssrs_potential_solve(
             nat.ptr(cond), nat.ptr(mask), nat.ptr(vals), nat.ptr(guess), nat.ptr(out),
-            rows, cols, C.c_double(rel_tol), int(max_iterations), flags, nat.ptr(ws),
-            C.c_size_t(nbytes), C.byref(stats), stream_ptr())
+            rows, cols, rel_tol, int(max_iterations), flags, nat.ptr(ws), nbytes, C.byref(stats), stream_ptr())
         if rc == nat.SSRS_ERR_INVALID and nbytes < full and \
                 b'workspace' in nat.lib().ssrs_last_error():
             del ws

@@ -1,7 +1,6 @@
 """Presence density (K3'/K4) host side, behind the reference's function names
 (/root/reference/ssrs/movmodel.py:410-439) plus the normalisation ladder of
 Simulator.plot_presence_map (simulator.py:520-546)."""
-import ctypes as C
 
 import numpy as np
 import torch
@@ -29,7 +28,7 @@ def compute_presence_counts(tracks, gridshape):
         pts = to_dev(flat, torch.int16)
     hist = torch.zeros((rows, cols), dtype=torch.int32, device=device())
     nat.check(nat.lib().ssrs_presence_count(
-        nat.ptr(pts), C.c_int64(int(pts.shape[0])), nat.ptr(hist), rows, cols,
+        nat.ptr(pts), int(pts.shape[0]), nat.ptr(hist), rows, cols,
         nat.ptr(_scratch(hist.device)), stream_ptr()))
     return hist.cpu().numpy() if as_numpy else hist
 
@@ -109,8 +108,8 @@ def compute_track_occupancy(tracks, gridshape, *, offsets=None, counts=None, cel
         nbytes = int(workspace.numel()) * workspace.element_size()
         try:
             nat.check(nat.lib().ssrs_track_occupancy(
-                nat.ptr(pts), nat.ptr(off), C.c_int64(ntracks), rows, cols, int(planes), nat.ptr(counts),
-                nat.ptr(per_track), nat.ptr(workspace), C.c_size_t(nbytes), stream_ptr()))
+                nat.ptr(pts), nat.ptr(off), ntracks, rows, cols, int(planes), nat.ptr(counts),
+                nat.ptr(per_track), nat.ptr(workspace), nbytes, stream_ptr()))
         except Exception:
             workspace.zero_()
             raise
@@ -135,8 +134,7 @@ def smooth_presence_counts(count_mat, radius):
     ws = torch.empty(nbytes, dtype=torch.uint8, device=cnt.device)
     fn = nat.lib().ssrs_presence_smooth_u64 if wide else nat.lib().ssrs_presence_smooth
     nat.check(fn(
-        nat.ptr(cnt), krad, nat.ptr(out), rows, cols, nat.ptr(ws), C.c_size_t(nbytes),
-        stream_ptr()))
+        nat.ptr(cnt), krad, nat.ptr(out), rows, cols, nat.ptr(ws), nbytes, stream_ptr()))
     return like_input(out, count_mat)
 
 
@@ -165,7 +163,7 @@ def normalise_add(src, acc):
         s = s.to(torch.float64)
     nat.check(nat.lib().ssrs_presence_normalise_add(
         nat.ptr(s), nat.SSRS_F64 if s.dtype == torch.float64 else nat.SSRS_F32,
-        nat.ptr(acc), C.c_size_t(s.numel()), nat.ptr(_scratch(s.device)), stream_ptr()))
+        nat.ptr(acc), s.numel(), nat.ptr(_scratch(s.device)), stream_ptr()))
     return acc
 
 
@@ -174,6 +172,5 @@ def normalise_to_f32(src):
     s = to_dev(src, torch.float64)
     out = torch.empty(s.shape, dtype=torch.float32, device=s.device)
     nat.check(nat.lib().ssrs_presence_normalise_f32(
-        nat.ptr(s), nat.ptr(out), C.c_size_t(s.numel()), nat.ptr(_scratch(s.device)),
-        stream_ptr()))
+        nat.ptr(s), nat.ptr(out), s.numel(), nat.ptr(_scratch(s.device)), stream_ptr()))
     return out

@@ -19,10 +19,9 @@ def gaussian_blur(field, sigma):
     x = to_dev(field, torch.float64)
     rows, cols = int(x.shape[0]), int(x.shape[1])
     out = torch.empty_like(x)
-    nbytes = nat.lib().ssrs_blur_workspace_bytes(rows, cols, C.c_double(sigma))
+    nbytes = nat.lib().ssrs_blur_workspace_bytes(rows, cols, sigma)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    nat.check(nat.lib().ssrs_gaussian_blur(nat.ptr(x), nat.ptr(out), C.c_double(sigma), rows, cols,
-                                           nat.ptr(ws), C.c_size_t(nbytes), stream_ptr()))
+    nat.check(nat.lib().ssrs_gaussian_blur(nat.ptr(x), nat.ptr(out), sigma, rows, cols, nat.ptr(ws), nbytes, stream_ptr()))
     return like_input(out, field)
 
 
@@ -30,8 +29,7 @@ def thermal_seeds(aspect, thermal_intensity_scale, seed=0):
     a = to_dev(aspect, torch.float64)
     rows, cols = int(a.shape[0]), int(a.shape[1])
     out = torch.empty_like(a)
-    nat.check(nat.lib().ssrs_thermal_seeds(nat.ptr(a), C.c_double(thermal_intensity_scale),
-                                           C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+    nat.check(nat.lib().ssrs_thermal_seeds(nat.ptr(a), thermal_intensity_scale, int(seed) & 0xFFFFFFFFFFFFFFFF,
                                            nat.ptr(out), rows, cols, stream_ptr()))
     return like_input(out, aspect)
 
@@ -48,7 +46,7 @@ def compute_thermals_batch(aspect, thermal_intensity_scale, seeds, dtype=torch.f
     rows, cols = int(a.shape[0]), int(a.shape[1])
     keys = [int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds]
     out = torch.empty((len(keys), rows, cols), dtype=dtype, device=a.device)
-    nat.check(nat.lib().ssrs_thermal_fields(nat.ptr(a), C.c_double(thermal_intensity_scale), C.c_double(sigma),
+    nat.check(nat.lib().ssrs_thermal_fields(nat.ptr(a), thermal_intensity_scale, sigma,
                                             (C.c_uint64 * len(keys))(*keys), len(keys), nat.ptr(out),
                                             int(dtype == torch.float32), rows, cols, stream_ptr()))
     return like_input(out, aspect)
@@ -91,7 +89,7 @@ def compute_wtk_thermals(x_km, y_km, pressure, temperature, blheight, surfheatfl
     zmat = to_dev(height, torch.float64) if raster_z else None
     z0 = 0. if raster_z else float(height)
     out = torch.empty((batch, rows, cols), dtype=dtype, device=keep['values'].device)
-    nat.check(nat.lib().ssrs_wtk_thermal_fields(*head, nat.ptr(zmat), C.c_double(z0), C.c_double(min_updraft_val),
+    nat.check(nat.lib().ssrs_wtk_thermal_fields(*head, nat.ptr(zmat), z0, min_updraft_val,
                                                 nat.ptr(out), int(dtype == torch.float32), rows, cols, int(batch), *tail))
     out = out[0] if single else out
     return out if any(isinstance(a, torch.Tensor) for a in given) else out.cpu().numpy()
@@ -246,10 +244,10 @@ def compute_allen_thermals(xt, yt, wgain, rgain, gridsize, resolution, z, zi, ws
     nbytes = nat.lib().ssrs_allen_workspace_bytes(n)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=out.device)
     nat.check(nat.lib().ssrs_allen_thermal_field(
-        *(nat.ptr(a) for a in d), n, nat.ptr(d_start), nat.ptr(d_items), C.c_double(bin_size_m), nbx, nby,
-        C.c_double(sc['rbar']), C.c_double(sc['wtbar']), C.c_double(sc['zzi']), int(sc['z_below_zi']), C.c_double(we),
-        C.c_double(res), rows, cols, nat.SSRS_ALLEN_PATH[path], nat.ptr(out), nat.SSRS_F32 if dtype == torch.float32
-        else nat.SSRS_F64, nat.ptr(nearest), nat.ptr(table), nat.ptr(ws), C.c_size_t(nbytes), stream_ptr()))
+        *(nat.ptr(a) for a in d), n, nat.ptr(d_start), nat.ptr(d_items), bin_size_m, nbx, nby,
+        sc['rbar'], sc['wtbar'], sc['zzi'], int(sc['z_below_zi']), we, res, rows, cols, nat.SSRS_ALLEN_PATH[path],
+        nat.ptr(out), nat.SSRS_F32 if dtype == torch.float32 else nat.SSRS_F64, nat.ptr(nearest), nat.ptr(table),
+        nat.ptr(ws), nbytes, stream_ptr()))
     res_ = [out] + [t for t in (nearest, table) if t is not None]
     if return_stats:
         res_.append(int(ws[:8].view(torch.int64).item()))

@@ -4,7 +4,6 @@
 encounter pass of the trajectories against them -- which simulated tracks came within R of which turbine, and
 after how many moves (include/ssrs_hip.h "turbines").
 """
-import ctypes as C
 
 import numpy as np
 import torch
@@ -247,7 +246,7 @@ def turbine_encounters(traj, offsets, xy_cells, radius_cells, gridshape, bins=No
             raise ValueError(f'radius_cells = {radius_cells!r}: expected a number >= 0')
         return hits, first_step
     nat.check(nat.lib().ssrs_turbine_encounters(
-        nat.ptr(pts), nat.ptr(off), C.c_int64(ntracks), nat.ptr(xy), nturb, C.c_double(float(radius_cells)),
+        nat.ptr(pts), nat.ptr(off), ntracks, nat.ptr(xy), nturb, float(radius_cells),
         nat.ptr(bin_start), nat.ptr(bin_items), rows, cols, nat.ptr(hits), nat.ptr(first_step), stream_ptr()))
     return hits, first_step
 
@@ -264,7 +263,7 @@ def encounter_counts(hits, nturb):
     per_track = torch.zeros(ntracks, dtype=torch.int32, device=h.device)
     if ntracks:
         nat.check(nat.lib().ssrs_turbine_encounter_counts(
-            nat.ptr(h), C.c_int64(ntracks), nturb, nat.ptr(per_turbine), nat.ptr(per_track), stream_ptr()))
+            nat.ptr(h), ntracks, nturb, nat.ptr(per_turbine), nat.ptr(per_track), stream_ptr()))
     return per_turbine, per_track
 
 
@@ -397,12 +396,12 @@ def rotor_encounters(traj, alt, offsets, cellinfo, xy_cells, reach, zband, grids
         return (hits, first_step, points) if dt is None else (hits, first_step, points, time)
     if dt is not None:
         nat.check(nat.lib().ssrs_rotor_encounters_timed(
-            nat.ptr(pts), nat.ptr(off), C.c_int64(ntracks), nat.ptr(heights), nat.ptr(moves), nat.ptr(cellinfo), rows, cols,
+            nat.ptr(pts), nat.ptr(off), ntracks, nat.ptr(heights), nat.ptr(moves), nat.ptr(cellinfo), rows, cols,
             nat.ptr(xy), nat.ptr(reach_dev), nat.ptr(zband_dev), nturb, nat.ptr(bin_start), nat.ptr(bin_items),
             nat.ptr(hits), nat.ptr(first_step), nat.ptr(points), nat.ptr(time), stream_ptr()))
         return hits, first_step, points, time
     nat.check(nat.lib().ssrs_rotor_encounters(
-        nat.ptr(pts), nat.ptr(off), C.c_int64(ntracks), nat.ptr(heights), nat.ptr(cellinfo), rows, cols, nat.ptr(xy),
+        nat.ptr(pts), nat.ptr(off), ntracks, nat.ptr(heights), nat.ptr(cellinfo), rows, cols, nat.ptr(xy),
         nat.ptr(reach_dev), nat.ptr(zband_dev), nturb, nat.ptr(bin_start), nat.ptr(bin_items), nat.ptr(hits),
         nat.ptr(first_step), nat.ptr(points), stream_ptr()))
     return hits, first_step, points

@@ -1,7 +1,6 @@
 """Wind-field preparation (K6) for snapshot / seasonal modes: WTK-shaped
 lattice samples -> per-cell speed and direction rasters, following the u/v
 recipe of /root/reference/ssrs/simulator.py:778-792."""
-import ctypes as C
 
 import numpy as np
 import torch
@@ -34,8 +33,7 @@ def interpolate_wind_lattice(x_km, y_km, wspeed, wdirn, gridsize, resolution):
     out_s = torch.empty((batch, rows, cols), dtype=torch.float64, device=ws.device)
     out_d = torch.empty_like(out_s)
     nat.check(nat.lib().ssrs_wind_from_lattice(
-        nat.ptr(ws.contiguous()), nat.ptr(wd.contiguous()), nx, ny, C.c_double(x[0]),
-        C.c_double(y[0]), C.c_double(dx), C.c_double(dy), C.c_double(resolution / 1000.),
+        nat.ptr(ws.contiguous()), nat.ptr(wd.contiguous()), nx, ny, x[0], y[0], dx, dy, resolution / 1000.,
         nat.ptr(out_s), nat.ptr(out_d), rows, cols, batch, stream_ptr()))
     return (out_s[0], out_d[0]) if single else (out_s, out_d)
 
@@ -109,7 +107,7 @@ def interpolate_wind_scattered(x_km, y_km, wspeed, wdirn, gridsize, resolution, 
     out_s = torch.empty((batch, rows, cols), dtype=torch.float64, device=d_a.device)
     out_d = torch.empty_like(out_s)
     L = nat.lib()
-    cell, out = C.c_double(resolution / 1000.), (nat.ptr(out_s), nat.ptr(out_d), rows, cols, batch)
+    cell, out = resolution / 1000., (nat.ptr(out_s), nat.ptr(out_d), rows, cols, batch)
     if method == 'nearest':
         nat.check(L.ssrs_wind_from_nearest(nat.ptr(geo['index']), nat.ptr(d_a), nat.ptr(d_b), npts, *out, stream_ptr()))
         return (out_s[0], out_d[0]) if single else (out_s, out_d)
@@ -119,14 +117,14 @@ def interpolate_wind_scattered(x_km, y_km, wspeed, wdirn, gridsize, resolution, 
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=d_a.device)
         nat.check(L.ssrs_wind_from_triangles(
             nat.ptr(geo['pts']), nat.ptr(geo['tri']), nat.ptr(geo['tr']), nat.ptr(d_a), nat.ptr(d_b), npts, ntri, cell, *out,
-            nat.ptr(scratch), C.c_size_t(nbytes), stream_ptr()))
+            nat.ptr(scratch), nbytes, stream_ptr()))
     else:
         nbytes = int(L.ssrs_wind_cubic_workspace_bytes(npts, ntri, rows, cols, batch))
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=d_a.device)
         nat.check(L.ssrs_wind_from_triangles_cubic(
             nat.ptr(geo['pts']), nat.ptr(geo['tri']), nat.ptr(geo['nbr']), nat.ptr(geo['tr']), nat.ptr(d_a), nat.ptr(d_b),
             nat.ptr(geo['grad'][:batch]), nat.ptr(geo['grad'][batch:]), npts, ntri, cell, *out,
-            nat.ptr(scratch), C.c_size_t(nbytes), stream_ptr()))
+            nat.ptr(scratch), nbytes, stream_ptr()))
     return (out_s[0], out_d[0]) if single else (out_s, out_d)
 
 
@@ -141,8 +139,8 @@ def nearest_sample_index(x_km, y_km, gridsize, resolution):
     L = nat.lib()
     nbytes = int(L.ssrs_wind_nearest_workspace_bytes(int(pts.shape[0]), rows, cols))
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=d_pts.device)
-    nat.check(L.ssrs_wind_nearest_index(nat.ptr(d_pts), int(pts.shape[0]), C.c_double(resolution / 1000.), nat.ptr(index),
-                                        rows, cols, nat.ptr(scratch), C.c_size_t(nbytes), stream_ptr()))
+    nat.check(L.ssrs_wind_nearest_index(nat.ptr(d_pts), int(pts.shape[0]), resolution / 1000., nat.ptr(index),
+                                        rows, cols, nat.ptr(scratch), nbytes, stream_ptr()))
     return index
 
 
@@ -162,9 +160,8 @@ def _scalar_geometry(x_km, y_km, values, gridsize, resolution, method, index, wh
     nbytes = int(nat.lib().ssrs_scalar_interp_workspace_bytes(code, ntri, rows, cols, int(values.shape[0])))
     keep['scratch'] = torch.empty(nbytes, dtype=torch.uint8, device=keep['values'].device)
     head = [code, nat.ptr(keep.get('pts')), nat.ptr(keep.get('tri')), nat.ptr(keep.get('nbr')), nat.ptr(keep.get('tr')),
-            nat.ptr(keep.get('index')), nat.ptr(keep['values']), nat.ptr(keep.get('grad')), npts, ntri,
-            C.c_double(resolution / 1000.)]
-    tail = [nat.ptr(keep['scratch']), C.c_size_t(nbytes), stream_ptr()]
+            nat.ptr(keep.get('index')), nat.ptr(keep['values']), nat.ptr(keep.get('grad')), npts, ntri, resolution / 1000.]
+    tail = [nat.ptr(keep['scratch']), nbytes, stream_ptr()]
     return head, tail, keep
 
 

@@ -15,6 +15,110 @@ def declared_functions():
     return sorted(set(re.findall(r'\b(ssrs_[a-z0-9_]+)\s*\(', text)))
 
 
+def header_code():
+    """include/ssrs_hip.h without comments and preprocessor lines."""
+    text = open(os.path.join(ROOT, 'include', 'ssrs_hip.h')).read()
+    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
+    text = re.sub(r'//[^\n]*', '', text)
+    return '\n'.join(line for line in text.splitlines() if not line.lstrip().startswith('#'))
+
+
+def header_defines():
+    """{name: value} of the header's integer `#define SSRS_...` lines."""
+    text = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'ssrs_hip.h')).read(), flags=re.S)
+    found = re.findall(r'^[ \t]*#[ \t]*define[ \t]+(SSRS_[A-Z0-9_]+)[ \t]+(\(?-?[0-9][0-9 <]*\)?)[ \t]*$', text, flags=re.M)
+    return {name: eval(value, {'__builtins__': {}}) for name, value in found}
+
+
+SCALARS = {'int': C.c_int, 'double': C.c_double, 'size_t': C.c_size_t, 'int64_t': C.c_int64, 'uint64_t': C.c_uint64}
+RETURNS = {'int': C.c_int, 'size_t': C.c_size_t, 'int64_t': C.c_int64, 'const char *': C.c_char_p,
+           'SsrsTrajRecorder *': C.c_void_p, 'void': None}
+
+
+def declared_prototypes():
+    """{name: (restype, [argtypes])} of every `ret ssrs_name(params);` of the header, by the rules of the binding: the five
+    scalar kinds by value, every pointer parameter a void pointer.  A type outside that vocabulary is an error."""
+    protos = {}
+    for ret, name, params in re.findall(r'([A-Za-z_][\w\s\*]*?)\b(ssrs_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', header_code()):
+        ret = ' '.join(ret.replace('*', ' * ').split())
+        assert ret in RETURNS, f'{name}: return type {ret!r} is not in the binding\'s vocabulary'
+        argtypes = []
+        for param in [' '.join(p.split()) for p in params.split(',')]:
+            if param == 'void' and ',' not in params:
+                break
+            if '*' in param:
+                argtypes.append(C.c_void_p)
+                continue
+            ctype, _, pname = param.rpartition(' ')
+            assert ctype in SCALARS and re.fullmatch(r'[A-Za-z_]\w*', pname), \
+                f'{name}: parameter {param!r} is not in the binding\'s vocabulary'
+            argtypes.append(SCALARS[ctype])
+        assert name not in protos, f'{name} declared twice'
+        protos[name] = (RETURNS[ret], argtypes)
+    return protos
+
+
+def test_prototypes_match_the_header():
+    """Every export carries the restype and argtypes that include/ssrs_hip.h declares for it."""
+    from ssrs_amd import _native
+    lib = _native.lib()
+    protos = declared_prototypes()
+    assert len(protos) == 79
+    assert sorted(protos) == declared_functions() == sorted(_native.EXPORTS)
+    assert len(set(_native.EXPORTS)) == len(_native.EXPORTS)
+    for name, (restype, argtypes) in protos.items():
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(argtypes), name
+        assert list(fn.argtypes) == argtypes, name
+        assert fn.restype is restype, name
+
+
+def test_typed_calls_convert_and_refuse():
+    """A bare Python float is converted where the header has a double, refused where it has an int, and an argument count
+    that differs from the header's is refused; all on paths that return before any GPU work."""
+    from ssrs_amd import _native
+    lib = _native.lib()
+    rc = lib.ssrs_slope_aspect(None, 1, 10., None, None, 1, 10, 10, None)
+    assert rc == _native.SSRS_ERR_INVALID and b'dem is NULL' in lib.ssrs_last_error()
+    with pytest.raises(C.ArgumentError):
+        lib.ssrs_slope_aspect(None, 1, 10., None, None, 1, 10.5, 10, None)
+    with pytest.raises(TypeError):
+        lib.ssrs_slope_aspect(None, 1, 10., None, None, 1, 10, 10)
+    p = _native.SsrsTrackParams()
+    assert lib.ssrs_track_params_init(C.byref(p), 500, 600, 1, 1.0) == 0
+    assert (p.rows, p.cols, p.burnin, p.max_moves) == (500, 600, 50, 75000)
+    assert (p.memory_parameter, p.scaling_parameter) == (1, 1.0)
+    assert lib.ssrs_track_params_init(C.byref(p), 31, 33, 3, 1.0) == 0
+    assert (p.burnin, p.max_moves, p.memory_parameter) == (3, 256, 3)
+    assert lib.ssrs_track_params_init(C.byref(p), 3, 600, 1, 1.0) == _native.SSRS_ERR_INVALID
+
+
+def test_constants_match_the_header():
+    """Every SSRS_* integer of ssrs_amd/_native.py, and every value of its SSRS_* dicts, is the header's #define."""
+    from ssrs_amd import _native
+    defines = header_defines()
+    assert defines['SSRS_ERR_START'] == -3 and defines['SSRS_ALLEN_MAX_UPDRAFTS'] == 1 << 22      # the parser's own check
+    prefixes = {'SSRS_RAY_AXES': 'SSRS_RAY_', 'SSRS_SHELTER_PATH': 'SSRS_SHELTER_', 'SSRS_SMOOTH_PATH': 'SSRS_SMOOTH_',
+                'SSRS_ALLEN_PATH': 'SSRS_ALLEN_', 'SSRS_INTERP': 'SSRS_INTERP_'}
+    mirrored = {}
+    for name, value in vars(_native).items():
+        if not name.startswith('SSRS_'):
+            continue
+        if isinstance(value, dict):
+            assert name in prefixes, f'{name}: a dict of constants this test does not know'
+            mirrored.update({prefixes[name] + key.upper(): v for key, v in value.items()})
+        else:
+            assert isinstance(value, int), name
+            mirrored[name] = value
+    for name in ('SSRS_TRACKS_THR_TABLE', 'SSRS_TURBINE_BIN', 'SSRS_TURBINE_MAX', 'SSRS_ROTOR_TIMED_LDS_TURBINES',
+                 'SSRS_OCCUPANCY_MAX_PLANES', 'SSRS_ALTITUDE_TILE', 'SSRS_ALLEN_MAX_UPDRAFTS', 'SSRS_ALLEN_TABLE_COLS',
+                 'SSRS_ALLEN_GLOBAL', 'SSRS_SHELTER_LDS', 'SSRS_SMOOTH_AUTO', 'SSRS_RAY_ROW_EAST', 'SSRS_INTERP_CUBIC'):
+        assert name in mirrored, name
+    for name, value in mirrored.items():
+        assert name in defines, f'{name} of _native.py is no #define of the header'
+        assert value == defines[name], (name, value, defines[name])
+
+
 def test_header_symbols_are_exported():
     from ssrs_amd import _native
     lib = _native.lib()
@@ -116,8 +220,15 @@ def test_ctypes_structs_match_the_header(tmp_path):
     from ssrs_amd import _native as nat
     if shutil.which('gcc') is None:
         pytest.skip('no gcc')
-    structs = {'SsrsTrackParams': nat.SsrsTrackParams, 'SsrsTrackStats': nat.SsrsTrackStats,
-               'SsrsSolveStats': nat.SsrsSolveStats}
+    bodies = dict(re.findall(r'typedef\s+struct\s+(\w+)\s*\{(.*?)\}', header_code(), flags=re.S))
+    assert {'SsrsTrackParams', 'SsrsTrackStats', 'SsrsSolveStats', 'SsrsShelterParams', 'SsrsProjection',
+            'SsrsAltitudeParams', 'SsrsFlightTimeParams'} <= set(bodies)
+    structs = {}
+    for name, body in bodies.items():
+        assert hasattr(nat, name), f'struct {name} of ssrs_hip.h has no ctypes mirror in ssrs_amd/_native.py'
+        structs[name] = getattr(nat, name)
+        declared = [re.sub(r'\[.*', '', f.split()[-1]) for decl in body.split(';') if decl.strip() for f in decl.split(',')]
+        assert [f for f, _ in structs[name]._fields_] == declared, name
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "ssrs_hip.h"', 'int main(void) {']
     for name, cls in structs.items():
         lines.append(f'  printf("{name} %zu", sizeof({name}));')
