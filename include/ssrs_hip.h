@@ -105,7 +105,8 @@ int ssrs_updraft_from_dem(const void *dem, int dem_type, double res, double wspe
  * usable updraft (batch, rows, cols) f64.  The DEM is read once for the whole batch and
  * no per-cell wind raster is materialised: bilinear east / north components at the cell,
  * w = -(Y north + X east) / sqrt(d^2 + X^2 + Y^2) (the wind speed cancels).
- * workspace: ssrs_lattice_workspace_bytes(nx, ny, batch) bytes of device scratch. */
+ * workspace: ssrs_lattice_workspace_bytes(nx, ny, batch) bytes of device scratch; its contents before a call mean
+ * nothing and after it are unspecified. */
 size_t ssrs_lattice_workspace_bytes(int nx, int ny, int batch);
 int ssrs_updraft_from_dem_lattice(const void *dem, int dem_type, double res,
                                   const double *lattice_speed, const double *lattice_dirn,
@@ -136,7 +137,8 @@ int ssrs_wind_from_lattice(const double *lattice_speed, const double *lattice_di
  * (batch, rows, cols) f64, direction in [0, 360); cells outside the convex hull are NaN (griddata's fill value).  A
  * cell on an edge shared by two triangles takes the one with the lower index (the interpolant is continuous there;
  * scipy's walk picks either), so results agree with griddata to rounding, not bit for bit.
- * workspace: ssrs_wind_triangles_workspace_bytes(npts, rows, cols, batch) bytes of device scratch. */
+ * workspace: ssrs_wind_triangles_workspace_bytes(npts, rows, cols, batch) bytes of device scratch; its contents before a
+ * call mean nothing and after it are unspecified. */
 size_t ssrs_wind_triangles_workspace_bytes(int npts, int rows, int cols, int batch);
 int ssrs_wind_from_triangles(const double *points, const int32_t *triangles, const double *transform,
                              const double *speed, const double *dirn, int npts, int ntri,
@@ -150,7 +152,8 @@ int ssrs_wind_from_triangles(const double *points, const int32_t *triangles, con
  * it once per wind geometry.  Samples are culled per 64 x 32 cell tile by the triangle inequality; the cull never
  * decides a result (a tile with too many candidates scans all samples).
  * workspace: ssrs_wind_nearest_workspace_bytes(npts, rows, cols) bytes of device scratch; on return its first int32
- * holds the number of tiles that scanned all samples.
+ * holds the number of tiles that scanned all samples; its contents before a call mean nothing and after it are
+ * otherwise unspecified.
  * ssrs_wind_from_nearest: speed / dirn (batch, npts) f64 -> per sample the u/v recipe of simulator.py:778-792
  * (speed = sqrt(e^2 + n^2), direction = mod(atan2(e, n) + 2 pi, 2 pi) in degrees) -> wspeed / wdirn (batch, rows, cols)
  * f64 gathered through `index`.  No NaN (nearest has no hull), except for an index outside [0, npts). */
@@ -170,7 +173,8 @@ int ssrs_wind_from_nearest(const int32_t *index, const double *speed, const doub
  * NaN outside the hull), the cubic in the four shifted barycentric coordinates, and the u/v recipe -> wspeed / wdirn
  * (batch, rows, cols) f64.  The interpolant is C1 across edges, so the triangle chosen on an edge changes a value by
  * rounding only; sums are taken in scipy's order but agreement with griddata is to rounding, not bit for bit.
- * workspace: ssrs_wind_cubic_workspace_bytes(npts, ntri, rows, cols, batch) bytes of device scratch. */
+ * workspace: ssrs_wind_cubic_workspace_bytes(npts, ntri, rows, cols, batch) bytes of device scratch; its contents before
+ * a call mean nothing and after it are unspecified. */
 size_t ssrs_wind_cubic_workspace_bytes(int npts, int ntri, int rows, int cols, int batch);
 int ssrs_wind_from_triangles_cubic(const double *points, const int32_t *triangles, const int32_t *neighbors,
                                    const double *transform, const double *east, const double *north,
@@ -184,7 +188,9 @@ int ssrs_wind_from_triangles_cubic(const double *points, const int32_t *triangle
  * lognormal(scale + 3, 0.5); counter-based (Philox keyed by seed and cell) --
  * statistical parity only, the reference replays a serial global RNG.
  * ssrs_gaussian_blur: scipy.ndimage.gaussian_filter(sigma, mode='constant'),
- * separable, truncated at 4 sigma.  thermals = blur(seeds, sigma = 4). */
+ * separable, truncated at 4 sigma.  thermals = blur(seeds, sigma = 4).
+ * workspace: ssrs_blur_workspace_bytes(rows, cols, sigma) bytes of device scratch; its contents before a call mean
+ * nothing and after it are unspecified. */
 int ssrs_thermal_seeds(const double *aspect, double thermal_intensity_scale,
                        uint64_t seed, double *seeds, int rows, int cols, void *stream);
 size_t ssrs_blur_workspace_bytes(int rows, int cols, double sigma);
@@ -232,7 +238,8 @@ int ssrs_thermal_updraft(const double *zmat, double z0, const double *deardorff_
  * also takes `neighbors` and `grad` (nfields, npts, 2), the vertex gradients of scipy's estimator, and builds the
  * ordinate table of ssrs_wind_from_triangles_cubic, [triangle][nfields][19].  A cell is evaluated by the very
  * expressions of the wind kernels.  workspace: ssrs_scalar_interp_workspace_bytes(method, ntri, rows, cols, nfields)
- * bytes of device scratch (ntri is ignored for 'nearest'); 0 for arguments the call would refuse. */
+ * bytes of device scratch (ntri is ignored for 'nearest'); 0 for arguments the call would refuse.  Its contents before a
+ * call mean nothing and after it are unspecified. */
 #define SSRS_INTERP_NEAREST 0
 #define SSRS_INTERP_LINEAR 1
 #define SSRS_INTERP_CUBIC 2
@@ -251,7 +258,8 @@ int ssrs_scalar_from_samples(int method, const double *points, const int32_t *tr
  * ssrs_scalar_from_samples -> ssrs_potential_temperature -> ssrs_deardorff_velocity -> ssrs_thermal_updraft, none of
  * whose 4 + 3 rasters per snapshot reaches memory: 4 B read per cell (owner or index), 4-8 B written per cell and
  * snapshot.  A lane owns four consecutive cells of a row (one 16-byte f32 store when cols % 4 == 0).
- * workspace: ssrs_scalar_interp_workspace_bytes(method, ntri, rows, cols, 4 * batch). */
+ * workspace: ssrs_scalar_interp_workspace_bytes(method, ntri, rows, cols, 4 * batch); its contents before a call mean
+ * nothing and after it are unspecified. */
 int ssrs_wtk_thermal_fields(int method, const double *points, const int32_t *triangles, const int32_t *neighbors,
                             const double *transform, const int32_t *index, const double *layers,
                             const double *grad, int npts, int ntri, double cell_size, const double *zmat,
@@ -354,7 +362,9 @@ int ssrs_transition_table_build(const double *updraft, const float *potential,
  * cell 10 f32 = the ring-ordered weights rounded to f32, stored as ring 7, 0, 1, ...,
  * 7, 0 (40 B), exact zeros as -0.0f; behind the records one zero-mask byte per cell (bit c:
  * ring weight c is exactly zero).  ring: ssrs_transition_ring_bytes(rows, cols) bytes,
- * 8-byte aligned. */
+ * 8-byte aligned.  The records and the mask are OVERWRITTEN; the 8 bytes between them and the
+ * bytes that round the size up to whole floats are not written (loads may touch them, no value
+ * of theirs is used). */
 size_t ssrs_transition_ring_bytes(int rows, int cols);
 int ssrs_transition_ring_build(const double *updraft, const float *potential, float *ring,
                                int rows, int cols, void *stream);
@@ -373,7 +383,9 @@ int ssrs_transition_ring_build(const double *updraft, const float *potential, fl
  * table carries a guard band of (cols + 2) dwords at either end, and the first bytes of the leading band
  * name the table (magic, rows, cols, the nine prior values): ssrs_tracks_simulate reads them back and returns
  * SSRS_ERR_INVALID, before any stepper kernel is launched, for a buffer that is not the threshold table of its
- * raster and prior (88 bytes and one stream wait per call). */
+ * raster and prior (88 bytes and one stream wait per call).  The header and the eight planes are
+ * OVERWRITTEN; the rest of the guard bands and the dwords between a plane's last cell and the next
+ * plane are not written (speculative loads may touch them, no value of theirs is used). */
 size_t ssrs_transition_thr_bytes(int rows, int cols);
 int ssrs_transition_thr_build(const double *updraft, const float *potential, const double *prior,
                               float *thr, int rows, int cols, void *stream);
@@ -384,7 +396,9 @@ int ssrs_transition_thr_build(const double *updraft, const float *potential, con
  * With the threshold table, a batch whose survivors roam a few basins of the potential
  * field until max_moves (the solved 10 m field: 44 %) is sorted into up to 16 histogram
  * windows of 144 x 256 cells and counted in LDS (SsrsTrackStats.block_window_launches);
- * nothing to size for it. */
+ * nothing to size for it.  A stepper workspace (this size or the next) may be handed from call to call as it stands,
+ * whatever the raster, table and path of the call before: its contents before a call mean nothing and after it are
+ * unspecified. */
 size_t ssrs_tracks_workspace_bytes(int64_t ntracks);
 /* The same plus (i) the pair table of the roaming regime and the fine table of its near-ties -- 128 + 64
  * bytes per cell (5.76 GB at 5000 x 6000),
@@ -417,7 +431,8 @@ size_t ssrs_tracks_workspace_bytes_ex(int64_t ntracks, int rows, int cols, int h
  *              traj_offsets int64 (ntracks + 1): exclusive prefix sums of the
  *              lengths of a previous call with the same arguments; points beyond
  *              a track's room [offsets[t], offsets[t+1]) are dropped, never written
- *   workspace  device scratch of ssrs_tracks_workspace_bytes(ntracks)
+ *   workspace  device scratch of ssrs_tracks_workspace_bytes(ntracks); its contents before a call mean nothing
+ *              and after it are unspecified
  *   stats      [host] out, may be NULL */
 int ssrs_tracks_simulate(const SsrsTrackParams *params, const double *updraft,
                          const float *potential, const double *table,
@@ -471,7 +486,8 @@ int ssrs_tracks_simulate_rec(const SsrsTrackParams *params, const double *updraf
  *   start_rc, ntracks   as passed to ssrs_tracks_simulate_rec
  *   traj_offsets        int64 (ntracks + 1), exclusive prefix sums of `lengths`; points
  *                       beyond a track's room are dropped, never written
- *   cursor_ws           device scratch, 4 bytes per track */
+ *   cursor_ws           device scratch, 4 bytes per track; its contents before a call mean nothing and after it
+ *                       are unspecified */
 int ssrs_tracks_gather(const SsrsTrajRecorder *recorder, const int32_t *start_rc,
                        int64_t ntracks, const int64_t *traj_offsets, int16_t *traj,
                        void *cursor_ws, size_t cursor_bytes, void *stream);
@@ -491,7 +507,7 @@ int ssrs_hist_reduce(uint32_t *hist, size_t n, int root, void *nccl_comm, void *
  * hist[row, col] += 1 for each of the npoints int16 (row, col) pairs.  uint32
  * counts (the reference's int16 matrix wraps above 32767 visits).  A point
  * outside the raster is an error (the reference raises IndexError).
- * scratch8: 8 bytes of device scratch. */
+ * scratch8: 8 bytes of device scratch; its contents before a call mean nothing and after it are unspecified. */
 int ssrs_presence_count(const int16_t *traj, int64_t npoints, uint32_t *hist,
                         int rows, int cols, void *scratch8, void *stream);
 
@@ -500,7 +516,9 @@ size_t ssrs_presence_workspace_bytes(int rows, int cols, int krad);
 /* compute_smooth_presence_counts (ssrs/movmodel.py:422-439) on a count matrix:
  * zero-padded 'same' convolution with the disk kernel (x^2+y^2 <= krad^2)/ntaps,
  * f32 out.  Evaluated as 2*krad+1 chords of row prefix sums: exact in integers,
- * then one multiply by 1/ntaps. */
+ * then one multiply by 1/ntaps.
+ * workspace: ssrs_presence_workspace_bytes(rows, cols, krad) bytes of device scratch, 256-byte aligned; its contents
+ * before a call mean nothing and after it are unspecified. */
 int ssrs_presence_smooth(const uint32_t *count, int krad, float *out, int rows,
                          int cols, void *workspace, size_t workspace_bytes,
                          void *stream);
@@ -515,7 +533,8 @@ int ssrs_presence_smooth_u64(const uint64_t *count, int krad, float *out, int ro
 /* The normalisation ladder of Simulator.plot_presence_map (simulator.py:529-546):
  *   acc += src / max(src)     (division in src's precision: f32 for `prprob`,
  *                              f64 for `case_prob`)
- *   out  = f32(src / max(src)) (summary_presence.npy) */
+ *   out  = f32(src / max(src)) (summary_presence.npy)
+ * scratch8: 8 bytes of device scratch; its contents before a call mean nothing and after it are unspecified. */
 int ssrs_presence_normalise_add(const void *src, int src_type, double *acc, size_t n,
                                 void *scratch8, void *stream);
 int ssrs_presence_normalise_f32(const double *src, float *out, size_t n,
@@ -696,7 +715,7 @@ int ssrs_track_occupancy(const int16_t *traj, const int64_t *traj_offsets, int64
  *                       greatest height over ALL its points; an empty track gets 0, INT32_MAX, INT32_MIN.
  *                       Sum(in_band) == Sum(added to band_hist): the caller's checksum
  *   workspace           24 bytes per tile of SSRS_ALTITUDE_TILE points (its operator and its first and last track), ssrs_track_altitude_workspace_bytes(points of the
- *                       chunk), 16-byte aligned; its contents before and after a call mean nothing
+ *                       chunk), 16-byte aligned; its contents before a call mean nothing and after it are unspecified
  * Three launches in `stream`'s order: the composed operator x -> min(max(x + A, L), H) of every tile of consecutive points
  * of the chunk; one block that scans those; every tile again behind its carry, writing the outputs.  No block waits for
  * another.  Exact, and independent of the launch order.  traj_offsets[0] and traj_offsets[ntracks] are read back first
@@ -881,7 +900,8 @@ int ssrs_updraft_sheltered_sector(const void *dem, int dem_type, double res, con
  * _LDS / _GLOBAL force one (A/B; _LDS with R > 128 is SSRS_ERR_INVALID).  All paths give the same bits.
  * workspace: ssrs_smooth_workspace_bytes() DEVICE bytes, 256-byte aligned -- the R + 1 weights and ONE f64 plane, which
  * the cases of a batch use one after the other (the size does not grow with `batch`; 0 for arguments that would be
- * refused).  Checked before any GPU work: `in` and workspace not NULL, rows, cols, batch >= 1, sigma finite and > 0,
+ * refused); its contents before a call mean nothing and after it are unspecified.
+ * Checked before any GPU work: `in` and workspace not NULL, rows, cols, batch >= 1, sigma finite and > 0,
  * R <= 512, min_updraft_val not NaN, a threshold > 0 when usable is asked for, path, the workspace size.
  * Asynchronous on `stream`; no host-device copy and no synchronisation (the weights travel as kernel arguments). */
 #define SSRS_SMOOTH_AUTO 0
@@ -929,7 +949,8 @@ int ssrs_smooth_reflect(const float *in, double sigma, int path, double min_updr
  * path alone synchronises `stream` (the longest list comes to the host).  All paths give the same bits.
  * workspace: ssrs_allen_workspace_bytes(n_updrafts) DEVICE bytes, 256-byte aligned (0 for a count that would be
  * refused): 256 bytes of counters, then the table.  After the call its first uint64 holds the number of cells that
- * finished on the ring scan under _AUTO / _LDS (a diagnostic; 0 under _GLOBAL).
+ * finished on the ring scan under _AUTO / _LDS (a diagnostic; 0 under _GLOBAL); its contents before a call mean nothing
+ * and after it are otherwise unspecified.
  * Checked before any GPU work, each refusal SSRS_ERR_INVALID naming the argument: xt, yt, wgain, rgain, bin_start,
  * bin_items, out, workspace not NULL; 1 <= n_updrafts <= SSRS_ALLEN_MAX_UPDRAFTS; rows, cols >= 1; res finite and > 0;
  * bin_size_m finite and >= res; nbx, nby in [1, 32768]; rbar, wtbar, zzi, we finite, zzi > 0, we <= 0; path; out_type;
@@ -1032,7 +1053,8 @@ typedef struct SsrsSolveStats {
 
 /* Device scratch that always suffices (about 1.5 KB per cell).  The hierarchy really takes ~840 B
  * per cell (SsrsSolveStats.workspace_used reports it); a smaller workspace is accepted and the call
- * fails with SSRS_ERR_INVALID ("workspace exhausted") when it does not suffice. */
+ * fails with SSRS_ERR_INVALID ("workspace exhausted") when it does not suffice.  Its contents before a call mean
+ * nothing and after it are unspecified. */
 size_t ssrs_potential_workspace_bytes(int rows, int cols);
 
 /* MovModel.assemble_sparse_linear_system + solve_sparse_linear_system
