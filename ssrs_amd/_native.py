@@ -119,11 +119,18 @@ PROTOTYPES = {
     'ssrs_tracks_roam_stopped_waves': 'q:',
 }
 EXPORTS = tuple(PROTOTYPES)
+# The exports of include/ssrs_hip_passage.h (K17), in the same letter code; tests/test_passage_host.py checks them against
+# that header.  They are bound after PROTOTYPES and stay out of it and of EXPORTS, which mirror ssrs_hip.h alone.
+PASSAGE_PROTOTYPES = {
+    'ssrs_track_passage_workspace_bytes': 'z:iii',
+    'ssrs_track_passage': 'i:ppqiiqippppzp',
+}
+PASSAGE_MAX_PLANES, PASSAGE_MAX_RADIUS = 8, 255
 
 
 def argtypes(name):
     """The ctypes argtypes of export `name`, from its line of PROTOTYPES."""
-    return [_KINDS[k] for k in PROTOTYPES[name].partition(':')[2]]
+    return [_KINDS[k] for k in {**PROTOTYPES, **PASSAGE_PROTOTYPES}[name].partition(':')[2]]
 
 
 # read by the host tests that bind a CPU build of one kernel file by the library's own prototypes
@@ -131,6 +138,7 @@ OCCUPANCY_ARGTYPES, ALLEN_FIELD_ARGTYPES, ALTITUDE_CELLINFO_ARGTYPES, ALTITUDE_A
     TRACK_TIME_ARGTYPES, ROTOR_ENCOUNTERS_ARGTYPES, ROTOR_ENCOUNTERS_TIMED_ARGTYPES = map(argtypes, (
         'ssrs_track_occupancy', 'ssrs_allen_thermal_field', 'ssrs_altitude_cellinfo', 'ssrs_track_altitude',
         'ssrs_flight_windinfo', 'ssrs_track_time', 'ssrs_rotor_encounters', 'ssrs_rotor_encounters_timed'))
+PASSAGE_ARGTYPES = argtypes('ssrs_track_passage')
 
 
 class SsrsTrackParams(C.Structure):
@@ -195,7 +203,7 @@ def lib():
                 f'{LIB_PATH} is missing: build it with `python ssrs_amd/csrc/build.py` '
                 '(hipcc, gfx950). ssrs_amd has no CPU fallback.')
         L = C.CDLL(LIB_PATH)
-        for name, proto in PROTOTYPES.items():
+        for name, proto in list(PROTOTYPES.items()) + list(PASSAGE_PROTOTYPES.items()):
             fn = getattr(L, name)
             fn.restype = _KINDS[proto[0]]
             fn.argtypes = argtypes(name)

@@ -35,7 +35,7 @@ _SECTIONS = (
     ('MI355X build', ('save_tracks', 'stepper_path', 'steps_per_launch', 'max_tracks_file_gb', 'track_occupancy',
                       'flight_height', 'flight_height_start', 'flight_height_floor', 'flight_height_ceiling',
                       'flight_airspeed', 'flight_sink_rate', 'rotor_zone', 'rotor_geometry', 'rotor_clearance',
-                      'flight_time', 'flight_min_groundspeed', 'rotor_exposure_time', 'hist_safe_tracks', 'thermal_model', 'thermal_allen_zi', 'thermal_allen_wstar', 'thermal_allen_sink',
+                      'flight_time', 'flight_min_groundspeed', 'rotor_exposure_time', 'track_passage_radius', 'hist_safe_tracks', 'thermal_model', 'thermal_allen_zi', 'thermal_allen_wstar', 'thermal_allen_sink',
                       'turbine_encounter_radius')),
 )
 
@@ -149,6 +149,13 @@ class Config:
     #                                     durations underneath are this build's placeholder models):
     #                                     <id>_turbine_rotor_time.npy, Simulator.compute_turbine_rotor_time().  It stands here,
     #                                     after flight_min_groundspeed, because tests pin every other slot
+    track_passage_radius: float = 0.    # metres; 0 = off.  > 0: simulate_tracks also counts, per cell, the DISTINCT tracks that
+    #                                     came within this distance of the cell's centre -- turbine_encounter_radius for a site
+    #                                     that is not in the turbine table yet -- from the trajectories on the device (produced
+    #                                     even with save_tracks=False; DESIGN.md K17, limit 16; at most 255 cells):
+    #                                     <id>_passage.npy, Simulator.compute_passage_map().  The file name does not carry the
+    #                                     radius: one radius per out_dir/run_name.  It stands here, not last, because tests pin
+    #                                     the last two fields and the last entry of _SECTIONS
     thermal_allen_zi: float = 0.        # thermal_model = 'allen': boundary-layer height zi in metres.  0 (snapshot / seasonal
     #                                     only) = the mean of the case's own blheight layer, clipped below at 100 m
     thermal_allen_wstar: float = 0.     # thermal_model = 'allen': convective velocity scale w* in m/s.  0 (snapshot / seasonal

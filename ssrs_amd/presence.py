@@ -2,6 +2,8 @@
 (/root/reference/ssrs/movmodel.py:410-439) plus the normalisation ladder of
 Simulator.plot_presence_map (simulator.py:520-546)."""
 
+import math
+
 import numpy as np
 import torch
 
@@ -113,6 +115,102 @@ def compute_track_occupancy(tracks, gridshape, *, offsets=None, counts=None, cel
         except Exception:
             workspace.zero_()
             raise
+    out = like_input(counts, None if as_numpy else counts)
+    if cells_per_track:
+        return out, like_input(per_track, None if as_numpy else per_track)
+    return out
+
+
+MAX_PASSAGE_PLANES = nat.PASSAGE_MAX_PLANES
+MAX_PASSAGE_RADIUS = nat.PASSAGE_MAX_RADIUS
+
+
+def passage_r2(radius_m, resolution):
+    """The r2 of compute_track_passage for a radius in metres: radius_cells = radius_m / resolution in f64 and
+    floor(radius_cells * radius_cells), no epsilon (a turbine on a cell centre is then counted by
+    turbines.turbine_encounters' f64 test for exactly the tracks the passage map counts at that cell).  ValueError for a
+    negative or NaN radius and for one of more than 255 cells."""
+    radius_m, resolution = float(radius_m), float(resolution)
+    if not resolution > 0.:
+        raise ValueError(f'passage_r2: resolution = {resolution!r}, expected metres > 0')
+    cells = radius_m / resolution
+    if not 0. <= cells <= float(MAX_PASSAGE_RADIUS):
+        raise ValueError(f'passage_r2: a radius of {radius_m!r} m at a resolution of {resolution!r} m is {cells!r} cells, '
+                         f'expected 0 to {MAX_PASSAGE_RADIUS}')
+    return int(math.floor(cells * cells))
+
+
+def passage_workspace(gridshape, planes):
+    """A workspace of ssrs_track_passage for `planes` rasters of `gridshape`.  Plain scratch: a call clears what it uses
+    itself, so one serves any number of calls, and what it holds in between means nothing."""
+    rows, cols = int(gridshape[0]), int(gridshape[1])
+    nbytes = nat.lib().ssrs_track_passage_workspace_bytes(rows, cols, int(planes))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device())
+
+
+def compute_track_passage(tracks, gridshape, r2, *, offsets=None, counts=None, cells_per_track=False, planes=None,
+                          workspace=None, stats=None):
+    """How many DISTINCT tracks came within a radius of each cell (K17, ssrs_track_passage): +1 in cell (r, c) for every
+    track with an in-raster point p such that (r, c) - p lies in D = {(dr, dc) : dr*dr + dc*dc <= r2}; points outside the
+    raster are ignored and disks are clipped to it.  r2: an int in 0..255*255 (passage_r2 makes it from metres); r2 = 0
+    is compute_track_occupancy.
+    `tracks`, `offsets`, `counts` (ADDED to), `cells_per_track` and what is returned: exactly as
+    compute_track_occupancy; cells_per_track counts each track's distinct in-raster cells within the radius, and their
+    sum is the raster's sum.
+    planes: 1..8 mask rasters of the workspace (None: occupancy_planes); the result does not depend on it.  workspace: of
+    passage_workspace(gridshape, planes), scratch whose contents mean nothing before or after; None allocates one.
+    stats: an int64 device tensor of two entries, ADDED to: [0] the mask words the set kernels tested (the work),
+    [1] the bits they won (= what the call added to the raster)."""
+    rows, cols = int(gridshape[0]), int(gridshape[1])
+    if isinstance(r2, bool) or not isinstance(r2, (int, np.integer)) or not 0 <= int(r2) <= MAX_PASSAGE_RADIUS ** 2:
+        raise ValueError(f'compute_track_passage: r2 = {r2!r}, expected an int from 0 to {MAX_PASSAGE_RADIUS} ** 2')
+    if planes is not None and not 1 <= int(planes) <= MAX_PASSAGE_PLANES:
+        raise ValueError(f'compute_track_passage: planes = {planes!r}, expected 1 to {MAX_PASSAGE_PLANES}')
+    as_numpy = not is_tensor(tracks)
+    if as_numpy:
+        if offsets is not None:
+            raise ValueError('compute_track_passage: offsets goes with a device tensor of points, not with a list of tracks')
+        tracks = [np.asarray(t) for t in tracks]
+        for k, t in enumerate(tracks):
+            if t.dtype != np.int16 or t.ndim != 2 or t.shape[1] != 2:
+                raise ValueError(f'compute_track_passage: track {k} is {t.dtype} {t.shape}, expected int16 (n, 2)')
+        flat = np.concatenate(tracks) if tracks else np.zeros((0, 2), dtype=np.int16)
+        offsets = np.concatenate([[0], np.cumsum([len(t) for t in tracks])]).astype(np.int64)
+    else:
+        if offsets is None:
+            raise ValueError('compute_track_passage: a tensor of points needs offsets= (int64, ntracks + 1)')
+        if tracks.dtype != torch.int16 or tracks.dim() != 2 or int(tracks.shape[1]) != 2:
+            raise ValueError(f'compute_track_passage: tracks is {tracks.dtype} {tuple(tracks.shape)}, expected int16 '
+                             '(points, 2)')
+        if not is_tensor(offsets):
+            offsets = np.asarray(offsets)
+        if offsets.dtype not in (torch.int64, np.int64) or len(offsets.shape) != 1 or int(offsets.shape[0]) < 1:
+            raise ValueError('compute_track_passage: offsets must be int64 (ntracks + 1)')
+        flat = tracks
+    if stats is not None and (not is_tensor(stats) or stats.dtype != torch.int64 or int(stats.numel()) != 2 or
+                              not stats.is_contiguous() or not stats.is_cuda):
+        raise ValueError('compute_track_passage: stats must be a contiguous int64 device tensor of two entries')
+    pts = to_dev(flat, torch.int16)
+    off = to_dev(offsets, torch.int64)
+    ntracks = int(off.numel()) - 1
+    dev = device()
+    if counts is None:
+        counts = torch.zeros((rows, cols), dtype=torch.int32, device=dev)
+    elif not is_tensor(counts) or counts.dtype != torch.int32 or tuple(counts.shape) != (rows, cols) or \
+            not counts.is_contiguous() or not counts.is_cuda:
+        raise ValueError(f'compute_track_passage: counts must be a contiguous int32 device tensor ({rows}, {cols})')
+    per_track = torch.zeros(ntracks, dtype=torch.int32, device=dev) if cells_per_track else None
+    if ntracks > 0 and pts.numel() > 0:                  # (empty tensors have no address to hand over)
+        if planes is None:
+            planes = occupancy_planes(ntracks, gridshape)
+        if workspace is None:
+            workspace = passage_workspace(gridshape, planes)
+        elif not is_tensor(workspace) or not workspace.is_cuda or not workspace.is_contiguous():
+            raise ValueError('compute_track_passage: workspace must be a contiguous device tensor (passage_workspace)')
+        nbytes = int(workspace.numel()) * workspace.element_size()
+        nat.check(nat.lib().ssrs_track_passage(
+            nat.ptr(pts), nat.ptr(off), ntracks, rows, cols, int(r2), int(planes), nat.ptr(counts),
+            nat.ptr(per_track), nat.ptr(stats), nat.ptr(workspace), nbytes, stream_ptr()))
     out = like_input(counts, None if as_numpy else counts)
     if cells_per_track:
         return out, like_input(per_track, None if as_numpy else per_track)

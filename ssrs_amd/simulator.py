@@ -77,6 +77,10 @@ class Simulator(Config):
         self._check_orographic_model()
         if not float(self.turbine_encounter_radius) >= 0.:
             raise ValueError(f'turbine_encounter_radius = {self.turbine_encounter_radius!r}: expected metres >= 0 (0 = off)')
+        if not float(self.track_passage_radius) >= 0.:
+            raise ValueError(f'track_passage_radius = {self.track_passage_radius!r}: expected metres >= 0 (0 = off)')
+        if float(self.track_passage_radius) > 0.:
+            presence.passage_r2(self.track_passage_radius, self.resolution)       # (at most 255 cells)
         if self.flight_height:
             self._flight_params()
         if self.flight_time:
@@ -131,6 +135,8 @@ class Simulator(Config):
         self.turbines = self._resolve_turbines(turbines)
         self.turbine_encounters = {}      # (case_id, real_id) -> dict(tracks_per_turbine, turbines_per_track, first_step)
         self.track_occupancy_counts = {}  # (case_id, real_id) -> int32 (rows, cols): the distinct tracks through each cell
+        self.track_passage_counts = {}    # (case_id, real_id) -> int32 (rows, cols): the distinct tracks within
+        #                                     track_passage_radius of each cell
         self.rotor_presence_counts = {}   # (case_id, real_id) -> int32 (rows, cols) holding uint32: points in the rotor zone
         self.flight_heights = {}          # (case_id, real_id) -> int32 (this rank's tracks, 3): [in zone, h_min, h_max] in mm
         self.rotor_turbine_encounters = {}  # as turbine_encounters, of the points in the rotor zone only
@@ -818,6 +824,7 @@ class Simulator(Config):
             rotor = (to_dev(cells, torch.float64), to_dev(reach, torch.float64), to_dev(zband, torch.int32),
                      tuple(to_dev(a, torch.int32) for a in bins))
         occupancy = bool(self.track_occupancy)
+        passage = float(self.track_passage_radius) > 0.
         heights = bool(self.flight_height)
         if heights:
             dem = to_dev(self._terrain['Elevation'], torch.float64)
@@ -847,6 +854,11 @@ class Simulator(Config):
                     occ_counts = torch.zeros(self.gridsize, dtype=torch.int32, device=my_starts.device)
                     occ_cells = torch.zeros((), dtype=torch.int64, device=my_starts.device)
                     consumers.append(self._occupancy_consumer(hi - lo, occ_counts, occ_cells))
+                if passage:
+                    # as the occupancy: one raster per item, accumulated over chunks and parts, and one workspace
+                    pas_counts = torch.zeros(self.gridsize, dtype=torch.int32, device=my_starts.device)
+                    pas_cells = torch.zeros((), dtype=torch.int64, device=my_starts.device)
+                    consumers.append(self._passage_consumer(hi - lo, pas_counts, pas_cells))
                 if heights:
                     # one rotor-zone raster per item, this rank's per-track rows, and (with encounters) a second bitmap
                     # from the points in the rotor zone alone
@@ -903,6 +915,9 @@ class Simulator(Config):
                 if occupancy:
                     # (track-sharded: the sum over the ranks is a collective as well, after the encounters' in every item)
                     self._store_occupancy(case_id, real_id, occ_counts, int(occ_cells.item()), sharded)
+                if passage:
+                    # (track-sharded: after the occupancy's collective in every item)
+                    self._store_passage(case_id, real_id, pas_counts, int(pas_cells.item()), sharded)
                 if heights:
                     # (track-sharded: its collectives come last in every item)
                     self._store_flight(case_id, real_id, fly, nturb if encounters else 0, sharded)
@@ -973,6 +988,20 @@ class Simulator(Config):
         def consume(t0, t1, traj, off):
             _, per_track = presence.compute_track_occupancy(traj, self.gridsize, offsets=off, counts=counts,
                                                             cells_per_track=True, planes=planes, workspace=workspace)
+            cells.add_(per_track.sum(dtype=torch.int64))
+        return consume
+
+    def _passage_consumer(self, ntracks, counts, cells):
+        """A chunk through the passage kernel (K17): `counts` (the item's raster) is added to, `cells` (a 0-d int64 tensor)
+        gets the sum of the chunk's cells_per_track, the checksum of _store_passage.  One workspace serves every chunk of
+        the item (scratch: a call clears what it uses)."""
+        planes = presence.occupancy_planes(ntracks, self.gridsize)
+        workspace = presence.passage_workspace(self.gridsize, planes)
+        r2 = presence.passage_r2(self.track_passage_radius, self.resolution)
+
+        def consume(t0, t1, traj, off):
+            _, per_track = presence.compute_track_passage(traj, self.gridsize, r2, offsets=off, counts=counts,
+                                                          cells_per_track=True, planes=planes, workspace=workspace)
             cells.add_(per_track.sum(dtype=torch.int64))
         return consume
 
@@ -1182,6 +1211,20 @@ class Simulator(Config):
         if not sharded or self._rank() == 0:
             np.save(os.path.join(self.mode_data_dir, f'{id_str}_occupancy.npy'), self.track_occupancy_counts[(case_id, real_id)])
 
+    def _store_passage(self, case_id, real_id, counts, cells, sharded):
+        """Keeps the passage raster of one (case, realisation) as numpy int32 and writes <id>_passage.npy: checksum, sum
+        over the ranks of a track-sharded run and writer exactly as _store_occupancy."""
+        id_str = self._get_id_string(case_id, real_id)
+        counted = int((counts.to(torch.int64) & 0xFFFFFFFF).sum().item())
+        if counted != int(cells):
+            raise RuntimeError(f'{id_str}: track passage: the raster adds up to {counted}, the cells within the radius of '
+                               f'the tracks to {int(cells)}')
+        if sharded:
+            counts = distributed.reduce_histogram(counts, all_ranks=True)
+        self.track_passage_counts[(case_id, real_id)] = counts.to(torch.int32).cpu().numpy()
+        if not sharded or self._rank() == 0:
+            np.save(os.path.join(self.mode_data_dir, f'{id_str}_passage.npy'), self.track_passage_counts[(case_id, real_id)])
+
     def _store_encounters(self, case_id, real_id, tracks_per_turbine, turbines_per_track, first_step, sharded):
         """Keeps the encounters of one (case, realisation) and writes <id>_turbine_encounters.npy (int64 (nturb,): the
         tracks that came within turbine_encounter_radius of each turbine).  Track-sharded runs sum the per-turbine
@@ -1216,7 +1259,7 @@ class Simulator(Config):
         parts, wide, stats = [], None, None
         # trajectories: for the pickle, or for the turbine encounters / the track occupancy (which read them on the device)
         want_tracks = bool(self.save_tracks) or float(self.turbine_encounter_radius) > 0. or bool(self.track_occupancy) or \
-            bool(self.flight_height) or bool(self.flight_time)
+            bool(self.flight_height) or bool(self.flight_time) or float(self.track_passage_radius) > 0.
         # (start, length) of the sub-batches still to step, in track-id order; one whose uint32 counts wrapped is stepped
         # again as two halves, added up in 64 bits like the rest
         todo = [(t0, min(step, n - t0)) for t0 in range(0, max(n, 1), step)]
@@ -1529,6 +1572,27 @@ class Simulator(Config):
         out = (total / nitems).to(torch.float32).cpu().numpy()
         if self._rank() == 0:
             np.save(os.path.join(self.mode_data_dir, 'summary_occupancy.npy'), out)
+        self._barrier()
+        return out
+
+    def compute_passage_map(self):
+        """Each cell's share of the simulated tracks that came within track_passage_radius of it, in [0, 1]: the f32 mean
+        over all kept (case, realisation) items of track_passage_counts / track_count; case-sharded runs take the mean
+        over every rank's items.  Writes summary_passage.npy.  ValueError when simulate_tracks computed no passage."""
+        if not self.track_passage_counts:
+            raise ValueError('no track passage was computed: run simulate_tracks() with track_passage_radius > 0')
+        total = torch.zeros(self.gridsize, dtype=torch.float64, device=self._presence_device())
+        for key in sorted(self.track_passage_counts):
+            counts = to_dev(self.track_passage_counts[key], torch.int32)
+            total += (counts.to(torch.int64) & 0xFFFFFFFF).to(torch.float64) / float(self.track_count)
+        nitems = float(len(self.track_passage_counts))
+        if self._world() > 1 and not self._shards_tracks():
+            # the cases of the other ranks
+            summed = self._allreduce_sum(np.append(total.cpu().numpy().ravel(), nitems))
+            total, nitems = to_dev(np.asarray(summed[:-1]).reshape(self.gridsize), torch.float64), float(summed[-1])
+        out = (total / nitems).to(torch.float32).cpu().numpy()
+        if self._rank() == 0:
+            np.save(os.path.join(self.mode_data_dir, 'summary_passage.npy'), out)
         self._barrier()
         return out
 
