@@ -126,11 +126,16 @@ PASSAGE_PROTOTYPES = {
     'ssrs_track_passage': 'i:ppqiiqippppzp',
 }
 PASSAGE_MAX_PLANES, PASSAGE_MAX_RADIUS = 8, 255
+# The export of include/ssrs_hip_transits.h (K18), bound the same way; tests/test_transit_host.py checks it against that header.
+TRANSIT_PROTOTYPES = {
+    'ssrs_rotor_transits': 'i:ppqppiippppdippppp',
+}
+ROTOR_TRANSIT_LDS_TURBINES = 7680
 
 
 def argtypes(name):
     """The ctypes argtypes of export `name`, from its line of PROTOTYPES."""
-    return [_KINDS[k] for k in {**PROTOTYPES, **PASSAGE_PROTOTYPES}[name].partition(':')[2]]
+    return [_KINDS[k] for k in {**PROTOTYPES, **PASSAGE_PROTOTYPES, **TRANSIT_PROTOTYPES}[name].partition(':')[2]]
 
 
 # read by the host tests that bind a CPU build of one kernel file by the library's own prototypes
@@ -139,6 +144,7 @@ OCCUPANCY_ARGTYPES, ALLEN_FIELD_ARGTYPES, ALTITUDE_CELLINFO_ARGTYPES, ALTITUDE_A
         'ssrs_track_occupancy', 'ssrs_allen_thermal_field', 'ssrs_altitude_cellinfo', 'ssrs_track_altitude',
         'ssrs_flight_windinfo', 'ssrs_track_time', 'ssrs_rotor_encounters', 'ssrs_rotor_encounters_timed'))
 PASSAGE_ARGTYPES = argtypes('ssrs_track_passage')
+ROTOR_TRANSITS_ARGTYPES = argtypes('ssrs_rotor_transits')
 
 
 class SsrsTrackParams(C.Structure):
@@ -203,7 +209,7 @@ def lib():
                 f'{LIB_PATH} is missing: build it with `python ssrs_amd/csrc/build.py` '
                 '(hipcc, gfx950). ssrs_amd has no CPU fallback.')
         L = C.CDLL(LIB_PATH)
-        for name, proto in list(PROTOTYPES.items()) + list(PASSAGE_PROTOTYPES.items()):
+        for name, proto in list(PROTOTYPES.items()) + list(PASSAGE_PROTOTYPES.items()) + list(TRANSIT_PROTOTYPES.items()):
             fn = getattr(L, name)
             fn.restype = _KINDS[proto[0]]
             fn.argtypes = argtypes(name)

@@ -35,7 +35,7 @@ _SECTIONS = (
     ('MI355X build', ('save_tracks', 'stepper_path', 'steps_per_launch', 'max_tracks_file_gb', 'track_occupancy',
                       'flight_height', 'flight_height_start', 'flight_height_floor', 'flight_height_ceiling',
                       'flight_airspeed', 'flight_sink_rate', 'rotor_zone', 'rotor_geometry', 'rotor_clearance',
-                      'flight_time', 'flight_min_groundspeed', 'rotor_exposure_time', 'track_passage_radius', 'hist_safe_tracks', 'thermal_model', 'thermal_allen_zi', 'thermal_allen_wstar', 'thermal_allen_sink',
+                      'flight_time', 'flight_min_groundspeed', 'rotor_exposure_time', 'track_passage_radius', 'rotor_transits', 'rotor_yaw', 'hist_safe_tracks', 'thermal_model', 'thermal_allen_zi', 'thermal_allen_wstar', 'thermal_allen_sink',
                       'turbine_encounter_radius')),
 )
 
@@ -156,6 +156,16 @@ class Config:
     #                                     <id>_passage.npy, Simulator.compute_passage_map().  The file name does not carry the
     #                                     radius: one radius per out_dir/run_name.  It stands here, not last, because tests pin
     #                                     the last two fields and the last entry of _SECTIONS
+    rotor_transits: bool = False        # True (needs flight_height=True, rotor_geometry='turbine' and turbines with t_hh and
+    #                                     t_rd; flight_time is not needed): simulate_tracks also counts, per turbine and direction,
+    #                                     the TRANSITS -- unit moves whose straight segment goes through the rotor DISK, a circle
+    #                                     of radius t_rd / 2 + rotor_clearance around the hub that stands across the wind -- on the
+    #                                     device (limit 17: a count of flights through the disk, NOT a collision
+    #                                     probability; K14's placeholder heights underneath):
+    #                                     <id>_turbine_rotor_transits.npy, Simulator.compute_turbine_rotor_transits()
+    rotor_yaw: float = -1.              # degrees clockwise from north the rotors face, for all turbines and cases; < 0: every
+    #                                     rotor faces the case's wind at the cell it stands on.  The two fields stand here, behind
+    #                                     track_passage_radius, because tests pin most other slots
     thermal_allen_zi: float = 0.        # thermal_model = 'allen': boundary-layer height zi in metres.  0 (snapshot / seasonal
     #                                     only) = the mean of the case's own blheight layer, clipped below at 100 m
     thermal_allen_wstar: float = 0.     # thermal_model = 'allen': convective velocity scale w* in m/s.  0 (snapshot / seasonal

@@ -86,6 +86,7 @@ class Simulator(Config):
         if self.flight_time:
             self._time_params()
         self._check_rotor_exposure_time()
+        self._check_rotor_transits(turbines)
         self._check_rotor_geometry(turbines)
         print(f'\n---- SSRS in {self.sim_mode} mode')
         print(f'Run name: {self.run_name}')
@@ -146,6 +147,8 @@ class Simulator(Config):
         self.turbine_rotor_encounters = {}  # rotor_geometry='turbine': (case_id, real_id) -> dict(tracks_per_turbine,
         #                                     points_per_turbine int64, turbines_per_track, first_step int32; with
         #                                     rotor_exposure_time also time_per_turbine int64, microseconds)
+        self.turbine_rotor_transits = {}  # rotor_transits: (case_id, real_id) -> int64 (nturb, 3): [tracks, transits with the
+        #                                     wind, against the wind]
         self.wtk_layers = {
             'wspeed': f'windspeed_{str(int(self.wtk_orographic_height))}m',
             'wdirn': f'winddirection_{str(int(self.wtk_orographic_height))}m',
@@ -250,6 +253,26 @@ class Simulator(Config):
             if not ok:
                 raise ValueError(f'rotor_exposure_time = True needs {field}: {why}')
 
+    def _check_rotor_transits(self, turbines):
+        """rotor_transits counts the moves through every turbine's disk along K14's heights: what it needs that can be told
+        before anything is computed.  (flight_time is not among it.)"""
+        if not self.rotor_transits:
+            return
+        yaw = float(self.rotor_yaw)
+        if yaw != yaw or yaw in (float('inf'), float('-inf')):
+            raise ValueError(f'rotor_yaw = {self.rotor_yaw!r}: expected degrees clockwise from north, or < 0 for the wind')
+        names = turbines_mod._column_names(turbines) if turbines is not None else []
+        for ok, field, why in ((self.flight_height, 'flight_height=True', 'the disks are tested against the heights along '
+                                'the tracks'),
+                               (self._rotor_per_turbine(), "rotor_geometry='turbine'", "the disk is every turbine's own, "
+                                'around its hub'),
+                               (turbines is not None, 'turbines', 'none were given (Simulator(..., turbines=...))'),
+                               ('t_hh' in names, 'turbines with t_hh', 'the hub height in metres, the centre of the disk'),
+                               ('t_rd' in names, 'turbines with t_rd', 'the rotor diameter in metres, twice the radius of '
+                                'the disk')):
+            if not ok:
+                raise ValueError(f'rotor_transits = True needs {field}: {why}')
+
     def _check_rotor_geometry(self, turbines):
         """rotor_geometry / rotor_clearance, and what 'turbine' needs that can be told before anything is computed."""
         if str(self.rotor_geometry).lower() not in ('band', 'turbine'):
@@ -304,6 +327,13 @@ class Simulator(Config):
                 warnings.warn(f"rotor_geometry = 'turbine': {nodata} of the {len(turbines)} turbines stand on a nodata cell "
                               'of the DEM; their cylinders are empty and nothing encounters them')
             self._rotor_cylinders = (cells, reach, zband, turbines_mod.build_bins(cells, reach, self.gridsize))
+            if self.rotor_transits:
+                # the disks of K18: the cylinders' reach, the hubs, and cull lists of their own (a move is culled by its
+                # first point: reach + 1.5)
+                _, disk_reach, hub, _ = turbines_mod.rotor_disks(turbines, dem, self.bounds, self.resolution,
+                                                                 float(self.rotor_clearance))
+                self._rotor_disks = (cells, disk_reach, hub, turbines_mod.build_bins(
+                    cells, disk_reach + turbines_mod.TRANSIT_CULL_MARGIN, self.gridsize))
         return turbines
 
     THERMAL_LAYERS = inputs.THERMAL_LAYERS      # keys of wtk_layers
@@ -804,14 +834,16 @@ class Simulator(Config):
                 # (flight_time: one windinfo per wind case, the scalar pair in uniform mode; finished before a worker's
                 # stream reads it)
                 wind = self._time_wind(case_id) if self.flight_time else None
-                if torch.is_tensor(wind):
+                # (rotor_transits: the rotors' axes, once per case)
+                axes = self._transit_axes(case_id) if transit else None
+                if torch.is_tensor(wind) or axes is not None:
                     torch.cuda.current_stream().synchronize()
                 for (real_id, updraft), lift in zip(enumerate(updrafts), raw):
                     if self.sim_seed > 0:
                         np.random.seed(self.sim_seed + real_id)
                     fields = (updraft, self._potential_dev(updraft, case_id, real_id)) if fluid \
                         else (None, None)
-                    yield (case_id, real_id, fields, self._stream_seed(real_id), lift, wind)
+                    yield (case_id, real_id, fields, self._stream_seed(real_id), lift, wind, axes)
 
         encounters = float(self.turbine_encounter_radius) > 0.
         if encounters:
@@ -830,9 +862,15 @@ class Simulator(Config):
             dem = to_dev(self._terrain['Elevation'], torch.float64)
         timed = bool(self.flight_time)
         exposure = bool(self.rotor_exposure_time)       # (the constructor saw to heights, timed and rotor)
+        transit = bool(self.rotor_transits)             # (the constructor saw to heights and rotor)
+        disks = None
+        if transit:
+            cells, reach, hub, bins = self._rotor_disks
+            disks = (to_dev(cells, torch.float64), to_dev(reach, torch.float64), to_dev(hub, torch.int32),
+                     tuple(to_dev(a, torch.int32) for a in bins))
 
         def run(item):
-            case_id, real_id, fields, seed, lift, wind = item
+            case_id, real_id, fields, seed, lift, wind, axes = item
             self.last_seeds[(case_id, real_id)] = seed
             id_str = self._get_id_string(case_id, real_id)
             start_time = time.time()
@@ -876,8 +914,13 @@ class Simulator(Config):
                         fly['rotor_points'] = torch.zeros(n_rotor, dtype=torch.int64, device=my_starts.device)
                         if exposure:
                             fly['rotor_time'] = torch.zeros(n_rotor, dtype=torch.int64, device=my_starts.device)
+                        if transit:
+                            # the disks: a fourth bitmap, and the transits of each by direction
+                            fly['transit_hits'] = torch.zeros_like(fly['rotor_hits'])
+                            fly['transits'] = torch.zeros((n_rotor, 2), dtype=torch.int64, device=my_starts.device)
                     consumers.append(self._flight_consumer(lift, dem, fly, enc_geometry if encounters else None, rotor,
-                                                           keep_masked=timed, defer_rotor=exposure))
+                                                           keep_masked=timed, defer_rotor=exposure,
+                                                           transit=(disks, axes) if transit else None))
                 if timed:
                     # after the flight consumer, whose traj_band of the chunk it reads: one raster of microseconds per
                     # item (two with flight_height), accumulated over chunks and parts, and this rank's per-track rows
@@ -1020,7 +1063,7 @@ class Simulator(Config):
         flight.height_params(who='Config.flight_height_* / rotor_zone', **kw)
         return kw, airspeed, sink
 
-    def _flight_consumer(self, lift, dem, fly, geometry, rotor=None, keep_masked=False, defer_rotor=False):
+    def _flight_consumer(self, lift, dem, fly, geometry, rotor=None, keep_masked=False, defer_rotor=False, transit=None):
         """A chunk through the flight-height scan (K14): `fly['band_hist']` is added to, the chunk's tracks get their rows of
         `fly['rows']`; with `geometry` the points in the rotor zone go through the encounter kernel into `fly['hits']` /
         `fly['first_step']`; with `rotor` (the cylinders on the device) the points and their heights go through the rotor
@@ -1028,7 +1071,9 @@ class Simulator(Config):
         built here, from its un-thresholded updraft `lift` and the DEM.  keep_masked: the chunk's traj_band stays in
         `fly['masked']` for the consumer behind this one (_time_consumer).  defer_rotor (rotor_exposure_time): the rotor
         kernel is not called here but behind K16, where the chunk's dt exists: the chunk's alt stays in `fly['alt']` and the
-        item's cellinfo in `fly['cellinfo']` for _time_consumer."""
+        item's cellinfo in `fly['cellinfo']` for _time_consumer.  transit (rotor_transits): ((cells, reach, hub, bins) on the
+        device, the case's axes): the chunk and its alt also go through the transit kernel (K18), here in either case, into
+        `fly['transit_hits']` / `fly['transits']`."""
         kw, airspeed, sink = self._flight_params()
         cellinfo = flight.altitude_cellinfo(lift, dem, self.resolution, airspeed, sink)
         if defer_rotor:
@@ -1049,11 +1094,40 @@ class Simulator(Config):
                 turbines_mod.rotor_encounters(traj, out['alt'], off, cellinfo, cells, reach, zband, self.gridsize,
                                               bins=rotor_bins, hits=fly['rotor_hits'][t0:t1],
                                               first_step=fly['rotor_first_step'][t0:t1], points=fly['rotor_points'])
+            if transit is not None:
+                (cells, reach, hub, disk_bins), axes = transit
+                turbines_mod.rotor_transits(traj, out['alt'], off, cellinfo, cells, reach, hub, axes, self.gridsize,
+                                            self.resolution, bins=disk_bins, hits=fly['transit_hits'][t0:t1],
+                                            transits=fly['transits'])
             if geometry is not None:
                 xy, bins = geometry
                 turbines_mod.turbine_encounters(out['masked'], off, xy, radius_cells, self.gridsize, bins=bins,
                                                 hits=fly['hits'][t0:t1], first_step=fly['first_step'][t0:t1])
         return consume
+
+    def _transit_axes(self, case_id):
+        """The rotors' axes of one case (turbines.rotor_axes, on the device): rotor_yaw >= 0 is that compass direction for
+        every turbine; otherwise every rotor faces the wind K16 reads -- uniform_winddirn in uniform mode, else the case's
+        wdirn raster (_wind_rasters, at wtk_orographic_height) at the cell the turbine stands on -- in the frame of
+        _time_ray_axes().  A NaN direction gives a turbine nothing can transit; one warning says how many."""
+        cells = self._rotor_disks[0]
+        nturb = int(cells.shape[0])
+        if float(self.rotor_yaw) >= 0.:
+            wdirn = float(self.rotor_yaw)
+        elif self.sim_mode.lower() == 'uniform':
+            wdirn = float(self.uniform_winddirn)
+        else:
+            entry = next(w for w in self._wind if w.case_id == case_id)
+            rb, cb, known = turbines_mod.base_cells(cells, self.gridsize)
+            raster = self._wind_rasters(entry)[1]
+            wdirn = raster[torch.from_numpy(rb).to(raster.device), torch.from_numpy(cb).to(raster.device)].cpu().numpy()
+            wdirn = np.where(known, wdirn.astype(np.float64), np.nan)
+        axes = turbines_mod.rotor_axes(wdirn, self._time_ray_axes(), nturb)
+        lost = int(np.isnan(axes).any(1).sum())
+        if lost:
+            warnings.warn(f'rotor_transits: {case_id}: {lost} of the {nturb} turbines have no wind direction (NaN) at the '
+                          'cell they stand on; nothing transits them')
+        return to_dev(axes, torch.float64)
 
     def _time_params(self):
         """Keyword arguments of flight.compute_track_times from the resolution and the flight_* fields, checked."""
@@ -1193,6 +1267,22 @@ class Simulator(Config):
                 np.save(os.path.join(self.mode_data_dir, f'{id_str}_turbine_rotor_encounters.npy'), both)
                 if spent is not None:
                     np.save(os.path.join(self.mode_data_dir, f'{id_str}_turbine_rotor_time.npy'), spent)
+        if 'transit_hits' in fly:
+            # rotor_transits: <id>_turbine_rotor_transits.npy, int64 (nturb, 3) [tracks, with the wind, against the wind].
+            # The cheap invariant that stands in for a checksum: a turbine has tracks iff it has transits.  Track-sharded
+            # runs sum the three columns over the ranks like the other per-turbine counts (untested on more than one rank)
+            per_turbine, _ = turbines_mod.encounter_counts(fly['transit_hits'], int(fly['transits'].shape[0]))
+            three = torch.cat([per_turbine[:, None], fly['transits']], 1).cpu().numpy().astype(np.int64)
+            wrong = np.nonzero((three[:, 0] > 0) != (three[:, 1:].sum(1) > 0))[0]
+            if wrong.size:
+                t = int(wrong[0])
+                raise RuntimeError(f'{id_str}: rotor transits: turbine {t} has {int(three[t, 0])} tracks for '
+                                   f'{int(three[t, 1])} + {int(three[t, 2])} transits ({wrong.size} turbines like it)')
+            if sharded:
+                three = np.asarray(self._allreduce_sum(three.reshape(-1)), dtype=np.int64).reshape(-1, 3)
+            self.turbine_rotor_transits[key] = three
+            if writes:
+                np.save(os.path.join(self.mode_data_dir, f'{id_str}_turbine_rotor_transits.npy'), three)
 
     def _store_occupancy(self, case_id, real_id, counts, cells, sharded):
         """Keeps the occupancy raster of one (case, realisation) as numpy int32 and writes <id>_occupancy.npy.  Checked
@@ -1519,6 +1609,29 @@ class Simulator(Config):
         out = np.ascontiguousarray((total[:-1] / total[-1]).reshape(2, nturb).T)
         if self._rank() == 0:
             np.save(os.path.join(self.mode_data_dir, 'summary_turbine_rotor_encounters.npy'), out)
+        self._barrier()
+        return out
+
+    def compute_turbine_rotor_transits(self):
+        """Per turbine, the share of the simulated tracks that went through its rotor disk and the transits per simulated
+        track, with and against the wind (rotor_transits = True; DESIGN.md K18, limit 17: flights through the disk, not
+        collisions): f64 (nturb, 3), the mean over all (case, realisation) items of [tracks, with the wind, against the
+        wind] / track_count, in the order of `turbines.get_locations()`; case-sharded runs take the mean over every
+        rank's items.  Writes summary_turbine_rotor_transits.npy.  ValueError when simulate_tracks computed none."""
+        if not self.turbine_rotor_transits:
+            raise ValueError("no rotor transits were computed: run simulate_tracks() with rotor_transits=True "
+                             "(flight_height=True, rotor_geometry='turbine' and turbines with t_hh and t_rd)")
+        items = [self.turbine_rotor_transits[key] for key in sorted(self.turbine_rotor_transits)]
+        nturb = items[0].shape[0]
+        total = np.zeros(3 * nturb + 1, dtype=np.float64)                  # [(nturb, 3) row by row, number of items]
+        for three in items:
+            total[:-1] += (three / float(self.track_count)).reshape(-1)
+            total[-1] += 1.
+        if self._world() > 1 and not self._shards_tracks():
+            total = self._allreduce_sum(total)                      # the cases of the other ranks
+        out = np.ascontiguousarray((total[:-1] / total[-1]).reshape(nturb, 3))
+        if self._rank() == 0:
+            np.save(os.path.join(self.mode_data_dir, 'summary_turbine_rotor_transits.npy'), out)
         self._barrier()
         return out
 

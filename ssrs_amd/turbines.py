@@ -405,3 +405,120 @@ def rotor_encounters(traj, alt, offsets, cellinfo, xy_cells, reach, zband, grids
         nat.ptr(reach_dev), nat.ptr(zband_dev), nturb, nat.ptr(bin_start), nat.ptr(bin_items), nat.ptr(hits),
         nat.ptr(first_step), nat.ptr(points), stream_ptr()))
     return hits, first_step, points
+
+
+def rotor_disks(turbines, dem, bounds, resolution, clearance=0.):
+    """The disks of ssrs_rotor_transits (K18) from a `Turbines` with `t_hh` and `t_rd`: (xy_cells f64 (nturb, 2), reach f64
+    (nturb,) in cells, hub int32 (nturb,) in mm above the DEM's datum, n_empty).  reach = (t_rd / 2 + clearance) / resolution;
+    hub = base + rint(1000 t_hh), summed in int64 and clipped to int32, with rotor_geometry's base: the elevation of the cell
+    the turbine stands on (base_cells), clip(rint(1000 z), +-2^30).  A NaN base (nodata), t_hh or t_rd gives reach = NaN
+    (and hub = 0): nothing transits such a turbine; n_empty counts them.  dem: numpy or a device tensor (rows, cols)."""
+    missing = [name for name in ('t_hh', 't_rd') if name not in turbines.columns]
+    if missing:
+        raise ValueError(f'rotor_disks: the turbines have no column {" / ".join(missing)} '
+                         '(t_hh = hub height, t_rd = rotor diameter, metres)')
+    resolution, clearance = float(resolution), float(clearance)
+    if not resolution > 0. or clearance != clearance:
+        raise ValueError(f'rotor_disks: resolution = {resolution!r}, clearance = {clearance!r} (resolution > 0)')
+    if len(np.shape(dem)) != 2:
+        raise ValueError(f'rotor_disks: dem has shape {tuple(np.shape(dem))}, expected (rows, cols)')
+    xy = turbines.cell_coordinates(bounds, resolution)
+    rb, cb, known = base_cells(xy, np.shape(dem))
+    if is_tensor(dem):
+        z = dem[torch.from_numpy(rb).to(dem.device), torch.from_numpy(cb).to(dem.device)].cpu().numpy()
+    else:
+        z = np.asarray(dem)[rb, cb]
+    z = np.where(known, z.astype(np.float64), np.nan)
+    hh = np.asarray(turbines.columns['t_hh'], dtype=np.float64)
+    rad = np.asarray(turbines.columns['t_rd'], dtype=np.float64) / 2. + clearance
+    empty = np.isnan(z) | np.isnan(hh) | np.isnan(rad)
+    base = np.clip(_mm(z), -2 ** 30, 2 ** 30)
+    i32 = np.iinfo(np.int32)
+    hub = np.where(empty, 0, np.clip(base + _mm(hh), i32.min, i32.max)).astype(np.int32)
+    return xy, np.where(empty, np.nan, rad / resolution), hub, int(empty.sum())
+
+
+def rotor_axes(wdirn, ray_axes, nturb=None):
+    """The axes of ssrs_rotor_transits: (n, 2) f64 [ax, ay], the upwind unit step along +col and +row of a wind from `wdirn`
+    degrees (clockwise from north), from layers.ray_step as (uc, ur).  wdirn: one direction per turbine, or a scalar, which
+    serves all turbines: one row, or `nturb` equal rows when that is given.  A NaN direction gives a NaN axis: nothing
+    transits such a turbine."""
+    from . import layers
+    ur, uc = layers.ray_step(wdirn, ray_axes)
+    axis = np.ascontiguousarray(np.stack([uc, ur], 1), dtype=np.float64)
+    if nturb is not None and axis.shape[0] != int(nturb):
+        if axis.shape[0] != 1:
+            raise ValueError(f'rotor_axes: {axis.shape[0]} directions for {int(nturb)} turbines')
+        axis = np.ascontiguousarray(np.repeat(axis, int(nturb), 0))
+    return axis
+
+
+TRANSIT_CULL_MARGIN = 1.5     # cells added to the reach for the cull lists of rotor_transits (include/ssrs_hip_transits.h)
+
+
+def rotor_transits(traj, alt, offsets, cellinfo, xy_cells, reach, hub, axis, gridshape, resolution, bins=None, hits=None,
+                   transits=None):
+    """ssrs_rotor_transits on device tensors (K18): the moves through every turbine's rotor disk, per direction.  traj, alt,
+    offsets, cellinfo, xy_cells and hits as rotor_encounters takes them (host or device); reach (nturb,) f64, hub (nturb,)
+    int32 of rotor_disks; axis (nturb, 2) f64 of rotor_axes (one row serves all turbines); resolution in metres
+    (mm_per_cell = 1000 * resolution).  bins: the cull lists, built here from reach + 1.5 when None -- the bin of a move's
+    FIRST point decides which turbines are tested.  transits: int64 device tensor (nturb, 2), ADDED to when given.
+    Returns dict(hits, tracks_per_turbine int64 (nturb), turbines_per_track int32 (ntracks), transits int64 (nturb, 2):
+    [with the wind, against the wind]), device tensors."""
+    who = 'rotor_transits'
+    rows, cols = int(gridshape[0]), int(gridshape[1])
+    xy = xy_cells if is_tensor(xy_cells) else np.asarray(xy_cells, dtype=np.float64).reshape(-1, 2)
+    xy = to_dev(xy, torch.float64).reshape(-1, 2)
+    nturb = int(xy.shape[0])
+    if not 1 <= nturb <= MAX_TURBINES:
+        raise ValueError(f'{who}: {nturb} turbines, expected 1 to {MAX_TURBINES}')
+    mm_per_cell = 1000. * float(resolution)
+    if not (mm_per_cell > 0. and np.isfinite(mm_per_cell)):
+        raise ValueError(f'{who}: resolution = {resolution!r}, expected metres > 0')
+    reach_dev = to_dev(reach if is_tensor(reach) else np.asarray(reach, dtype=np.float64), torch.float64).reshape(-1)
+    hub_dev = to_dev(hub if is_tensor(hub) else np.asarray(hub, dtype=np.int32), torch.int32).reshape(-1)
+    axis_dev = to_dev(axis if is_tensor(axis) else np.asarray(axis, dtype=np.float64), torch.float64).reshape(-1, 2)
+    if int(axis_dev.shape[0]) == 1 and nturb > 1:
+        axis_dev = axis_dev.expand(nturb, 2)
+    axis_dev = axis_dev.contiguous()
+    if int(reach_dev.numel()) != nturb or int(hub_dev.numel()) != nturb or tuple(axis_dev.shape) != (nturb, 2):
+        raise ValueError(f'{who}: reach has {reach_dev.numel()} entries, hub {hub_dev.numel()} and axis shape '
+                         f'{tuple(axis_dev.shape)} for {nturb} turbines, expected ({nturb},), ({nturb},) and ({nturb}, 2)')
+    off = to_dev(offsets, torch.int64).reshape(-1)
+    ntracks = int(off.numel()) - 1
+    if ntracks < 0:
+        raise ValueError(f'{who}: offsets needs at least one entry')
+    pts = to_dev(traj, torch.int16).reshape(-1, 2)
+    heights = to_dev(alt, torch.int32).reshape(-1)
+    if int(heights.numel()) != int(pts.shape[0]):
+        raise ValueError(f'{who}: alt has {heights.numel()} entries for {pts.shape[0]} points (it is indexed like traj)')
+    if not is_tensor(cellinfo) or cellinfo.dtype != torch.int32 or tuple(cellinfo.shape) != (rows, cols, 2) or \
+            not cellinfo.is_contiguous() or not cellinfo.is_cuda:
+        raise ValueError(f'{who}: cellinfo must be a contiguous int32 device tensor ({rows}, {cols}, 2) (altitude_cellinfo)')
+    words = (nturb + 31) // 32
+    dev = device()
+    if hits is None:
+        hits = torch.zeros((ntracks, words), dtype=torch.int32, device=dev)
+    if transits is None:
+        transits = torch.zeros((nturb, 2), dtype=torch.int64, device=dev)
+    if hits.dtype != torch.int32 or tuple(hits.shape) != (ntracks, words) or not hits.is_contiguous() or not hits.is_cuda:
+        raise ValueError(f'{who}: hits must be a contiguous int32 device tensor ({ntracks}, {words})')
+    if not is_tensor(transits) or transits.dtype != torch.int64 or tuple(transits.shape) != (nturb, 2) or \
+            not transits.is_contiguous() or not transits.is_cuda:
+        raise ValueError(f'{who}: transits must be a contiguous int64 device tensor ({nturb}, 2)')
+    nbins = -(-rows // BIN) * -(-cols // BIN)
+    if bins is None:
+        bins = build_bins(xy.cpu().numpy(), reach_dev.cpu().numpy() + TRANSIT_CULL_MARGIN, gridshape)
+    if not is_tensor(bins[0]):
+        _check_bins(bins[0], bins[1], nbins, nturb)
+    bin_start, bin_items = to_dev(bins[0], torch.int32), to_dev(bins[1], torch.int32)
+    if int(bin_start.numel()) != nbins + 1:
+        raise ValueError(f'bins: bin_start has {bin_start.numel()} entries, expected {nbins + 1} for this raster')
+    if ntracks and pts.numel() and bin_items.numel():
+        # (otherwise nothing to read, or no disk reaches the raster: empty tensors have no address to hand over)
+        nat.check(nat.lib().ssrs_rotor_transits(
+            nat.ptr(pts), nat.ptr(off), ntracks, nat.ptr(heights), nat.ptr(cellinfo), rows, cols, nat.ptr(xy),
+            nat.ptr(reach_dev), nat.ptr(hub_dev), nat.ptr(axis_dev), mm_per_cell, nturb, nat.ptr(bin_start),
+            nat.ptr(bin_items), nat.ptr(hits), nat.ptr(transits), stream_ptr()))
+    per_turbine, per_track = encounter_counts(hits, nturb)
+    return dict(hits=hits, tracks_per_turbine=per_turbine, turbines_per_track=per_track, transits=transits)
