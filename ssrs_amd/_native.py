@@ -131,11 +131,17 @@ TRANSIT_PROTOTYPES = {
     'ssrs_rotor_transits': 'i:ppqppiippppdippppp',
 }
 ROTOR_TRANSIT_LDS_TURBINES = 7680
+# The export of include/ssrs_hip_collision.h (K19), a group of its own bound the same way; tests/test_collision_host.py checks
+# it against that header.
+COLLISION_PROTOTYPES = {
+    'ssrs_rotor_collision_risk': 'i:ppqppiippppdippppppippp',
+}
+COLLISION_RINGS, ROTOR_COLLISION_LDS_TURBINES = 256, 2560
 
 
 def argtypes(name):
     """The ctypes argtypes of export `name`, from its line of PROTOTYPES."""
-    return [_KINDS[k] for k in {**PROTOTYPES, **PASSAGE_PROTOTYPES, **TRANSIT_PROTOTYPES}[name].partition(':')[2]]
+    return [_KINDS[k] for k in {**PROTOTYPES, **PASSAGE_PROTOTYPES, **TRANSIT_PROTOTYPES, **COLLISION_PROTOTYPES}[name].partition(':')[2]]
 
 
 # read by the host tests that bind a CPU build of one kernel file by the library's own prototypes
@@ -145,6 +151,7 @@ OCCUPANCY_ARGTYPES, ALLEN_FIELD_ARGTYPES, ALTITUDE_CELLINFO_ARGTYPES, ALTITUDE_A
         'ssrs_flight_windinfo', 'ssrs_track_time', 'ssrs_rotor_encounters', 'ssrs_rotor_encounters_timed'))
 PASSAGE_ARGTYPES = argtypes('ssrs_track_passage')
 ROTOR_TRANSITS_ARGTYPES = argtypes('ssrs_rotor_transits')
+ROTOR_COLLISION_RISK_ARGTYPES = argtypes('ssrs_rotor_collision_risk')
 
 
 class SsrsTrackParams(C.Structure):
@@ -209,7 +216,8 @@ def lib():
                 f'{LIB_PATH} is missing: build it with `python ssrs_amd/csrc/build.py` '
                 '(hipcc, gfx950). ssrs_amd has no CPU fallback.')
         L = C.CDLL(LIB_PATH)
-        for name, proto in list(PROTOTYPES.items()) + list(PASSAGE_PROTOTYPES.items()) + list(TRANSIT_PROTOTYPES.items()):
+        for name, proto in list(PROTOTYPES.items()) + list(PASSAGE_PROTOTYPES.items()) + list(TRANSIT_PROTOTYPES.items()) + \
+                list(COLLISION_PROTOTYPES.items()):
             fn = getattr(L, name)
             fn.restype = _KINDS[proto[0]]
             fn.argtypes = argtypes(name)

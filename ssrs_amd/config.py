@@ -35,7 +35,9 @@ _SECTIONS = (
     ('MI355X build', ('save_tracks', 'stepper_path', 'steps_per_launch', 'max_tracks_file_gb', 'track_occupancy',
                       'flight_height', 'flight_height_start', 'flight_height_floor', 'flight_height_ceiling',
                       'flight_airspeed', 'flight_sink_rate', 'rotor_zone', 'rotor_geometry', 'rotor_clearance',
-                      'flight_time', 'flight_min_groundspeed', 'rotor_exposure_time', 'track_passage_radius', 'rotor_transits', 'rotor_yaw', 'hist_safe_tracks', 'thermal_model', 'thermal_allen_zi', 'thermal_allen_wstar', 'thermal_allen_sink',
+                      'flight_time', 'flight_min_groundspeed', 'rotor_exposure_time', 'track_passage_radius', 'rotor_transits', 'rotor_yaw',
+                      'collision_risk', 'bird_length', 'bird_wingspan', 'bird_flight', 'collision_avoidance', 'collision_model_3d',
+                      'rotor_blades', 'rotor_rpm', 'rotor_max_chord', 'rotor_pitch', 'rotor_chord_profile', 'hist_safe_tracks', 'thermal_model', 'thermal_allen_zi', 'thermal_allen_wstar', 'thermal_allen_sink',
                       'turbine_encounter_radius')),
 )
 
@@ -166,6 +168,31 @@ class Config:
     rotor_yaw: float = -1.              # degrees clockwise from north the rotors face, for all turbines and cases; < 0: every
     #                                     rotor faces the case's wind at the cell it stands on.  The two fields stand here, behind
     #                                     track_passage_radius, because tests pin most other slots
+    collision_risk: bool = False        # True (needs what rotor_transits needs: flight_height=True, rotor_geometry='turbine' and
+    #                                     turbines with t_hh and t_rd; rotor_transits itself is not needed): simulate_tracks also
+    #                                     weights every transit with Band's (2012) single-transit collision probability at the
+    #                                     place in the disk it goes through and sums them exactly, per turbine, direction and
+    #                                     track, on the device in the transits' own pass (limit 18: the formula
+    #                                     and the chord profile are RECALLED, not verified):
+    #                                     <id>_turbine_collision_risk.npy, <id>_track_collision_risk.npy,
+    #                                     Simulator.compute_turbine_collision_risk().  The bird and rotor numbers below are
+    #                                     PLACEHOLDERS, like rotor_zone: set them for the species and the fleet at hand.  The
+    #                                     eleven fields stand here, behind rotor_yaw, because tests pin most other slots
+    bird_length: float = 0.85           # metres, bill to tail
+    bird_wingspan: float = 2.1          # metres
+    bird_flight: str = 'gliding'        # gliding | flapping (Band's F = 2 / pi or 1)
+    collision_avoidance: float = 0.     # in [0, 1]: the share of collisions avoided; a scalar factor applied on the host only
+    #                                     (compute_turbine_collision_risk), the files hold the raw sums
+    collision_model_3d: bool = True     # Band's K: True = the 3-D model (chord and pitch count), False = the 1-D model
+    rotor_blades: int = 3               # for turbines without a column t_blades
+    rotor_rpm: float = 12.              # revolutions per minute, for turbines without a column t_rpm
+    rotor_max_chord: float = 4.         # metres, the blade's greatest chord, for turbines without a column t_chord
+    rotor_pitch: float = 15.            # degrees, the blade's pitch, for turbines without a column t_pitch
+    rotor_chord_profile: Tuple = (0.73, 0.79, 0.88, 0.96, 1.00, 0.98, 0.92, 0.85, 0.80, 0.75, 0.70, 0.64, 0.58, 0.52, 0.47,
+                                  0.41, 0.37, 0.30, 0.24, 0.00)   # chord / rotor_max_chord at r / R = 0.05, 0.10, ..., 1.00,
+    #                                     linear between the nodes and constant below 0.05: Band's generic blade, recalled from
+    #                                     the published spreadsheet and NOT verified against it: correct it here, no rebuild
+    #                                     is needed
     thermal_allen_zi: float = 0.        # thermal_model = 'allen': boundary-layer height zi in metres.  0 (snapshot / seasonal
     #                                     only) = the mean of the case's own blheight layer, clipped below at 100 m
     thermal_allen_wstar: float = 0.     # thermal_model = 'allen': convective velocity scale w* in m/s.  0 (snapshot / seasonal

@@ -26,7 +26,7 @@ def hipcc():
 def build(force=False, verbose=False):
     srcs = [os.path.join(HERE, s) for s in SOURCES if os.path.exists(os.path.join(HERE, s))]
     headers = [os.path.join(HERE, h) for h in ('amg.h', 'common.h', 'gauss.h', 'georef.h', 'interp.h', 'raster_math.h', 'track_plan.h', 'track_policy.h')] + \
-              [os.path.join(os.path.dirname(PKG), 'include', h) for h in ('ssrs_hip.h', 'ssrs_hip_passage.h', 'ssrs_hip_transits.h')]
+              [os.path.join(os.path.dirname(PKG), 'include', h) for h in ('ssrs_hip.h', 'ssrs_hip_passage.h', 'ssrs_hip_transits.h', 'ssrs_hip_collision.h')]
     if not force and os.path.exists(LIB) and os.path.getmtime(LIB) >= _newest(srcs + headers):
         return LIB
     objs = []

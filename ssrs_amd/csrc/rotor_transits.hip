@@ -1,4 +1,4 @@
-// K18 -- rotor transits for gfx950 (MI355X).
+// K18 -- rotor transits, and K19 -- collision risk, for gfx950 (MI355X).
 //
 // How many simulated flights went THROUGH each turbine's rotor disk, and which way: the disk is a circle of radius reach_t
 // around the hub in the plane whose normal is the turbine's axis (the upwind unit step the host hands over), and a transit
@@ -24,11 +24,18 @@
 // No lane talks to another lane (no shuffles, ballots or DPP); the block's lanes meet at two __syncthreads() around the
 // walk.  tests/hip_host_stub runs the file on the CPU as it stands.  Integer adds and ORs: the result does not depend on
 // the launch order.
+//
+// K19 (ssrs_rotor_collision_risk, include/ssrs_hip_collision.h) is the same walk with one more compile-time switch, kRisk:
+// the test keeps the ratio lhs / rhs it compares and turns it into one of 256 equal-area rings; the transit reads its
+// probability q32 from the host's table in global memory (once per transit, and transits are rare); the lane's pending
+// pair carries the q32 sum beside the count and hands it to a uint64 sum beside the uint32 counter in LDS; and one more
+// pending (track, q32 sum) goes to `track_risk` with one 64-bit global add when the lane's track changes and at its end.
+// The instantiations without kRisk are K18's as they were.
 #include <climits>
 #include <cmath>
 
 #include "common.h"
-#include "../../include/ssrs_hip_transits.h"
+#include "../../include/ssrs_hip_collision.h"
 
 namespace ssrs {
 
@@ -39,6 +46,7 @@ constexpr int kTrnBlocks = 256 * 6;           // K8's cap: six blocks per CU
 constexpr int kTrnMaskWords = 8192;           // 32 KB of LDS: rasters of up to 262 144 bins keep the mask there
 constexpr int kTrnLdsWords = 15 * 1024;       // mask and counters (two uint32 a turbine) together, 60 KB
 static_assert(kTrnLdsWords / 2 == SSRS_ROTOR_TRANSIT_LDS_TURBINES, "the header's LDS rule");
+static_assert(kTrnLdsWords / 6 == SSRS_ROTOR_COLLISION_LDS_TURBINES, "K19's LDS rule: two uint32 and two uint64 a turbine");
 static_assert(SSRS_TURBINE_BIN == 32, "a point's bin is (r >> 5, c >> 5)");
 
 // a load that is served by L2, where the atomics land (K8's load_l2)
@@ -64,11 +72,21 @@ struct TrnArgs {
     unsigned long long *transits;  // (nturb, 2)
     int cnt_off;                   // the block's counters: s_lds[cnt_off + 2 * turbine + direction]
     int cnt_lds;                   // turbines [0, cnt_lds) have them; the others' hand-overs go to `transits`
+    // ---- K19 only
+    const int32_t *cls;            // (nturb): the turbine's row of `table`; outside [0, nclass): no risk
+    const uint32_t *table;         // (nclass, 2, SSRS_COLLISION_RINGS) probabilities in units of 2^-32
+    int nclass;
+    unsigned long long *risk;      // (nturb, 2)
+    unsigned long long *track_risk;  // (ntracks) or NULL
+    int sum_off;                   // the block's uint64 sums start at word s_lds[sum_off] (even), indexed like the counters
 };
 
 // The header's test of one testable move (r0, c0, z0) -> (r1, c1, z1) against turbine tb: -1 for no transit, else the
-// direction.  Every operation rounds on its own; the plane test comes first.
-__device__ __forceinline__ int trn_test(const TrnArgs &a, int tb, int r0, int c0, long long z0, int r1, int c1, long long z1)
+// direction.  Every operation rounds on its own; the plane test comes first.  kRing (K19): `ring` gets the equal-area ring
+// of the crossing point, from the two numbers the test compares.
+template <bool kRing>
+__device__ __forceinline__ int trn_test(const TrnArgs &a, int tb, int r0, int c0, long long z0, int r1, int c1, long long z1,
+                                        int &ring)
 {
     const double xt = a.turb[2 * tb], yt = a.turb[2 * tb + 1];
     const double ax = a.axis[2 * tb], ay = a.axis[2 * tb + 1];
@@ -90,14 +108,24 @@ __device__ __forceinline__ int trn_test(const TrnArgs &a, int tb, int r0, int c0
     const double lhs = __dadd_rn(__dmul_rn(U, U), __dmul_rn(H, H));
     const double rhs = __dmul_rn(__dmul_rn(reach, reach), __dmul_rn(d, d));
     if (!(lhs <= rhs)) return -1;
+    if constexpr (kRing) {
+        if (rhs == 0.0) ring = 0;
+        else if (!(lhs < rhs)) ring = SSRS_COLLISION_RINGS - 1;
+        else {
+            const int k = static_cast<int>((lhs / rhs) * static_cast<double>(SSRS_COLLISION_RINGS));
+            ring = k < SSRS_COLLISION_RINGS - 1 ? k : SSRS_COLLISION_RINGS - 1;
+        }
+    }
     return s0 < 0.0 ? 1 : 0;
 }
 
 // The walk of one lane over its wave's spans (no barrier inside: a wave without spans returns at once).
-// kVec: 16-byte loads (traj and alt are 16-byte aligned).  kMask: the occupied-bin mask is in LDS.
-template <bool kVec, bool kMask>
-__device__ __forceinline__ void trn_walk(const TrnArgs &a, const uint32_t *s_mask, uint32_t *s_cnt, const long long a0,
-                                         const long long nspans, const long long per_wave)
+// kVec: 16-byte loads (traj and alt are 16-byte aligned).  kMask: the occupied-bin mask is in LDS.  kRisk: K19, with the
+// block's uint64 sums in s_sum.
+template <bool kVec, bool kMask, bool kRisk>
+__device__ __forceinline__ void trn_walk(const TrnArgs &a, const uint32_t *s_mask, uint32_t *s_cnt,
+                                         unsigned long long *s_sum, const long long a0, const long long nspans,
+                                         const long long per_wave)
 {
     const int lane = threadIdx.x & 63, wave = static_cast<int>(threadIdx.x) >> 6;
     const long long p0 = a.p0, p1 = a.p1;
@@ -156,10 +184,20 @@ __device__ __forceinline__ void trn_walk(const TrnArgs &a, const uint32_t *s_mas
     // the transits this lane has not handed on yet: pend_cnt of key pend_key = 2 * turbine + direction
     int pend_key = 0;
     uint32_t pend_cnt = 0;
+    // kRisk: their q32 sum (below 2^32 a transit, and a lane walks fewer than 2^32 moves), and the q32 sum of track
+    // pend_trk that has not gone to track_risk yet
+    unsigned long long pend_sum = 0, pend_trk_sum = 0;
+    long long pend_trk = 0;
     auto hand_over = [&]() {
-        if ((pend_key >> 1) < a.cnt_lds) atomicAdd(&s_cnt[pend_key], pend_cnt);
-        else atomicAdd(a.transits + pend_key, static_cast<unsigned long long>(pend_cnt));
+        if ((pend_key >> 1) < a.cnt_lds) {
+            atomicAdd(&s_cnt[pend_key], pend_cnt);
+            if constexpr (kRisk) if (pend_sum != 0) atomicAdd(&s_sum[pend_key], pend_sum);
+        } else {
+            atomicAdd(a.transits + pend_key, static_cast<unsigned long long>(pend_cnt));
+            if constexpr (kRisk) if (pend_sum != 0) atomicAdd(a.risk + pend_key, pend_sum);
+        }
         pend_cnt = 0;
+        pend_sum = 0;
     };
 
     auto span = [&](const long long u, const Fetched cur) {
@@ -199,13 +237,30 @@ __device__ __forceinline__ void trn_walk(const TrnArgs &a, const uint32_t *s_mas
             for (int k = k0; k < k1; ++k) {
                 const int tb = a.bin_items[k];
                 if (static_cast<unsigned>(tb) >= static_cast<unsigned>(a.nturb)) continue;
-                const int dir = trn_test(a, tb, r, c, z0, r1, c1, z1);
+                int ring = 0;
+                const int dir = trn_test<kRisk>(a, tb, r, c, z0, r1, c1, z1, ring);
                 if (dir < 0) continue;
                 // ---- one more transit of tb in direction dir
                 const int key = 2 * tb + dir;
                 if (key != pend_key && pend_cnt != 0) hand_over();
                 pend_key = key;
                 ++pend_cnt;
+                if constexpr (kRisk) {
+                    // ---- its probability, from the class's row of the table
+                    const int cl = a.cls[tb];
+                    if (static_cast<unsigned>(cl) < static_cast<unsigned>(a.nclass)) {
+                        const unsigned long long q32 = a.table[(cl * 2 + dir) * SSRS_COLLISION_RINGS + ring];
+                        pend_sum += q32;
+                        if (a.track_risk) {
+                            if (t != pend_trk && pend_trk_sum != 0) {
+                                atomicAdd(a.track_risk + pend_trk, pend_trk_sum);
+                                pend_trk_sum = 0;
+                            }
+                            pend_trk = t;
+                            pend_trk_sum += q32;
+                        }
+                    }
+                }
                 // ---- hits: bit tb of the track's row
                 const long long word = t * a.words + (tb >> 5);
                 const uint32_t bit = 1u << (tb & 31);
@@ -235,12 +290,14 @@ __device__ __forceinline__ void trn_walk(const TrnArgs &a, const uint32_t *s_mas
     }
     for (; u < u1; ++u) span(u, fetch_edge(u));
     if (pend_cnt != 0) hand_over();
+    if constexpr (kRisk) if (pend_trk_sum != 0) atomicAdd(a.track_risk + pend_trk, pend_trk_sum);
 }
 
-template <bool kVec, bool kMask>
+template <bool kVec, bool kMask, bool kRisk>
 __global__ __launch_bounds__(kBlock) void k_rotor_transits(const TrnArgs a)
 {
-    extern __shared__ uint32_t s_trn_lds[];      // the mask (kMask), then two counters a turbine below cnt_lds
+    // the mask (kMask), then two counters a turbine below cnt_lds, then (kRisk) two uint64 sums a turbine
+    extern __shared__ uint32_t s_trn_lds[];
 
     // spans are cut at multiples of four points of the BUFFER, so that a lane's four points are one aligned load
     const long long a0 = a.p0 & ~3LL;
@@ -266,14 +323,20 @@ __global__ __launch_bounds__(kBlock) void k_rotor_transits(const TrnArgs a)
     // the block's counters, uint32: a block walks far fewer than 2^32 moves
     uint32_t *const s_cnt = s_trn_lds + a.cnt_off;
     for (int k = threadIdx.x; k < 2 * a.cnt_lds; k += kBlock) s_cnt[k] = 0;
+    unsigned long long *const s_sum = kRisk ? reinterpret_cast<unsigned long long *>(s_trn_lds + a.sum_off) : nullptr;
+    if constexpr (kRisk)
+        for (int k = threadIdx.x; k < 2 * a.cnt_lds; k += kBlock) s_sum[k] = 0;
     __syncthreads();
 
-    trn_walk<kVec, kMask>(a, s_trn_lds, s_cnt, a0, nspans, per_wave);
+    trn_walk<kVec, kMask, kRisk>(a, s_trn_lds, s_cnt, s_sum, a0, nspans, per_wave);
 
     // every wave of the block arrives here: one 64-bit add per (turbine, direction) the block met
     __syncthreads();
     for (int k = threadIdx.x; k < 2 * a.cnt_lds; k += kBlock)
         if (s_cnt[k] != 0) atomicAdd(a.transits + k, static_cast<unsigned long long>(s_cnt[k]));
+    if constexpr (kRisk)
+        for (int k = threadIdx.x; k < 2 * a.cnt_lds; k += kBlock)
+            if (s_sum[k] != 0) atomicAdd(a.risk + k, s_sum[k]);
 }
 
 // blocks of a launch over the points [p0, p1): enough for kTrnMinSpans spans a wave, K8's cap at most
@@ -289,13 +352,14 @@ inline unsigned trn_grid(long long p0, long long p1)
 
 using namespace ssrs;
 
-extern "C" int ssrs_rotor_transits(const int16_t *traj, const int64_t *traj_offsets, int64_t ntracks, const int32_t *alt,
-                                   const int32_t *cellinfo, int rows, int cols, const double *turbines, const double *reach,
-                                   const int32_t *hub, const double *axis, double mm_per_cell, int nturb,
-                                   const int32_t *bin_start, const int32_t *bin_items, uint32_t *hits, uint64_t *transits,
-                                   void *stream)
+// Both exports: the checks, the chunk's ends, the LDS rule and the launch.  kRisk: K19, with its five arguments.
+template <bool kRisk>
+static int trn_call(const char *who, const int16_t *traj, const int64_t *traj_offsets, int64_t ntracks, const int32_t *alt,
+                    const int32_t *cellinfo, int rows, int cols, const double *turbines, const double *reach,
+                    const int32_t *hub, const double *axis, double mm_per_cell, int nturb, const int32_t *bin_start,
+                    const int32_t *bin_items, uint32_t *hits, uint64_t *transits, const int32_t *cls, const uint32_t *table,
+                    int nclass, uint64_t *risk, uint64_t *track_risk, void *stream)
 {
-    const char *who = "ssrs_rotor_transits";
     SSRS_REQUIRE(traj && traj_offsets && alt && cellinfo && turbines && reach && bin_start && bin_items && hits,
                  "%s: NULL pointer", who);
     SSRS_REQUIRE(hub && axis && transits, "%s: NULL pointer (hub, axis and transits are required)", who);
@@ -311,6 +375,14 @@ extern "C" int ssrs_rotor_transits(const int16_t *traj, const int64_t *traj_offs
                  "%s: transits and axis must be 8-byte aligned", who);
     SSRS_REQUIRE((reinterpret_cast<uintptr_t>(hub) & 3u) == 0, "%s: hub must be 4-byte aligned", who);
     SSRS_REQUIRE(std::isfinite(mm_per_cell) && mm_per_cell > 0.0, "%s: mm_per_cell = %g (finite and > 0)", who, mm_per_cell);
+    if (kRisk) {
+        SSRS_REQUIRE(cls && table && risk, "%s: NULL pointer (cls, table and risk are required)", who);
+        SSRS_REQUIRE(nclass >= 1, "%s: nclass = %d (at least one class)", who, nclass);
+        SSRS_REQUIRE((reinterpret_cast<uintptr_t>(cls) & 3u) == 0 && (reinterpret_cast<uintptr_t>(table) & 3u) == 0,
+                     "%s: cls and table must be 4-byte aligned", who);
+        SSRS_REQUIRE((reinterpret_cast<uintptr_t>(risk) & 7u) == 0 && (reinterpret_cast<uintptr_t>(track_risk) & 7u) == 0,
+                     "%s: risk and track_risk must be 8-byte aligned", who);
+    }
     if (ntracks == 0) return SSRS_OK;
     hipStream_t st = as_stream(stream);
 
@@ -346,19 +418,52 @@ extern "C" int ssrs_rotor_transits(const int16_t *traj, const int64_t *traj_offs
     a.bin_items = bin_items;
     a.hits = hits;
     a.transits = reinterpret_cast<unsigned long long *>(transits);
-    // the header's LDS rule: the mask stays while it and every turbine's two counters fit the 60 KB; without it the
-    // counters of the first SSRS_ROTOR_TRANSIT_LDS_TURBINES turbines do
+    a.cls = cls;
+    a.table = table;
+    a.nclass = nclass;
+    a.risk = reinterpret_cast<unsigned long long *>(risk);
+    a.track_risk = reinterpret_cast<unsigned long long *>(track_risk);
+    // the headers' LDS rule: the mask stays while it and every turbine's counters fit the 60 KB; without it the counters of
+    // the first SSRS_ROTOR_TRANSIT_LDS_TURBINES (K19: SSRS_ROTOR_COLLISION_LDS_TURBINES) turbines do.  A turbine has two
+    // uint32 counters and, in K19, two uint64 sums behind all counters; K19 pads the mask to an even number of words
+    constexpr int per_turbine = kRisk ? 6 : 2;
+    constexpr int lds_turbines = kRisk ? SSRS_ROTOR_COLLISION_LDS_TURBINES : SSRS_ROTOR_TRANSIT_LDS_TURBINES;
     const int mask_words = (a.nbins + 31) / 32;
-    const bool mask = mask_words <= kTrnMaskWords && mask_words + 2 * nturb <= kTrnLdsWords;
-    a.cnt_off = mask ? mask_words : 0;
-    a.cnt_lds = mask || nturb < SSRS_ROTOR_TRANSIT_LDS_TURBINES ? nturb : SSRS_ROTOR_TRANSIT_LDS_TURBINES;
-    const size_t lds = static_cast<size_t>(a.cnt_off + 2 * a.cnt_lds) * 4;
+    const int mask_room = kRisk ? (mask_words + 1) & ~1 : mask_words;
+    const bool mask = mask_words <= kTrnMaskWords && mask_room + per_turbine * nturb <= kTrnLdsWords;
+    a.cnt_off = mask ? mask_room : 0;
+    a.cnt_lds = mask || nturb < lds_turbines ? nturb : lds_turbines;
+    a.sum_off = a.cnt_off + 2 * a.cnt_lds;
+    const size_t lds = static_cast<size_t>(a.cnt_off + per_turbine * a.cnt_lds) * 4;
     const bool vec = ((reinterpret_cast<uintptr_t>(traj) | reinterpret_cast<uintptr_t>(alt)) & 15u) == 0;
     const dim3 grid(trn_grid(a.p0, a.p1)), block(kBlock);
-    if (vec && mask) hipLaunchKernelGGL((k_rotor_transits<true, true>), grid, block, lds, st, a);
-    else if (vec) hipLaunchKernelGGL((k_rotor_transits<true, false>), grid, block, lds, st, a);
-    else if (mask) hipLaunchKernelGGL((k_rotor_transits<false, true>), grid, block, lds, st, a);
-    else hipLaunchKernelGGL((k_rotor_transits<false, false>), grid, block, lds, st, a);
+    if (vec && mask) hipLaunchKernelGGL((k_rotor_transits<true, true, kRisk>), grid, block, lds, st, a);
+    else if (vec) hipLaunchKernelGGL((k_rotor_transits<true, false, kRisk>), grid, block, lds, st, a);
+    else if (mask) hipLaunchKernelGGL((k_rotor_transits<false, true, kRisk>), grid, block, lds, st, a);
+    else hipLaunchKernelGGL((k_rotor_transits<false, false, kRisk>), grid, block, lds, st, a);
     SSRS_HIP_CHECK(hipGetLastError());
     return SSRS_OK;
+}
+
+extern "C" int ssrs_rotor_transits(const int16_t *traj, const int64_t *traj_offsets, int64_t ntracks, const int32_t *alt,
+                                   const int32_t *cellinfo, int rows, int cols, const double *turbines, const double *reach,
+                                   const int32_t *hub, const double *axis, double mm_per_cell, int nturb,
+                                   const int32_t *bin_start, const int32_t *bin_items, uint32_t *hits, uint64_t *transits,
+                                   void *stream)
+{
+    return trn_call<false>("ssrs_rotor_transits", traj, traj_offsets, ntracks, alt, cellinfo, rows, cols, turbines, reach, hub,
+                           axis, mm_per_cell, nturb, bin_start, bin_items, hits, transits, nullptr, nullptr, 0, nullptr,
+                           nullptr, stream);
+}
+
+extern "C" int ssrs_rotor_collision_risk(const int16_t *traj, const int64_t *traj_offsets, int64_t ntracks,
+                                         const int32_t *alt, const int32_t *cellinfo, int rows, int cols,
+                                         const double *turbines, const double *reach, const int32_t *hub, const double *axis,
+                                         double mm_per_cell, int nturb, const int32_t *bin_start, const int32_t *bin_items,
+                                         uint32_t *hits, uint64_t *transits, const int32_t *cls, const uint32_t *table,
+                                         int nclass, uint64_t *risk, uint64_t *track_risk, void *stream)
+{
+    return trn_call<true>("ssrs_rotor_collision_risk", traj, traj_offsets, ntracks, alt, cellinfo, rows, cols, turbines, reach,
+                          hub, axis, mm_per_cell, nturb, bin_start, bin_items, hits, transits, cls, table, nclass, risk,
+                          track_risk, stream);
 }

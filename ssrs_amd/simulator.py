@@ -87,6 +87,7 @@ class Simulator(Config):
             self._time_params()
         self._check_rotor_exposure_time()
         self._check_rotor_transits(turbines)
+        self._check_collision_risk(turbines)
         self._check_rotor_geometry(turbines)
         print(f'\n---- SSRS in {self.sim_mode} mode')
         print(f'Run name: {self.run_name}')
@@ -149,6 +150,9 @@ class Simulator(Config):
         #                                     rotor_exposure_time also time_per_turbine int64, microseconds)
         self.turbine_rotor_transits = {}  # rotor_transits: (case_id, real_id) -> int64 (nturb, 3): [tracks, transits with the
         #                                     wind, against the wind]
+        self.turbine_collision_risk = {}  # collision_risk: (case_id, real_id) -> int64 (nturb, 2): the summed collision
+        #                                     probabilities of the transits in units of 2^-32 [with the wind, against the wind]
+        self.track_collision_risk = {}    # (case_id, real_id) -> int64 (this rank's tracks,): the same per track
         self.wtk_layers = {
             'wspeed': f'windspeed_{str(int(self.wtk_orographic_height))}m',
             'wdirn': f'winddirection_{str(int(self.wtk_orographic_height))}m',
@@ -273,6 +277,44 @@ class Simulator(Config):
             if not ok:
                 raise ValueError(f'rotor_transits = True needs {field}: {why}')
 
+    def _check_collision_risk(self, turbines):
+        """collision_risk weights K18's transits with Band's probability: it needs what rotor_transits needs (not
+        rotor_transits itself), and a bird and a rotor the model can be evaluated for."""
+        if not self.collision_risk:
+            return
+        yaw = float(self.rotor_yaw)
+        if yaw != yaw or yaw in (float('inf'), float('-inf')):
+            raise ValueError(f'rotor_yaw = {self.rotor_yaw!r}: expected degrees clockwise from north, or < 0 for the wind')
+        names = turbines_mod._column_names(turbines) if turbines is not None else []
+        for ok, field, why in ((self.flight_height, 'flight_height=True', 'the disks are tested against the heights along '
+                                'the tracks'),
+                               (self._rotor_per_turbine(), "rotor_geometry='turbine'", "the disk is every turbine's own, "
+                                'around its hub'),
+                               (turbines is not None, 'turbines', 'none were given (Simulator(..., turbines=...))'),
+                               ('t_hh' in names, 'turbines with t_hh', 'the hub height in metres, the centre of the disk'),
+                               ('t_rd' in names, 'turbines with t_rd', 'the rotor diameter in metres, twice the length of '
+                                'a blade')):
+            if not ok:
+                raise ValueError(f'collision_risk = True needs {field}: {why}')
+        for name in ('bird_length', 'bird_wingspan'):
+            if not 0. < float(getattr(self, name)) < float('inf'):
+                raise ValueError(f'{name} = {getattr(self, name)!r}: expected metres > 0 (collision_risk)')
+        if str(self.bird_flight).lower() not in ('gliding', 'flapping'):
+            raise ValueError(f"bird_flight = {self.bird_flight!r}: expected 'gliding' or 'flapping' (collision_risk)")
+        if not 0. <= float(self.collision_avoidance) <= 1.:
+            raise ValueError(f'collision_avoidance = {self.collision_avoidance!r}: expected a share in [0, 1] (collision_risk)')
+        for name, what in (('rotor_blades', 'a number of blades'), ('rotor_rpm', 'revolutions per minute'),
+                           ('rotor_max_chord', 'metres')):
+            if not 0. <= float(getattr(self, name)) < float('inf'):
+                raise ValueError(f'{name} = {getattr(self, name)!r}: expected {what} >= 0 (collision_risk)')
+        pitch = float(self.rotor_pitch)
+        if pitch != pitch or pitch in (float('inf'), float('-inf')):
+            raise ValueError(f'rotor_pitch = {self.rotor_pitch!r}: expected degrees (collision_risk)')
+        profile = np.asarray(self.rotor_chord_profile, dtype=np.float64)
+        if profile.shape != turbines_mod.BAND_CHORD_NODES.shape or not (profile >= 0.).all():
+            raise ValueError(f'rotor_chord_profile: expected {turbines_mod.BAND_CHORD_NODES.size} values >= 0, the chord over '
+                             'rotor_max_chord at r / R = 0.05, 0.10, ..., 1.00 (collision_risk)')
+
     def _check_rotor_geometry(self, turbines):
         """rotor_geometry / rotor_clearance, and what 'turbine' needs that can be told before anything is computed."""
         if str(self.rotor_geometry).lower() not in ('band', 'turbine'):
@@ -327,13 +369,21 @@ class Simulator(Config):
                 warnings.warn(f"rotor_geometry = 'turbine': {nodata} of the {len(turbines)} turbines stand on a nodata cell "
                               'of the DEM; their cylinders are empty and nothing encounters them')
             self._rotor_cylinders = (cells, reach, zband, turbines_mod.build_bins(cells, reach, self.gridsize))
-            if self.rotor_transits:
-                # the disks of K18: the cylinders' reach, the hubs, and cull lists of their own (a move is culled by its
-                # first point: reach + 1.5)
+            if self.rotor_transits or self.collision_risk:
+                # the disks of K18 / K19: the cylinders' reach, the hubs, and cull lists of their own (a move is culled by
+                # its first point: reach + 1.5)
                 _, disk_reach, hub, _ = turbines_mod.rotor_disks(turbines, dem, self.bounds, self.resolution,
                                                                  float(self.rotor_clearance))
                 self._rotor_disks = (cells, disk_reach, hub, turbines_mod.build_bins(
                     cells, disk_reach + turbines_mod.TRANSIT_CULL_MARGIN, self.gridsize))
+            if self.collision_risk:
+                # K19: the classes of the fleet and Band's probability per class, direction and ring, once per run
+                self._collision_table = turbines_mod.band_collision_table(
+                    np.asarray(turbines.columns['t_rd'], dtype=np.float64) / 2., float(self.rotor_clearance),
+                    turbines_mod.band_parameters(turbines, self.rotor_blades, self.rotor_rpm, self.rotor_max_chord,
+                                                 self.rotor_pitch),
+                    float(self.flight_airspeed), float(self.bird_length), float(self.bird_wingspan),
+                    str(self.bird_flight).lower() == 'flapping', bool(self.collision_model_3d), self.rotor_chord_profile)[:2]
         return turbines
 
     THERMAL_LAYERS = inputs.THERMAL_LAYERS      # keys of wtk_layers
@@ -862,12 +912,18 @@ class Simulator(Config):
             dem = to_dev(self._terrain['Elevation'], torch.float64)
         timed = bool(self.flight_time)
         exposure = bool(self.rotor_exposure_time)       # (the constructor saw to heights, timed and rotor)
-        transit = bool(self.rotor_transits)             # (the constructor saw to heights and rotor)
+        collision = bool(self.collision_risk)           # (the constructor saw to heights and rotor)
+        transit = bool(self.rotor_transits) or collision
         disks = None
         if transit:
             cells, reach, hub, bins = self._rotor_disks
             disks = (to_dev(cells, torch.float64), to_dev(reach, torch.float64), to_dev(hub, torch.int32),
                      tuple(to_dev(a, torch.int32) for a in bins))
+        classes = None
+        if collision:
+            # (the uint32 table travels as int32 bit patterns, like the bitmaps)
+            cls, table = self._collision_table
+            classes = (to_dev(cls, torch.int32), to_dev(np.ascontiguousarray(table).view(np.int32), torch.int32))
 
         def run(item):
             case_id, real_id, fields, seed, lift, wind, axes = item
@@ -918,9 +974,13 @@ class Simulator(Config):
                             # the disks: a fourth bitmap, and the transits of each by direction
                             fly['transit_hits'] = torch.zeros_like(fly['rotor_hits'])
                             fly['transits'] = torch.zeros((n_rotor, 2), dtype=torch.int64, device=my_starts.device)
+                        if collision:
+                            # their summed collision probabilities, by turbine and direction and by track
+                            fly['risk'] = torch.zeros((n_rotor, 2), dtype=torch.int64, device=my_starts.device)
+                            fly['track_risk'] = torch.zeros((hi - lo,), dtype=torch.int64, device=my_starts.device)
                     consumers.append(self._flight_consumer(lift, dem, fly, enc_geometry if encounters else None, rotor,
                                                            keep_masked=timed, defer_rotor=exposure,
-                                                           transit=(disks, axes) if transit else None))
+                                                           transit=(disks, axes, classes) if transit else None))
                 if timed:
                     # after the flight consumer, whose traj_band of the chunk it reads: one raster of microseconds per
                     # item (two with flight_height), accumulated over chunks and parts, and this rank's per-track rows
@@ -1071,9 +1131,10 @@ class Simulator(Config):
         built here, from its un-thresholded updraft `lift` and the DEM.  keep_masked: the chunk's traj_band stays in
         `fly['masked']` for the consumer behind this one (_time_consumer).  defer_rotor (rotor_exposure_time): the rotor
         kernel is not called here but behind K16, where the chunk's dt exists: the chunk's alt stays in `fly['alt']` and the
-        item's cellinfo in `fly['cellinfo']` for _time_consumer.  transit (rotor_transits): ((cells, reach, hub, bins) on the
-        device, the case's axes): the chunk and its alt also go through the transit kernel (K18), here in either case, into
-        `fly['transit_hits']` / `fly['transits']`."""
+        item's cellinfo in `fly['cellinfo']` for _time_consumer.  transit (rotor_transits, collision_risk): ((cells, reach, hub,
+        bins) on the device, the case's axes, (cls, table) on the device or None): the chunk and its alt also go through the
+        transit kernel (K18), here in either case, into `fly['transit_hits']` / `fly['transits']` -- or, with (cls, table),
+        through the collision-risk kernel (K19), whose one pass gives the same two and `fly['risk']` / `fly['track_risk']`."""
         kw, airspeed, sink = self._flight_params()
         cellinfo = flight.altitude_cellinfo(lift, dem, self.resolution, airspeed, sink)
         if defer_rotor:
@@ -1095,10 +1156,16 @@ class Simulator(Config):
                                               bins=rotor_bins, hits=fly['rotor_hits'][t0:t1],
                                               first_step=fly['rotor_first_step'][t0:t1], points=fly['rotor_points'])
             if transit is not None:
-                (cells, reach, hub, disk_bins), axes = transit
-                turbines_mod.rotor_transits(traj, out['alt'], off, cellinfo, cells, reach, hub, axes, self.gridsize,
-                                            self.resolution, bins=disk_bins, hits=fly['transit_hits'][t0:t1],
-                                            transits=fly['transits'])
+                (cells, reach, hub, disk_bins), axes, classes = transit
+                if classes is None:
+                    turbines_mod.rotor_transits(traj, out['alt'], off, cellinfo, cells, reach, hub, axes, self.gridsize,
+                                                self.resolution, bins=disk_bins, hits=fly['transit_hits'][t0:t1],
+                                                transits=fly['transits'])
+                else:
+                    turbines_mod.rotor_collision_risk(traj, out['alt'], off, cellinfo, cells, reach, hub, axes, *classes,
+                                                      self.gridsize, self.resolution, bins=disk_bins,
+                                                      hits=fly['transit_hits'][t0:t1], transits=fly['transits'],
+                                                      risk=fly['risk'], track_risk=fly['track_risk'][t0:t1])
             if geometry is not None:
                 xy, bins = geometry
                 turbines_mod.turbine_encounters(out['masked'], off, xy, radius_cells, self.gridsize, bins=bins,
@@ -1267,7 +1334,31 @@ class Simulator(Config):
                 np.save(os.path.join(self.mode_data_dir, f'{id_str}_turbine_rotor_encounters.npy'), both)
                 if spent is not None:
                     np.save(os.path.join(self.mode_data_dir, f'{id_str}_turbine_rotor_time.npy'), spent)
-        if 'transit_hits' in fly:
+        if 'risk' in fly:
+            # collision_risk: <id>_turbine_collision_risk.npy, int64 (nturb, 2) raw sums in units of 2^-32 [with the wind,
+            # against the wind], and <id>_track_collision_risk.npy, int64 (tracks,).  The invariants that stand in for a
+            # checksum: a transit adds less than 2^32, and the tracks' sums add up to the turbines'.  Track-sharded runs sum
+            # the per-turbine columns over the ranks like the transits (untested on more than one rank); the per-track
+            # rows stay this rank's tracks, like first_step, and the file is then rank 0's share
+            risk = fly['risk'].cpu().numpy().astype(np.int64)
+            per_track = fly['track_risk'].cpu().numpy().astype(np.int64)
+            passes = fly['transits'].cpu().numpy().astype(np.int64)
+            wrong = np.nonzero(((risk < 0) | (risk.astype(object) > passes.astype(object) * (2 ** 32 - 1)).astype(bool)).any(1))[0]
+            if wrong.size:
+                t = int(wrong[0])
+                raise RuntimeError(f'{id_str}: collision risk: turbine {t} has the sums {risk[t].tolist()} (2^-32) for '
+                                   f'{passes[t].tolist()} transits ({wrong.size} turbines like it)')
+            if int(per_track.astype(object).sum()) != int(risk.astype(object).sum()):
+                raise RuntimeError(f'{id_str}: collision risk: the tracks add up to {int(per_track.astype(object).sum())}, '
+                                   f'the turbines to {int(risk.astype(object).sum())} (2^-32)')
+            if sharded:
+                risk = np.asarray(self._allreduce_sum(risk.reshape(-1)), dtype=np.int64).reshape(-1, 2)
+            self.turbine_collision_risk[key] = risk
+            self.track_collision_risk[key] = per_track
+            if writes:
+                np.save(os.path.join(self.mode_data_dir, f'{id_str}_turbine_collision_risk.npy'), risk)
+                np.save(os.path.join(self.mode_data_dir, f'{id_str}_track_collision_risk.npy'), per_track)
+        if 'transit_hits' in fly and self.rotor_transits:
             # rotor_transits: <id>_turbine_rotor_transits.npy, int64 (nturb, 3) [tracks, with the wind, against the wind].
             # The cheap invariant that stands in for a checksum: a turbine has tracks iff it has transits.  Track-sharded
             # runs sum the three columns over the ranks like the other per-turbine counts (untested on more than one rank)
@@ -1632,6 +1723,31 @@ class Simulator(Config):
         out = np.ascontiguousarray((total[:-1] / total[-1]).reshape(nturb, 3))
         if self._rank() == 0:
             np.save(os.path.join(self.mode_data_dir, 'summary_turbine_rotor_transits.npy'), out)
+        self._barrier()
+        return out
+
+    def compute_turbine_collision_risk(self):
+        """Per turbine, the expected collisions per simulated track (collision_risk = True; DESIGN.md K19, limit 18: Band's
+        single-transit probability, recalled and not verified, summed over the transits): f64 (nturb, 3) [with the wind,
+        against the wind, in total], the mean over all (case, realisation) items of the raw sums x 2^-32 x
+        (1 - collision_avoidance) / track_count, in the order of `turbines.get_locations()`; case-sharded runs take the mean
+        over every rank's items.  Writes summary_turbine_collision_risk.npy.  ValueError when simulate_tracks computed none."""
+        if not self.turbine_collision_risk:
+            raise ValueError("no collision risk was computed: run simulate_tracks() with collision_risk=True "
+                             "(flight_height=True, rotor_geometry='turbine' and turbines with t_hh and t_rd)")
+        items = [self.turbine_collision_risk[key] for key in sorted(self.turbine_collision_risk)]
+        nturb = items[0].shape[0]
+        scale = (1. - float(self.collision_avoidance)) / float(self.track_count)
+        total = np.zeros(2 * nturb + 1, dtype=np.float64)                  # [(nturb, 2) row by row, number of items]
+        for risk in items:
+            total[:-1] += (risk.astype(np.float64) * 2. ** -32 * scale).reshape(-1)
+            total[-1] += 1.
+        if self._world() > 1 and not self._shards_tracks():
+            total = self._allreduce_sum(total)                      # the cases of the other ranks
+        two = (total[:-1] / total[-1]).reshape(nturb, 2)
+        out = np.ascontiguousarray(np.concatenate([two, two.sum(1, keepdims=True)], 1))
+        if self._rank() == 0:
+            np.save(os.path.join(self.mode_data_dir, 'summary_turbine_collision_risk.npy'), out)
         self._barrier()
         return out
 

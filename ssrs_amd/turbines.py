@@ -465,7 +465,14 @@ def rotor_transits(traj, alt, offsets, cellinfo, xy_cells, reach, hub, axis, gri
     FIRST point decides which turbines are tested.  transits: int64 device tensor (nturb, 2), ADDED to when given.
     Returns dict(hits, tracks_per_turbine int64 (nturb), turbines_per_track int32 (ntracks), transits int64 (nturb, 2):
     [with the wind, against the wind]), device tensors."""
-    who = 'rotor_transits'
+    return _transit_pass('rotor_transits', traj, alt, offsets, cellinfo, xy_cells, reach, hub, axis, gridshape, resolution, bins,
+                         hits, transits)
+
+
+def _transit_pass(who, traj, alt, offsets, cellinfo, xy_cells, reach, hub, axis, gridshape, resolution, bins, hits, transits,
+                  collision=None):
+    """rotor_transits' checks and call; with collision = (cls, table, risk, track_risk) rotor_collision_risk's, whose one
+    pass gives the transits too."""
     rows, cols = int(gridshape[0]), int(gridshape[1])
     xy = xy_cells if is_tensor(xy_cells) else np.asarray(xy_cells, dtype=np.float64).reshape(-1, 2)
     xy = to_dev(xy, torch.float64).reshape(-1, 2)
@@ -506,6 +513,27 @@ def rotor_transits(traj, alt, offsets, cellinfo, xy_cells, reach, hub, axis, gri
     if not is_tensor(transits) or transits.dtype != torch.int64 or tuple(transits.shape) != (nturb, 2) or \
             not transits.is_contiguous() or not transits.is_cuda:
         raise ValueError(f'{who}: transits must be a contiguous int64 device tensor ({nturb}, 2)')
+    if collision is not None:
+        cls, table, risk, track_risk = collision
+        cls_dev = to_dev(cls if is_tensor(cls) else np.asarray(cls, dtype=np.int32), torch.int32).reshape(-1)
+        if not is_tensor(table):
+            table = torch.from_numpy(np.ascontiguousarray(table, dtype=np.uint32).view(np.int32))
+        table_dev = to_dev(table, torch.int32)                 # (uint32 bit patterns in int32, as hits)
+        nclass = int(table_dev.shape[0]) if table_dev.dim() == 3 else 0
+        if int(cls_dev.numel()) != nturb or nclass < 1 or tuple(table_dev.shape) != (nclass, 2, COLLISION_RINGS):
+            raise ValueError(f'{who}: cls has {cls_dev.numel()} entries and table shape {tuple(table_dev.shape)} for {nturb} '
+                             f'turbines, expected ({nturb},) and (nclass >= 1, 2, {COLLISION_RINGS})')
+        table_dev = table_dev.contiguous()
+        if risk is None:
+            risk = torch.zeros((nturb, 2), dtype=torch.int64, device=dev)
+        if track_risk is None:
+            track_risk = torch.zeros((ntracks,), dtype=torch.int64, device=dev)
+        if not is_tensor(risk) or risk.dtype != torch.int64 or tuple(risk.shape) != (nturb, 2) or \
+                not risk.is_contiguous() or not risk.is_cuda:
+            raise ValueError(f'{who}: risk must be a contiguous int64 device tensor ({nturb}, 2)')
+        if not is_tensor(track_risk) or track_risk.dtype != torch.int64 or tuple(track_risk.shape) != (ntracks,) or \
+                not track_risk.is_contiguous() or not track_risk.is_cuda:
+            raise ValueError(f'{who}: track_risk must be a contiguous int64 device tensor ({ntracks},)')
     nbins = -(-rows // BIN) * -(-cols // BIN)
     if bins is None:
         bins = build_bins(xy.cpu().numpy(), reach_dev.cpu().numpy() + TRANSIT_CULL_MARGIN, gridshape)
@@ -516,9 +544,109 @@ def rotor_transits(traj, alt, offsets, cellinfo, xy_cells, reach, hub, axis, gri
         raise ValueError(f'bins: bin_start has {bin_start.numel()} entries, expected {nbins + 1} for this raster')
     if ntracks and pts.numel() and bin_items.numel():
         # (otherwise nothing to read, or no disk reaches the raster: empty tensors have no address to hand over)
-        nat.check(nat.lib().ssrs_rotor_transits(
-            nat.ptr(pts), nat.ptr(off), ntracks, nat.ptr(heights), nat.ptr(cellinfo), rows, cols, nat.ptr(xy),
-            nat.ptr(reach_dev), nat.ptr(hub_dev), nat.ptr(axis_dev), mm_per_cell, nturb, nat.ptr(bin_start),
-            nat.ptr(bin_items), nat.ptr(hits), nat.ptr(transits), stream_ptr()))
+        args = (nat.ptr(pts), nat.ptr(off), ntracks, nat.ptr(heights), nat.ptr(cellinfo), rows, cols, nat.ptr(xy),
+                nat.ptr(reach_dev), nat.ptr(hub_dev), nat.ptr(axis_dev), mm_per_cell, nturb, nat.ptr(bin_start),
+                nat.ptr(bin_items), nat.ptr(hits), nat.ptr(transits))
+        if collision is None:
+            nat.check(nat.lib().ssrs_rotor_transits(*args, stream_ptr()))
+        else:
+            nat.check(nat.lib().ssrs_rotor_collision_risk(*args, nat.ptr(cls_dev), nat.ptr(table_dev), nclass, nat.ptr(risk),
+                                                          nat.ptr(track_risk), stream_ptr()))
     per_turbine, per_track = encounter_counts(hits, nturb)
-    return dict(hits=hits, tracks_per_turbine=per_turbine, turbines_per_track=per_track, transits=transits)
+    out = dict(hits=hits, tracks_per_turbine=per_turbine, turbines_per_track=per_track, transits=transits)
+    if collision is not None:
+        out.update(risk=risk, track_risk=track_risk)
+    return out
+
+
+COLLISION_RINGS = nat.COLLISION_RINGS     # equal-area rings of the disk (include/ssrs_hip_collision.h)
+BAND_CHORD_NODES = np.arange(1, 21) * 0.05     # r / R of the chord profile's 20 values
+
+
+def band_probability(r, rotor_radius, rpm, max_chord, pitch, blades, speed, bird_length, bird_wingspan, flapping=False,
+                     model_3d=True, chord_profile=None, upwind=True):
+    """Band's (2012) probability that ONE transit of the rotor at radius r (metres, array) collides, for one rotor (scalars:
+    radius R in metres, rpm, max chord in metres, pitch in degrees, blades) and one bird (speed v through the disk in m/s,
+    length L and wingspan W in metres):
+        Omega = 2 pi rpm / 60     alpha = v / (r Omega)     beta = L / W
+        p = (b Omega / 2 pi v) (K |+- c sin(pitch) + alpha c cos(pitch)| + (L if alpha < beta else W alpha F))
+    with + for a bird flying upwind, - downwind, F = 1 flapping and 2 / pi gliding, K = 1 for the 3-D model and 0 for the 1-D
+    one, c = max_chord * the chord profile at r / R (20 values at 0.05, 0.10, ..., 1.00, linear between them, constant below
+    0.05); clipped to [0, 1]; 0 for r > R and where r, b, Omega or v is not positive.  The formula and the default profile
+    are recalled from the published model and NOT verified (DESIGN.md limit 18)."""
+    r = np.asarray(r, dtype=np.float64)
+    R, v, L, W = float(rotor_radius), float(speed), float(bird_length), float(bird_wingspan)
+    omega = 2. * np.pi * float(rpm) / 60.
+    b = float(blades)
+    if not (b > 0. and omega > 0. and v > 0. and R > 0.):
+        return np.zeros(r.shape)
+    if not (L > 0. and W > 0.):
+        raise ValueError(f'band_probability: bird_length = {bird_length!r}, bird_wingspan = {bird_wingspan!r} (metres > 0)')
+    profile = np.asarray(chord_profile, dtype=np.float64).reshape(-1)
+    if profile.shape != BAND_CHORD_NODES.shape or not (profile >= 0.).all():
+        raise ValueError(f'band_probability: the chord profile needs {BAND_CHORD_NODES.size} values >= 0 '
+                         '(r / R = 0.05, 0.10, ..., 1.00)')
+    inside = (r > 0.) & (r <= R)
+    rr = np.where(inside, r, R)                                             # (no division by zero; masked below)
+    chord = float(max_chord) * np.interp(rr / R, BAND_CHORD_NODES, profile)
+    gamma = np.deg2rad(float(pitch))
+    alpha = v / (rr * omega)
+    sign = 1. if upwind else -1.
+    swept = np.abs(sign * chord * np.sin(gamma) + alpha * chord * np.cos(gamma)) if model_3d else 0.
+    body = np.where(alpha < L / W, L, W * alpha * (1. if flapping else 2. / np.pi))
+    p = b * omega / (2. * np.pi * v) * (swept + body)
+    return np.where(inside, np.clip(p, 0., 1.), 0.)
+
+
+def band_parameters(turbines, blades, rpm, max_chord, pitch):
+    """f64 (nturb, 4) [rpm, max chord, pitch, blades]: the turbine columns `t_rpm`, `t_chord`, `t_pitch`, `t_blades` where
+    the `Turbines` carry them, the given scalars otherwise."""
+    n = len(turbines)
+    cols = [np.asarray(turbines.columns[name], dtype=np.float64) if name in turbines.columns else np.full(n, float(default))
+            for name, default in (('t_rpm', rpm), ('t_chord', max_chord), ('t_pitch', pitch), ('t_blades', blades))]
+    return np.stack(cols, 1).reshape(n, 4)
+
+
+def band_collision_table(rotor_radius, clearance, params, speed, bird_length, bird_wingspan, flapping=False, model_3d=True,
+                         chord_profile=None):
+    """The classes and the table of ssrs_rotor_collision_risk (K19): (cls int32 (nturb,), table uint32 (nclass, 2, 256),
+    classes f64 (nclass, 6)).  rotor_radius (nturb,) = t_rd / 2 in metres; clearance metres (reach = R + clearance, the disk
+    K18 tests); params (nturb, 4) of band_parameters.  A class is a distinct row [R, reach, rpm, max chord, pitch, blades],
+    numbered in order of first appearance; a turbine with a NaN in its row gets class -1 and contributes nothing.  Ring k
+    is the equal-area annulus k / 256 <= rho^2 / reach^2 < (k + 1) / 256; its entry is band_probability at the area midpoint
+    r = reach sqrt((k + 0.5) / 256), min(2^32 - 1, rint(p 2^32)); [c, 0] is with the wind (the bird flies downwind, the
+    formula's -), [c, 1] against it (+).  Without a valid turbine the table is one row of zeros."""
+    R = np.asarray(rotor_radius, dtype=np.float64).reshape(-1)
+    params = np.asarray(params, dtype=np.float64).reshape(-1, 4)
+    if params.shape[0] != R.size:
+        raise ValueError(f'band_collision_table: params has {params.shape[0]} rows for {R.size} turbines')
+    rows = np.concatenate([R[:, None], R[:, None] + float(clearance), params], 1)
+    cls = np.full(R.size, -1, dtype=np.int32)
+    classes = []
+    for t, row in enumerate(rows):
+        if np.isnan(row).any():
+            continue
+        key = tuple(row.tolist())
+        if key not in classes:
+            classes.append(key)
+        cls[t] = classes.index(key)
+    table = np.zeros((max(1, len(classes)), 2, COLLISION_RINGS), dtype=np.uint32)
+    mid = np.sqrt((np.arange(COLLISION_RINGS) + 0.5) / COLLISION_RINGS)
+    for c, (radius, reach, rpm, chord, pitch, blades) in enumerate(classes):
+        for dirn in (0, 1):
+            p = band_probability(reach * mid, radius, rpm, chord, pitch, blades, speed, bird_length, bird_wingspan, flapping,
+                                 model_3d, chord_profile, upwind=dirn == 1)
+            table[c, dirn] = np.minimum(2. ** 32 - 1., np.rint(p * 2. ** 32)).astype(np.uint32)
+    return cls, table, np.array(classes, dtype=np.float64).reshape(-1, 6)
+
+
+def rotor_collision_risk(traj, alt, offsets, cellinfo, xy_cells, reach, hub, axis, cls, table, gridshape, resolution, bins=None,
+                         hits=None, transits=None, risk=None, track_risk=None):
+    """ssrs_rotor_collision_risk on device tensors (K19): rotor_transits' pass, every transit also weighted with its class's
+    collision probability at the ring of the disk it goes through.  Every argument of rotor_transits as there (the cull
+    lists are built from reach + 1.5 when None); cls (nturb,) int32 and table uint32 (nclass, 2, 256) of
+    band_collision_table (host or device; a device table is int32 holding the uint32 bit patterns).  risk: int64 device
+    tensor (nturb, 2), track_risk: int64 (ntracks,), both ADDED to when given.  Returns rotor_transits' dict plus risk and
+    track_risk: the raw uint64 sums in units of 2^-32, [with the wind, against the wind] per turbine."""
+    return _transit_pass('rotor_collision_risk', traj, alt, offsets, cellinfo, xy_cells, reach, hub, axis, gridshape, resolution,
+                         bins, hits, transits, collision=(cls, table, risk, track_risk))
