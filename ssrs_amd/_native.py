@@ -137,11 +137,17 @@ COLLISION_PROTOTYPES = {
     'ssrs_rotor_collision_risk': 'i:ppqppiippppdippppppippp',
 }
 COLLISION_RINGS, ROTOR_COLLISION_LDS_TURBINES = 256, 2560
+# The export of include/ssrs_hip_sites.h (K20), a group of its own bound the same way; tests/test_site_host.py checks it
+# against that header.
+SITE_PROTOTYPES = {
+    'ssrs_site_collision_risk': 'i:ppqppiidipidpppp',
+}
+SITE_MAX_REACH = 62.
 
 
 def argtypes(name):
     """The ctypes argtypes of export `name`, from its line of PROTOTYPES."""
-    return [_KINDS[k] for k in {**PROTOTYPES, **PASSAGE_PROTOTYPES, **TRANSIT_PROTOTYPES, **COLLISION_PROTOTYPES}[name].partition(':')[2]]
+    return [_KINDS[k] for k in {**PROTOTYPES, **PASSAGE_PROTOTYPES, **TRANSIT_PROTOTYPES, **COLLISION_PROTOTYPES, **SITE_PROTOTYPES}[name].partition(':')[2]]
 
 
 # read by the host tests that bind a CPU build of one kernel file by the library's own prototypes
@@ -152,6 +158,7 @@ OCCUPANCY_ARGTYPES, ALLEN_FIELD_ARGTYPES, ALTITUDE_CELLINFO_ARGTYPES, ALTITUDE_A
 PASSAGE_ARGTYPES = argtypes('ssrs_track_passage')
 ROTOR_TRANSITS_ARGTYPES = argtypes('ssrs_rotor_transits')
 ROTOR_COLLISION_RISK_ARGTYPES = argtypes('ssrs_rotor_collision_risk')
+SITE_COLLISION_RISK_ARGTYPES = argtypes('ssrs_site_collision_risk')
 
 
 class SsrsTrackParams(C.Structure):
@@ -217,7 +224,7 @@ def lib():
                 '(hipcc, gfx950). ssrs_amd has no CPU fallback.')
         L = C.CDLL(LIB_PATH)
         for name, proto in list(PROTOTYPES.items()) + list(PASSAGE_PROTOTYPES.items()) + list(TRANSIT_PROTOTYPES.items()) + \
-                list(COLLISION_PROTOTYPES.items()):
+                list(COLLISION_PROTOTYPES.items()) + list(SITE_PROTOTYPES.items()):
             fn = getattr(L, name)
             fn.restype = _KINDS[proto[0]]
             fn.argtypes = argtypes(name)

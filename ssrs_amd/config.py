@@ -37,7 +37,8 @@ _SECTIONS = (
                       'flight_airspeed', 'flight_sink_rate', 'rotor_zone', 'rotor_geometry', 'rotor_clearance',
                       'flight_time', 'flight_min_groundspeed', 'rotor_exposure_time', 'track_passage_radius', 'rotor_transits', 'rotor_yaw',
                       'collision_risk', 'bird_length', 'bird_wingspan', 'bird_flight', 'collision_avoidance', 'collision_model_3d',
-                      'rotor_blades', 'rotor_rpm', 'rotor_max_chord', 'rotor_pitch', 'rotor_chord_profile', 'hist_safe_tracks', 'thermal_model', 'thermal_allen_zi', 'thermal_allen_wstar', 'thermal_allen_sink',
+                      'rotor_blades', 'rotor_rpm', 'rotor_max_chord', 'rotor_pitch', 'rotor_chord_profile',
+                      'site_collision_risk', 'site_hub_height', 'site_rotor_diameter', 'hist_safe_tracks', 'thermal_model', 'thermal_allen_zi', 'thermal_allen_wstar', 'thermal_allen_sink',
                       'turbine_encounter_radius')),
 )
 
@@ -193,6 +194,20 @@ class Config:
     #                                     linear between the nodes and constant below 0.05: Band's generic blade, recalled from
     #                                     the published spreadsheet and NOT verified against it: correct it here, no rebuild
     #                                     is needed
+    site_collision_risk: bool = False   # True (needs flight_height=True; no turbines and no rotor_geometry): simulate_tracks also
+    #                                     computes, for EVERY cell of the raster, the collision risk of one candidate turbine
+    #                                     class standing on that cell -- collision_risk turned inside out, for siting -- on the
+    #                                     device (limit 19): the transits through a disk of radius
+    #                                     site_rotor_diameter / 2 + rotor_clearance around a hub site_hub_height above the
+    #                                     cell's ground, each weighted with Band's probability as collision_risk does.  It
+    #                                     reads rotor_clearance, rotor_yaw, rotor_blades / rpm / max_chord / pitch /
+    #                                     chord_profile, bird_*, collision_model_3d, flight_airspeed and collision_avoidance
+    #                                     exactly as collision_risk does.  Writes <id>_site_collision_risk.npy,
+    #                                     <id>_site_transits.npy, Simulator.compute_site_collision_risk_map().  The three
+    #                                     fields stand here, behind rotor_chord_profile, because tests pin most other slots
+    site_hub_height: float = 90.        # metres above the ground of the cell.  This and the diameter are PLACEHOLDERS, like
+    #                                     rotor_zone: set them for the turbine class at hand
+    site_rotor_diameter: float = 120.   # metres; (site_rotor_diameter / 2 + rotor_clearance) / resolution is at most 62 cells
     thermal_allen_zi: float = 0.        # thermal_model = 'allen': boundary-layer height zi in metres.  0 (snapshot / seasonal
     #                                     only) = the mean of the case's own blheight layer, clipped below at 100 m
     thermal_allen_wstar: float = 0.     # thermal_model = 'allen': convective velocity scale w* in m/s.  0 (snapshot / seasonal

@@ -35,6 +35,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "rotor_disk.h"
 #include "../../include/ssrs_hip_collision.h"
 
 namespace ssrs {
@@ -82,41 +83,17 @@ struct TrnArgs {
 };
 
 // The header's test of one testable move (r0, c0, z0) -> (r1, c1, z1) against turbine tb: -1 for no transit, else the
-// direction.  Every operation rounds on its own; the plane test comes first.  kRing (K19): `ring` gets the equal-area ring
-// of the crossing point, from the two numbers the test compares.
+// direction.  The arithmetic is rotor_disk.h's, which K20 shares; the plane test comes first, and the turbine's reach and
+// hub are read only behind it.  kRing (K19): `ring` gets the equal-area ring of the crossing point.
 template <bool kRing>
 __device__ __forceinline__ int trn_test(const TrnArgs &a, int tb, int r0, int c0, long long z0, int r1, int c1, long long z1,
                                         int &ring)
 {
     const double xt = a.turb[2 * tb], yt = a.turb[2 * tb + 1];
     const double ax = a.axis[2 * tb], ay = a.axis[2 * tb + 1];
-    const double dx0 = __dsub_rn(static_cast<double>(c0), xt), dy0 = __dsub_rn(static_cast<double>(r0), yt);
-    const double dx1 = __dsub_rn(static_cast<double>(c1), xt), dy1 = __dsub_rn(static_cast<double>(r1), yt);
-    const double s0 = __dadd_rn(__dmul_rn(ax, dx0), __dmul_rn(ay, dy0));
-    const double s1 = __dadd_rn(__dmul_rn(ax, dx1), __dmul_rn(ay, dy1));
-    if ((s0 < 0.0) == (s1 < 0.0)) return -1;
-    const double reach = a.reach[tb];
-    if (!(reach >= 0.0)) return -1;
-    const double u0 = __dsub_rn(__dmul_rn(ax, dy0), __dmul_rn(ay, dx0));
-    const double u1 = __dsub_rn(__dmul_rn(ax, dy1), __dmul_rn(ay, dx1));
-    const long long hub = a.hub[tb];
-    const double h0 = static_cast<double>(z0 - hub) / a.mm_per_cell;
-    const double h1 = static_cast<double>(z1 - hub) / a.mm_per_cell;
-    const double d = __dsub_rn(s0, s1);
-    const double U = __dsub_rn(__dmul_rn(s0, u1), __dmul_rn(s1, u0));
-    const double H = __dsub_rn(__dmul_rn(s0, h1), __dmul_rn(s1, h0));
-    const double lhs = __dadd_rn(__dmul_rn(U, U), __dmul_rn(H, H));
-    const double rhs = __dmul_rn(__dmul_rn(reach, reach), __dmul_rn(d, d));
-    if (!(lhs <= rhs)) return -1;
-    if constexpr (kRing) {
-        if (rhs == 0.0) ring = 0;
-        else if (!(lhs < rhs)) ring = SSRS_COLLISION_RINGS - 1;
-        else {
-            const int k = static_cast<int>((lhs / rhs) * static_cast<double>(SSRS_COLLISION_RINGS));
-            ring = k < SSRS_COLLISION_RINGS - 1 ? k : SSRS_COLLISION_RINGS - 1;
-        }
-    }
-    return s0 < 0.0 ? 1 : 0;
+    RotorPlane plane;
+    if (!rotor_plane_test(xt, yt, ax, ay, r0, c0, r1, c1, plane)) return -1;
+    return rotor_disk_test<kRing>(plane, ax, ay, a.reach[tb], a.hub[tb], z0, z1, a.mm_per_cell, ring);
 }
 
 // The walk of one lane over its wave's spans (no barrier inside: a wave without spans returns at once).

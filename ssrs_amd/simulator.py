@@ -88,6 +88,7 @@ class Simulator(Config):
         self._check_rotor_exposure_time()
         self._check_rotor_transits(turbines)
         self._check_collision_risk(turbines)
+        self._check_site_collision_risk()
         self._check_rotor_geometry(turbines)
         print(f'\n---- SSRS in {self.sim_mode} mode')
         print(f'Run name: {self.run_name}')
@@ -135,6 +136,7 @@ class Simulator(Config):
                                'Aspect': 'Aspect Degrees'}
         self._terrain = self._resolve_terrain(terrain)
         self.turbines = self._resolve_turbines(turbines)
+        self._site_class = self._resolve_site_class()
         self.turbine_encounters = {}      # (case_id, real_id) -> dict(tracks_per_turbine, turbines_per_track, first_step)
         self.track_occupancy_counts = {}  # (case_id, real_id) -> int32 (rows, cols): the distinct tracks through each cell
         self.track_passage_counts = {}    # (case_id, real_id) -> int32 (rows, cols): the distinct tracks within
@@ -153,6 +155,9 @@ class Simulator(Config):
         self.turbine_collision_risk = {}  # collision_risk: (case_id, real_id) -> int64 (nturb, 2): the summed collision
         #                                     probabilities of the transits in units of 2^-32 [with the wind, against the wind]
         self.track_collision_risk = {}    # (case_id, real_id) -> int64 (this rank's tracks,): the same per track
+        self.site_collision_risk_sums = {}  # site_collision_risk: (case_id, real_id) -> int64 (rows, cols, 2): the summed
+        #                                     collision probabilities of a turbine on each cell, in units of 2^-32
+        self.site_transit_counts = {}     # (case_id, real_id) -> int64 (rows, cols, 2): its transits [with, against the wind]
         self.wtk_layers = {
             'wspeed': f'windspeed_{str(int(self.wtk_orographic_height))}m',
             'wdirn': f'winddirection_{str(int(self.wtk_orographic_height))}m',
@@ -282,9 +287,6 @@ class Simulator(Config):
         rotor_transits itself), and a bird and a rotor the model can be evaluated for."""
         if not self.collision_risk:
             return
-        yaw = float(self.rotor_yaw)
-        if yaw != yaw or yaw in (float('inf'), float('-inf')):
-            raise ValueError(f'rotor_yaw = {self.rotor_yaw!r}: expected degrees clockwise from north, or < 0 for the wind')
         names = turbines_mod._column_names(turbines) if turbines is not None else []
         for ok, field, why in ((self.flight_height, 'flight_height=True', 'the disks are tested against the heights along '
                                 'the tracks'),
@@ -296,24 +298,72 @@ class Simulator(Config):
                                 'a blade')):
             if not ok:
                 raise ValueError(f'collision_risk = True needs {field}: {why}')
+        self._check_band_model('collision_risk')
+
+    def _check_band_model(self, who):
+        """The bird and the rotor Band's model is evaluated for, and rotor_yaw: what collision_risk and site_collision_risk
+        (`who`) both read."""
+        yaw = float(self.rotor_yaw)
+        if yaw != yaw or yaw in (float('inf'), float('-inf')):
+            raise ValueError(f'rotor_yaw = {self.rotor_yaw!r}: expected degrees clockwise from north, or < 0 for the wind')
         for name in ('bird_length', 'bird_wingspan'):
             if not 0. < float(getattr(self, name)) < float('inf'):
-                raise ValueError(f'{name} = {getattr(self, name)!r}: expected metres > 0 (collision_risk)')
+                raise ValueError(f'{name} = {getattr(self, name)!r}: expected metres > 0 ({who})')
         if str(self.bird_flight).lower() not in ('gliding', 'flapping'):
-            raise ValueError(f"bird_flight = {self.bird_flight!r}: expected 'gliding' or 'flapping' (collision_risk)")
+            raise ValueError(f"bird_flight = {self.bird_flight!r}: expected 'gliding' or 'flapping' ({who})")
         if not 0. <= float(self.collision_avoidance) <= 1.:
-            raise ValueError(f'collision_avoidance = {self.collision_avoidance!r}: expected a share in [0, 1] (collision_risk)')
+            raise ValueError(f'collision_avoidance = {self.collision_avoidance!r}: expected a share in [0, 1] ({who})')
         for name, what in (('rotor_blades', 'a number of blades'), ('rotor_rpm', 'revolutions per minute'),
                            ('rotor_max_chord', 'metres')):
             if not 0. <= float(getattr(self, name)) < float('inf'):
-                raise ValueError(f'{name} = {getattr(self, name)!r}: expected {what} >= 0 (collision_risk)')
+                raise ValueError(f'{name} = {getattr(self, name)!r}: expected {what} >= 0 ({who})')
         pitch = float(self.rotor_pitch)
         if pitch != pitch or pitch in (float('inf'), float('-inf')):
-            raise ValueError(f'rotor_pitch = {self.rotor_pitch!r}: expected degrees (collision_risk)')
+            raise ValueError(f'rotor_pitch = {self.rotor_pitch!r}: expected degrees ({who})')
         profile = np.asarray(self.rotor_chord_profile, dtype=np.float64)
         if profile.shape != turbines_mod.BAND_CHORD_NODES.shape or not (profile >= 0.).all():
             raise ValueError(f'rotor_chord_profile: expected {turbines_mod.BAND_CHORD_NODES.size} values >= 0, the chord over '
-                             'rotor_max_chord at r / R = 0.05, 0.10, ..., 1.00 (collision_risk)')
+                             f'rotor_max_chord at r / R = 0.05, 0.10, ..., 1.00 ({who})')
+
+    def _check_site_collision_risk(self):
+        """site_collision_risk puts one candidate turbine class on every cell: it needs K14's heights, a class the disk and
+        Band's model can be evaluated for, and no turbines."""
+        if not self.site_collision_risk:
+            return
+        if not self.flight_height:
+            raise ValueError('site_collision_risk = True needs flight_height=True: the disks are tested against the heights '
+                             'along the tracks')
+        for name in ('site_hub_height', 'site_rotor_diameter'):
+            if not 0. < float(getattr(self, name)) < float('inf'):
+                raise ValueError(f'{name} = {getattr(self, name)!r}: expected metres > 0 (site_collision_risk)')
+        clearance = float(self.rotor_clearance)
+        if clearance != clearance or clearance in (float('inf'), float('-inf')):
+            raise ValueError(f'rotor_clearance = {self.rotor_clearance!r}: expected metres (site_collision_risk)')
+        self._check_band_model('site_collision_risk')
+        radius = float(self.site_rotor_diameter) / 2.
+        reach = (radius + clearance) / float(self.resolution)
+        if not reach <= turbines_mod.SITE_MAX_REACH:
+            raise ValueError(f'site_collision_risk: (site_rotor_diameter / 2 + rotor_clearance) / resolution = '
+                             f'({float(self.site_rotor_diameter):g} / 2 + {clearance:g}) / {float(self.resolution):g} = {reach:g} '
+                             f'cells, expected at most {turbines_mod.SITE_MAX_REACH:g}')
+        if int(np.rint(1000. * float(self.site_hub_height))) >= 2 ** 31:
+            raise ValueError(f'site_hub_height = {self.site_hub_height!r}: expected metres below 2^31 mm (site_collision_risk)')
+
+    def _resolve_site_class(self):
+        """(reach in cells, hub_mm, table uint32 (2, 256)) of the candidate class of site_collision_risk, once per run: the
+        disk's reach and the hub's height as turbines.rotor_disks makes them, and the class's two rows of
+        turbines.band_collision_table -- what collision_risk gives a fleet of this class.  None when the feature is off."""
+        if not self.site_collision_risk:
+            return None
+        radius, clearance = float(self.site_rotor_diameter) / 2., float(self.rotor_clearance)
+        reach = (radius + clearance) / float(self.resolution)
+        hub_mm = int(np.rint(1000. * float(self.site_hub_height)))
+        table = turbines_mod.band_collision_table(
+            np.array([radius]), clearance,
+            np.array([[float(self.rotor_rpm), float(self.rotor_max_chord), float(self.rotor_pitch), float(self.rotor_blades)]]),
+            float(self.flight_airspeed), float(self.bird_length), float(self.bird_wingspan),
+            str(self.bird_flight).lower() == 'flapping', bool(self.collision_model_3d), self.rotor_chord_profile)[1]
+        return reach, hub_mm, np.ascontiguousarray(table[0])
 
     def _check_rotor_geometry(self, turbines):
         """rotor_geometry / rotor_clearance, and what 'turbine' needs that can be told before anything is computed."""
@@ -886,14 +936,16 @@ class Simulator(Config):
                 wind = self._time_wind(case_id) if self.flight_time else None
                 # (rotor_transits: the rotors' axes, once per case)
                 axes = self._transit_axes(case_id) if transit else None
-                if torch.is_tensor(wind) or axes is not None:
+                # (site_collision_risk: the one axis, or the case's axis per cell, once per case)
+                site_axes = self._site_axes(case_id) if site else None
+                if torch.is_tensor(wind) or axes is not None or site_axes is not None:
                     torch.cuda.current_stream().synchronize()
                 for (real_id, updraft), lift in zip(enumerate(updrafts), raw):
                     if self.sim_seed > 0:
                         np.random.seed(self.sim_seed + real_id)
                     fields = (updraft, self._potential_dev(updraft, case_id, real_id)) if fluid \
                         else (None, None)
-                    yield (case_id, real_id, fields, self._stream_seed(real_id), lift, wind, axes)
+                    yield (case_id, real_id, fields, self._stream_seed(real_id), lift, wind, axes, site_axes)
 
         encounters = float(self.turbine_encounter_radius) > 0.
         if encounters:
@@ -924,9 +976,13 @@ class Simulator(Config):
             # (the uint32 table travels as int32 bit patterns, like the bitmaps)
             cls, table = self._collision_table
             classes = (to_dev(cls, torch.int32), to_dev(np.ascontiguousarray(table).view(np.int32), torch.int32))
+        site = bool(self.site_collision_risk)           # (the constructor saw to heights and the class)
+        if site:
+            site_reach, site_hub_mm, site_table = self._site_class
+            site_table = to_dev(site_table.view(np.int32), torch.int32)
 
         def run(item):
-            case_id, real_id, fields, seed, lift, wind, axes = item
+            case_id, real_id, fields, seed, lift, wind, axes, site_axes = item
             self.last_seeds[(case_id, real_id)] = seed
             id_str = self._get_id_string(case_id, real_id)
             start_time = time.time()
@@ -978,9 +1034,14 @@ class Simulator(Config):
                             # their summed collision probabilities, by turbine and direction and by track
                             fly['risk'] = torch.zeros((n_rotor, 2), dtype=torch.int64, device=my_starts.device)
                             fly['track_risk'] = torch.zeros((hi - lo,), dtype=torch.int64, device=my_starts.device)
+                    if site:
+                        # a candidate turbine on every cell: its summed collision probabilities and its transits, by direction
+                        fly['site_risk'] = torch.zeros(tuple(self.gridsize) + (2,), dtype=torch.int64, device=my_starts.device)
+                        fly['site_transits'] = torch.zeros_like(fly['site_risk'])
                     consumers.append(self._flight_consumer(lift, dem, fly, enc_geometry if encounters else None, rotor,
                                                            keep_masked=timed, defer_rotor=exposure,
-                                                           transit=(disks, axes, classes) if transit else None))
+                                                           transit=(disks, axes, classes) if transit else None,
+                                                           site=(site_reach, site_hub_mm, site_axes, site_table) if site else None))
                 if timed:
                     # after the flight consumer, whose traj_band of the chunk it reads: one raster of microseconds per
                     # item (two with flight_height), accumulated over chunks and parts, and this rank's per-track rows
@@ -1123,7 +1184,8 @@ class Simulator(Config):
         flight.height_params(who='Config.flight_height_* / rotor_zone', **kw)
         return kw, airspeed, sink
 
-    def _flight_consumer(self, lift, dem, fly, geometry, rotor=None, keep_masked=False, defer_rotor=False, transit=None):
+    def _flight_consumer(self, lift, dem, fly, geometry, rotor=None, keep_masked=False, defer_rotor=False, transit=None,
+                         site=None):
         """A chunk through the flight-height scan (K14): `fly['band_hist']` is added to, the chunk's tracks get their rows of
         `fly['rows']`; with `geometry` the points in the rotor zone go through the encounter kernel into `fly['hits']` /
         `fly['first_step']`; with `rotor` (the cylinders on the device) the points and their heights go through the rotor
@@ -1134,7 +1196,9 @@ class Simulator(Config):
         item's cellinfo in `fly['cellinfo']` for _time_consumer.  transit (rotor_transits, collision_risk): ((cells, reach, hub,
         bins) on the device, the case's axes, (cls, table) on the device or None): the chunk and its alt also go through the
         transit kernel (K18), here in either case, into `fly['transit_hits']` / `fly['transits']` -- or, with (cls, table),
-        through the collision-risk kernel (K19), whose one pass gives the same two and `fly['risk']` / `fly['track_risk']`."""
+        through the collision-risk kernel (K19), whose one pass gives the same two and `fly['risk']` / `fly['track_risk']`.
+        site (site_collision_risk): (reach in cells, hub_mm, the axis or the axes per cell, the class's table) on the device:
+        the chunk and its alt also go through the site kernel (K20) into `fly['site_risk']` / `fly['site_transits']`."""
         kw, airspeed, sink = self._flight_params()
         cellinfo = flight.altitude_cellinfo(lift, dem, self.resolution, airspeed, sink)
         if defer_rotor:
@@ -1144,7 +1208,7 @@ class Simulator(Config):
         def consume(t0, t1, traj, off):
             out = flight.compute_track_altitudes(traj, cellinfo, self.gridsize, offsets=off, band_hist=fly['band_hist'],
                                                  want_masked=geometry is not None or keep_masked,
-                                                 want_alt=rotor is not None, **kw)
+                                                 want_alt=rotor is not None or site is not None, **kw)
             fly['rows'][t0:t1] = out['heights']
             if keep_masked:
                 fly['masked'] = out['masked']
@@ -1166,6 +1230,10 @@ class Simulator(Config):
                                                       self.gridsize, self.resolution, bins=disk_bins,
                                                       hits=fly['transit_hits'][t0:t1], transits=fly['transits'],
                                                       risk=fly['risk'], track_risk=fly['track_risk'][t0:t1])
+            if site is not None:
+                reach, hub_mm, site_axes, table = site
+                turbines_mod.site_collision_risk(traj, out['alt'], off, cellinfo, reach, hub_mm, site_axes, table, self.gridsize,
+                                                 self.resolution, transits=fly['site_transits'], risk=fly['site_risk'])
             if geometry is not None:
                 xy, bins = geometry
                 turbines_mod.turbine_encounters(out['masked'], off, xy, radius_cells, self.gridsize, bins=bins,
@@ -1195,6 +1263,20 @@ class Simulator(Config):
             warnings.warn(f'rotor_transits: {case_id}: {lost} of the {nturb} turbines have no wind direction (NaN) at the '
                           'cell they stand on; nothing transits them')
         return to_dev(axes, torch.float64)
+
+    def _site_axes(self, case_id):
+        """The axis of the candidate turbines of one case, on the device: rotor_yaw >= 0 is that compass direction, and in
+        uniform mode the rotors face uniform_winddirn -- one pair [ax, ay] for all sites; otherwise every site faces the wind
+        of its own cell, the case's wdirn raster (_wind_rasters, at wtk_orographic_height) through layers.ray_step in the
+        frame of _time_ray_axes(): f64 (rows, cols, 2), 16 B a cell on the device.  A NaN direction gives a site nothing can
+        transit."""
+        if float(self.rotor_yaw) >= 0. or self.sim_mode.lower() == 'uniform':
+            wdirn = float(self.rotor_yaw) if float(self.rotor_yaw) >= 0. else float(self.uniform_winddirn)
+            return to_dev(turbines_mod.rotor_axes(wdirn, self._time_ray_axes())[0], torch.float64)
+        entry = next(w for w in self._wind if w.case_id == case_id)
+        wdirn = self._wind_rasters(entry)[1].cpu().numpy().astype(np.float64).reshape(-1)
+        axes = turbines_mod.rotor_axes(wdirn, self._time_ray_axes())
+        return to_dev(axes.reshape(tuple(self.gridsize) + (2,)), torch.float64)
 
     def _time_params(self):
         """Keyword arguments of flight.compute_track_times from the resolution and the flight_* fields, checked."""
@@ -1358,6 +1440,28 @@ class Simulator(Config):
             if writes:
                 np.save(os.path.join(self.mode_data_dir, f'{id_str}_turbine_collision_risk.npy'), risk)
                 np.save(os.path.join(self.mode_data_dir, f'{id_str}_track_collision_risk.npy'), per_track)
+        if 'site_risk' in fly:
+            # site_collision_risk: <id>_site_collision_risk.npy, int64 (rows, cols, 2) raw sums in units of 2^-32 [with the
+            # wind, against the wind], and <id>_site_transits.npy, int64 (rows, cols, 2).  The invariant that stands in for a
+            # checksum: a transit adds less than 2^32.  Track-sharded runs sum both rasters over the ranks as the other
+            # rasters are summed (untested on more than one rank)
+            risk, passes = fly['site_risk'], fly['site_transits']
+            if sharded:
+                risk = distributed.reduce_histogram(risk, all_ranks=True)
+                passes = distributed.reduce_histogram(passes, all_ranks=True)
+            risk, passes = risk.cpu().numpy().astype(np.int64), passes.cpu().numpy().astype(np.int64)
+            # (sum <= transits x (2^32 - 1) as ceil(sum / (2^32 - 1)) <= transits: the product passes int64 from 2^31 transits
+            # on; a negative sum is a wrapped one)
+            wrong = np.argwhere((risk < 0) | (passes < 0) | ((risk + (2 ** 32 - 2)) // (2 ** 32 - 1) > passes))
+            if wrong.size:
+                r, c, d = (int(v) for v in wrong[0])
+                raise RuntimeError(f'{id_str}: site collision risk: cell ({r}, {c}) has the sum {int(risk[r, c, d])} (2^-32) for '
+                                   f'{int(passes[r, c, d])} transits in direction {d} ({wrong.shape[0]} entries like it)')
+            self.site_collision_risk_sums[key] = risk
+            self.site_transit_counts[key] = passes
+            if writes:
+                np.save(os.path.join(self.mode_data_dir, f'{id_str}_site_collision_risk.npy'), risk)
+                np.save(os.path.join(self.mode_data_dir, f'{id_str}_site_transits.npy'), passes)
         if 'transit_hits' in fly and self.rotor_transits:
             # rotor_transits: <id>_turbine_rotor_transits.npy, int64 (nturb, 3) [tracks, with the wind, against the wind].
             # The cheap invariant that stands in for a checksum: a turbine has tracks iff it has transits.  Track-sharded
@@ -1748,6 +1852,29 @@ class Simulator(Config):
         out = np.ascontiguousarray(np.concatenate([two, two.sum(1, keepdims=True)], 1))
         if self._rank() == 0:
             np.save(os.path.join(self.mode_data_dir, 'summary_turbine_collision_risk.npy'), out)
+        self._barrier()
+        return out
+
+    def compute_site_collision_risk_map(self):
+        """For every cell, the expected collisions per simulated track of a turbine of the candidate class standing on it
+        (site_collision_risk = True; DESIGN.md K20, limit 19): f64 (rows, cols), the mean over all (case, realisation) items
+        of the raw sums of both directions x 2^-32 x (1 - collision_avoidance) / track_count; case-sharded runs take the mean
+        over every rank's items.  Writes summary_site_collision_risk.npy.  ValueError when simulate_tracks computed none."""
+        if not self.site_collision_risk_sums:
+            raise ValueError('no site collision risk was computed: run simulate_tracks() with site_collision_risk=True '
+                             '(flight_height=True)')
+        items = [self.site_collision_risk_sums[key] for key in sorted(self.site_collision_risk_sums)]
+        shape = items[0].shape[:2]
+        scale = (1. - float(self.collision_avoidance)) / float(self.track_count)
+        total = np.zeros(shape[0] * shape[1] + 1, dtype=np.float64)        # [the raster row by row, number of items]
+        for risk in items:
+            total[:-1] += (risk.astype(np.float64).sum(2) * 2. ** -32 * scale).reshape(-1)
+            total[-1] += 1.
+        if self._world() > 1 and not self._shards_tracks():
+            total = self._allreduce_sum(total)                      # the cases of the other ranks
+        out = np.ascontiguousarray((total[:-1] / total[-1]).reshape(shape))
+        if self._rank() == 0:
+            np.save(os.path.join(self.mode_data_dir, 'summary_site_collision_risk.npy'), out)
         self._barrier()
         return out
 

@@ -650,3 +650,66 @@ def rotor_collision_risk(traj, alt, offsets, cellinfo, xy_cells, reach, hub, axi
     track_risk: the raw uint64 sums in units of 2^-32, [with the wind, against the wind] per turbine."""
     return _transit_pass('rotor_collision_risk', traj, alt, offsets, cellinfo, xy_cells, reach, hub, axis, gridshape, resolution,
                          bins, hits, transits, collision=(cls, table, risk, track_risk))
+
+
+SITE_MAX_REACH = nat.SITE_MAX_REACH     # cells: the largest reach of a candidate class (include/ssrs_hip_sites.h)
+
+
+def site_collision_risk(traj, alt, offsets, cellinfo, reach, hub_mm, axis, table, gridshape, resolution, transits=None, risk=None,
+                        want_transits=True):
+    """ssrs_site_collision_risk on device tensors (K20): rotor_collision_risk turned inside out -- for every cell of the
+    raster the transits through the disk of ONE candidate turbine class standing on that cell, and their summed collision
+    probabilities.  traj, alt, offsets and cellinfo as rotor_transits takes them (host or device; cellinfo a device tensor);
+    reach in cells (0 .. SITE_MAX_REACH; NaN or negative: nothing is transited), hub_mm the hub's height above the ground of
+    its cell in mm; axis f64 (2,) -- one upwind step [ax, ay] for all sites, rotor_axes' row -- or (rows, cols, 2), one per
+    cell (16 bytes a cell on the device); table uint32 (2, 256), one class's rows of band_collision_table (host or device; a
+    device table is int32 holding the uint32 bit patterns); resolution in metres.  transits, risk: int64 device tensors
+    (rows, cols, 2), ADDED to when given; want_transits=False leaves the counts out (transits comes back None).
+    Returns dict(transits, risk): [with the wind, against the wind] per cell, risk the raw uint64 sums in units of 2^-32."""
+    who = 'site_collision_risk'
+    rows, cols = int(gridshape[0]), int(gridshape[1])
+    mm_per_cell = 1000. * float(resolution)
+    if not (mm_per_cell > 0. and np.isfinite(mm_per_cell)):
+        raise ValueError(f'{who}: resolution = {resolution!r}, expected metres > 0')
+    reach = float(reach)
+    if reach > SITE_MAX_REACH:
+        raise ValueError(f'{who}: reach = {reach!r} cells, expected at most {SITE_MAX_REACH}')
+    hub_mm = int(hub_mm)
+    if not -2 ** 31 <= hub_mm < 2 ** 31:
+        raise ValueError(f'{who}: hub_mm = {hub_mm} does not fit int32')
+    axis_dev = to_dev(axis if is_tensor(axis) else np.asarray(axis, dtype=np.float64), torch.float64).contiguous()
+    if tuple(axis_dev.shape) not in ((2,), (rows, cols, 2)):
+        raise ValueError(f'{who}: axis has shape {tuple(axis_dev.shape)}, expected (2,) or ({rows}, {cols}, 2)')
+    per_cell = axis_dev.dim() == 3
+    off = to_dev(offsets, torch.int64).reshape(-1)
+    ntracks = int(off.numel()) - 1
+    if ntracks < 0:
+        raise ValueError(f'{who}: offsets needs at least one entry')
+    pts = to_dev(traj, torch.int16).reshape(-1, 2)
+    heights = to_dev(alt, torch.int32).reshape(-1)
+    if int(heights.numel()) != int(pts.shape[0]):
+        raise ValueError(f'{who}: alt has {heights.numel()} entries for {pts.shape[0]} points (it is indexed like traj)')
+    if not is_tensor(cellinfo) or cellinfo.dtype != torch.int32 or tuple(cellinfo.shape) != (rows, cols, 2) or \
+            not cellinfo.is_contiguous() or not cellinfo.is_cuda:
+        raise ValueError(f'{who}: cellinfo must be a contiguous int32 device tensor ({rows}, {cols}, 2) (altitude_cellinfo)')
+    if not is_tensor(table):
+        table = torch.from_numpy(np.ascontiguousarray(table, dtype=np.uint32).view(np.int32))
+    table_dev = to_dev(table, torch.int32).contiguous()            # (uint32 bit patterns in int32)
+    if tuple(table_dev.shape) != (2, COLLISION_RINGS):
+        raise ValueError(f'{who}: table has shape {tuple(table_dev.shape)}, expected (2, {COLLISION_RINGS}): one class')
+    dev = device()
+    if risk is None:
+        risk = torch.zeros((rows, cols, 2), dtype=torch.int64, device=dev)
+    if transits is None and want_transits:
+        transits = torch.zeros((rows, cols, 2), dtype=torch.int64, device=dev)
+    for name, out in (('risk', risk), ('transits', transits)):
+        if out is None:
+            continue
+        if not is_tensor(out) or out.dtype != torch.int64 or tuple(out.shape) != (rows, cols, 2) or \
+                not out.is_contiguous() or not out.is_cuda:
+            raise ValueError(f'{who}: {name} must be a contiguous int64 device tensor ({rows}, {cols}, 2)')
+    if ntracks and pts.numel():
+        nat.check(nat.lib().ssrs_site_collision_risk(
+            nat.ptr(pts), nat.ptr(off), ntracks, nat.ptr(heights), nat.ptr(cellinfo), rows, cols, reach, hub_mm,
+            nat.ptr(axis_dev), int(per_cell), mm_per_cell, nat.ptr(table_dev), nat.ptr(transits), nat.ptr(risk), stream_ptr()))
+    return dict(transits=transits, risk=risk)
