@@ -336,11 +336,12 @@ typedef struct SsrsTrackStats {
     int64_t roam_slow_wave_pairs; /* ... and how many of them sent some lane through the single-move sequence
                                      (near-ties, flag entries, moves out of the window, burn-in) */
     int32_t roam_shuffles;        /* times a SETTLED roaming batch had the tracks of its windows dealt afresh
-                                     (every SSRS_TRACKS_ROAM_SHUFFLE batches: default 16, and 4 while 256-lane blocks step
+                                     (every SSRS_TRACKS_ROAM_SHUFFLE batches: default 16, and 2 while 256-lane blocks step
                                      with feeder waves; part of wander_sorts) */
     int32_t roam_wide_launches;   /* of roam_launches: those run with 512-lane blocks (two list blocks of one window per CU: batches
                                      whose survivors outnumber one round of 256-lane blocks; SSRS_TRACKS_ROAM_WIDE) */
-} SsrsTrackStats;
+    int32_t window_scans;         /* of wander_sorts: those that looked for the windows anew.  A shuffle of a settled batch deals
+                                     into the windows of the last scan (SSRS_TRACKS_NO_SHUFFLE_REUSE: every sort scans) */} SsrsTrackStats;
 
 /* Fills rows/cols/burnin/max_moves/memory/nu and zeroes the rest; `prior` must
  * still be supplied by the caller (it needs the host libm/numpy cos). */

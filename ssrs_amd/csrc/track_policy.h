@@ -26,36 +26,64 @@ struct TrackPolicy {
     bool front = false;                      // a north / south front (prefetch wave)
     bool may_rebalance = true, debug = false;
     int roam_shuffle = 16;
+    bool reuse_windows = true;               // a periodic shuffle deals into the windows of the last scan
     long long ntracks = 0, crossing = 0;     // crossing: rows + cols
     // the path
     bool binning_on = false, tiles_on = false, cached = false, scattered = false;
     bool want_wander_sort = false, want_rebalance = false, sort_is_periodic = false;
+    bool shuffle_rescans = false;            // ... a periodic one whose batch strayed like one that asks for a real sort
     int wander_cooldown = 0;
     int rebalance_cooldown = 0;              // batches to look past after a re-deal (their counts are older than it)
     int stable_batches = 0, stable_roam = 0, since_shuffle = 0;
     int judge_from = 0;
     uint32_t upper = 0;                      // bound on the longest XCD list
     int upper_from = 0;
+    uint32_t undealt = 0;                    // the last bound that was seen on lists, not derived from a deal's padding
+    bool upper_is_padded = false;
     uint32_t prev_total = 0;
     unsigned long long seen_steps = 0, seen_strays = 0;
     // the batches examined so far
     int checked = 0;
     bool finished = false;
     int wander_sorts = 0, roam_shuffles = 0;
+    int window_scans = 0;                    // sorts that looked for the windows anew (k_wander_windows)
+    int dealt_width = 0;                     // block width of the last deal (0: none yet)
     long long block_window_steps = 0;
 
-    // a wander sort's deal of `width` was queued as batch `batches` was being filled
-    void dealt(int batches, uint32_t cap, bool contiguous, int width)
+    // Does the sort that is wanted now look for the windows anew?  A periodic shuffle of a settled batch does not: the
+    // basins stay where they are, and the windows of the last scan are still on the device.  It does when its batch
+    // strayed like one that asks for a real sort (those are capped), and when the deal's width hangs on the live count
+    // that the scan takes (`width_by_live`: the lists are long enough for wide blocks) and the last deal was wide -- a
+    // narrow deal stays narrow, the live count only shrinks.
+    bool scan_windows(bool width_by_live) const
+    {
+        if (!sort_is_periodic || !reuse_windows || window_scans == 0 || shuffle_rescans) return true;
+        return width_by_live && dealt_width > 1;
+    }
+
+    // a wander sort's deal of `width` was queued as batch `batches` was being filled; `scanned`: it looked for its windows
+    void dealt(int batches, uint32_t cap, bool contiguous, int width, bool scanned = true)
     {
         ++wander_sorts;
+        if (scanned) ++window_scans;
+        dealt_width = width;
+        shuffle_rescans = false;
         want_wander_sort = false;
         want_rebalance = false;
-        wander_cooldown = 3;
+        // (the batches queued before a real sort report the strays of the old windows: they are looked past.  A shuffle
+        // into the same windows changes nothing about the strays, and with no scan to pay for the next may follow at once)
+        wander_cooldown = (sort_is_periodic && !scanned) ? 0 : 3;
         stable_roam = sort_is_periodic ? 2 : 0;      // (a shuffle of a settled batch: the launches stay long)
         if (sort_is_periodic) ++roam_shuffles;
         sort_is_periodic = false;
-        // the padded deal makes the lists LONGER: raise the bound now, and let no batch queued before this point lower it
-        upper = deal_upper(upper, cap, contiguous, static_cast<uint32_t>(width));
+        // the padded deal makes the lists LONGER: raise the bound now, and let no batch queued before this point lower it.
+        // A deal places the live tracks afresh, whatever the lists' lengths: deal_upper of ANY bound on an eighth of the
+        // live tracks holds behind it, and the live count only shrinks.  So when deals follow each other faster than their
+        // batches are read back, each pads the last bound that was seen on lists (`undealt`), not the padded bound of
+        // the deal before it -- that would grow to the lists' capacity, and every launch would start that many blocks
+        if (!upper_is_padded) undealt = upper;
+        upper = deal_upper(undealt, cap, contiguous, static_cast<uint32_t>(width));
+        upper_is_padded = true;
         upper_from = batches;
     }
 
@@ -80,7 +108,8 @@ struct TrackPolicy {
         if (block_window) block_window_steps += static_cast<long long>(tot[0] - seen_steps);
         if (c == 0) { finished = true; return; }
         // the live count only shrinks, a stale bound is safe -- except across a wander sort
-        upper = (checked - 1 >= upper_from || c > upper) ? c : upper;
+        if (checked - 1 >= upper_from) { upper = c; upper_is_padded = false; }      // (lists as the last deal left them, or shorter)
+        else if (c > upper) upper = c;
         uint32_t total = 0;
         for (int x = 0; x < kXcd; ++x) total += cnt[x];
         if (tiles_on && cache_ok && front) {
@@ -141,6 +170,7 @@ struct TrackPolicy {
             else if (roam_shuffle > 0 && ++since_shuffle >= roam_shuffle && stable_roam >= 2 && roam_ready) {
                 want_wander_sort = true;            // settled: every roam_shuffle batches the windows' tracks are dealt afresh
                 sort_is_periodic = true;
+                shuffle_rescans = dsteps > 0 && dstray * 64 > dsteps;      // (the real sorts have run out)
                 since_shuffle = 0;
             } else ++stable_roam;                   // settled in its windows: the launches may grow
         }

@@ -4065,7 +4065,9 @@ struct TrackSwitches {
     int roam_width;              // SSRS_TRACKS_ROAM_WIDTH=1|2|4: that width at every deal (A/B); 0: chosen
     int roam_shuffle;            // batches between two shuffles of a settled roaming batch (SSRS_TRACKS_ROAM_SHUFFLE, 0: never)
     int roam_shuffle_fed;        // ... while its blocks are narrow and step with feeder waves
-    int roam_feed;               // SSRS_TRACKS_ROAM_FEED: narrow roaming launches with feeder waves (unset, 1: on; 0: off; 2: the feeders
+    bool shuffle_reuse;          // such a shuffle deals into the windows of the last scan: no k_wander_windows, no live count read
+                                 // back (off: SSRS_TRACKS_NO_SHUFFLE_REUSE)
+    int roam_feed;              // SSRS_TRACKS_ROAM_FEED: narrow roaming launches with feeder waves (unset, 1: on; 0: off; 2: the feeders
                                  // skip every odd trip -- tests: fed trips and the stepping wave's own Philox alternate)
 };
 
@@ -4096,9 +4098,12 @@ static TrackSwitches read_track_switches()
     // Every 16 batches (round 3) -- but every 4 while the deal is narrow and its launches have feeder waves: a block's pair
     // time then follows its CU's live lanes (620 to 720 clocks where every wave took ~757) and a launch ends with its
     // fastest wave, so the tracks of the slower blocks fell behind between two shuffles and the pass grew a tail of 20
-    // nearly empty launches (profiles/roam_feed.md)
+    // nearly empty launches (profiles/roam_feed.md).  Such a shuffle then came every 7 batches (three more are looked past
+    // behind a deal); now that it scans no windows it costs 0.08 ms, no batch is looked past behind it, and it comes every
+    // 2 batches (profiles/roam_gaps.md)
+    sw.shuffle_reuse = !set("SSRS_TRACKS_NO_SHUFFLE_REUSE");
     sw.roam_shuffle = 16;
-    sw.roam_shuffle_fed = sw.roam_feed ? 4 : 16;
+    sw.roam_shuffle_fed = sw.roam_feed ? (sw.shuffle_reuse ? 2 : 4) : 16;
     if (const char *e = std::getenv("SSRS_TRACKS_ROAM_SHUFFLE")) sw.roam_shuffle = sw.roam_shuffle_fed = std::atoi(e);
     return sw;
 }
@@ -4451,6 +4456,7 @@ int TrackRun::choose_front_path()
 
     pol.thr = thr; pol.tiles_ok = tiles_ok; pol.cache_ok = cache_ok; pol.never_scattered = never_scattered;
     pol.front = a.pf_dir != 0; pol.may_rebalance = sw.rebalance; pol.debug = sw.debug; pol.roam_shuffle = sw.roam_shuffle_fed;   // (narrow until a deal says otherwise)
+    pol.reuse_windows = sw.shuffle_reuse;
     pol.ntracks = ntracks; pol.crossing = p->rows + p->cols;
     pol.binning_on = binning_on; pol.tiles_on = tiles_on; pol.scattered = scattered;
     pol.cached = cache_ok && scattered;
@@ -4691,8 +4697,17 @@ int TrackRun::wander_sort()
     const uint32_t slots = ws.cap * kXcd;
     uint32_t *k0 = reinterpret_cast<uint32_t *>(ws.keys[0]), *k1 = reinterpret_cast<uint32_t *>(ws.keys[1]);
     int32_t *sorted = reinterpret_cast<int32_t *>(ws.bucket);
-    hipLaunchKernelGGL(k_wander_windows, dim3(1), dim3(1024), 0, st, ws.list[launch & 1], ws.state, ws.ctl, launch & 3, ws.cap,
-                       p->rows, p->cols, ws.wander);
+    // the deal's width goes by the live count only where wide blocks are possible, not forced either way, and the lists are
+    // long enough for the question to arise
+    const bool wide_ok = roam_ok && sw.deal_contiguous;
+    const bool width_by_live = wide_ok && !sw.roam_width && sw.roam_wide_from > 1 &&
+                               static_cast<long long>(pol.prev_total) >= sw.roam_wide_from;
+    // a periodic shuffle keeps the windows of the last scan in ws.wander (one block of 1 024 threads walks every list slot
+    // for them, 0.24 - 0.40 ms during which the other CUs idle: profiles/roam_gaps.md)
+    const bool scan = pol.scan_windows(width_by_live);
+    if (scan)
+        hipLaunchKernelGGL(k_wander_windows, dim3(1), dim3(1024), 0, st, ws.list[launch & 1], ws.state, ws.ctl, launch & 3, ws.cap,
+                           p->rows, p->cols, ws.wander);
     hipLaunchKernelGGL(k_wander_keys, dim3((slots + kBlock - 1) / kBlock), dim3(kBlock), 0, st, ws.list[launch & 1], ws.state,
                        ws.ctl, launch & 3, ws.cap, ws.wander, k0, pol.sort_is_periodic ? static_cast<uint32_t>(launch) : 0u);
     size_t temp_bytes = ws.sort_temp_bytes;
@@ -4704,12 +4719,12 @@ int TrackRun::wander_sort()
     // blocks measured 3-4x slower than either -- four waves per SIMD and a launch that ends with its first wave --,
     // SSRS_TRACKS_ROAM_WIDTH=4 keeps the A/B).  The lists' lengths count tombstones and padding, so the width goes by
     // the live tracks k_wander_windows has just counted: one word read back synchronously, and only when the lists are
-    // long enough for the question to arise
+    // long enough for the question to arise.  (a shuffle without a scan: the last deal was narrow, and it stays narrow)
     roam_width = 1;
-    if (roam_ok && sw.deal_contiguous) {
+    if (wide_ok) {
         if (sw.roam_wide_from == 1) {
             roam_width = 2;
-        } else if (sw.roam_wide_from > 1 && static_cast<long long>(pol.prev_total) >= sw.roam_wide_from) {
+        } else if (width_by_live && scan) {
             uint32_t *word = &host_counts[kFinalSlot];
             if (hipMemcpyAsync(word, &ws.ctl->deal_live, sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
                 hipStreamSynchronize(st) != hipSuccess)
@@ -4723,7 +4738,7 @@ int TrackRun::wander_sort()
                        (launch + 1) & 3, (launch + 2) & 3, ws.cap, sw.deal_contiguous ? 1 : 0, roam_width);
     ++launch;
     marks_adjacent = false;
-    pol.dealt(batches, ws.cap, sw.deal_contiguous, roam_width);
+    pol.dealt(batches, ws.cap, sw.deal_contiguous, roam_width, scan);
     return SSRS_OK;
 }
 
@@ -4912,6 +4927,7 @@ int TrackRun::finish(int rc, SsrsTrackStats *stats)
         stats->roam_launches = roam_launches;
         stats->roam_shuffles = pol.roam_shuffles;
         stats->roam_wide_launches = roam_wide_launches;
+        stats->window_scans = pol.window_scans;
         stats->roam_wave_pairs = static_cast<int64_t>(host_ctl.roam_pairs);
         stats->roam_slow_wave_pairs = static_cast<int64_t>(host_ctl.roam_slow);
         stats->reserved0 = static_cast<int32_t>(host_ctl.pad);                   // near-ties settled by the fine table

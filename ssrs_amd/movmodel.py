@@ -474,7 +474,8 @@ def simulate_tracks(move_dirn, starts, grid_shape, memory_parameter=1,
                            roam_fed_wave_pairs=int(roam_fed.value), roam_own_wave_pairs=int(roam_own.value),
                            roam_stopped_waves=int(nat.lib().ssrs_tracks_roam_stopped_waves()),
                            roam_shuffles=int(stats.roam_shuffles),
-                           roam_wide_launches=int(stats.roam_wide_launches)))
+                           roam_wide_launches=int(stats.roam_wide_launches),
+                           window_scans=int(stats.window_scans)))
 
 
 def generate_simulated_tracks(move_dirn, start_location, grid_shape, memory_parameter=1,
