@@ -14,6 +14,10 @@
  *  - `stream` is a hipStream_t passed as void* (NULL = the null stream);
  *  - raster entry points are asynchronous on `stream`; ssrs_tracks_simulate
  *    drives a launch loop and returns after the last launch has completed;
+ *    every launch, memset and copy of an export goes to `stream` and nowhere else.
+ *    An export whose comment says it waits for `stream` once needs a value on the
+ *    host (a size, a flag, a host temporary it is about to drop); it puts its
+ *    launches to `stream` in order like the others;
  *  - return value: SSRS_OK (0) or a negative SSRS_ERR_* code, with a
  *    thread-local message available from ssrs_last_error();
  *  - no hidden global state: the random stream is a pure function of
@@ -190,7 +194,9 @@ int ssrs_wind_from_triangles_cubic(const double *points, const int32_t *triangle
  * ssrs_gaussian_blur: scipy.ndimage.gaussian_filter(sigma, mode='constant'),
  * separable, truncated at 4 sigma.  thermals = blur(seeds, sigma = 4).
  * workspace: ssrs_blur_workspace_bytes(rows, cols, sigma) bytes of device scratch; its contents before a call mean
- * nothing and after it are unspecified. */
+ * nothing and after it are unspecified.
+ * ssrs_thermal_seeds is asynchronous on `stream`; ssrs_gaussian_blur copies its weights from a host temporary and
+ * waits for `stream` once, before its two passes, which go to `stream` in order. */
 int ssrs_thermal_seeds(const double *aspect, double thermal_intensity_scale,
                        uint64_t seed, double *seeds, int rows, int cols, void *stream);
 size_t ssrs_blur_workspace_bytes(int rows, int cols, double sigma);
@@ -221,7 +227,8 @@ int ssrs_thermal_fields(const double *aspect, double thermal_intensity_scale, do
  *   z = zmat[i], or z0 everywhere when zmat is NULL; zi is not clipped here (the reference does not).
  * max / clip are numpy's: a NaN argument gives NaN (fmax / fmin would drop it).  The IEEE specials follow from plain
  * division: zi = 0 with z > 0 gives x = 1, zi < 0 gives x = 0 and so the floor `min`, p = 0 gives theta = inf and so
- * the floor, p < 0 gives NaN.  NULL pointers (zmat excepted) or n == 0 -> SSRS_ERR_INVALID before any GPU work. */
+ * the floor, p < 0 gives NaN.  NULL pointers (zmat excepted) or n == 0 -> SSRS_ERR_INVALID before any GPU work.
+ * One launch each, asynchronous on `stream`. */
 int ssrs_potential_temperature(const double *pressure, const double *temperature, double *out, size_t n,
                                void *stream);
 int ssrs_deardorff_velocity(const double *pot_temperature, const double *blayer_height,
@@ -353,7 +360,8 @@ int ssrs_track_params_init(SsrsTrackParams *p, int rows, int cols,
  * clipped at 0 (:231), the 8 neighbours k = 0,1,2,3,5,6,7,8 of one cell stored
  * as 8 consecutive f64 (64 B, one aligned fetch per step).  A cell with any NaN
  * weight stores NaN in all 8 (the stepper then takes the :228-230 fallback).
- * potential may be NULL (updraft-only weights).  table: rows*cols*8 f64. */
+ * potential may be NULL (updraft-only weights).  table: rows*cols*8 f64.
+ * This and the two builders below: one launch each, asynchronous on `stream` (`prior` travels as a kernel argument). */
 int ssrs_transition_table_build(const double *updraft, const float *potential,
                                 double *table, int rows, int cols, void *stream);
 
@@ -508,7 +516,8 @@ int ssrs_hist_reduce(uint32_t *hist, size_t n, int root, void *nccl_comm, void *
  * hist[row, col] += 1 for each of the npoints int16 (row, col) pairs.  uint32
  * counts (the reference's int16 matrix wraps above 32767 visits).  A point
  * outside the raster is an error (the reference raises IndexError).
- * scratch8: 8 bytes of device scratch; its contents before a call mean nothing and after it are unspecified. */
+ * scratch8: 8 bytes of device scratch; its contents before a call mean nothing and after it are unspecified.
+ * The out-of-raster flag is read back, so the call waits for `stream` once, after its launch. */
 int ssrs_presence_count(const int16_t *traj, int64_t npoints, uint32_t *hist,
                         int rows, int cols, void *scratch8, void *stream);
 
@@ -519,7 +528,9 @@ size_t ssrs_presence_workspace_bytes(int rows, int cols, int krad);
  * f32 out.  Evaluated as 2*krad+1 chords of row prefix sums: exact in integers,
  * then one multiply by 1/ntaps.
  * workspace: ssrs_presence_workspace_bytes(rows, cols, krad) bytes of device scratch, 256-byte aligned; its contents
- * before a call mean nothing and after it are unspecified. */
+ * before a call mean nothing and after it are unspecified.
+ * The chord half-widths are copied from a host temporary, so the call (and the _u64 form) waits for `stream` once,
+ * before its two launches, which go to `stream` in order. */
 int ssrs_presence_smooth(const uint32_t *count, int krad, float *out, int rows,
                          int cols, void *workspace, size_t workspace_bytes,
                          void *stream);
@@ -535,7 +546,8 @@ int ssrs_presence_smooth_u64(const uint64_t *count, int krad, float *out, int ro
  *   acc += src / max(src)     (division in src's precision: f32 for `prprob`,
  *                              f64 for `case_prob`)
  *   out  = f32(src / max(src)) (summary_presence.npy)
- * scratch8: 8 bytes of device scratch; its contents before a call mean nothing and after it are unspecified. */
+ * scratch8: 8 bytes of device scratch; its contents before a call mean nothing and after it are unspecified.
+ * A memset and two launches each (the maximum stays on the device), asynchronous on `stream`. */
 int ssrs_presence_normalise_add(const void *src, int src_type, double *acc, size_t n,
                                 void *scratch8, void *stream);
 int ssrs_presence_normalise_f32(const double *src, float *out, size_t n,
@@ -726,7 +738,7 @@ int ssrs_track_occupancy(const int16_t *traj, const int64_t *traj_offsets, int64
  * misaligned traj, traj_band, cellinfo or workspace, floor > ceil, band_lo > band_hi, a workspace smaller than
  * ssrs_track_altitude_workspace_bytes(0) -> SSRS_ERR_INVALID before any GPU work; a workspace too small for the chunk's
  * points -> SSRS_ERR_INVALID once the two offsets are known, before any launch.  ntracks == 0, or no points, returns
- * SSRS_OK and touches nothing. */
+ * SSRS_OK and touches nothing.  ssrs_altitude_cellinfo is one raster launch, asynchronous on `stream`. */
 #define SSRS_ALTITUDE_TILE 4096
 typedef struct SsrsAltitudeParams {
     int32_t start, floor, ceil, band_lo, band_hi;
@@ -779,7 +791,8 @@ int ssrs_track_altitude(const int16_t *traj, const int64_t *traj_offsets, int64_
  * bytes a lane.
  * NULL traj / traj_offsets / params, rows / cols outside [1, 32767], ntracks outside [0, 2^31), a misaligned buffer, a
  * scalar out of range, band_time_hist without masked -> SSRS_ERR_INVALID before any GPU work.  ntracks == 0 returns SSRS_OK
- * and touches nothing; no points writes per_track only. */
+ * and touches nothing; no points writes per_track only.  ssrs_flight_windinfo is one raster launch, asynchronous on
+ * `stream`. */
 #define SSRS_FLIGHT_TIME_TILE 4096
 typedef struct SsrsFlightTimeParams {
     int32_t va, gmin, res_mm;
@@ -1076,7 +1089,12 @@ size_t ssrs_potential_workspace_bytes(int rows, int cols);
  *                 the range of the Dirichlet values (the solution obeys the maximum
  *                 principle, an unfinished iterate need not; a converged field is written
  *                 as it is).  Only the fall-back after a BiCGStab breakdown has a budget
- *                 of its own. */
+ *                 of its own.
+ * Synchronous: the call returns after its last kernel, with `potential` and `stats` final.  All its work, the
+ * hierarchy's set-up, the scans and the captured graph of the V-cycle included, goes to `stream`.  A NULL `stream`
+ * is the one case in this library where work leaves the caller's stream: the null stream cannot be captured, so the
+ * solve waits for the null stream once at entry and then runs on a non-blocking stream of its own (one per host
+ * thread), which it waits for before it returns. */
 int ssrs_potential_solve(const double *conductivity, const uint8_t *fixed_mask,
                          const double *fixed_values, const double *initial_guess,
                          float *potential, int rows, int cols, double rel_tol,
@@ -1086,7 +1104,7 @@ int ssrs_potential_solve(const double *conductivity, const uint8_t *fixed_mask,
                          void *stream);
 
 /* n uniforms of the contract above: out[i] = u(seed, track[i], step[i]).
- * Device self-check of the rocRAND-backed draw used by the stepper. */
+ * Device self-check of the rocRAND-backed draw used by the stepper.  One launch, asynchronous on `stream`. */
 int ssrs_uniform_selftest(uint64_t seed, const uint64_t *track,
                           const uint64_t *step, double *out, size_t n,
                           void *stream);
@@ -1094,7 +1112,7 @@ int ssrs_uniform_selftest(uint64_t seed, const uint64_t *track,
 /* The roaming stepper's hand-over word of n (track, block) pairs next to the
  * four words of rocRAND's engine for the same block:
  *   packed[i] = (x & 0xFFFF0000) | (z >> 16) of words[4 i .. 4 i + 3] = x, y, z, w.
- * Device self-check of what a feeder wave writes for its stepping wave. */
+ * Device self-check of what a feeder wave writes for its stepping wave.  One launch, asynchronous on `stream`. */
 int ssrs_roam_pair_word_selftest(uint64_t seed, const uint64_t *track,
                                  const uint64_t *block, uint32_t *packed,
                                  uint32_t *words, size_t n, void *stream);

@@ -58,7 +58,8 @@ extern "C" {
  *
  * Argument errors are ssrs_rotor_transits'; and a NULL cls, table or risk, nclass < 1, a cls or table that is not
  * 4-byte aligned, a risk or track_risk that is not 8-byte aligned -> SSRS_ERR_INVALID before any GPU work.  ntracks == 0,
- * or no points, returns SSRS_OK and touches nothing. */
+ * or no points, returns SSRS_OK and touches nothing.  Like ssrs_rotor_transits the call reads the chunk's first and
+ * last offset back and so waits for `stream` once; its launch goes to `stream`. */
 #define SSRS_COLLISION_RINGS 256
 #define SSRS_ROTOR_COLLISION_LDS_TURBINES 2560
 int ssrs_rotor_collision_risk(const int16_t *traj, const int64_t *traj_offsets, int64_t ntracks, const int32_t *alt,

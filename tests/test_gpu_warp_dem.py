@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from ssrs_amd import _native as nat
+from ssrs_amd._device import stream_ptr
 from ssrs_amd.georef import LonLatRaster, Projection, warp_to_grid
 from warp_ref import Geometry, bilinear_ref, geometries, pixel_coordinates
 
@@ -89,7 +90,7 @@ def test_outputs_may_be_left_out(gpu):
     for a, b in ((lon2, None), (None, lat2)):
         nat.check(nat.lib().ssrs_warp_lonlat_raster(
             None, nat.SSRS_F32, 41, 29, raster.lon0, raster.lat0, raster.dlon, raster.dlat, float('nan'), C.byref(proj),
-            geo.west, geo.south, geo.res, None, nat.SSRS_F64, nat.ptr(a), nat.ptr(b), None, 37, 53, None))
+            geo.west, geo.south, geo.res, None, nat.SSRS_F64, nat.ptr(a), nat.ptr(b), None, 37, 53, stream_ptr()))
     torch.cuda.synchronize()
     assert torch.equal(lon2, lon) and torch.equal(lat2, lat)
 

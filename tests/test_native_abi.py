@@ -15,9 +15,9 @@ def declared_functions():
     return sorted(set(re.findall(r'\b(ssrs_[a-z0-9_]+)\s*\(', text)))
 
 
-def header_code():
-    """include/ssrs_hip.h without comments and preprocessor lines."""
-    text = open(os.path.join(ROOT, 'include', 'ssrs_hip.h')).read()
+def header_code(name='ssrs_hip.h'):
+    """include/ssrs_hip.h (or another header of include/) without comments and preprocessor lines."""
+    text = open(os.path.join(ROOT, 'include', name)).read()
     text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
     text = re.sub(r'//[^\n]*', '', text)
     return '\n'.join(line for line in text.splitlines() if not line.lstrip().startswith('#'))
@@ -35,11 +35,15 @@ RETURNS = {'int': C.c_int, 'size_t': C.c_size_t, 'int64_t': C.c_int64, 'const ch
            'SsrsTrajRecorder *': C.c_void_p, 'void': None}
 
 
+# `ret ssrs_name(params);` -> (ret, name, params); tests/stream_order.py reads the parameter names with it
+PROTOTYPE = r'([A-Za-z_][\w\s\*]*?)\b(ssrs_[a-z0-9_]+)\s*\(([^()]*)\)\s*;'
+
+
 def declared_prototypes():
     """{name: (restype, [argtypes])} of every `ret ssrs_name(params);` of the header, by the rules of the binding: the five
     scalar kinds by value, every pointer parameter a void pointer.  A type outside that vocabulary is an error."""
     protos = {}
-    for ret, name, params in re.findall(r'([A-Za-z_][\w\s\*]*?)\b(ssrs_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', header_code()):
+    for ret, name, params in re.findall(PROTOTYPE, header_code()):
         ret = ' '.join(ret.replace('*', ' * ').split())
         assert ret in RETURNS, f'{name}: return type {ret!r} is not in the binding\'s vocabulary'
         argtypes = []
