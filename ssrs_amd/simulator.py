@@ -20,12 +20,14 @@ import pickle
 import time
 import warnings
 from dataclasses import asdict
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from .config import Config
 from . import distributed, flight, inputs, layers, movmodel, presence
+from . import products as products_mod
 from . import turbines as turbines_mod
 from . import potential as potential_mod
 from ._device import to_dev
@@ -262,14 +264,14 @@ class Simulator(Config):
             if not ok:
                 raise ValueError(f'rotor_exposure_time = True needs {field}: {why}')
 
-    def _check_rotor_transits(self, turbines):
-        """rotor_transits counts the moves through every turbine's disk along K14's heights: what it needs that can be told
-        before anything is computed.  (flight_time is not among it.)"""
-        if not self.rotor_transits:
-            return
+    def _check_rotor_yaw(self):
         yaw = float(self.rotor_yaw)
         if yaw != yaw or yaw in (float('inf'), float('-inf')):
             raise ValueError(f'rotor_yaw = {self.rotor_yaw!r}: expected degrees clockwise from north, or < 0 for the wind')
+
+    def _check_disk_needs(self, option, turbines, twice):
+        """What K18's disks need that can be told before anything is computed, for rotor_transits and collision_risk
+        (`option`; `twice`: what the option takes the rotor diameter to be twice of)."""
         names = turbines_mod._column_names(turbines) if turbines is not None else []
         for ok, field, why in ((self.flight_height, 'flight_height=True', 'the disks are tested against the heights along '
                                 'the tracks'),
@@ -277,35 +279,28 @@ class Simulator(Config):
                                 'around its hub'),
                                (turbines is not None, 'turbines', 'none were given (Simulator(..., turbines=...))'),
                                ('t_hh' in names, 'turbines with t_hh', 'the hub height in metres, the centre of the disk'),
-                               ('t_rd' in names, 'turbines with t_rd', 'the rotor diameter in metres, twice the radius of '
-                                'the disk')):
+                               ('t_rd' in names, 'turbines with t_rd', f'the rotor diameter in metres, twice the {twice}')):
             if not ok:
-                raise ValueError(f'rotor_transits = True needs {field}: {why}')
+                raise ValueError(f'{option} = True needs {field}: {why}')
+
+    def _check_rotor_transits(self, turbines):
+        """rotor_transits counts the moves through every turbine's disk along K14's heights.  (flight_time is not among what
+        it needs.)"""
+        if self.rotor_transits:
+            self._check_rotor_yaw()
+            self._check_disk_needs('rotor_transits', turbines, 'radius of the disk')
 
     def _check_collision_risk(self, turbines):
         """collision_risk weights K18's transits with Band's probability: it needs what rotor_transits needs (not
         rotor_transits itself), and a bird and a rotor the model can be evaluated for."""
-        if not self.collision_risk:
-            return
-        names = turbines_mod._column_names(turbines) if turbines is not None else []
-        for ok, field, why in ((self.flight_height, 'flight_height=True', 'the disks are tested against the heights along '
-                                'the tracks'),
-                               (self._rotor_per_turbine(), "rotor_geometry='turbine'", "the disk is every turbine's own, "
-                                'around its hub'),
-                               (turbines is not None, 'turbines', 'none were given (Simulator(..., turbines=...))'),
-                               ('t_hh' in names, 'turbines with t_hh', 'the hub height in metres, the centre of the disk'),
-                               ('t_rd' in names, 'turbines with t_rd', 'the rotor diameter in metres, twice the length of '
-                                'a blade')):
-            if not ok:
-                raise ValueError(f'collision_risk = True needs {field}: {why}')
-        self._check_band_model('collision_risk')
+        if self.collision_risk:
+            self._check_disk_needs('collision_risk', turbines, 'length of a blade')
+            self._check_band_model('collision_risk')
 
     def _check_band_model(self, who):
         """The bird and the rotor Band's model is evaluated for, and rotor_yaw: what collision_risk and site_collision_risk
         (`who`) both read."""
-        yaw = float(self.rotor_yaw)
-        if yaw != yaw or yaw in (float('inf'), float('-inf')):
-            raise ValueError(f'rotor_yaw = {self.rotor_yaw!r}: expected degrees clockwise from north, or < 0 for the wind')
+        self._check_rotor_yaw()
         for name in ('bird_length', 'bird_wingspan'):
             if not 0. < float(getattr(self, name)) < float('inf'):
                 raise ValueError(f'{name} = {getattr(self, name)!r}: expected metres > 0 ({who})')
@@ -917,6 +912,12 @@ class Simulator(Config):
         # must not depend on the rank, or the ranks would meet in the reduce with different dtypes
         widest_share = -(-len(starts) // self._world()) if sharded else len(starts)
 
+        # everything accumulated from the trajectory chunks (ssrs_amd/products.py), in the order of that module's docstring:
+        # the constants and device uploads of this call, made once
+        products = products_mod.enabled(self)
+        # trajectories: for the pickle, or for the products (which read them on the device)
+        want_tracks = bool(self.save_tracks) or bool(products)
+
         # (case, realisation) items are independent: like the reference's loop
         # they are prepared in order on this thread (file cache, reseeding), then
         # stepped concurrently, one HIP stream per worker thread (seasonal mode
@@ -928,129 +929,33 @@ class Simulator(Config):
                     raise ValueError(f'unknown movement_model {self.movement_model!r}')
                 updrafts = self._load_updrafts_dev(case_id) if fluid else \
                     [None] * (1 + int(self.thermals_realization_count))
-                # (flight_height reads the UN-thresholded field of every item, whatever the movement model)
-                raw = self._updraft_fields(case_id, lambda fname: to_dev(np.load(fname), torch.float32)) \
-                    if self.flight_height else [None] * len(updrafts)
-                # (flight_time: one windinfo per wind case, the scalar pair in uniform mode; finished before a worker's
-                # stream reads it)
-                wind = self._time_wind(case_id) if self.flight_time else None
-                # (rotor_transits: the rotors' axes, once per case)
-                axes = self._transit_axes(case_id) if transit else None
-                # (site_collision_risk: the one axis, or the case's axis per cell, once per case)
-                site_axes = self._site_axes(case_id) if site else None
-                if torch.is_tensor(wind) or axes is not None or site_axes is not None:
-                    torch.cuda.current_stream().synchronize()
-                for (real_id, updraft), lift in zip(enumerate(updrafts), raw):
+                # what the products read per case (the wind, the rotors' axes, the un-thresholded updrafts), once per case
+                inputs = {}
+                for product in products:
+                    product.prepare(case_id, inputs)
+                for real_id, updraft in enumerate(updrafts):
                     if self.sim_seed > 0:
                         np.random.seed(self.sim_seed + real_id)
                     fields = (updraft, self._potential_dev(updraft, case_id, real_id)) if fluid \
                         else (None, None)
-                    yield (case_id, real_id, fields, self._stream_seed(real_id), lift, wind, axes, site_axes)
-
-        encounters = float(self.turbine_encounter_radius) > 0.
-        if encounters:
-            # (one upload for all cases: the kernel reads the turbines and their cull lists from the device)
-            enc_geometry = (to_dev(self._turbine_cells, torch.float64),
-                            tuple(to_dev(a, torch.int32) for a in self._turbine_bins))
-        rotor = None
-        if self._rotor_per_turbine():
-            cells, reach, zband, bins = self._rotor_cylinders
-            rotor = (to_dev(cells, torch.float64), to_dev(reach, torch.float64), to_dev(zband, torch.int32),
-                     tuple(to_dev(a, torch.int32) for a in bins))
-        occupancy = bool(self.track_occupancy)
-        passage = float(self.track_passage_radius) > 0.
-        heights = bool(self.flight_height)
-        if heights:
-            dem = to_dev(self._terrain['Elevation'], torch.float64)
-        timed = bool(self.flight_time)
-        exposure = bool(self.rotor_exposure_time)       # (the constructor saw to heights, timed and rotor)
-        collision = bool(self.collision_risk)           # (the constructor saw to heights and rotor)
-        transit = bool(self.rotor_transits) or collision
-        disks = None
-        if transit:
-            cells, reach, hub, bins = self._rotor_disks
-            disks = (to_dev(cells, torch.float64), to_dev(reach, torch.float64), to_dev(hub, torch.int32),
-                     tuple(to_dev(a, torch.int32) for a in bins))
-        classes = None
-        if collision:
-            # (the uint32 table travels as int32 bit patterns, like the bitmaps)
-            cls, table = self._collision_table
-            classes = (to_dev(cls, torch.int32), to_dev(np.ascontiguousarray(table).view(np.int32), torch.int32))
-        site = bool(self.site_collision_risk)           # (the constructor saw to heights and the class)
-        if site:
-            site_reach, site_hub_mm, site_table = self._site_class
-            site_table = to_dev(site_table.view(np.int32), torch.int32)
+                    yield SimpleNamespace(case_id=case_id, real_id=real_id, fields=fields, seed=self._stream_seed(real_id),
+                                          inputs=inputs, state={})
 
         def run(item):
-            case_id, real_id, fields, seed, lift, wind, axes, site_axes = item
-            self.last_seeds[(case_id, real_id)] = seed
-            id_str = self._get_id_string(case_id, real_id)
+            key = (item.case_id, item.real_id)
+            self.last_seeds[key] = item.seed
+            id_str = self._get_id_string(*key)
             start_time = time.time()
             with torch.cuda.stream(torch.cuda.Stream()):
-                batch = self._step_case(my_starts, lo, fields, seed, use_table, widest_share)
+                batch = self._step_case(my_starts, lo, item.fields, item.seed, use_table, widest_share, want_tracks)
                 torch.cuda.current_stream().synchronize()
                 print(f'{id_str}: Simulating {hi - lo} tracks..took {_elapsed(start_time)}',
                       flush=True)
-                # every device chunk of the trajectories goes through its consumers on the device (the encounter kernel,
-                # the occupancy kernel), then (save_tracks) on to the pickle: a replay range is stepped ONCE for all
-                consumers = []
-                if encounters:
-                    nturb = int(enc_geometry[0].shape[0])
-                    hits = torch.zeros((hi - lo, (nturb + 31) // 32), dtype=torch.int32, device=my_starts.device)
-                    first_step = torch.full((hi - lo,), -1, dtype=torch.int32, device=my_starts.device)
-                    consumers.append(self._encounter_consumer(enc_geometry, hits, first_step))
-                if occupancy:
-                    # one raster per item, accumulated over chunks and parts, and one workspace (a call leaves it zero)
-                    occ_counts = torch.zeros(self.gridsize, dtype=torch.int32, device=my_starts.device)
-                    occ_cells = torch.zeros((), dtype=torch.int64, device=my_starts.device)
-                    consumers.append(self._occupancy_consumer(hi - lo, occ_counts, occ_cells))
-                if passage:
-                    # as the occupancy: one raster per item, accumulated over chunks and parts, and one workspace
-                    pas_counts = torch.zeros(self.gridsize, dtype=torch.int32, device=my_starts.device)
-                    pas_cells = torch.zeros((), dtype=torch.int64, device=my_starts.device)
-                    consumers.append(self._passage_consumer(hi - lo, pas_counts, pas_cells))
-                if heights:
-                    # one rotor-zone raster per item, this rank's per-track rows, and (with encounters) a second bitmap
-                    # from the points in the rotor zone alone
-                    fly = dict(band_hist=torch.zeros(self.gridsize, dtype=torch.int32, device=my_starts.device),
-                               rows=torch.zeros((hi - lo, 3), dtype=torch.int32, device=my_starts.device))
-                    if encounters:
-                        fly['hits'] = torch.zeros_like(hits)
-                        fly['first_step'] = torch.full_like(first_step, -1)
-                    if rotor is not None:
-                        # every turbine's own cylinder: a third bitmap, and the points inside each (the exposure)
-                        n_rotor = int(rotor[0].shape[0])
-                        fly['rotor_hits'] = torch.zeros((hi - lo, (n_rotor + 31) // 32), dtype=torch.int32,
-                                                        device=my_starts.device)
-                        fly['rotor_first_step'] = torch.full((hi - lo,), -1, dtype=torch.int32, device=my_starts.device)
-                        fly['rotor_points'] = torch.zeros(n_rotor, dtype=torch.int64, device=my_starts.device)
-                        if exposure:
-                            fly['rotor_time'] = torch.zeros(n_rotor, dtype=torch.int64, device=my_starts.device)
-                        if transit:
-                            # the disks: a fourth bitmap, and the transits of each by direction
-                            fly['transit_hits'] = torch.zeros_like(fly['rotor_hits'])
-                            fly['transits'] = torch.zeros((n_rotor, 2), dtype=torch.int64, device=my_starts.device)
-                        if collision:
-                            # their summed collision probabilities, by turbine and direction and by track
-                            fly['risk'] = torch.zeros((n_rotor, 2), dtype=torch.int64, device=my_starts.device)
-                            fly['track_risk'] = torch.zeros((hi - lo,), dtype=torch.int64, device=my_starts.device)
-                    if site:
-                        # a candidate turbine on every cell: its summed collision probabilities and its transits, by direction
-                        fly['site_risk'] = torch.zeros(tuple(self.gridsize) + (2,), dtype=torch.int64, device=my_starts.device)
-                        fly['site_transits'] = torch.zeros_like(fly['site_risk'])
-                    consumers.append(self._flight_consumer(lift, dem, fly, enc_geometry if encounters else None, rotor,
-                                                           keep_masked=timed, defer_rotor=exposure,
-                                                           transit=(disks, axes, classes) if transit else None,
-                                                           site=(site_reach, site_hub_mm, site_axes, site_table) if site else None))
-                if timed:
-                    # after the flight consumer, whose traj_band of the chunk it reads: one raster of microseconds per
-                    # item (two with flight_height), accumulated over chunks and parts, and this rank's per-track rows
-                    spent = dict(time_hist=torch.zeros(self.gridsize, dtype=torch.int64, device=my_starts.device),
-                                 rows=torch.zeros((hi - lo, 2), dtype=torch.int64, device=my_starts.device))
-                    if heights:
-                        spent['band_time_hist'] = torch.zeros_like(spent['time_hist'])
-                    consumers.append(self._time_consumer(wind, spent, fly if heights else None, rotor if exposure else None))
-                chunks = self._device_chunks(batch, consumers) if consumers else None
+                for product in products:
+                    item.state[product] = product.begin(item, hi - lo, my_starts.device)
+                # every device chunk of the trajectories goes through the products on the device, then (save_tracks) on to
+                # the pickle: a replay range is stepped ONCE for all
+                chunks = self._device_chunks(batch, products, item.state) if products else None
                 if self.save_tracks:
                     # (inside the stream's scope: long trajectories are stepped again range by range while written)
                     need = sum(b.total_points for b in batch.parts) * 4
@@ -1063,7 +968,7 @@ class Simulator(Config):
                             f'{id_str}: the trajectories of these {len(starts)} tracks are {need / 2 ** 30:.1f} GiB '
                             f'(Sum lengths x 4 B; max_tracks_file_gb = {self.max_tracks_file_gb:g}): on fields where '
                             'tracks wander to max_moves run with save_tracks=False, or raise max_tracks_file_gb')
-                    fname = self._get_tracks_fname(case_id, real_id, self.mode_data_dir)
+                    fname = self._get_tracks_fname(item.case_id, item.real_id, self.mode_data_dir)
                     tracks = (t for b in batch.parts for t in b.iter_tracks()) if chunks is None else \
                         (t for traj, off in chunks for t in movmodel.TrackBatch.host_tracks(traj, off))
                     self._write_tracks(fname, tracks, sharded)
@@ -1071,26 +976,12 @@ class Simulator(Config):
                 elif chunks is not None:
                     for _ in chunks:
                         pass
-                if encounters:
-                    per_turbine, per_track = turbines_mod.encounter_counts(hits, nturb)
-                    # (track-sharded: the sum over the ranks is a collective, issued here in item order like the rest)
-                    self._store_encounters(case_id, real_id, per_turbine.cpu().numpy(), per_track.cpu().numpy(),
-                                           first_step.cpu().numpy(), sharded)
-                if occupancy:
-                    # (track-sharded: the sum over the ranks is a collective as well, after the encounters' in every item)
-                    self._store_occupancy(case_id, real_id, occ_counts, int(occ_cells.item()), sharded)
-                if passage:
-                    # (track-sharded: after the occupancy's collective in every item)
-                    self._store_passage(case_id, real_id, pas_counts, int(pas_cells.item()), sharded)
-                if heights:
-                    # (track-sharded: its collectives come last in every item)
-                    self._store_flight(case_id, real_id, fly, nturb if encounters else 0, sharded)
-                if timed:
-                    # (track-sharded: after the heights' collectives in every item)
-                    self._store_flight_time(case_id, real_id, spent, sharded)
+                # (track-sharded: every store is a collective or several, issued here in list and item order like the rest)
+                for product in products:
+                    product.store(item.state[product], key, sharded)
             if sharded:
                 batch.hist = distributed.reduce_histogram(batch.hist, all_ranks=True)
-            return (case_id, real_id), batch
+            return key, batch
 
         nitems = max(1, len(self.my_case_ids())) * (1 + int(self.thermals_realization_count))
         # collectives of the track-sharded form must be issued in the same order on every rank
@@ -1121,53 +1012,18 @@ class Simulator(Config):
                 collect(f.result() for f in pending)
 
     @staticmethod
-    def _device_chunks(batch, consumers):
-        """The device chunks (traj, offsets) of every part of `batch` in track order, each one handed to every
-        consumer(first track, end track, traj, offsets) -- track numbers within the batch -- before it is handed on."""
+    def _device_chunks(batch, products, states):
+        """The device chunks (traj, offsets) of every part of `batch` in track order, each one handed as a `Chunk` -- its
+        track numbers within the batch -- to every product in list order before it is handed on."""
         base = 0
         for part in batch.parts:
             for t0, t1, traj, off in part.iter_device_chunks():
-                for consume in consumers:
-                    consume(base + t0, base + t1, traj, off)
+                chunk = products_mod.Chunk(base + t0, base + t1, traj, off)
+                for product in products:
+                    product.consume(states[product], chunk)
+                del chunk                   # (its masked / alt / dt go before the chunk is handed on)
                 yield traj, off
             base += int(part.lengths.numel())
-
-    def _encounter_consumer(self, geometry, hits, first_step):
-        """A chunk through the encounter kernel, into its rows of `hits` / `first_step`."""
-        xy, bins = geometry
-        radius_cells = float(self.turbine_encounter_radius) / float(self.resolution)
-
-        def consume(t0, t1, traj, off):
-            turbines_mod.turbine_encounters(traj, off, xy, radius_cells, self.gridsize, bins=bins,
-                                            hits=hits[t0:t1], first_step=first_step[t0:t1])
-        return consume
-
-    def _occupancy_consumer(self, ntracks, counts, cells):
-        """A chunk through the occupancy kernel: `counts` (the item's raster) is added to, `cells` (a 0-d int64 tensor)
-        gets the sum of the chunk's cells_per_track, the checksum of _store_occupancy.  One zeroed workspace serves
-        every chunk of the item."""
-        planes = presence.occupancy_planes(ntracks, self.gridsize)
-        workspace = presence.occupancy_workspace(self.gridsize, planes)
-
-        def consume(t0, t1, traj, off):
-            _, per_track = presence.compute_track_occupancy(traj, self.gridsize, offsets=off, counts=counts,
-                                                            cells_per_track=True, planes=planes, workspace=workspace)
-            cells.add_(per_track.sum(dtype=torch.int64))
-        return consume
-
-    def _passage_consumer(self, ntracks, counts, cells):
-        """A chunk through the passage kernel (K17): `counts` (the item's raster) is added to, `cells` (a 0-d int64 tensor)
-        gets the sum of the chunk's cells_per_track, the checksum of _store_passage.  One workspace serves every chunk of
-        the item (scratch: a call clears what it uses)."""
-        planes = presence.occupancy_planes(ntracks, self.gridsize)
-        workspace = presence.passage_workspace(self.gridsize, planes)
-        r2 = presence.passage_r2(self.track_passage_radius, self.resolution)
-
-        def consume(t0, t1, traj, off):
-            _, per_track = presence.compute_track_passage(traj, self.gridsize, r2, offsets=off, counts=counts,
-                                                          cells_per_track=True, planes=planes, workspace=workspace)
-            cells.add_(per_track.sum(dtype=torch.int64))
-        return consume
 
     def _flight_params(self):
         """(heights in metres for flight.compute_track_altitudes, airspeed, sink rate) of the flight_* fields, checked."""
@@ -1184,100 +1040,6 @@ class Simulator(Config):
         flight.height_params(who='Config.flight_height_* / rotor_zone', **kw)
         return kw, airspeed, sink
 
-    def _flight_consumer(self, lift, dem, fly, geometry, rotor=None, keep_masked=False, defer_rotor=False, transit=None,
-                         site=None):
-        """A chunk through the flight-height scan (K14): `fly['band_hist']` is added to, the chunk's tracks get their rows of
-        `fly['rows']`; with `geometry` the points in the rotor zone go through the encounter kernel into `fly['hits']` /
-        `fly['first_step']`; with `rotor` (the cylinders on the device) the points and their heights go through the rotor
-        kernel (K15) into `fly['rotor_hits']` / `fly['rotor_first_step']` / `fly['rotor_points']`.  The item's cellinfo is
-        built here, from its un-thresholded updraft `lift` and the DEM.  keep_masked: the chunk's traj_band stays in
-        `fly['masked']` for the consumer behind this one (_time_consumer).  defer_rotor (rotor_exposure_time): the rotor
-        kernel is not called here but behind K16, where the chunk's dt exists: the chunk's alt stays in `fly['alt']` and the
-        item's cellinfo in `fly['cellinfo']` for _time_consumer.  transit (rotor_transits, collision_risk): ((cells, reach, hub,
-        bins) on the device, the case's axes, (cls, table) on the device or None): the chunk and its alt also go through the
-        transit kernel (K18), here in either case, into `fly['transit_hits']` / `fly['transits']` -- or, with (cls, table),
-        through the collision-risk kernel (K19), whose one pass gives the same two and `fly['risk']` / `fly['track_risk']`.
-        site (site_collision_risk): (reach in cells, hub_mm, the axis or the axes per cell, the class's table) on the device:
-        the chunk and its alt also go through the site kernel (K20) into `fly['site_risk']` / `fly['site_transits']`."""
-        kw, airspeed, sink = self._flight_params()
-        cellinfo = flight.altitude_cellinfo(lift, dem, self.resolution, airspeed, sink)
-        if defer_rotor:
-            fly['cellinfo'] = cellinfo
-        radius_cells = float(self.turbine_encounter_radius) / float(self.resolution)
-
-        def consume(t0, t1, traj, off):
-            out = flight.compute_track_altitudes(traj, cellinfo, self.gridsize, offsets=off, band_hist=fly['band_hist'],
-                                                 want_masked=geometry is not None or keep_masked,
-                                                 want_alt=rotor is not None or site is not None, **kw)
-            fly['rows'][t0:t1] = out['heights']
-            if keep_masked:
-                fly['masked'] = out['masked']
-            if defer_rotor:
-                fly['alt'] = out['alt']
-            elif rotor is not None:
-                cells, reach, zband, rotor_bins = rotor
-                turbines_mod.rotor_encounters(traj, out['alt'], off, cellinfo, cells, reach, zband, self.gridsize,
-                                              bins=rotor_bins, hits=fly['rotor_hits'][t0:t1],
-                                              first_step=fly['rotor_first_step'][t0:t1], points=fly['rotor_points'])
-            if transit is not None:
-                (cells, reach, hub, disk_bins), axes, classes = transit
-                if classes is None:
-                    turbines_mod.rotor_transits(traj, out['alt'], off, cellinfo, cells, reach, hub, axes, self.gridsize,
-                                                self.resolution, bins=disk_bins, hits=fly['transit_hits'][t0:t1],
-                                                transits=fly['transits'])
-                else:
-                    turbines_mod.rotor_collision_risk(traj, out['alt'], off, cellinfo, cells, reach, hub, axes, *classes,
-                                                      self.gridsize, self.resolution, bins=disk_bins,
-                                                      hits=fly['transit_hits'][t0:t1], transits=fly['transits'],
-                                                      risk=fly['risk'], track_risk=fly['track_risk'][t0:t1])
-            if site is not None:
-                reach, hub_mm, site_axes, table = site
-                turbines_mod.site_collision_risk(traj, out['alt'], off, cellinfo, reach, hub_mm, site_axes, table, self.gridsize,
-                                                 self.resolution, transits=fly['site_transits'], risk=fly['site_risk'])
-            if geometry is not None:
-                xy, bins = geometry
-                turbines_mod.turbine_encounters(out['masked'], off, xy, radius_cells, self.gridsize, bins=bins,
-                                                hits=fly['hits'][t0:t1], first_step=fly['first_step'][t0:t1])
-        return consume
-
-    def _transit_axes(self, case_id):
-        """The rotors' axes of one case (turbines.rotor_axes, on the device): rotor_yaw >= 0 is that compass direction for
-        every turbine; otherwise every rotor faces the wind K16 reads -- uniform_winddirn in uniform mode, else the case's
-        wdirn raster (_wind_rasters, at wtk_orographic_height) at the cell the turbine stands on -- in the frame of
-        _time_ray_axes().  A NaN direction gives a turbine nothing can transit; one warning says how many."""
-        cells = self._rotor_disks[0]
-        nturb = int(cells.shape[0])
-        if float(self.rotor_yaw) >= 0.:
-            wdirn = float(self.rotor_yaw)
-        elif self.sim_mode.lower() == 'uniform':
-            wdirn = float(self.uniform_winddirn)
-        else:
-            entry = next(w for w in self._wind if w.case_id == case_id)
-            rb, cb, known = turbines_mod.base_cells(cells, self.gridsize)
-            raster = self._wind_rasters(entry)[1]
-            wdirn = raster[torch.from_numpy(rb).to(raster.device), torch.from_numpy(cb).to(raster.device)].cpu().numpy()
-            wdirn = np.where(known, wdirn.astype(np.float64), np.nan)
-        axes = turbines_mod.rotor_axes(wdirn, self._time_ray_axes(), nturb)
-        lost = int(np.isnan(axes).any(1).sum())
-        if lost:
-            warnings.warn(f'rotor_transits: {case_id}: {lost} of the {nturb} turbines have no wind direction (NaN) at the '
-                          'cell they stand on; nothing transits them')
-        return to_dev(axes, torch.float64)
-
-    def _site_axes(self, case_id):
-        """The axis of the candidate turbines of one case, on the device: rotor_yaw >= 0 is that compass direction, and in
-        uniform mode the rotors face uniform_winddirn -- one pair [ax, ay] for all sites; otherwise every site faces the wind
-        of its own cell, the case's wdirn raster (_wind_rasters, at wtk_orographic_height) through layers.ray_step in the
-        frame of _time_ray_axes(): f64 (rows, cols, 2), 16 B a cell on the device.  A NaN direction gives a site nothing can
-        transit."""
-        if float(self.rotor_yaw) >= 0. or self.sim_mode.lower() == 'uniform':
-            wdirn = float(self.rotor_yaw) if float(self.rotor_yaw) >= 0. else float(self.uniform_winddirn)
-            return to_dev(turbines_mod.rotor_axes(wdirn, self._time_ray_axes())[0], torch.float64)
-        entry = next(w for w in self._wind if w.case_id == case_id)
-        wdirn = self._wind_rasters(entry)[1].cpu().numpy().astype(np.float64).reshape(-1)
-        axes = turbines_mod.rotor_axes(wdirn, self._time_ray_axes())
-        return to_dev(axes.reshape(tuple(self.gridsize) + (2,)), torch.float64)
-
     def _time_params(self):
         """Keyword arguments of flight.compute_track_times from the resolution and the flight_* fields, checked."""
         kw = dict(resolution=self.resolution, airspeed=self.flight_airspeed, min_groundspeed=self.flight_min_groundspeed)
@@ -1288,248 +1050,12 @@ class Simulator(Config):
         """The frame of the wind's components: that of the aspect, as _improved_args chooses the shelter ray's."""
         return 'row_north' if 'Slope' in self._terrain or 'Aspect' in self._terrain else 'row_east'
 
-    def _time_wind(self, case_id):
-        """The wind compute_track_times reads for one case: the scalar pair in uniform mode, otherwise the windinfo raster
-        of the case's per-cell wind (_wind_rasters, at wtk_orographic_height)."""
-        if self.sim_mode.lower() == 'uniform':
-            return float(self.uniform_windspeed), float(self.uniform_winddirn)
-        entry = next(w for w in self._wind if w.case_id == case_id)
-        return flight.wind_cellinfo(*self._wind_rasters(entry), self._time_ray_axes())
-
-    def _time_consumer(self, wind, spent, fly, rotor=None):
-        """A chunk through the flight-time kernel (K16): `spent['time_hist']` (and, with `fly`, the flight consumer's dict
-        whose 'masked' is the chunk's traj_band, `spent['band_time_hist']`) is added to, the chunk's tracks get their rows
-        of `spent['rows']`.  With `rotor` (rotor_exposure_time: the cylinders on the device) the chunk's dt is kept and the
-        rotor kernel runs here in its timed form, on the chunk's alt that the flight consumer left in `fly['alt']`, into
-        `fly['rotor_hits']` / `fly['rotor_first_step']` / `fly['rotor_points']` / `fly['rotor_time']`."""
-        kw = self._time_params()
-        ray_axes = self._time_ray_axes()
-
-        def consume(t0, t1, traj, off):
-            out = flight.compute_track_times(traj, self.gridsize, offsets=off, wind=wind, ray_axes=ray_axes,
-                                             masked=None if fly is None else fly.pop('masked'),
-                                             time_hist=spent['time_hist'], band_time_hist=spent.get('band_time_hist'),
-                                             want_dt=rotor is not None, **kw)
-            spent['rows'][t0:t1] = out['times']
-            if rotor is not None:
-                cells, reach, zband, rotor_bins = rotor
-                turbines_mod.rotor_encounters(traj, fly.pop('alt'), off, fly['cellinfo'], cells, reach, zband, self.gridsize,
-                                              bins=rotor_bins, hits=fly['rotor_hits'][t0:t1],
-                                              first_step=fly['rotor_first_step'][t0:t1], points=fly['rotor_points'],
-                                              dt=out['dt'], time=fly['rotor_time'])
-        return consume
-
-    def _store_flight_time(self, case_id, real_id, spent, sharded):
-        """Keeps the flight-time rasters and the per-track rows of one (case, realisation) and writes
-        <id>_residence_time.npy (int64 holding uint64 microseconds), <id>_flight_times.npy (int64 (tracks, 2): [total, in
-        the rotor zone]) and, with flight_height, <id>_rotor_residence_time.npy.  Checked by its checksums: each raster of
-        this rank must add up, modulo 2^64, to its column of the rows.  Track-sharded runs sum the rasters over the ranks
-        as _store_flight does and rank 0 writes; the per-track rows stay this rank's tracks, and <id>_flight_times.npy
-        is then rank 0's share."""
-        id_str = self._get_id_string(case_id, real_id)
-        rows = spent['rows']
-        names = (('time_hist', 0, 'residence_time', self.residence_time_counts),
-                 ('band_time_hist', 1, 'rotor_residence_time', self.rotor_residence_time_counts))
-        key = (case_id, real_id)
-        writes = not sharded or self._rank() == 0
-        for name, column, stem, keep in names:
-            if name not in spent:
-                continue
-            raster = spent[name]
-            # (int64 sums wrap like the uint64 ones they hold: equal modulo 2^64 is equal here)
-            counted, summed = int(raster.sum().item()), int(rows[:, column].sum().item())
-            if counted != summed:
-                raise RuntimeError(f'{id_str}: flight time: the {stem} raster adds up to {counted % 2 ** 64} us, the tracks '
-                                   f'to {summed % 2 ** 64} us')
-            if sharded:
-                raster = distributed.reduce_histogram(raster, all_ranks=True)
-            keep[key] = raster.cpu().numpy()
-            if writes:
-                np.save(os.path.join(self.mode_data_dir, f'{id_str}_{stem}.npy'), keep[key])
-        self.flight_times[key] = rows.cpu().numpy()
-        if writes:
-            np.save(os.path.join(self.mode_data_dir, f'{id_str}_flight_times.npy'), self.flight_times[key])
-
-    def _store_flight(self, case_id, real_id, fly, nturb, sharded):
-        """Keeps the rotor-zone raster and the per-track heights of one (case, realisation) and writes
-        <id>_rotor_presence.npy (int32 holding uint32) and <id>_flight_heights.npy (int32 (tracks, 3): [points in the zone,
-        least, greatest height in mm]); with encounters also <id>_rotor_turbine_encounters.npy; with rotor_geometry = 'turbine'
-        <id>_turbine_rotor_encounters.npy and, with rotor_exposure_time, <id>_turbine_rotor_time.npy (int64 (nturb,)
-        microseconds, refused when a turbine has time without points or more than points x (2^31 - 1)).  Checked by its checksum:
-        this rank's raster must add up to the in-zone points of its tracks.  Track-sharded runs sum the raster (and the
-        per-turbine counts) over the ranks as _store_occupancy does and rank 0 writes the raster; the per-track rows stay
-        this rank's tracks, like first_step, and <id>_flight_heights.npy is then rank 0's share."""
-        id_str = self._get_id_string(case_id, real_id)
-        counts, rows = fly['band_hist'], fly['rows']
-        counted = int((counts.to(torch.int64) & 0xFFFFFFFF).sum().item())
-        in_zone = int(rows[:, 0].sum(dtype=torch.int64).item())
-        if counted != in_zone:
-            raise RuntimeError(f'{id_str}: rotor presence: the raster adds up to {counted}, the in-zone points of the '
-                               f'tracks to {in_zone}')
-        if sharded:
-            counts = distributed.reduce_histogram(counts, all_ranks=True)
-        key = (case_id, real_id)
-        self.rotor_presence_counts[key] = counts.to(torch.int32).cpu().numpy()
-        self.flight_heights[key] = rows.cpu().numpy()
-        writes = not sharded or self._rank() == 0
-        if writes:
-            np.save(os.path.join(self.mode_data_dir, f'{id_str}_rotor_presence.npy'), self.rotor_presence_counts[key])
-            np.save(os.path.join(self.mode_data_dir, f'{id_str}_flight_heights.npy'), self.flight_heights[key])
-        if 'hits' in fly:
-            per_turbine, per_track = turbines_mod.encounter_counts(fly['hits'], nturb)
-            per_turbine = per_turbine.cpu().numpy().astype(np.int64)
-            if sharded:
-                per_turbine = np.asarray(self._allreduce_sum(per_turbine), dtype=np.int64)
-            self.rotor_turbine_encounters[key] = dict(
-                tracks_per_turbine=per_turbine, turbines_per_track=per_track.cpu().numpy().astype(np.int32),
-                first_step=fly['first_step'].cpu().numpy().astype(np.int32))
-            if writes:
-                np.save(os.path.join(self.mode_data_dir, f'{id_str}_rotor_turbine_encounters.npy'), per_turbine)
-        if 'rotor_hits' in fly:
-            # rotor_geometry = 'turbine': <id>_turbine_rotor_encounters.npy, int64 (nturb, 2) [tracks, points]; track-sharded
-            # runs sum both columns over the ranks, the per-track rows stay this rank's
-            per_turbine, per_track = turbines_mod.encounter_counts(fly['rotor_hits'], int(fly['rotor_points'].numel()))
-            both = torch.stack([per_turbine, fly['rotor_points']], 1).cpu().numpy().astype(np.int64)
-            spent = fly['rotor_time'].cpu().numpy().astype(np.int64) if 'rotor_time' in fly else None
-            if spent is not None:
-                # rotor_exposure_time: the cheap invariant that stands in for a checksum -- K16 writes 0 <= dt <= 2^31 - 1, so
-                # a turbine's time is at most that much per point inside it, and none without a point
-                # (Python integers: points x (2^31 - 1) passes int64 from 2^32 points on)
-                most = both[:, 1].astype(object) * (2 ** 31 - 1)
-                wrong = np.nonzero((spent < 0) | (spent.astype(object) > most).astype(bool))[0]
-                if wrong.size:
-                    t = int(wrong[0])
-                    raise RuntimeError(f'{id_str}: rotor exposure time: turbine {t} has {int(spent[t]) % 2 ** 64} us for '
-                                       f'{int(both[t, 1])} points inside its cylinder ({wrong.size} turbines like it)')
-            if sharded:
-                both = np.asarray(self._allreduce_sum(both.reshape(-1)), dtype=np.int64).reshape(-1, 2)
-                if spent is not None:
-                    spent = np.asarray(self._allreduce_sum(spent), dtype=np.int64)
-            self.turbine_rotor_encounters[key] = dict(
-                tracks_per_turbine=both[:, 0].copy(), points_per_turbine=both[:, 1].copy(),
-                turbines_per_track=per_track.cpu().numpy().astype(np.int32),
-                first_step=fly['rotor_first_step'].cpu().numpy().astype(np.int32))
-            if spent is not None:
-                # <id>_turbine_rotor_time.npy, int64 (nturb,) microseconds
-                self.turbine_rotor_encounters[key]['time_per_turbine'] = spent
-            if writes:
-                np.save(os.path.join(self.mode_data_dir, f'{id_str}_turbine_rotor_encounters.npy'), both)
-                if spent is not None:
-                    np.save(os.path.join(self.mode_data_dir, f'{id_str}_turbine_rotor_time.npy'), spent)
-        if 'risk' in fly:
-            # collision_risk: <id>_turbine_collision_risk.npy, int64 (nturb, 2) raw sums in units of 2^-32 [with the wind,
-            # against the wind], and <id>_track_collision_risk.npy, int64 (tracks,).  The invariants that stand in for a
-            # checksum: a transit adds less than 2^32, and the tracks' sums add up to the turbines'.  Track-sharded runs sum
-            # the per-turbine columns over the ranks like the transits (untested on more than one rank); the per-track
-            # rows stay this rank's tracks, like first_step, and the file is then rank 0's share
-            risk = fly['risk'].cpu().numpy().astype(np.int64)
-            per_track = fly['track_risk'].cpu().numpy().astype(np.int64)
-            passes = fly['transits'].cpu().numpy().astype(np.int64)
-            wrong = np.nonzero(((risk < 0) | (risk.astype(object) > passes.astype(object) * (2 ** 32 - 1)).astype(bool)).any(1))[0]
-            if wrong.size:
-                t = int(wrong[0])
-                raise RuntimeError(f'{id_str}: collision risk: turbine {t} has the sums {risk[t].tolist()} (2^-32) for '
-                                   f'{passes[t].tolist()} transits ({wrong.size} turbines like it)')
-            if int(per_track.astype(object).sum()) != int(risk.astype(object).sum()):
-                raise RuntimeError(f'{id_str}: collision risk: the tracks add up to {int(per_track.astype(object).sum())}, '
-                                   f'the turbines to {int(risk.astype(object).sum())} (2^-32)')
-            if sharded:
-                risk = np.asarray(self._allreduce_sum(risk.reshape(-1)), dtype=np.int64).reshape(-1, 2)
-            self.turbine_collision_risk[key] = risk
-            self.track_collision_risk[key] = per_track
-            if writes:
-                np.save(os.path.join(self.mode_data_dir, f'{id_str}_turbine_collision_risk.npy'), risk)
-                np.save(os.path.join(self.mode_data_dir, f'{id_str}_track_collision_risk.npy'), per_track)
-        if 'site_risk' in fly:
-            # site_collision_risk: <id>_site_collision_risk.npy, int64 (rows, cols, 2) raw sums in units of 2^-32 [with the
-            # wind, against the wind], and <id>_site_transits.npy, int64 (rows, cols, 2).  The invariant that stands in for a
-            # checksum: a transit adds less than 2^32.  Track-sharded runs sum both rasters over the ranks as the other
-            # rasters are summed (untested on more than one rank)
-            risk, passes = fly['site_risk'], fly['site_transits']
-            if sharded:
-                risk = distributed.reduce_histogram(risk, all_ranks=True)
-                passes = distributed.reduce_histogram(passes, all_ranks=True)
-            risk, passes = risk.cpu().numpy().astype(np.int64), passes.cpu().numpy().astype(np.int64)
-            # (sum <= transits x (2^32 - 1) as ceil(sum / (2^32 - 1)) <= transits: the product passes int64 from 2^31 transits
-            # on; a negative sum is a wrapped one)
-            wrong = np.argwhere((risk < 0) | (passes < 0) | ((risk + (2 ** 32 - 2)) // (2 ** 32 - 1) > passes))
-            if wrong.size:
-                r, c, d = (int(v) for v in wrong[0])
-                raise RuntimeError(f'{id_str}: site collision risk: cell ({r}, {c}) has the sum {int(risk[r, c, d])} (2^-32) for '
-                                   f'{int(passes[r, c, d])} transits in direction {d} ({wrong.shape[0]} entries like it)')
-            self.site_collision_risk_sums[key] = risk
-            self.site_transit_counts[key] = passes
-            if writes:
-                np.save(os.path.join(self.mode_data_dir, f'{id_str}_site_collision_risk.npy'), risk)
-                np.save(os.path.join(self.mode_data_dir, f'{id_str}_site_transits.npy'), passes)
-        if 'transit_hits' in fly and self.rotor_transits:
-            # rotor_transits: <id>_turbine_rotor_transits.npy, int64 (nturb, 3) [tracks, with the wind, against the wind].
-            # The cheap invariant that stands in for a checksum: a turbine has tracks iff it has transits.  Track-sharded
-            # runs sum the three columns over the ranks like the other per-turbine counts (untested on more than one rank)
-            per_turbine, _ = turbines_mod.encounter_counts(fly['transit_hits'], int(fly['transits'].shape[0]))
-            three = torch.cat([per_turbine[:, None], fly['transits']], 1).cpu().numpy().astype(np.int64)
-            wrong = np.nonzero((three[:, 0] > 0) != (three[:, 1:].sum(1) > 0))[0]
-            if wrong.size:
-                t = int(wrong[0])
-                raise RuntimeError(f'{id_str}: rotor transits: turbine {t} has {int(three[t, 0])} tracks for '
-                                   f'{int(three[t, 1])} + {int(three[t, 2])} transits ({wrong.size} turbines like it)')
-            if sharded:
-                three = np.asarray(self._allreduce_sum(three.reshape(-1)), dtype=np.int64).reshape(-1, 3)
-            self.turbine_rotor_transits[key] = three
-            if writes:
-                np.save(os.path.join(self.mode_data_dir, f'{id_str}_turbine_rotor_transits.npy'), three)
-
-    def _store_occupancy(self, case_id, real_id, counts, cells, sharded):
-        """Keeps the occupancy raster of one (case, realisation) as numpy int32 and writes <id>_occupancy.npy.  Checked
-        like the histogram by its checksum: this rank's counts must add up to the sum of its cells_per_track (`cells`).
-        Track-sharded runs then sum the raster over the ranks the way the histogram is summed (shards hold disjoint
-        tracks, so the sum is exact; every rank must call this, in the same item order) and rank 0 writes; otherwise
-        the rank that owns the case does."""
-        id_str = self._get_id_string(case_id, real_id)
-        counted = int((counts.to(torch.int64) & 0xFFFFFFFF).sum().item())
-        if counted != int(cells):
-            raise RuntimeError(f'{id_str}: track occupancy: the raster adds up to {counted}, the distinct cells of the '
-                               f'tracks to {int(cells)}')
-        if sharded:
-            counts = distributed.reduce_histogram(counts, all_ranks=True)
-        self.track_occupancy_counts[(case_id, real_id)] = counts.to(torch.int32).cpu().numpy()
-        if not sharded or self._rank() == 0:
-            np.save(os.path.join(self.mode_data_dir, f'{id_str}_occupancy.npy'), self.track_occupancy_counts[(case_id, real_id)])
-
-    def _store_passage(self, case_id, real_id, counts, cells, sharded):
-        """Keeps the passage raster of one (case, realisation) as numpy int32 and writes <id>_passage.npy: checksum, sum
-        over the ranks of a track-sharded run and writer exactly as _store_occupancy."""
-        id_str = self._get_id_string(case_id, real_id)
-        counted = int((counts.to(torch.int64) & 0xFFFFFFFF).sum().item())
-        if counted != int(cells):
-            raise RuntimeError(f'{id_str}: track passage: the raster adds up to {counted}, the cells within the radius of '
-                               f'the tracks to {int(cells)}')
-        if sharded:
-            counts = distributed.reduce_histogram(counts, all_ranks=True)
-        self.track_passage_counts[(case_id, real_id)] = counts.to(torch.int32).cpu().numpy()
-        if not sharded or self._rank() == 0:
-            np.save(os.path.join(self.mode_data_dir, f'{id_str}_passage.npy'), self.track_passage_counts[(case_id, real_id)])
-
-    def _store_encounters(self, case_id, real_id, tracks_per_turbine, turbines_per_track, first_step, sharded):
-        """Keeps the encounters of one (case, realisation) and writes <id>_turbine_encounters.npy (int64 (nturb,): the
-        tracks that came within turbine_encounter_radius of each turbine).  Track-sharded runs sum the per-turbine
-        counts over the ranks (every rank must call this, in the same item order) and rank 0 writes; otherwise the
-        rank that owns the case does.  turbines_per_track / first_step stay this rank's tracks."""
-        per_turbine = np.asarray(tracks_per_turbine, dtype=np.int64)
-        if sharded:
-            per_turbine = np.asarray(self._allreduce_sum(per_turbine), dtype=np.int64)
-        self.turbine_encounters[(case_id, real_id)] = dict(
-            tracks_per_turbine=per_turbine, turbines_per_track=np.asarray(turbines_per_track, dtype=np.int32),
-            first_step=np.asarray(first_step, dtype=np.int32))
-        if not sharded or self._rank() == 0:
-            fname = os.path.join(self.mode_data_dir, f'{self._get_id_string(case_id, real_id)}_turbine_encounters')
-            np.save(f'{fname}.npy', per_turbine)
-
     _MIN_SPLIT_TRACKS = 64          # a wrapped sub-batch smaller than twice this is an error, not a split
     _HIST64_FROM_TRACKS = 100_000   # sub-batches larger than this count in 64 bits (when no trajectories are asked for)
 
-    def _step_case(self, my_starts, lo, fields, seed, use_table, widest_share=None):
-        """The tracks of one (case, realisation) on this rank.  The presence histogram is uint32 (the
+    def _step_case(self, my_starts, lo, fields, seed, use_table, widest_share=None, want_tracks=None):
+        """The tracks of one (case, realisation) on this rank; want_tracks: with their trajectories, for the pickle or for
+        the track products (None: as save_tracks says).  The presence histogram is uint32 (the
         reference's int16 wraps at 32 767, movmodel.py:415): a trap cell of the solved 10 m field takes
         ~1e9 visits per 100k tracks, so more than `hist_safe_tracks` tracks are stepped in sub-batches whose
         histograms are added up in 64 bits (K4 takes that form), and every sub-batch is checked by its
@@ -1542,9 +1068,8 @@ class Simulator(Config):
         # short last sub-batch would cost a full pass's time for a fraction of the work
         step = max(1, -(-n // max(1, -(-n // safe))))
         parts, wide, stats = [], None, None
-        # trajectories: for the pickle, or for the turbine encounters / the track occupancy (which read them on the device)
-        want_tracks = bool(self.save_tracks) or float(self.turbine_encounter_radius) > 0. or bool(self.track_occupancy) or \
-            bool(self.flight_height) or bool(self.flight_time) or float(self.track_passage_radius) > 0.
+        if want_tracks is None:
+            want_tracks = bool(self.save_tracks)
         # (start, length) of the sub-batches still to step, in track-id order; one whose uint32 counts wrapped is stepped
         # again as two halves, added up in 64 bits like the rest
         todo = [(t0, min(step, n - t0)) for t0 in range(0, max(n, 1), step)]
@@ -1689,10 +1214,7 @@ class Simulator(Config):
         the f32 summary map and writes summary_presence.npy."""
         out, self.case_presence = self._presence_summary(
             presence.presence_kernel_radius(radius, self.resolution, self.gridsize))
-        if self._rank() == 0:
-            np.save(os.path.join(self.mode_data_dir, 'summary_presence.npy'), out)
-        self._barrier()
-        return out
+        return self._save_summary('presence', out)
 
     def compute_rotor_presence_map(self, radius: float = 1000.):
         """compute_presence_map of the points in the rotor zone alone (flight_height=True): the same ladder
@@ -1704,10 +1226,7 @@ class Simulator(Config):
             presence.presence_kernel_radius(radius, self.resolution, self.gridsize),
             counts_for=lambda case_id, real_id: to_dev(self.rotor_presence_counts[(case_id, real_id)], torch.int32),
             may_be_empty=True)
-        if self._rank() == 0:
-            np.save(os.path.join(self.mode_data_dir, 'summary_rotor_presence.npy'), out)
-        self._barrier()
-        return out
+        return self._save_summary('rotor_presence', out)
 
     def _time_share_map(self, counts, radius, fname, what):
         if not counts:
@@ -1762,6 +1281,31 @@ class Simulator(Config):
         self._barrier()
         return out, window
 
+    def _item_mean(self, items):
+        """The mean over all (case, realisation) items of the f64 arrays `items` (numpy, or tensors on the device), added up
+        in the order given -- the callers give sorted keys -- with the number of items behind them; case-sharded runs sum
+        both over the ranks, so the mean is over every rank's items."""
+        total, nitems = 0., 0.
+        for item in items:
+            total, nitems = total + item, nitems + 1.
+        if self._world() > 1 and not self._shards_tracks():
+            # the cases of the other ranks
+            flat = total.cpu().numpy() if torch.is_tensor(total) else total
+            summed = np.asarray(self._allreduce_sum(np.append(flat.ravel(), nitems)))
+            mean = summed[:-1].reshape(flat.shape)
+            total, nitems = to_dev(mean, torch.float64) if torch.is_tensor(total) else mean, float(summed[-1])
+        return total / nitems
+
+    def _save_summary(self, name, out):
+        """summary_<name>.npy, written by rank 0; every rank returns `out` behind the barrier."""
+        if self._rank() == 0:
+            np.save(os.path.join(self.mode_data_dir, f'summary_{name}.npy'), out)
+        self._barrier()
+        return out
+
+    def _sorted_items(self, per_item):
+        return [per_item[key] for key in sorted(per_item)]
+
     def compute_turbine_encounters(self):
         """Per turbine, the share of the simulated tracks that came within turbine_encounter_radius of it: the mean over
         all (case, realisation) items of tracks_per_turbine / track_count, f64 (nturb,) in the order of
@@ -1770,18 +1314,8 @@ class Simulator(Config):
         if not self.turbine_encounters:
             raise ValueError('no turbine encounters were computed: run simulate_tracks() with turbine_encounter_radius > 0 '
                              'and turbines')
-        items = [self.turbine_encounters[key] for key in sorted(self.turbine_encounters)]
-        total = np.zeros(items[0]['tracks_per_turbine'].size + 1, dtype=np.float64)        # [..., number of items]
-        for enc in items:
-            total[:-1] += enc['tracks_per_turbine'] / float(self.track_count)
-            total[-1] += 1.
-        if self._world() > 1 and not self._shards_tracks():
-            total = self._allreduce_sum(total)                      # the cases of the other ranks
-        out = total[:-1] / total[-1]
-        if self._rank() == 0:
-            np.save(os.path.join(self.mode_data_dir, 'summary_turbine_encounters.npy'), out)
-        self._barrier()
-        return out
+        return self._save_summary('turbine_encounters', self._item_mean(
+            enc['tracks_per_turbine'] / float(self.track_count) for enc in self._sorted_items(self.turbine_encounters)))
 
     def compute_turbine_rotor_encounters(self):
         """Per turbine, the share of the simulated tracks that passed through its own rotor cylinder and the points they
@@ -1792,20 +1326,10 @@ class Simulator(Config):
         if not self.turbine_rotor_encounters:
             raise ValueError("no rotor encounters were computed: run simulate_tracks() with flight_height=True, "
                              "rotor_geometry='turbine' and turbines")
-        items = [self.turbine_rotor_encounters[key] for key in sorted(self.turbine_rotor_encounters)]
-        nturb = items[0]['tracks_per_turbine'].size
-        total = np.zeros(2 * nturb + 1, dtype=np.float64)                  # [tracks ..., points ..., number of items]
-        for enc in items:
-            total[:nturb] += enc['tracks_per_turbine'] / float(self.track_count)
-            total[nturb:-1] += enc['points_per_turbine'] / float(self.track_count)
-            total[-1] += 1.
-        if self._world() > 1 and not self._shards_tracks():
-            total = self._allreduce_sum(total)                      # the cases of the other ranks
-        out = np.ascontiguousarray((total[:-1] / total[-1]).reshape(2, nturb).T)
-        if self._rank() == 0:
-            np.save(os.path.join(self.mode_data_dir, 'summary_turbine_rotor_encounters.npy'), out)
-        self._barrier()
-        return out
+        mean = self._item_mean(np.stack([enc['tracks_per_turbine'] / float(self.track_count),
+                                         enc['points_per_turbine'] / float(self.track_count)])
+                               for enc in self._sorted_items(self.turbine_rotor_encounters))
+        return self._save_summary('turbine_rotor_encounters', np.ascontiguousarray(mean.T))
 
     def compute_turbine_rotor_transits(self):
         """Per turbine, the share of the simulated tracks that went through its rotor disk and the transits per simulated
@@ -1816,19 +1340,8 @@ class Simulator(Config):
         if not self.turbine_rotor_transits:
             raise ValueError("no rotor transits were computed: run simulate_tracks() with rotor_transits=True "
                              "(flight_height=True, rotor_geometry='turbine' and turbines with t_hh and t_rd)")
-        items = [self.turbine_rotor_transits[key] for key in sorted(self.turbine_rotor_transits)]
-        nturb = items[0].shape[0]
-        total = np.zeros(3 * nturb + 1, dtype=np.float64)                  # [(nturb, 3) row by row, number of items]
-        for three in items:
-            total[:-1] += (three / float(self.track_count)).reshape(-1)
-            total[-1] += 1.
-        if self._world() > 1 and not self._shards_tracks():
-            total = self._allreduce_sum(total)                      # the cases of the other ranks
-        out = np.ascontiguousarray((total[:-1] / total[-1]).reshape(nturb, 3))
-        if self._rank() == 0:
-            np.save(os.path.join(self.mode_data_dir, 'summary_turbine_rotor_transits.npy'), out)
-        self._barrier()
-        return out
+        return self._save_summary('turbine_rotor_transits', self._item_mean(
+            three / float(self.track_count) for three in self._sorted_items(self.turbine_rotor_transits)))
 
     def compute_turbine_collision_risk(self):
         """Per turbine, the expected collisions per simulated track (collision_risk = True; DESIGN.md K19, limit 18: Band's
@@ -1839,21 +1352,11 @@ class Simulator(Config):
         if not self.turbine_collision_risk:
             raise ValueError("no collision risk was computed: run simulate_tracks() with collision_risk=True "
                              "(flight_height=True, rotor_geometry='turbine' and turbines with t_hh and t_rd)")
-        items = [self.turbine_collision_risk[key] for key in sorted(self.turbine_collision_risk)]
-        nturb = items[0].shape[0]
         scale = (1. - float(self.collision_avoidance)) / float(self.track_count)
-        total = np.zeros(2 * nturb + 1, dtype=np.float64)                  # [(nturb, 2) row by row, number of items]
-        for risk in items:
-            total[:-1] += (risk.astype(np.float64) * 2. ** -32 * scale).reshape(-1)
-            total[-1] += 1.
-        if self._world() > 1 and not self._shards_tracks():
-            total = self._allreduce_sum(total)                      # the cases of the other ranks
-        two = (total[:-1] / total[-1]).reshape(nturb, 2)
-        out = np.ascontiguousarray(np.concatenate([two, two.sum(1, keepdims=True)], 1))
-        if self._rank() == 0:
-            np.save(os.path.join(self.mode_data_dir, 'summary_turbine_collision_risk.npy'), out)
-        self._barrier()
-        return out
+        two = self._item_mean(risk.astype(np.float64) * 2. ** -32 * scale
+                              for risk in self._sorted_items(self.turbine_collision_risk))
+        return self._save_summary('turbine_collision_risk',
+                                  np.ascontiguousarray(np.concatenate([two, two.sum(1, keepdims=True)], 1)))
 
     def compute_site_collision_risk_map(self):
         """For every cell, the expected collisions per simulated track of a turbine of the candidate class standing on it
@@ -1863,42 +1366,25 @@ class Simulator(Config):
         if not self.site_collision_risk_sums:
             raise ValueError('no site collision risk was computed: run simulate_tracks() with site_collision_risk=True '
                              '(flight_height=True)')
-        items = [self.site_collision_risk_sums[key] for key in sorted(self.site_collision_risk_sums)]
-        shape = items[0].shape[:2]
         scale = (1. - float(self.collision_avoidance)) / float(self.track_count)
-        total = np.zeros(shape[0] * shape[1] + 1, dtype=np.float64)        # [the raster row by row, number of items]
-        for risk in items:
-            total[:-1] += (risk.astype(np.float64).sum(2) * 2. ** -32 * scale).reshape(-1)
-            total[-1] += 1.
-        if self._world() > 1 and not self._shards_tracks():
-            total = self._allreduce_sum(total)                      # the cases of the other ranks
-        out = np.ascontiguousarray((total[:-1] / total[-1]).reshape(shape))
-        if self._rank() == 0:
-            np.save(os.path.join(self.mode_data_dir, 'summary_site_collision_risk.npy'), out)
-        self._barrier()
-        return out
+        return self._save_summary('site_collision_risk', self._item_mean(
+            risk.astype(np.float64).sum(2) * 2. ** -32 * scale for risk in self._sorted_items(self.site_collision_risk_sums)))
 
     def compute_turbine_rotor_time(self):
         """Per turbine, the seconds spent inside its own rotor cylinder per simulated track (rotor_exposure_time = True;
         DESIGN.md K15 timed): f64 (nturb,), the mean over all (case, realisation) items of time_per_turbine / 1e6 /
         track_count, in the order of `turbines.get_locations()`; case-sharded runs take the mean over every rank's items.
         Writes summary_turbine_rotor_time.npy.  ValueError when simulate_tracks computed none."""
-        items = [self.turbine_rotor_encounters[key] for key in sorted(self.turbine_rotor_encounters)]
-        items = [enc for enc in items if 'time_per_turbine' in enc]
+        items = [enc for enc in self._sorted_items(self.turbine_rotor_encounters) if 'time_per_turbine' in enc]
         if not items:
             raise ValueError('no rotor exposure time was computed: run simulate_tracks() with rotor_exposure_time=True '
                              "(flight_height=True, rotor_geometry='turbine', flight_time=True and turbines)")
-        total = np.zeros(items[0]['time_per_turbine'].size + 1, dtype=np.float64)          # [..., number of items]
-        for enc in items:
-            total[:-1] += enc['time_per_turbine'] / 1e6 / float(self.track_count)
-            total[-1] += 1.
-        if self._world() > 1 and not self._shards_tracks():
-            total = self._allreduce_sum(total)                      # the cases of the other ranks
-        out = total[:-1] / total[-1]
-        if self._rank() == 0:
-            np.save(os.path.join(self.mode_data_dir, 'summary_turbine_rotor_time.npy'), out)
-        self._barrier()
-        return out
+        return self._save_summary('turbine_rotor_time', self._item_mean(
+            enc['time_per_turbine'] / 1e6 / float(self.track_count) for enc in items))
+
+    def _share_of_tracks(self, counts):
+        """uint32 counts (numpy int32) on the device as f64 / track_count: one item of the occupancy and passage means."""
+        return (to_dev(counts, torch.int32).to(torch.int64) & 0xFFFFFFFF).to(torch.float64) / float(self.track_count)
 
     def compute_occupancy_map(self, radius: float = 0.):
         """Each cell's share of the simulated tracks that passed through it, in [0, 1]: the f32 mean over all kept
@@ -1911,25 +1397,13 @@ class Simulator(Config):
         computed no occupancy."""
         if not self.track_occupancy_counts:
             raise ValueError('no track occupancy was computed: run simulate_tracks() with track_occupancy=True')
-        total = torch.zeros(self.gridsize, dtype=torch.float64, device=self._presence_device())
-        for key in sorted(self.track_occupancy_counts):
-            counts = to_dev(self.track_occupancy_counts[key], torch.int32)
-            if float(radius) > 0.:
-                krad = presence.presence_kernel_radius(float(radius), self.resolution, self.gridsize)
-                item = presence.smooth_presence_counts(counts, krad).to(torch.float64)
-            else:
-                item = (counts.to(torch.int64) & 0xFFFFFFFF).to(torch.float64)
-            total += item / float(self.track_count)
-        nitems = float(len(self.track_occupancy_counts))
-        if self._world() > 1 and not self._shards_tracks():
-            # the cases of the other ranks
-            summed = self._allreduce_sum(np.append(total.cpu().numpy().ravel(), nitems))
-            total, nitems = to_dev(np.asarray(summed[:-1]).reshape(self.gridsize), torch.float64), float(summed[-1])
-        out = (total / nitems).to(torch.float32).cpu().numpy()
-        if self._rank() == 0:
-            np.save(os.path.join(self.mode_data_dir, 'summary_occupancy.npy'), out)
-        self._barrier()
-        return out
+        share = self._share_of_tracks
+        if float(radius) > 0.:
+            krad = presence.presence_kernel_radius(float(radius), self.resolution, self.gridsize)
+            share = lambda counts: presence.smooth_presence_counts(to_dev(counts, torch.int32), krad).to(torch.float64) / \
+                float(self.track_count)
+        mean = self._item_mean(share(counts) for counts in self._sorted_items(self.track_occupancy_counts))
+        return self._save_summary('occupancy', mean.to(torch.float32).cpu().numpy())
 
     def compute_passage_map(self):
         """Each cell's share of the simulated tracks that came within track_passage_radius of it, in [0, 1]: the f32 mean
@@ -1937,20 +1411,8 @@ class Simulator(Config):
         over every rank's items.  Writes summary_passage.npy.  ValueError when simulate_tracks computed no passage."""
         if not self.track_passage_counts:
             raise ValueError('no track passage was computed: run simulate_tracks() with track_passage_radius > 0')
-        total = torch.zeros(self.gridsize, dtype=torch.float64, device=self._presence_device())
-        for key in sorted(self.track_passage_counts):
-            counts = to_dev(self.track_passage_counts[key], torch.int32)
-            total += (counts.to(torch.int64) & 0xFFFFFFFF).to(torch.float64) / float(self.track_count)
-        nitems = float(len(self.track_passage_counts))
-        if self._world() > 1 and not self._shards_tracks():
-            # the cases of the other ranks
-            summed = self._allreduce_sum(np.append(total.cpu().numpy().ravel(), nitems))
-            total, nitems = to_dev(np.asarray(summed[:-1]).reshape(self.gridsize), torch.float64), float(summed[-1])
-        out = (total / nitems).to(torch.float32).cpu().numpy()
-        if self._rank() == 0:
-            np.save(os.path.join(self.mode_data_dir, 'summary_passage.npy'), out)
-        self._barrier()
-        return out
+        mean = self._item_mean(self._share_of_tracks(counts) for counts in self._sorted_items(self.track_passage_counts))
+        return self._save_summary('passage', mean.to(torch.float32).cpu().numpy())
 
     @staticmethod
     def _presence_device():

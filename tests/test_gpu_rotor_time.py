@@ -378,18 +378,22 @@ def test_simulator_end_to_end(gpu, tmp_path):
             assert np.array_equal(np.load(os.path.join(bare.mode_data_dir, f'{stems[real_id]}_{name}')),
                                   np.load(os.path.join(sim.mode_data_dir, f'{stems[real_id]}_{name}'))), name
 
-    # the invariant _store_flight raises on (last: it overwrites this run's files): time without points, and more time than
-    # the points' dt can hold
+    # the invariant the heights' store raises on through its cylinders (last: it overwrites this run's files): time without
+    # points, and more time than the points' dt can hold
+    from types import SimpleNamespace
+    from ssrs_amd.products import Heights
+    heights = Heights(bare)
+
     def fly(points, time):
-        return dict(band_hist=torch.zeros((50, 60), dtype=torch.int32, device=gpu),
-                    rows=torch.zeros((64, 3), dtype=torch.int32, device=gpu),
-                    rotor_hits=torch.zeros((64, 1), dtype=torch.int32, device=gpu),
-                    rotor_first_step=torch.full((64,), -1, dtype=torch.int32, device=gpu),
-                    rotor_points=torch.tensor(points, dtype=torch.int64, device=gpu),
-                    rotor_time=torch.tensor(time, dtype=torch.int64, device=gpu))
+        rotor = SimpleNamespace(hits=torch.zeros((64, 1), dtype=torch.int32, device=gpu),
+                                first_step=torch.full((64,), -1, dtype=torch.int32, device=gpu),
+                                points=torch.tensor(points, dtype=torch.int64, device=gpu),
+                                time=torch.tensor(time, dtype=torch.int64, device=gpu))
+        return SimpleNamespace(band_hist=torch.zeros((50, 60), dtype=torch.int32, device=gpu),
+                               rows=torch.zeros((64, 3), dtype=torch.int32, device=gpu), subs={heights.deferred: rotor})
     for points, time in (([0, 3, 0, 0, 0], [1, 0, 0, 0, 0]), ([0, 3, 0, 0, 0], [0, 3 * ref.CAP + 1, 0, 0, 0])):
         with pytest.raises(RuntimeError, match='rotor exposure time'):
-            bare._store_flight('s10d270', 0, fly(points, time), 0, False)
-    bare._store_flight('s10d270', 0, fly([0, 3, 0, 0, 0], [0, 3 * ref.CAP, 0, 0, 0]), 0, False)
+            heights.store(fly(points, time), ('s10d270', 0), False)
+    heights.store(fly([0, 3, 0, 0, 0], [0, 3 * ref.CAP, 0, 0, 0]), ('s10d270', 0), False)
     assert bare.turbine_rotor_encounters[('s10d270', 0)]['time_per_turbine'].tolist() == [0, 3 * ref.CAP, 0, 0, 0]
 

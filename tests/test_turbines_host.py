@@ -179,9 +179,13 @@ def test_library_validates_without_a_gpu():
 def test_track_sharded_runs_sum_the_per_turbine_counts_once_per_item(tmp_path):
     """Every rank of a track-sharded run hands its per-turbine counts to ONE all-reduce per (case, realisation); rank 0
     writes the sum; the per-track results stay the rank's own.  A case-sharded (or single) run reduces nothing.
-    This drives Simulator._store_encounters, the one place that issues the collective, directly: that simulate_tracks calls it
-    once per item from run(), in item order and before the histogram's reduce, needs a GPU and is not checked here."""
+    This drives the encounters product's store_counts (ssrs_amd/products.py: the host half of its store, and the one place
+    that issues the collective) directly: that simulate_tracks calls store once per item from run(), in item order and before
+    the histogram's reduce, needs a GPU and is checked in test_gpu_track_products.py."""
+    from ssrs_amd.products import Encounters
     sim = object.__new__(Simulator)
+    enc_product = object.__new__(Encounters)
+    enc_product.sim = sim
     sim.mode_data_dir, sim.track_direction, sim.updraft_threshold, sim.movement_model = str(tmp_path), 0., 0.75, 'fluidflow'
     sim.turbine_encounters = {}
     calls = []
@@ -196,7 +200,7 @@ def test_track_sharded_runs_sum_the_per_turbine_counts_once_per_item(tmp_path):
         sim._rank = lambda rank=rank: rank
         calls.clear()
         for real_id, counts in enumerate(([3, 0, 1], [0, 2, 2])):
-            sim._store_encounters('s10d270', real_id, np.array(counts, dtype=np.int64), per_track, first, sharded=True)
+            enc_product.store_counts(('s10d270', real_id), np.array(counts, dtype=np.int64), per_track, first, sharded=True)
         assert len(calls) == 2
         assert [c.tolist() for c in calls] == [[3, 0, 1], [0, 2, 2]] and all(c.dtype == np.int64 for c in calls)
         enc = sim.turbine_encounters[('s10d270', 1)]
@@ -213,7 +217,7 @@ def test_track_sharded_runs_sum_the_per_turbine_counts_once_per_item(tmp_path):
     # not track-sharded: no collective, the owning rank writes whatever its number
     calls.clear()
     sim._rank = lambda: 3
-    sim._store_encounters('other', 0, np.array([7], dtype=np.int64), per_track, first, sharded=False)
+    enc_product.store_counts(('other', 0), np.array([7], dtype=np.int64), per_track, first, sharded=False)
     assert calls == [] and np.load(os.path.join(tmp_path, 'other_d0_t75_fluidflow_r0_turbine_encounters.npy')).tolist() == [7]
     # the summary: the mean over the items of counts / track_count
     sim.track_count, sim._world, sim._rank, sim._barrier = 10, (lambda: 1), (lambda: 0), (lambda: None)
