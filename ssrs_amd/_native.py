@@ -143,11 +143,19 @@ SITE_PROTOTYPES = {
     'ssrs_site_collision_risk': 'i:ppqppiidipidpppp',
 }
 SITE_MAX_REACH = 62.
+# The export of include/ssrs_score.h (K21), a group of its own bound the same way; tests/test_score_host.py checks it against
+# that header.
+SCORE_PROTOTYPES = {
+    'ssrs_tracks_score': 'i:pppppqpppppp',
+}
+SCORE_SCORED, SCORE_ZERO, SCORE_NOT_A_MOVE, SCORE_OUT, SCORE_UNDEFINED, SCORE_LAST = range(6)
+SCORE_MAX_MEMORY, SCORE_ROW = 8, 6
 
 
 def argtypes(name):
     """The ctypes argtypes of export `name`, from its line of PROTOTYPES."""
-    return [_KINDS[k] for k in {**PROTOTYPES, **PASSAGE_PROTOTYPES, **TRANSIT_PROTOTYPES, **COLLISION_PROTOTYPES, **SITE_PROTOTYPES}[name].partition(':')[2]]
+    return [_KINDS[k] for k in {**PROTOTYPES, **PASSAGE_PROTOTYPES, **TRANSIT_PROTOTYPES, **COLLISION_PROTOTYPES, **SITE_PROTOTYPES,
+                                **SCORE_PROTOTYPES}[name].partition(':')[2]]
 
 
 # read by the host tests that bind a CPU build of one kernel file by the library's own prototypes
@@ -159,6 +167,7 @@ PASSAGE_ARGTYPES = argtypes('ssrs_track_passage')
 ROTOR_TRANSITS_ARGTYPES = argtypes('ssrs_rotor_transits')
 ROTOR_COLLISION_RISK_ARGTYPES = argtypes('ssrs_rotor_collision_risk')
 SITE_COLLISION_RISK_ARGTYPES = argtypes('ssrs_site_collision_risk')
+SCORE_ARGTYPES = argtypes('ssrs_tracks_score')
 
 
 class SsrsTrackParams(C.Structure):
@@ -225,7 +234,7 @@ def lib():
                 '(hipcc, gfx950). ssrs_amd has no CPU fallback.')
         L = C.CDLL(LIB_PATH)
         for name, proto in list(PROTOTYPES.items()) + list(PASSAGE_PROTOTYPES.items()) + list(TRANSIT_PROTOTYPES.items()) + \
-                list(COLLISION_PROTOTYPES.items()) + list(SITE_PROTOTYPES.items()):
+                list(COLLISION_PROTOTYPES.items()) + list(SITE_PROTOTYPES.items()) + list(SCORE_PROTOTYPES.items()):
             fn = getattr(L, name)
             fn.restype = _KINDS[proto[0]]
             fn.argtypes = argtypes(name)

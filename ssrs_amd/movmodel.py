@@ -538,6 +538,152 @@ def roam_tables_selftest(updraft, potential, move_dirn, thr=None):
     return pair.cpu().numpy().view(np.uint32), fine.cpu().numpy().view(np.uint32), words
 
 
+# ---------------------------------------------------------------- the score of observed tracks (K21)
+SCORE_COLUMNS = ('S', 'scored', 'zero', 'not_a_move', 'out', 'undefined')
+
+
+class TrackScores:
+    """Result of score_tracks: device tensors + host views of the per-track sums.
+
+    p          f64 (points,)     the model's probability of the move that LEAVES each point (0 where the status is
+                                 LAST, OUT or NOT_A_MOVE, NaN where it is UNDEFINED); None when not asked for
+    status     uint8 (points,)   nat.SCORE_SCORED / _ZERO / _NOT_A_MOVE / _OUT / _UNDEFINED / _LAST; None when not asked for
+    rows       int64 (ntracks, 6)  per track: S (the surprisal of its SCORED moves in units of 2^-32 bit) and the numbers
+                                 of moves by status, in the order of SCORE_COLUMNS
+    surprisal_map, scored_map    int64 / int32 (rows, cols), accumulated at the base cell of each SCORED move; None when
+                                 not asked for
+    offsets    int64 (ntracks + 1)  into p and status
+    p and status are parallel to the trajectory tensor; entries outside [offsets[0], offsets[-1]) are not written."""
+
+    def __init__(self, p, status, rows, surprisal_map, scored_map, offsets):
+        self.p, self.status, self.rows = p, status, rows
+        self.surprisal_map, self.scored_map, self.offsets = surprisal_map, scored_map, offsets
+        self._host = None
+
+    def host_rows(self):
+        """rows as int64 numpy (ntracks, 6), copied once."""
+        if self._host is None:
+            self._host = self.rows.cpu().numpy()
+        return self._host
+
+    def loglik(self):
+        """The log-likelihood (natural log) of every track's SCORED moves: -ln 2 * S / 2^32, f64 (ntracks,).  A track with
+        ZERO or UNDEFINED moves has, strictly, likelihood 0: counts() says whether it has any."""
+        return -np.log(2.) * self.host_rows()[:, 0].astype(np.float64) / 4294967296.
+
+    def bits_per_move(self):
+        """The mean surprisal of every track's SCORED moves in bits (NaN for a track without one)."""
+        rows = self.host_rows()
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return rows[:, 0].astype(np.float64) / 4294967296. / rows[:, 1]
+
+    def counts(self):
+        """{'scored', 'zero', 'not_a_move', 'out', 'undefined': int64 (ntracks,)}."""
+        rows = self.host_rows()
+        return {name: rows[:, k].copy() for k, name in enumerate(SCORE_COLUMNS) if k > 0}
+
+
+def score_tracks(tracks, grid_shape, move_dirn, memory_parameter=1, scaling_parameter=1., updraft_field=None,
+                 potential_field=None, *, offsets=None, want_p=True, want_status=True, surprisal_map=None, scored_map=None):
+    """The probability the movement model gives to every move of OBSERVED tracks (include/ssrs_score.h, K21): the
+    stepper of simulate_tracks read backwards, with the same arguments -- heading, memory, nu and the two rasters
+    (both None = 'drw').  Nothing is drawn.
+
+    tracks: a list of int16 (n_i, 2) [row, col] arrays (TrackBatch.tracks(), the pickle), or a device int16 (points, 2)
+    tensor with `offsets` (int64, ntracks + 1), as TrackBatch holds them.  surprisal_map / scored_map: True for a fresh
+    map, or an int64 / int32 (rows, cols) device tensor that is accumulated into (a sweep over chunks).  One nu per call;
+    memory_parameter 1..8 (0, the whole history, is not supported)."""
+    rows, cols = int(grid_shape[0]), int(grid_shape[1])
+    if int(memory_parameter) == 0:
+        raise ValueError('score_tracks: memory_parameter = 0 (the whole history) is not supported; give 1..'
+                         f'{nat.SCORE_MAX_MEMORY}')
+    dev = device()
+    if is_tensor(tracks):
+        if offsets is None:
+            raise ValueError('score_tracks: a trajectory tensor needs its offsets')
+        if tracks.dtype != torch.int16 or tracks.dim() != 2 or tracks.shape[1] != 2:
+            raise ValueError('score_tracks: the trajectory tensor is int16 (points, 2)')
+        traj = to_dev(tracks)
+        off = to_dev(offsets, torch.int64).reshape(-1)
+        if off.numel() and not 0 <= int(off[0]) <= int(off[-1]) <= int(traj.shape[0]):
+            raise ValueError(f'score_tracks: offsets {int(off[0])} .. {int(off[-1])} do not lie inside the '
+                             f'{int(traj.shape[0])} points of the trajectory tensor')
+    else:
+        if offsets is not None:
+            raise ValueError('score_tracks: offsets go with a trajectory tensor, not with a list of tracks')
+        parts = [np.asarray(t).reshape(-1, 2) for t in tracks]
+        for t in parts:
+            if t.size and (t.min() < -32768 or t.max() > 32767):
+                raise ValueError('score_tracks: a point does not fit int16')
+        flat = np.concatenate([np.zeros((0, 2), dtype=np.int16)] + [t.astype(np.int16) for t in parts])
+        traj = to_dev(flat, torch.int16)
+        off = to_dev(np.concatenate([[0], np.cumsum([len(t) for t in parts])]).astype(np.int64), torch.int64)
+    ntracks = int(off.numel()) - 1
+    if ntracks < 0:
+        raise ValueError('score_tracks: offsets is empty (ntracks + 1 entries)')
+    upd = to_dev(updraft_field, torch.float64)
+    pot = to_dev(potential_field, torch.float32)
+    for name, f in (('updraft_field', upd), ('potential_field', pot)):
+        if f is not None and tuple(f.shape) != (rows, cols):
+            raise ValueError(f'{name} shape {tuple(f.shape)} != grid_shape {(rows, cols)}')
+    if pot is not None and upd is None:
+        raise ValueError('potential_field needs updraft_field')
+
+    def a_map(given, dtype, name):
+        if given is None or given is False:
+            return None
+        if given is True:
+            return torch.zeros((rows, cols), dtype=dtype, device=dev)
+        if not is_tensor(given) or given.dtype != dtype or tuple(given.shape) != (rows, cols) or not given.is_cuda \
+                or not given.is_contiguous():
+            raise ValueError(f'score_tracks: {name} is True or a contiguous {dtype} device tensor of shape {(rows, cols)}')
+        return given
+
+    smap = a_map(surprisal_map, torch.int64, 'surprisal_map')
+    cmap = a_map(scored_map, torch.int32, 'scored_map')
+    npts = int(traj.shape[0])
+    p = torch.empty(npts, dtype=torch.float64, device=dev) if want_p else None
+    status = torch.empty(npts, dtype=torch.uint8, device=dev) if want_status else None
+    sums = torch.zeros((ntracks, nat.SCORE_ROW), dtype=torch.int64, device=dev)
+    if not 1 <= int(memory_parameter) <= nat.SCORE_MAX_MEMORY:
+        raise ValueError(f'score_tracks: memory_parameter = {int(memory_parameter)} outside [1, {nat.SCORE_MAX_MEMORY}]')
+    prm = make_track_params((rows, cols), move_dirn, memory_parameter, scaling_parameter)
+    if ntracks > 0 and npts > 0:                           # (an empty tensor has no address to hand over)
+        nat.check(nat.lib().ssrs_tracks_score(
+            C.byref(prm), nat.ptr(upd), nat.ptr(pot), nat.ptr(traj), nat.ptr(off), ntracks, nat.ptr(p),
+            nat.ptr(status), nat.ptr(sums), nat.ptr(smap), nat.ptr(cmap), stream_ptr()))
+    return TrackScores(p, status, sums, smap, cmap, off)
+
+
+def rasterize_track(rows, cols):
+    """Real-valued cell coordinates of successive fixes (telemetry already converted to the grid) -> the 8-connected cell
+    sequence that score_tracks takes, int16 (n, 2).  Every fix is rounded to its cell (numpy's rint); between two cells a and
+    b with d = b - a and N = max(|d_row|, |d_col|) the cells a + sgn(d) * ((2 i |d| + N) // (2 N)), i = 1..N, are emitted
+    per axis: the straight line, the minor axis rounded half up.  Repeated cells are dropped, so every consecutive pair is a
+    unit move; the first and the last fix keep their cells.  A plain line walk, not a resampling model: a fix interval
+    longer than a cell is filled with a line the bird may not have flown."""
+    r = np.rint(np.asarray(rows, dtype=np.float64)).reshape(-1)
+    c = np.rint(np.asarray(cols, dtype=np.float64)).reshape(-1)
+    if r.size != c.size:
+        raise ValueError('rasterize_track: rows and cols differ in length')
+    if not (np.isfinite(r).all() and np.isfinite(c).all()):
+        raise ValueError('rasterize_track: a fix is not finite')
+    if r.size and (min(r.min(), c.min()) < -32768 or max(r.max(), c.max()) > 32767):
+        raise ValueError('rasterize_track: a fix does not fit int16 cell coordinates')
+    cells = np.stack([r, c], 1).astype(np.int64)
+    if len(cells) == 0:
+        return np.zeros((0, 2), dtype=np.int16)
+    out = [cells[:1]]
+    for a, b in zip(cells[:-1], cells[1:]):
+        d = b - a
+        n = int(np.abs(d).max())
+        if n == 0:
+            continue
+        i = np.arange(1, n + 1, dtype=np.int64)[:, None]
+        out.append(a + np.sign(d) * ((2 * i * np.abs(d) + n) // (2 * n)))
+    return np.concatenate(out).astype(np.int16)
+
+
 # ---------------------------------------------------------------- re-exports
 from .presence import (compute_presence_counts, compute_smooth_presence_counts)  # noqa: E402
 from . import potential as _potential  # noqa: E402

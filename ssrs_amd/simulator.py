@@ -1170,6 +1170,51 @@ class Simulator(Config):
                 self._dump_tracks(fobj, parts())
         self._barrier()
 
+    # ------------------------------------------------------------- the score of observed tracks
+    def score_tracks(self, tracks, case_id=None, real_id=0, xy=False):
+        """The probability this run's movement model gives to every move of OBSERVED tracks (movmodel.score_tracks,
+        DESIGN.md K21): the fields of `case_id` (default: the first case) and realisation `real_id`, resolved as
+        simulate_tracks resolves them, with track_direction, track_dirn_restrict and track_stochastic_nu.
+
+        tracks: a list of (n_i, 2) arrays, [row, col] cells of 8-connected sequences -- what <id>_tracks.pkl holds --
+        or, with xy=True, [x, y] in projected metres of successive fixes, which are converted to cells like the turbine
+        table's coordinates ((x - west) / resolution along columns, (y - south) / resolution along rows) and joined by
+        movmodel.rasterize_track's line walk.  Returns the TrackScores and writes <id>_track_scores.npy, int64
+        (ntracks, 6): S and the numbers of moves by status (movmodel.SCORE_COLUMNS).  Every rank that calls it scores all
+        the tracks it is given; there are no collectives."""
+        if self.movement_model not in ('fluidflow', 'drw'):
+            raise ValueError(f'unknown movement_model {self.movement_model!r}')
+        case_id = self.case_ids[0] if case_id is None else case_id
+        if case_id not in self.case_ids:
+            raise ValueError(f'score_tracks: case_id {case_id!r} is not one of {self.case_ids}')
+        real_id = int(real_id)
+        if xy:
+            cells = []
+            for t in tracks:
+                t = np.asarray(t, dtype=np.float64).reshape(-1, 2)
+                cells.append(movmodel.rasterize_track((t[:, 1] - float(self.bounds[1])) / float(self.resolution),
+                                                      (t[:, 0] - float(self.bounds[0])) / float(self.resolution)))
+            tracks = cells
+        fields = (None, None)
+        if self.movement_model == 'fluidflow':
+            updrafts = self._load_updrafts_dev(case_id)
+            if not 0 <= real_id < len(updrafts):
+                raise ValueError(f'score_tracks: real_id {real_id} outside the {len(updrafts)} realisations of {case_id}')
+            updraft = updrafts[real_id]
+            if self._shards_tracks():
+                # (_potential_dev meets the other ranks in a barrier; here nothing is shared)
+                cached = self._cached_potential(case_id, real_id)
+                potential = to_dev(cached, torch.float32) if cached is not None else \
+                    potential_mod.solve_potential(updraft, self.track_direction)
+            else:
+                potential = self._potential_dev(updraft, case_id, real_id)
+            fields = (updraft, potential)
+        scores = movmodel.score_tracks(tracks, self.gridsize, self.track_direction, self.track_dirn_restrict,
+                                       self.track_stochastic_nu, fields[0], fields[1])
+        fname = os.path.join(self.mode_data_dir, f'{self._get_id_string(case_id, real_id)}_track_scores')
+        np.save(f'{fname}.npy', scores.host_rows())
+        return scores
+
     # ------------------------------------------------------------- presence
     def _counts_for(self, case_id, real_id):
         hist = self._presence_counts.get((case_id, real_id))
