@@ -150,12 +150,18 @@ SCORE_PROTOTYPES = {
 }
 SCORE_SCORED, SCORE_ZERO, SCORE_NOT_A_MOVE, SCORE_OUT, SCORE_UNDEFINED, SCORE_LAST = range(6)
 SCORE_MAX_MEMORY, SCORE_ROW = 8, 6
+# The export of include/ssrs_score_profile.h (K22), a group of its own bound the same way; tests/test_score_profile_host.py
+# checks it against that header.
+PROFILE_PROTOTYPES = {
+    'ssrs_tracks_score_profile': 'i:pppppqpipipp',
+}
+PROFILE_MAX_MEMORIES, PROFILE_MAX_NUS = 8, 32
 
 
 def argtypes(name):
     """The ctypes argtypes of export `name`, from its line of PROTOTYPES."""
     return [_KINDS[k] for k in {**PROTOTYPES, **PASSAGE_PROTOTYPES, **TRANSIT_PROTOTYPES, **COLLISION_PROTOTYPES, **SITE_PROTOTYPES,
-                                **SCORE_PROTOTYPES}[name].partition(':')[2]]
+                                **SCORE_PROTOTYPES, **PROFILE_PROTOTYPES}[name].partition(':')[2]]
 
 
 # read by the host tests that bind a CPU build of one kernel file by the library's own prototypes
@@ -168,6 +174,7 @@ ROTOR_TRANSITS_ARGTYPES = argtypes('ssrs_rotor_transits')
 ROTOR_COLLISION_RISK_ARGTYPES = argtypes('ssrs_rotor_collision_risk')
 SITE_COLLISION_RISK_ARGTYPES = argtypes('ssrs_site_collision_risk')
 SCORE_ARGTYPES = argtypes('ssrs_tracks_score')
+PROFILE_ARGTYPES = argtypes('ssrs_tracks_score_profile')
 
 
 class SsrsTrackParams(C.Structure):
@@ -234,7 +241,8 @@ def lib():
                 '(hipcc, gfx950). ssrs_amd has no CPU fallback.')
         L = C.CDLL(LIB_PATH)
         for name, proto in list(PROTOTYPES.items()) + list(PASSAGE_PROTOTYPES.items()) + list(TRANSIT_PROTOTYPES.items()) + \
-                list(COLLISION_PROTOTYPES.items()) + list(SITE_PROTOTYPES.items()) + list(SCORE_PROTOTYPES.items()):
+                list(COLLISION_PROTOTYPES.items()) + list(SITE_PROTOTYPES.items()) + list(SCORE_PROTOTYPES.items()) + \
+                list(PROFILE_PROTOTYPES.items()):
             fn = getattr(L, name)
             fn.restype = _KINDS[proto[0]]
             fn.argtypes = argtypes(name)

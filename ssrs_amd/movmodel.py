@@ -583,6 +583,47 @@ class TrackScores:
         return {name: rows[:, k].copy() for k, name in enumerate(SCORE_COLUMNS) if k > 0}
 
 
+def _pack_tracks(who, tracks, offsets):
+    """(traj int16 (points, 2), offsets int64 (ntracks + 1,), ntracks) on the device, from a list of (n_i, 2) arrays or from
+    a device tensor with its offsets: what score_tracks and score_tracks_profile take, with their refusals under `who`."""
+    if is_tensor(tracks):
+        if offsets is None:
+            raise ValueError(f'{who}: a trajectory tensor needs its offsets')
+        if tracks.dtype != torch.int16 or tracks.dim() != 2 or tracks.shape[1] != 2:
+            raise ValueError(f'{who}: the trajectory tensor is int16 (points, 2)')
+        traj = to_dev(tracks)
+        off = to_dev(offsets, torch.int64).reshape(-1)
+        if off.numel() and not 0 <= int(off[0]) <= int(off[-1]) <= int(traj.shape[0]):
+            raise ValueError(f'{who}: offsets {int(off[0])} .. {int(off[-1])} do not lie inside the '
+                             f'{int(traj.shape[0])} points of the trajectory tensor')
+    else:
+        if offsets is not None:
+            raise ValueError(f'{who}: offsets go with a trajectory tensor, not with a list of tracks')
+        parts = [np.asarray(t).reshape(-1, 2) for t in tracks]
+        for t in parts:
+            if t.size and (t.min() < -32768 or t.max() > 32767):
+                raise ValueError(f'{who}: a point does not fit int16')
+        flat = np.concatenate([np.zeros((0, 2), dtype=np.int16)] + [t.astype(np.int16) for t in parts])
+        traj = to_dev(flat, torch.int16)
+        off = to_dev(np.concatenate([[0], np.cumsum([len(t) for t in parts])]).astype(np.int64), torch.int64)
+    ntracks = int(off.numel()) - 1
+    if ntracks < 0:
+        raise ValueError(f'{who}: offsets is empty (ntracks + 1 entries)')
+    return traj, off, ntracks
+
+
+def _score_fields(updraft_field, potential_field, rows, cols):
+    """The two rasters of a score on the device (None = not given), checked against the grid."""
+    upd = to_dev(updraft_field, torch.float64)
+    pot = to_dev(potential_field, torch.float32)
+    for name, f in (('updraft_field', upd), ('potential_field', pot)):
+        if f is not None and tuple(f.shape) != (rows, cols):
+            raise ValueError(f'{name} shape {tuple(f.shape)} != grid_shape {(rows, cols)}')
+    if pot is not None and upd is None:
+        raise ValueError('potential_field needs updraft_field')
+    return upd, pot
+
+
 def score_tracks(tracks, grid_shape, move_dirn, memory_parameter=1, scaling_parameter=1., updraft_field=None,
                  potential_field=None, *, offsets=None, want_p=True, want_status=True, surprisal_map=None, scored_map=None):
     """The probability the movement model gives to every move of OBSERVED tracks (include/ssrs_score.h, K21): the
@@ -598,36 +639,8 @@ def score_tracks(tracks, grid_shape, move_dirn, memory_parameter=1, scaling_para
         raise ValueError('score_tracks: memory_parameter = 0 (the whole history) is not supported; give 1..'
                          f'{nat.SCORE_MAX_MEMORY}')
     dev = device()
-    if is_tensor(tracks):
-        if offsets is None:
-            raise ValueError('score_tracks: a trajectory tensor needs its offsets')
-        if tracks.dtype != torch.int16 or tracks.dim() != 2 or tracks.shape[1] != 2:
-            raise ValueError('score_tracks: the trajectory tensor is int16 (points, 2)')
-        traj = to_dev(tracks)
-        off = to_dev(offsets, torch.int64).reshape(-1)
-        if off.numel() and not 0 <= int(off[0]) <= int(off[-1]) <= int(traj.shape[0]):
-            raise ValueError(f'score_tracks: offsets {int(off[0])} .. {int(off[-1])} do not lie inside the '
-                             f'{int(traj.shape[0])} points of the trajectory tensor')
-    else:
-        if offsets is not None:
-            raise ValueError('score_tracks: offsets go with a trajectory tensor, not with a list of tracks')
-        parts = [np.asarray(t).reshape(-1, 2) for t in tracks]
-        for t in parts:
-            if t.size and (t.min() < -32768 or t.max() > 32767):
-                raise ValueError('score_tracks: a point does not fit int16')
-        flat = np.concatenate([np.zeros((0, 2), dtype=np.int16)] + [t.astype(np.int16) for t in parts])
-        traj = to_dev(flat, torch.int16)
-        off = to_dev(np.concatenate([[0], np.cumsum([len(t) for t in parts])]).astype(np.int64), torch.int64)
-    ntracks = int(off.numel()) - 1
-    if ntracks < 0:
-        raise ValueError('score_tracks: offsets is empty (ntracks + 1 entries)')
-    upd = to_dev(updraft_field, torch.float64)
-    pot = to_dev(potential_field, torch.float32)
-    for name, f in (('updraft_field', upd), ('potential_field', pot)):
-        if f is not None and tuple(f.shape) != (rows, cols):
-            raise ValueError(f'{name} shape {tuple(f.shape)} != grid_shape {(rows, cols)}')
-    if pot is not None and upd is None:
-        raise ValueError('potential_field needs updraft_field')
+    traj, off, ntracks = _pack_tracks('score_tracks', tracks, offsets)
+    upd, pot = _score_fields(updraft_field, potential_field, rows, cols)
 
     def a_map(given, dtype, name):
         if given is None or given is False:
@@ -653,6 +666,174 @@ def score_tracks(tracks, grid_shape, move_dirn, memory_parameter=1, scaling_para
             C.byref(prm), nat.ptr(upd), nat.ptr(pot), nat.ptr(traj), nat.ptr(off), ntracks, nat.ptr(p),
             nat.ptr(status), nat.ptr(sums), nat.ptr(smap), nat.ptr(cmap), stream_ptr()))
     return TrackScores(p, status, sums, smap, cmap, off)
+
+
+# ---------------------------------------------------------------- the likelihood profile and the fit (K22)
+class TrackProfile:
+    """Result of score_tracks_profile: K21's per-track rows over a grid of memories x nus.
+
+    rows       int64 (ntracks, nmem, nnu, 6)  rows[t, a, b] is what score_tracks gives track t under memories[a] and nus[b],
+                                 in the order of SCORE_COLUMNS
+    memories   tuple of int, ascending;  nus  f64 numpy (nnu,), in the order given (repeats allowed)"""
+
+    def __init__(self, rows, memories, nus):
+        self.rows = rows
+        self.memories = tuple(int(m) for m in memories)
+        self.nus = np.array(nus, dtype=np.float64).reshape(-1)
+        if tuple(rows.shape[1:]) != (len(self.memories), self.nus.size, nat.SCORE_ROW):
+            raise ValueError(f'TrackProfile: rows of shape {tuple(rows.shape)} for {len(self.memories)} memories and '
+                             f'{self.nus.size} nus')
+        self._host = None
+
+    def host_rows(self):
+        """rows as int64 numpy (ntracks, nmem, nnu, 6), copied once."""
+        if self._host is None:
+            self._host = self.rows.cpu().numpy() if is_tensor(self.rows) else np.asarray(self.rows, dtype=np.int64)
+        return self._host
+
+    def row(self, memory, nu):
+        """The int64 numpy (ntracks, 6) slice of one combination (the first of equal nus)."""
+        if int(memory) not in self.memories:
+            raise ValueError(f'TrackProfile.row: memory {memory} is not one of {self.memories}')
+        hits = np.nonzero(self.nus == float(nu))[0]
+        if not hits.size:
+            raise ValueError(f'TrackProfile.row: nu {nu} is not one of {self.nus.tolist()}')
+        return self.host_rows()[:, self.memories.index(int(memory)), int(hits[0])]
+
+    def forbidden(self):
+        """int64 (nmem, nnu): the observed moves a combination gives no probability, zero + undefined over the tracks."""
+        total = self.host_rows().sum(0)
+        return total[..., 2] + total[..., 5]
+
+    def total_bits(self, zero_bits=np.inf):
+        """f64 (nmem, nnu): sum_t S / 2^32 + zero_bits * sum_t (zero + undefined), the surprisal of all tracks in bits.
+        A move the model forbids has likelihood 0: with the default inf, a combination that forbids any observed move is
+        out.  A finite zero_bits is the price per such move, a telemetry-error allowance the caller owns.  0 * inf is 0."""
+        bits = self.host_rows()[..., 0].sum(0).astype(np.float64) / 4294967296.
+        forbidden = self.forbidden()
+        penalty = np.zeros_like(bits)
+        penalty[forbidden > 0] = float(zero_bits) * forbidden[forbidden > 0]
+        return bits + penalty
+
+    def best(self, zero_bits=np.inf):
+        """(memory, nu, bits) of the smallest total_bits; ties go to the first in order of ascending memory, then ascending
+        nu.  ValueError when every combination forbids a move and zero_bits is inf."""
+        total = self.total_bits(zero_bits)
+        order = np.argsort(self.nus, kind='stable')
+        ranked = total[:, order]
+        if not np.isfinite(ranked).any():
+            forbidden = self.forbidden()[:, order]
+            a, b = np.unravel_index(int(np.argmin(forbidden)), forbidden.shape)
+            raise ValueError(f'TrackProfile.best: every combination forbids an observed move; the fewest, '
+                             f'{int(forbidden[a, b])}, under memory {self.memories[a]} and nu {self.nus[order[b]]:g} '
+                             '(a finite zero_bits prices them)')
+        a, b = np.unravel_index(int(np.argmin(ranked)), ranked.shape)      # (argmin: the first of equal values, row-major)
+        return self.memories[a], float(self.nus[order[b]]), float(ranked[a, b])
+
+
+def _profile_grid(memories, nus):
+    """(sorted distinct memories as int32, nus as f64), refused as the library refuses them."""
+    mem = np.unique(np.asarray(memories, dtype=np.int64).reshape(-1))
+    if not mem.size:
+        raise ValueError('score_tracks_profile: memories is empty')
+    if mem[0] < 1 or mem[-1] > nat.SCORE_MAX_MEMORY:
+        raise ValueError(f'score_tracks_profile: memories {mem.tolist()} outside [1, {nat.SCORE_MAX_MEMORY}] (0, the whole '
+                         'history, is not supported)')
+    nu = np.ascontiguousarray(nus, dtype=np.float64).reshape(-1)
+    if not 1 <= nu.size <= nat.PROFILE_MAX_NUS:
+        raise ValueError(f'score_tracks_profile: {nu.size} nus (1 .. {nat.PROFILE_MAX_NUS} a call)')
+    if not (nu >= 0.).all():
+        raise ValueError(f'score_tracks_profile: nus {nu.tolist()} (not negative, not NaN)')
+    return np.ascontiguousarray(mem, dtype=np.int32), nu
+
+
+def score_tracks_profile(tracks, grid_shape, move_dirn, memories, nus, updraft_field=None, potential_field=None, *,
+                         offsets=None):
+    """score_tracks' per-track rows for every combination of `memories` (1..8, sorted and de-duplicated on the way in) and
+    `nus` (1..32 values, any order) in ONE pass over the points (include/ssrs_score_profile.h, K22): what calibrating
+    track_dirn_restrict and track_stochastic_nu on telemetry needs.  tracks, offsets and the fields as score_tracks takes
+    them.  Returns a TrackProfile; p, status and the maps come from score_tracks at the fitted values."""
+    rows, cols = int(grid_shape[0]), int(grid_shape[1])
+    mem, nu = _profile_grid(memories, nus)
+    dev = device()
+    traj, off, ntracks = _pack_tracks('score_tracks_profile', tracks, offsets)
+    upd, pot = _score_fields(updraft_field, potential_field, rows, cols)
+    sums = torch.zeros((ntracks, mem.size, nu.size, nat.SCORE_ROW), dtype=torch.int64, device=dev)
+    prm = make_track_params((rows, cols), move_dirn, 1, 1.)
+    if ntracks > 0 and int(traj.shape[0]) > 0:             # (an empty tensor has no address to hand over)
+        nat.check(nat.lib().ssrs_tracks_score_profile(
+            C.byref(prm), nat.ptr(upd), nat.ptr(pot), nat.ptr(traj), nat.ptr(off), ntracks, mem.ctypes.data_as(C.c_void_p),
+            int(mem.size), nu.ctypes.data_as(C.c_void_p), int(nu.size), nat.ptr(sums), stream_ptr()))
+    return TrackProfile(sums, mem.tolist(), nu)
+
+
+class TrackFit:
+    """Result of fit_tracks: the maximum-likelihood memory and nu on the last round's grid.
+
+    memory, nu, bits     TrackProfile.best of the last round
+    nu_lo, nu_hi         the last bracket, ONE spacing of the last round's grid wide.  For fixed statuses the surprisal of
+                         `memory` is convex in nu, so its minimum lies between the neighbours of nu on that grid; the closing
+                         profile at the two midpoints beside nu says in which half: [left neighbour, nu] when the left
+                         midpoint is lower than nu, [nu, right neighbour] when the right one is, else between the midpoints.
+                         nu lies inside or on its rim.  At an end of the grid nu itself bounds that side
+    at_edge              True when round 1's best nu is its grid's largest: the bracket is then ONE-SIDED -- the rounds zoom
+                         in below that nu and say nothing about larger ones; give a grid that reaches further
+    profiles             one TrackProfile per round
+    closing              the TrackProfile of all the memories at the midpoints (None for a grid of one nu); a lower total
+                         there moves the bracket, not nu and bits"""
+
+    def __init__(self, memory, nu, bits, nu_lo, nu_hi, at_edge, profiles, closing=None):
+        self.memory, self.nu, self.bits, self.nu_lo, self.nu_hi = memory, nu, bits, nu_lo, nu_hi
+        self.at_edge, self.profiles, self.closing = at_edge, profiles, closing
+
+
+def _nu_bracket(nus, nu):
+    """The neighbours of `nu` on the sorted grid `nus`; at an end of the grid, nu itself."""
+    grid = np.unique(np.asarray(nus, dtype=np.float64))
+    k = int(np.searchsorted(grid, nu))
+    return float(grid[max(k - 1, 0)]), float(grid[min(k + 1, grid.size - 1)])
+
+
+def _close_bracket(lo, nu, hi, bits, left, right):
+    """The half of [lo, hi] that holds the minimum of a convex function with the value `bits` at nu, `left` at the midpoint
+    of [lo, nu] and `right` at that of [nu, hi] (None: that side is an end of the grid, lo or hi is nu)."""
+    mid_lo = nu if left is None else .5 * (lo + nu)
+    mid_hi = nu if right is None else .5 * (nu + hi)
+    if left is not None and left < bits and (right is None or left <= right):
+        return lo, nu
+    if right is not None and right < bits:
+        return nu, hi
+    return mid_lo, mid_hi
+
+
+def fit_tracks(tracks, grid_shape, move_dirn, updraft_field=None, potential_field=None, *, memories=(1, 2, 3, 4), nus=None,
+               rounds=3, zero_bits=np.inf, offsets=None):
+    """The memory and nu under which the movement model gives OBSERVED tracks the largest likelihood: a coarse grid and a
+    zoom, every round one score_tracks_profile.  Round 1 profiles memories x nus (default np.linspace(0, 4, 17)); every
+    later round profiles ALL the memories again on np.linspace(lo, hi, len(nus)) between the neighbours of the best nu on
+    the sorted grid of the round before.  A closing profile at the two midpoints beside the last best nu halves the last
+    bracket (TrackFit.nu_lo, .nu_hi).  zero_bits as TrackProfile.total_bits takes it.  No derivative, no other parameter, no
+    collectives.  Returns a TrackFit."""
+    nus = np.linspace(0., 4., 17) if nus is None else np.asarray(nus, dtype=np.float64).reshape(-1)
+    if int(rounds) < 1:
+        raise ValueError(f'fit_tracks: rounds = {rounds} (at least 1)')
+    profiles = []
+    for _ in range(int(rounds)):
+        profiles.append(score_tracks_profile(tracks, grid_shape, move_dirn, memories, nus, updraft_field, potential_field,
+                                             offsets=offsets))
+        memory, nu, bits = profiles[-1].best(zero_bits)
+        lo, hi = _nu_bracket(nus, nu)
+        if len(profiles) == 1:
+            at_edge = nu == float(np.max(nus))
+        nus = np.linspace(lo, hi, len(nus))
+    mids = [.5 * (lo + nu)] * (lo < nu) + [.5 * (nu + hi)] * (nu < hi)
+    closing = None
+    if mids:
+        closing = score_tracks_profile(tracks, grid_shape, move_dirn, memories, mids, updraft_field, potential_field,
+                                       offsets=offsets)
+        at = [float(v) for v in closing.total_bits(zero_bits)[closing.memories.index(memory)]]
+        lo, hi = _close_bracket(lo, nu, hi, bits, at[0] if lo < nu else None, at[-1] if nu < hi else None)
+    return TrackFit(memory, nu, bits, lo, hi, at_edge, profiles, closing)
 
 
 def rasterize_track(rows, cols):

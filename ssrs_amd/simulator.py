@@ -1171,22 +1171,14 @@ class Simulator(Config):
         self._barrier()
 
     # ------------------------------------------------------------- the score of observed tracks
-    def score_tracks(self, tracks, case_id=None, real_id=0, xy=False):
-        """The probability this run's movement model gives to every move of OBSERVED tracks (movmodel.score_tracks,
-        DESIGN.md K21): the fields of `case_id` (default: the first case) and realisation `real_id`, resolved as
-        simulate_tracks resolves them, with track_direction, track_dirn_restrict and track_stochastic_nu.
-
-        tracks: a list of (n_i, 2) arrays, [row, col] cells of 8-connected sequences -- what <id>_tracks.pkl holds --
-        or, with xy=True, [x, y] in projected metres of successive fixes, which are converted to cells like the turbine
-        table's coordinates ((x - west) / resolution along columns, (y - south) / resolution along rows) and joined by
-        movmodel.rasterize_track's line walk.  Returns the TrackScores and writes <id>_track_scores.npy, int64
-        (ntracks, 6): S and the numbers of moves by status (movmodel.SCORE_COLUMNS).  Every rank that calls it scores all
-        the tracks it is given; there are no collectives."""
+    def _score_inputs(self, who, tracks, case_id, real_id, xy):
+        """(tracks as cells, case_id, real_id, (updraft, potential)) of score_tracks and fit_tracks: the case and the
+        realisation resolved as simulate_tracks resolves them, [x, y] metres walked to cells when xy."""
         if self.movement_model not in ('fluidflow', 'drw'):
             raise ValueError(f'unknown movement_model {self.movement_model!r}')
         case_id = self.case_ids[0] if case_id is None else case_id
         if case_id not in self.case_ids:
-            raise ValueError(f'score_tracks: case_id {case_id!r} is not one of {self.case_ids}')
+            raise ValueError(f'{who}: case_id {case_id!r} is not one of {self.case_ids}')
         real_id = int(real_id)
         if xy:
             cells = []
@@ -1199,7 +1191,7 @@ class Simulator(Config):
         if self.movement_model == 'fluidflow':
             updrafts = self._load_updrafts_dev(case_id)
             if not 0 <= real_id < len(updrafts):
-                raise ValueError(f'score_tracks: real_id {real_id} outside the {len(updrafts)} realisations of {case_id}')
+                raise ValueError(f'{who}: real_id {real_id} outside the {len(updrafts)} realisations of {case_id}')
             updraft = updrafts[real_id]
             if self._shards_tracks():
                 # (_potential_dev meets the other ranks in a barrier; here nothing is shared)
@@ -1209,11 +1201,43 @@ class Simulator(Config):
             else:
                 potential = self._potential_dev(updraft, case_id, real_id)
             fields = (updraft, potential)
+        return tracks, case_id, real_id, fields
+
+    def score_tracks(self, tracks, case_id=None, real_id=0, xy=False):
+        """The probability this run's movement model gives to every move of OBSERVED tracks (movmodel.score_tracks,
+        DESIGN.md K21): the fields of `case_id` (default: the first case) and realisation `real_id`, resolved as
+        simulate_tracks resolves them, with track_direction, track_dirn_restrict and track_stochastic_nu.
+
+        tracks: a list of (n_i, 2) arrays, [row, col] cells of 8-connected sequences -- what <id>_tracks.pkl holds --
+        or, with xy=True, [x, y] in projected metres of successive fixes, which are converted to cells like the turbine
+        table's coordinates ((x - west) / resolution along columns, (y - south) / resolution along rows) and joined by
+        movmodel.rasterize_track's line walk.  Returns the TrackScores and writes <id>_track_scores.npy, int64
+        (ntracks, 6): S and the numbers of moves by status (movmodel.SCORE_COLUMNS).  Every rank that calls it scores all
+        the tracks it is given; there are no collectives."""
+        tracks, case_id, real_id, fields = self._score_inputs('score_tracks', tracks, case_id, real_id, xy)
         scores = movmodel.score_tracks(tracks, self.gridsize, self.track_direction, self.track_dirn_restrict,
                                        self.track_stochastic_nu, fields[0], fields[1])
         fname = os.path.join(self.mode_data_dir, f'{self._get_id_string(case_id, real_id)}_track_scores')
         np.save(f'{fname}.npy', scores.host_rows())
         return scores
+
+    def fit_tracks(self, tracks, case_id=None, real_id=0, xy=False, memories=(1, 2, 3, 4), nus=None, rounds=3,
+                   zero_bits=np.inf):
+        """The memory (track_dirn_restrict) and nu (track_stochastic_nu) under which this run's movement model gives
+        OBSERVED tracks the largest likelihood (movmodel.fit_tracks), on the fields and the heading that
+        score_tracks uses; tracks, case_id, real_id and xy as score_tracks takes them.  It neither reads nor sets the run's
+        own track_dirn_restrict and track_stochastic_nu.  Returns the TrackFit and writes <id>_track_fit.npz: memory, nu,
+        bits, nu_lo, nu_hi, and of the last round memories, nus and rows_total, int64 (nmem, nnu, 6), its rows summed
+        over the tracks.  No collectives."""
+        tracks, case_id, real_id, fields = self._score_inputs('fit_tracks', tracks, case_id, real_id, xy)
+        fit = movmodel.fit_tracks(tracks, self.gridsize, self.track_direction, fields[0], fields[1], memories=memories,
+                                  nus=nus, rounds=rounds, zero_bits=zero_bits)
+        last = fit.profiles[-1]
+        fname = os.path.join(self.mode_data_dir, f'{self._get_id_string(case_id, real_id)}_track_fit')
+        np.savez(f'{fname}.npz', memory=np.int64(fit.memory), nu=np.float64(fit.nu), bits=np.float64(fit.bits),
+                 nu_lo=np.float64(fit.nu_lo), nu_hi=np.float64(fit.nu_hi), memories=np.array(last.memories, dtype=np.int64),
+                 nus=last.nus, rows_total=last.host_rows().sum(0))
+        return fit
 
     # ------------------------------------------------------------- presence
     def _counts_for(self, case_id, real_id):
