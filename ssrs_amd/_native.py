@@ -156,12 +156,19 @@ PROFILE_PROTOTYPES = {
     'ssrs_tracks_score_profile': 'i:pppppqpipipp',
 }
 PROFILE_MAX_MEMORIES, PROFILE_MAX_NUS = 8, 32
+# The export of include/ssrs_bridge.h (K23), a group of its own bound the same way; tests/test_bridge_host.py checks it
+# against that header.
+BRIDGE_PROTOTYPES = {
+    'ssrs_tracks_bridge': 'i:ppppqppppp',
+}
+BRIDGE_SCORED, BRIDGE_ZERO, BRIDGE_TOO_LONG, BRIDGE_OUT, BRIDGE_UNDEFINED = range(5)
+BRIDGE_MAX_MOVES, BRIDGE_JOB = 32, 6
 
 
 def argtypes(name):
     """The ctypes argtypes of export `name`, from its line of PROTOTYPES."""
     return [_KINDS[k] for k in {**PROTOTYPES, **PASSAGE_PROTOTYPES, **TRANSIT_PROTOTYPES, **COLLISION_PROTOTYPES, **SITE_PROTOTYPES,
-                                **SCORE_PROTOTYPES, **PROFILE_PROTOTYPES}[name].partition(':')[2]]
+                                **SCORE_PROTOTYPES, **PROFILE_PROTOTYPES, **BRIDGE_PROTOTYPES}[name].partition(':')[2]]
 
 
 # read by the host tests that bind a CPU build of one kernel file by the library's own prototypes
@@ -175,6 +182,7 @@ ROTOR_COLLISION_RISK_ARGTYPES = argtypes('ssrs_rotor_collision_risk')
 SITE_COLLISION_RISK_ARGTYPES = argtypes('ssrs_site_collision_risk')
 SCORE_ARGTYPES = argtypes('ssrs_tracks_score')
 PROFILE_ARGTYPES = argtypes('ssrs_tracks_score_profile')
+BRIDGE_ARGTYPES = argtypes('ssrs_tracks_bridge')
 
 
 class SsrsTrackParams(C.Structure):
@@ -242,7 +250,7 @@ def lib():
         L = C.CDLL(LIB_PATH)
         for name, proto in list(PROTOTYPES.items()) + list(PASSAGE_PROTOTYPES.items()) + list(TRANSIT_PROTOTYPES.items()) + \
                 list(COLLISION_PROTOTYPES.items()) + list(SITE_PROTOTYPES.items()) + list(SCORE_PROTOTYPES.items()) + \
-                list(PROFILE_PROTOTYPES.items()):
+                list(PROFILE_PROTOTYPES.items()) + list(BRIDGE_PROTOTYPES.items()):
             fn = getattr(L, name)
             fn.restype = _KINDS[proto[0]]
             fn.argtypes = argtypes(name)

@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 SOURCES = ['capi.hip', 'raster.hip', 'tracks.hip', 'presence.hip', 'potential.hip', 'thermals.hip', 'amg.hip', 'wtk_thermals.hip',
            'turbines.hip', 'shelter.hip', 'georef.hip', 'smooth.hip', 'allen_thermals.hip', 'occupancy.hip', 'altitude.hip',
-           'flight_time.hip', 'passage.hip', 'rotor_transits.hip', 'site_risk.hip', 'score.hip', 'score_profile.hip']
+           'flight_time.hip', 'passage.hip', 'rotor_transits.hip', 'site_risk.hip', 'score.hip', 'score_profile.hip', 'bridge.hip']
 LIB = os.path.join(PKG, 'libssrs_hip.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off',
          '-fno-fast-math', '-fgpu-rdc=0' if False else '-Wall', '-Wno-unused-function']
@@ -26,7 +26,7 @@ def hipcc():
 def build(force=False, verbose=False):
     srcs = [os.path.join(HERE, s) for s in SOURCES if os.path.exists(os.path.join(HERE, s))]
     headers = [os.path.join(HERE, h) for h in ('amg.h', 'common.h', 'gauss.h', 'georef.h', 'interp.h', 'raster_math.h', 'rotor_disk.h', 'score_model.h', 'track_plan.h', 'track_policy.h')] + \
-              [os.path.join(os.path.dirname(PKG), 'include', h) for h in ('ssrs_hip.h', 'ssrs_hip_passage.h', 'ssrs_hip_transits.h', 'ssrs_hip_collision.h', 'ssrs_hip_sites.h', 'ssrs_score.h', 'ssrs_score_profile.h')]
+              [os.path.join(os.path.dirname(PKG), 'include', h) for h in ('ssrs_hip.h', 'ssrs_hip_passage.h', 'ssrs_hip_transits.h', 'ssrs_hip_collision.h', 'ssrs_hip_sites.h', 'ssrs_score.h', 'ssrs_score_profile.h', 'ssrs_bridge.h')]
     if not force and os.path.exists(LIB) and os.path.getmtime(LIB) >= _newest(srcs + headers):
         return LIB
     objs = []

@@ -865,6 +865,143 @@ def rasterize_track(rows, cols):
     return np.concatenate(out).astype(np.int16)
 
 
+# ---------------------------------------------------------------- gaps between sparse fixes (K23)
+GAP_STATUSES = ('scored', 'zero', 'too_long', 'out', 'undefined')
+
+
+class GapScores:
+    """Result of score_gaps: device tensors + host views.
+
+    g          f64 (ngaps, 9)    the probability of being at B after the job's moves, by the move k = 3 (dr + 1) + (dc + 1)
+                                 that arrived there (what a later gap would take as its incoming state); 0 where the job
+                                 was not evaluated
+    status     uint8 (ngaps,)    nat.BRIDGE_SCORED / _ZERO / _TOO_LONG / _OUT / _UNDEFINED
+    surprisal  int64 (ngaps,)    rint(-log2(P) * 2^32) of a SCORED gap, 0 otherwise: score_tracks' unit
+    arrivals   f64 (ngaps, 32)   the probability of being at B after 1, 2, ... moves, 0 past the job's own number; None when
+                                 not asked for
+    jobs       int32 (ngaps, 6)  what was scored: row_a, col_a, incoming, row_b, col_b, moves"""
+
+    def __init__(self, g, status, surprisal, arrivals, jobs):
+        self.g, self.status, self.surprisal, self.arrivals, self.jobs = g, status, surprisal, arrivals, jobs
+        self._host = None
+
+    def _views(self):
+        if self._host is None:
+            self._host = (self.g.cpu().numpy(), self.status.cpu().numpy(), self.surprisal.cpu().numpy())
+        return self._host
+
+    def p(self):
+        """P of every gap, f64 (ngaps,): the sum of g in numpy's pairwise order, as the library forms it."""
+        g = self._views()[0]
+        return (((g[:, 0] + g[:, 1]) + (g[:, 2] + g[:, 3])) + ((g[:, 4] + g[:, 5]) + (g[:, 6] + g[:, 7]))) + g[:, 8]
+
+    def bits(self):
+        """The surprisal of every gap in bits, f64 (ngaps,): inf where the model forbids the gap (ZERO, UNDEFINED), NaN where
+        it was not evaluated (TOO_LONG, OUT)."""
+        _, status, s = self._views()
+        out = s.astype(np.float64) / 4294967296.
+        out[(status == nat.BRIDGE_ZERO) | (status == nat.BRIDGE_UNDEFINED)] = np.inf
+        out[(status == nat.BRIDGE_TOO_LONG) | (status == nat.BRIDGE_OUT)] = np.nan
+        return out
+
+    def total_bits(self, zero_bits=np.inf):
+        """sum S / 2^32 + zero_bits * (zero + undefined), with the meaning TrackProfile.total_bits gives it: a forbidden
+        gap has likelihood 0, a finite zero_bits is the price per such gap; 0 * inf is 0.  Gaps that were not evaluated
+        (TOO_LONG, OUT) add nothing: counts() says whether there are any."""
+        _, status, s = self._views()
+        forbidden = int(((status == nat.BRIDGE_ZERO) | (status == nat.BRIDGE_UNDEFINED)).sum())
+        return float(int(s.sum()) / 4294967296.) + (float(zero_bits) * forbidden if forbidden else 0.)
+
+    def counts(self):
+        """{'scored', 'zero', 'too_long', 'out', 'undefined': int}."""
+        n = np.bincount(self._views()[1], minlength=len(GAP_STATUSES))
+        return {name: int(n[k]) for k, name in enumerate(GAP_STATUSES)}
+
+
+def score_gaps(jobs, grid_shape, move_dirn, scaling_parameter=1., updraft_field=None, potential_field=None, *,
+               want_arrivals=False):
+    """The probability that the movement model with memory 1 is at cell B `moves` moves after it was at cell A, for every
+    job (include/ssrs_bridge.h, K23): the sum over EVERY path between two fixes of sparse telemetry, where score_tracks on
+    rasterize_track's line gives the probability of one.  jobs: int32 (ngaps, 6) rows of row_a, col_a, incoming, row_b,
+    col_b, moves (fix_gaps makes them), numpy or a device tensor; heading, nu and the two rasters as score_tracks takes them
+    (both None = 'drw').  One nu per call, 1 <= moves <= 32, gaps independent of each other.  Returns a GapScores."""
+    rows, cols = int(grid_shape[0]), int(grid_shape[1])
+    if not is_tensor(jobs):
+        jobs = np.ascontiguousarray(jobs)
+        if jobs.dtype.kind not in 'iu':
+            raise ValueError(f'score_gaps: jobs is an integer array, not {jobs.dtype}')
+        if jobs.size and (jobs.min() < -2 ** 31 or jobs.max() >= 2 ** 31):
+            raise ValueError('score_gaps: a job does not fit int32')
+    elif jobs.dtype != torch.int32:
+        raise ValueError(f'score_gaps: a jobs tensor is int32, not {jobs.dtype}')
+    if jobs.ndim != 2 or jobs.shape[1] != nat.BRIDGE_JOB:
+        raise ValueError(f'score_gaps: jobs of shape {tuple(jobs.shape)}, not (ngaps, {nat.BRIDGE_JOB}): row_a, col_a, '
+                         'incoming, row_b, col_b, moves')
+    if not float(scaling_parameter) >= 0.:
+        raise ValueError(f'score_gaps: scaling_parameter = {scaling_parameter} (not negative, not NaN)')
+    dev = device()
+    jobs = to_dev(jobs, torch.int32)
+    ngaps = int(jobs.shape[0])
+    upd, pot = _score_fields(updraft_field, potential_field, rows, cols)
+    g = torch.empty((ngaps, 9), dtype=torch.float64, device=dev)
+    status = torch.empty(ngaps, dtype=torch.uint8, device=dev)
+    surprisal = torch.empty(ngaps, dtype=torch.int64, device=dev)
+    arrivals = torch.empty((ngaps, nat.BRIDGE_MAX_MOVES), dtype=torch.float64, device=dev) if want_arrivals else None
+    prm = make_track_params((rows, cols), move_dirn, 1, scaling_parameter)
+    if ngaps > 0:                                          # (an empty tensor has no address to hand over)
+        nat.check(nat.lib().ssrs_tracks_bridge(C.byref(prm), nat.ptr(upd), nat.ptr(pot), nat.ptr(jobs), ngaps, nat.ptr(g),
+                                               nat.ptr(status), nat.ptr(surprisal), nat.ptr(arrivals), stream_ptr()))
+    return GapScores(g, status, surprisal, arrivals, jobs)
+
+
+def fix_gaps(fixes, moves=None):
+    """One track's successive fix cells, int (n, 2) [row, col], NOT necessarily adjacent -> (jobs int32 (m, 6), pair int64
+    (m,)): one job of score_gaps per pair (fixes[j], fixes[j + 1]) and the j it came from.
+
+    moves[j] is the number of moves of pair j (n - 1 of them).  The default is the Chebyshev distance of its cells: the
+    FEWEST moves that join them -- a lower bound, not an estimate of what the bird flew, and the probability of a gap
+    depends strongly on it; give the number that the fix interval and the bird's speed suggest.  A pair of equal cells has
+    no such number and is left out unless `moves` is given.  A pair of more than 32 moves is kept, so that it comes back
+    TOO_LONG and is seen.  incoming is the move of the pair before when that pair was a single unit move (one move between
+    adjacent cells), else 4, no last move: the track's first pair, after a longer gap, after a repeated cell."""
+    cells = np.asarray(fixes)
+    if cells.size and cells.dtype.kind not in 'iu':
+        raise ValueError(f'fix_gaps: fixes are integer cells, not {cells.dtype} (Simulator.score_fixes takes metres)')
+    cells = cells.astype(np.int64).reshape(-1, 2)
+    npairs = max(len(cells) - 1, 0)
+    d = cells[1:] - cells[:-1]
+    cheb = np.abs(d).max(1) if npairs else np.zeros(0, dtype=np.int64)
+    if moves is None:
+        n = cheb
+        keep = cheb > 0
+    else:
+        n = np.asarray(moves).astype(np.int64).reshape(-1)
+        if n.size != npairs:
+            raise ValueError(f'fix_gaps: {n.size} moves for {npairs} pairs of fixes')
+        keep = np.ones(npairs, dtype=bool)
+    unit = keep & (n == 1) & (cheb <= 1)
+    incoming = np.full(npairs, 4, dtype=np.int64)
+    incoming[1:][unit[:-1]] = (3 * (d[:, 0] + 1) + (d[:, 1] + 1))[:-1][unit[:-1]]
+    jobs = np.stack([cells[:-1, 0], cells[:-1, 1], incoming, cells[1:, 0], cells[1:, 1], n], 1)[keep]
+    if jobs.size and (jobs.min() < -2 ** 31 or jobs.max() >= 2 ** 31):
+        raise ValueError('fix_gaps: a cell or a number of moves does not fit int32')
+    return np.ascontiguousarray(jobs, dtype=np.int32).reshape(-1, nat.BRIDGE_JOB), np.nonzero(keep)[0].astype(np.int64)
+
+
+def thin_track(track, every):
+    """Every `every`-th point of an 8-connected track, and its last one -> (fixes (m, 2), moves int64 (m - 1,)): what a
+    logger that fixes every `every` moves would have kept, with the true number of moves between the fixes, as fix_gaps
+    takes them."""
+    track = np.asarray(track).reshape(-1, 2)
+    every = int(every)
+    if every < 1:
+        raise ValueError(f'thin_track: every = {every} (at least 1)')
+    idx = np.arange(0, len(track), every, dtype=np.int64)
+    if len(track) and idx[-1] != len(track) - 1:
+        idx = np.append(idx, len(track) - 1)
+    return track[idx], np.diff(idx)
+
+
 # ---------------------------------------------------------------- re-exports
 from .presence import (compute_presence_counts, compute_smooth_presence_counts)  # noqa: E402
 from . import potential as _potential  # noqa: E402

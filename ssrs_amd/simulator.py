@@ -1239,6 +1239,46 @@ class Simulator(Config):
                  nus=last.nus, rows_total=last.host_rows().sum(0))
         return fit
 
+    def score_fixes(self, fixes, moves=None, case_id=None, real_id=0, xy=False):
+        """The probability this run's movement model gives to the gaps between successive fixes of SPARSE telemetry
+        (movmodel.score_gaps): for every pair of fixes the sum over every path of `moves` moves between
+        them, on the fields and the heading that score_tracks uses, with track_stochastic_nu.  The gap states are (cell,
+        last move), so the run's track_dirn_restrict must be 1.
+
+        fixes: a list of (n_i, 2) integer arrays, [row, col] cells that need not be adjacent, or, with xy=True, [x, y] in
+        projected metres, rounded to their cells ((x - west) / resolution along columns, (y - south) / resolution along
+        rows) and NOT joined by a line.  moves: None (the Chebyshev distance of every pair: the fewest moves, a lower
+        bound) or a list of one (n_i - 1,) integer array per track, as movmodel.fix_gaps takes them.  Returns the GapScores
+        with two more host arrays, track and pair (int64 (ngaps,): the track and the pair of it each gap came from), and
+        writes <id>_gap_scores.npy, int64 (ngaps, 4): track, pair, status, surprisal.  No collectives."""
+        if int(self.track_dirn_restrict) != 1:
+            raise ValueError(f'score_fixes: track_dirn_restrict = {self.track_dirn_restrict} is not supported: the states of '
+                             'a gap are (cell, last move), which is track_dirn_restrict = 1')
+        fixes = list(fixes)
+        if moves is not None and len(moves) != len(fixes):
+            raise ValueError(f'score_fixes: {len(moves)} arrays of moves for {len(fixes)} tracks')
+        if xy:
+            cells = []
+            for t in fixes:
+                t = np.asarray(t, dtype=np.float64).reshape(-1, 2)
+                if not np.isfinite(t).all():
+                    raise ValueError('score_fixes: a fix is not finite')
+                cells.append(np.stack([np.rint((t[:, 1] - float(self.bounds[1])) / float(self.resolution)),
+                                       np.rint((t[:, 0] - float(self.bounds[0])) / float(self.resolution))], 1).astype(np.int64))
+            fixes = cells
+        fixes, case_id, real_id, fields = self._score_inputs('score_fixes', fixes, case_id, real_id, False)
+        jobs, track, pair = [np.zeros((0, 6), dtype=np.int32)], [np.zeros(0, dtype=np.int64)], [np.zeros(0, dtype=np.int64)]
+        for t, cells in enumerate(fixes):
+            j, k = movmodel.fix_gaps(cells, None if moves is None else moves[t])
+            jobs.append(j), pair.append(k), track.append(np.full(len(k), t, dtype=np.int64))
+        scores = movmodel.score_gaps(np.concatenate(jobs), self.gridsize, self.track_direction, self.track_stochastic_nu,
+                                     fields[0], fields[1])
+        scores.track, scores.pair = np.concatenate(track), np.concatenate(pair)
+        fname = os.path.join(self.mode_data_dir, f'{self._get_id_string(case_id, real_id)}_gap_scores')
+        np.save(f'{fname}.npy', np.stack([scores.track, scores.pair, scores.status.cpu().numpy().astype(np.int64),
+                                          scores.surprisal.cpu().numpy()], 1))
+        return scores
+
     # ------------------------------------------------------------- presence
     def _counts_for(self, case_id, real_id):
         hist = self._presence_counts.get((case_id, real_id))
